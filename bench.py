@@ -9,6 +9,12 @@ One "step" = one full iteration: E fwd, G fwd, 5 D fwd, all backward passes, 4 A
 all-reduces over RCCL when N > 1).  Workload (BASELINE.json configs[1], SURVEY.md 8(d) "C2"): CelebA-shaped
 synthetic 64x64 images, batch 128 PER GPU (weak scaling), inputs (images and the three noise tensors) resident
 in HBM before the timed region, seed-42 random-init weights of the A0 size family.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times --steps iterations and prints the line (`value`, `ms_per_step`, `losses`, `config`).
+--full adds what the headline number does not need: the kernel-family rooflines and launch counts (with --graph 1 from an
+extra eager pass after the timed region), the secondary paths and the CPU baseline.  --dump-outputs DIR writes what the
+last timed step computed (dump_outputs); inputs, weights and device noise are seeded, so runs with the same arguments
+are comparable output for output.
 """
 import argparse
 import json
@@ -141,6 +147,104 @@ def build_models(V, S, dtype, dev):
     g.apply(V.weights_init), d.apply(V.weights_init)
     e.to(dev), g.to(dev), d.to(dev)
     return e, g, d
+
+
+DUMP_MAX_PER_NET = 4 << 20      # float32 values per network file: three files of <= 16 MiB and the losses stay under 64 MB
+
+
+def dump_outputs(out_dir, losses, nets):
+    """--dump-outputs: what the last timed step computed, as float32 .npy files -- `losses` (the [recon_loss, kl_loss,
+    g_loss_adv, d_loss_1, d_loss_2] the step returns) and `encoder_state` / `generator_state` / `discriminator_state`
+    (the floating-point entries of each network's state_dict after the step -- fp32 master weights and BatchNorm running
+    statistics -- flattened in key order).  A network with more than DUMP_MAX_PER_NET values is written as a fixed sample:
+    the values at the sorted first DUMP_MAX_PER_NET indices of a seed-0 permutation, the same indices in every build."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "losses.npy"), losses[:5].float().cpu().numpy())
+    for name, net in zip(("encoder", "generator", "discriminator"), nets):
+        flat = torch.cat([v.detach().reshape(-1).float().cpu() for v in net.state_dict().values() if v.is_floating_point()])
+        if flat.numel() > DUMP_MAX_PER_NET:
+            idx = torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_MAX_PER_NET]
+            flat = flat[idx.sort().values]
+        np.save(os.path.join(out_dir, f"{name}_state.npy"), flat.numpy())
+
+
+def kernel_family_figures(timer, dtype, S, B, steps, ms, eager_pass):
+    """--full (or --graph 0, where the timed region itself carries the timer): rooflines of the kernel families from the
+    live per-launch timing -- the dominant implicit-GEMM conv fprop+dgrad family, the edge layers, BatchNorm / activation
+    and, with --dtype fp8, the fp8 GEMMs."""
+    out = {}
+    fam = timer.summary()
+    gg = fam.get("gather_gemm", dict(launches=0, ms=1e-9, flops=0, bytes=0))
+    wg = fam.get("wgrad", dict(launches=0, ms=1e-9, flops=0, bytes=0))
+    ed = fam.get("edge", dict(launches=0, ms=0.0, flops=0, bytes=0))
+    bn = fam.get("bn", dict(launches=0, ms=0.0, flops=0, bytes=0))
+    ach = gg["flops"] / (gg["ms"] * 1e-3) / 1e12
+    traffic, traffic_src = pmc_traffic(dtype)
+    peak = PEAK["bf16" if dtype == "fp8" else dtype]
+    roofline = {"bound": "mfma", "kernel": "gg_kernel (gather-GEMM: conv/convT/linear fprop + dgrad)",
+                "achieved": round(ach, 2), "peak": peak, "unit": "TFLOP/s", "frac": round(ach / peak, 4),
+                # HBM-side bytes per launch from the committed rocprofv3 PMC passes (profiles/), not re-measured here
+                "traffic": traffic if (S, B) == (64, 128) else None,
+                "traffic_source": (f"{traffic_src}: separate rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE passes of this "
+                                   f"command (FETCH_SIZE doubled: gfx950 counter correction), measured offline"
+                                   if (S, B) == (64, 128) and traffic_src else None),
+                "timed_in": ("eager pass after the timed region: HIP start/stop events around every launch on its stream "
+                             "(a replayed hipGraph cannot carry per-launch events)" if eager_pass else
+                             "the timed region itself: HIP start/stop events around every launch on its stream"),
+                "launches_per_step": gg["launches"] // steps,
+                "avg_launch_us": round(gg["ms"] * 1e3 / max(gg["launches"], 1), 2),
+                "alg_gflop_per_launch": round(gg["flops"] / max(gg["launches"], 1) / 1e9, 3),
+                "share_of_step": round(gg["ms"] / steps / ms, 3),
+                "alg_bytes_gbs": round(gg["bytes"] / (gg["ms"] * 1e-3) / 1e9, 1),
+                "wgrad": {"achieved": round(wg["flops"] / (wg["ms"] * 1e-3) / 1e12, 2),
+                          "launches_per_step": wg["launches"] // steps,
+                          "share_of_step": round(wg["ms"] / steps / ms, 3)},
+                "step_alg_tflops": round(ALG_GFLOP_PER_IMAGE.get(S, 0) * B / ms, 2)}
+    busy, busy_all, busy_src = pmc_mfma_busy(dtype)
+    if busy is not None and (S, B) == (64, 128):
+        # north_star's own wording of the target ("MFMA utilisation ... from rocprof"): matrix-pipe busy cycles over
+        # SIMD cycles, from a separate rocprofv3 PMC pass of this command (offline)
+        roofline["mfma_busy_frac"] = round(busy, 4)
+        roofline["mfma_busy_frac_whole_step"] = round(busy_all, 4)
+        roofline["mfma_busy_source"] = f"{busy_src}: rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE pass of bench.py --graph 0, measured offline"
+    out["roofline"] = roofline
+    # the 3-channel image-side layers (SURVEY.md 8(d): <= 20 FLOP/B, priced against HBM): own kernels, own roofline
+    if ed["launches"]:
+        gbs = ed["bytes"] / (ed["ms"] * 1e-3) / 1e9
+        etraffic, esrc = pmc_traffic(dtype, "edge")
+        out["roofline_edge"] = {"bound": "hbm", "kernel": "edge layers: tnconv_kernel (narrow-N transposed conv, GEMM + col2im), "
+                                                          "ggn_kernel (narrow-K direct conv)",
+                                "achieved": round(gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(gbs / HBM_PEAK_GBS, 4),
+                                "traffic": etraffic if (S, B) == (64, 128) else None,
+                                "traffic_source": (f"{esrc}: separate rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE passes (FETCH_SIZE "
+                                                   f"doubled), measured offline" if (S, B) == (64, 128) and esrc else None),
+                                "launches_per_step": ed["launches"] // steps,
+                                "avg_launch_us": round(ed["ms"] * 1e3 / ed["launches"], 2),
+                                "alg_mbytes_per_launch": round(ed["bytes"] / ed["launches"] / 1e6, 2),
+                                "share_of_step": round(ed["ms"] / steps / ms, 3)}
+    if bn["launches"]:
+        # the second-largest consumer of the step: every launch of csrc/bn_act.hip (BatchNorm finalize, normalise +
+        # activation, backward reduce + apply, activation backward, bias-gradient column sums) against HBM.  Algorithmic
+        # bytes: 2 |Y| per forward pass of a BatchNorm layer, 5 |Y| per backward pass (ops._bn_bytes)
+        gbs = bn["bytes"] / (bn["ms"] * 1e-3) / 1e9
+        out["roofline_bn"] = {"bound": "hbm", "kernel": "bn_act.hip: BatchNorm finalize / normalise + activation / backward reduce + apply, "
+                                                        "activation backward, bias-gradient sums",
+                              "achieved": round(gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(gbs / HBM_PEAK_GBS, 4),
+                              "traffic": None, "launches_per_step": bn["launches"] // steps,
+                              "avg_launch_us": round(bn["ms"] * 1e3 / bn["launches"], 2),
+                              "alg_mbytes_per_step": round(bn["bytes"] / steps / 1e6, 1),
+                              "us_per_step": round(bn["ms"] * 1e3 / steps, 1),
+                              "share_of_step": round(bn["ms"] / steps / ms, 3)}
+    f8 = fam.get("gather_gemm_fp8", dict(launches=0, ms=0.0, flops=0, bytes=0))
+    if f8["launches"]:
+        a8 = f8["flops"] / (f8["ms"] * 1e-3) / 1e12
+        out["roofline_fp8"] = {"bound": "mfma", "kernel": "gg_kernel<fp8> (conv / convT fprop on v_mfma_scale_f32_16x16x128_f8f6f4, e4m3)",
+                               "achieved": round(a8, 2), "peak": PEAK["fp8"], "unit": "TFLOP/s", "frac": round(a8 / PEAK["fp8"], 4),
+                               "traffic": None, "launches_per_step": f8["launches"] // steps,
+                               "avg_launch_us": round(f8["ms"] * 1e3 / f8["launches"], 2),
+                               "share_of_step": round(f8["ms"] / steps / ms, 3)}
+    return out
 
 
 def time_steps(fn, warm, steps):
@@ -292,14 +396,23 @@ def main():
                     help="bf16 = BASELINE configs[1] (bf16 storage, f32 accumulate, fp32 master weights); fp32 = parity path; "
                          "fp8 = BASELINE configs[4] (e4m3 operands for the forward GEMMs of the wide conv layers on the "
                          "block-scaled MFMA, everything else as bf16; quoted at --size 256 --batch 32; roofline run, no parity claim)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline number does not need: kernel-family rooflines and launch counts "
+                         "(--graph 1: an extra eager pass after the timed region), the secondary paths and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the losses and the updated E/G/D state of the last timed step to DIR/<name>.npy "
+                         "(float32, < 64 MB in all; see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-extra-paths", action="store_true",
-                    help="skip the secondary legs (fp32 parity path, drop-in autograd path) reported beside the main number")
+                    help="with --full: skip the secondary legs (fp32 parity path, drop-in autograd path) reported beside "
+                         "the main number")
     ap.add_argument("--graph", type=int, default=int(os.environ.get("VAEGAN_BENCH_GRAPH", "1")),
                     help="1: replay the iteration from captured hipGraph(s); with N > 1 the graph is cut at the all-reduces")
     ap.add_argument("--elide-dead-grads", action="store_true",
                     help="skip the D weight gradients of the generator-loss pass that the reference computes and discards")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     # stdout carries exactly ONE line, the JSON result: keep a private handle on it and point fd 1 at stderr, so that
     # nothing a library prints (RCCL writes its version banner to stdout at communicator creation) can get in front
@@ -397,7 +510,10 @@ def main():
         tmax = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
-    if args.graph:
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, losses, (e, g, d))     # before --full's eager pass moves the weights on
+    eager_pass = bool(args.graph) and args.full
+    if eager_pass:
         # graph replay: per-launch HIP events cannot be recorded inside captured graphs, so the kernel families are
         # timed in an extra EAGER pass of the same steps after the timed region (every rank runs it: it contains
         # the collectives; only rank 0 records).  Keyed on the REQUESTED mode so that a rank that fell back to
@@ -410,8 +526,10 @@ def main():
         torch.cuda.synchronize()
         ops.set_timer(None)
         launches_per_step = (ops.launch_count() - n_launch0) / args.steps
-    else:
+    elif not use_graph:
         launches_per_step = n_launch_timed / args.steps      # eager launches: the timed region itself
+    else:
+        launches_per_step = None                             # a plain replayed run: no eager pass, no kernel figures
     if rank != 0:
         if multi:
             dist.destroy_process_group()
@@ -422,56 +540,6 @@ def main():
     ld = tr.loss_dict(losses, epoch)
     assert all(v == v and abs(v) < 1e6 for v in ld.values()), f"non-finite losses: {ld}"
 
-    # ---- roofline of the dominant kernel family (implicit-GEMM conv fprop+dgrad), measured live ----
-    fam = timer.summary()
-    gg = fam.get("gather_gemm", dict(launches=0, ms=1e-9, flops=0, bytes=0))
-    wg = fam.get("wgrad", dict(launches=0, ms=1e-9, flops=0, bytes=0))
-    ed = fam.get("edge", dict(launches=0, ms=0.0, flops=0, bytes=0))
-    bn = fam.get("bn", dict(launches=0, ms=0.0, flops=0, bytes=0))
-    ach = gg["flops"] / (gg["ms"] * 1e-3) / 1e12
-    traffic, traffic_src = pmc_traffic(args.dtype)
-    roofline = {"bound": "mfma", "kernel": "gg_kernel (gather-GEMM: conv/convT/linear fprop + dgrad)",
-                "achieved": round(ach, 2), "peak": PEAK["bf16" if args.dtype == "fp8" else args.dtype], "unit": "TFLOP/s",
-                "frac": round(ach / PEAK["bf16" if args.dtype == "fp8" else args.dtype], 4),
-                # HBM-side bytes per launch from the committed rocprofv3 PMC passes (profiles/), not re-measured here
-                "traffic": traffic if (S, B) == (64, 128) else None,
-                "traffic_source": (f"{traffic_src}: separate rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE passes of this "
-                                   f"command (FETCH_SIZE doubled, MI355X_MICROARCH.md section HBM), measured offline"
-                                   if (S, B) == (64, 128) and traffic_src else None),
-                "timed_in": ("eager pass after the timed region: HIP start/stop events around every launch on its stream "
-                             "(a replayed hipGraph cannot carry per-launch events)" if args.graph else
-                             "the timed region itself: HIP start/stop events around every launch on its stream"),
-                "launches_per_step": gg["launches"] // args.steps,
-                "avg_launch_us": round(gg["ms"] * 1e3 / max(gg["launches"], 1), 2),
-                "alg_gflop_per_launch": round(gg["flops"] / max(gg["launches"], 1) / 1e9, 3),
-                "share_of_step": round(gg["ms"] / args.steps / ms, 3),
-                "alg_bytes_gbs": round(gg["bytes"] / (gg["ms"] * 1e-3) / 1e9, 1),
-                "wgrad": {"achieved": round(wg["flops"] / (wg["ms"] * 1e-3) / 1e12, 2),
-                          "launches_per_step": wg["launches"] // args.steps,
-                          "share_of_step": round(wg["ms"] / args.steps / ms, 3)},
-                "step_alg_tflops": round(ALG_GFLOP_PER_IMAGE.get(S, 0) * B / ms, 2)}
-    busy, busy_all, busy_src = pmc_mfma_busy(args.dtype)
-    if busy is not None and (S, B) == (64, 128):
-        # north_star's own wording of the target ("MFMA utilisation ... from rocprof"): matrix-pipe busy cycles over
-        # SIMD cycles, from a separate rocprofv3 PMC pass of this command (offline)
-        roofline["mfma_busy_frac"] = round(busy, 4)
-        roofline["mfma_busy_frac_whole_step"] = round(busy_all, 4)
-        roofline["mfma_busy_source"] = f"{busy_src}: rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE pass of bench.py --graph 0, measured offline"
-    # the 3-channel image-side layers (<= 20 FLOP/B, priced against HBM): own kernels, own roofline
-    roofline_edge = None
-    if ed["launches"]:
-        gbs = ed["bytes"] / (ed["ms"] * 1e-3) / 1e9
-        etraffic, esrc = pmc_traffic(args.dtype, "edge")
-        roofline_edge = {"bound": "hbm", "kernel": "edge layers: tnconv_kernel (narrow-N transposed conv, GEMM + col2im), "
-                                                   "ggn_kernel (narrow-K direct conv)",
-                         "achieved": round(gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(gbs / HBM_PEAK_GBS, 4),
-                         "traffic": etraffic if (S, B) == (64, 128) else None,
-                         "traffic_source": (f"{esrc}: separate rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE passes (FETCH_SIZE "
-                                            f"doubled), measured offline" if (S, B) == (64, 128) and esrc else None),
-                         "launches_per_step": ed["launches"] // args.steps,
-                         "avg_launch_us": round(ed["ms"] * 1e3 / ed["launches"], 2),
-                         "alg_mbytes_per_launch": round(ed["bytes"] / ed["launches"] / 1e6, 2),
-                         "share_of_step": round(ed["ms"] / args.steps / ms, 3)}
     out = {"metric": "images/sec/GPU VAE-GAN train step", "value": round(value, 1), "unit": "images/sec",
            "per_gpu": round(value / world, 1), "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
            "ms_per_step": round(ms, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
@@ -482,36 +550,15 @@ def main():
                       "elide_dead_grads": bool(args.elide_dead_grads), "hip_graph": use_graph,
                       # graphs one iteration is replayed from: 1 = the whole iteration incl. its RCCL collectives (N > 1:
                       # captured inside the graph); > 1 = cut at the hand-offs to the reducer (gloo rehearsals, fallback)
-                      "hip_graph_segments": (len(tr._graph[1]) if (use_graph and tr._graph is not None) else 0)},
-           # kernel launches of libvaegan_hip.so per iteration (vg_launch_count over the eager pass that follows the timed
-           # region; the replayed graph holds the same launches).  Round 3: 193 by rocprofv3.
-           "kernel_launches_per_step": launches_per_step,
-           "losses": {k: round(v, 5) for k, v in ld.items()},
-           "roofline": roofline}
-    if roofline_edge is not None:
-        out["roofline_edge"] = roofline_edge
-    if bn["launches"]:
-        # the second-largest consumer of the step: every launch of csrc/bn_act.hip (BatchNorm finalize, normalise +
-        # activation, backward reduce + apply, activation backward, bias-gradient column sums) against HBM.  Algorithmic
-        # bytes: 2 |Y| per forward pass of a BatchNorm layer, 5 |Y| per backward pass (ops._bn_bytes)
-        gbs = bn["bytes"] / (bn["ms"] * 1e-3) / 1e9
-        out["roofline_bn"] = {"bound": "hbm", "kernel": "bn_act.hip: BatchNorm finalize / normalise + activation / backward reduce + apply, "
-                                                        "activation backward, bias-gradient sums",
-                              "achieved": round(gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(gbs / HBM_PEAK_GBS, 4),
-                              "traffic": None, "launches_per_step": bn["launches"] // args.steps,
-                              "avg_launch_us": round(bn["ms"] * 1e3 / bn["launches"], 2),
-                              "alg_mbytes_per_step": round(bn["bytes"] / args.steps / 1e6, 1),
-                              "us_per_step": round(bn["ms"] * 1e3 / args.steps, 1),
-                              "share_of_step": round(bn["ms"] / args.steps / ms, 3)}
-    f8 = fam.get("gather_gemm_fp8", dict(launches=0, ms=0.0, flops=0, bytes=0))
-    if f8["launches"]:
-        a8 = f8["flops"] / (f8["ms"] * 1e-3) / 1e12
-        out["roofline_fp8"] = {"bound": "mfma", "kernel": "gg_kernel<fp8> (conv / convT fprop on v_mfma_scale_f32_16x16x128_f8f6f4, e4m3)",
-                               "achieved": round(a8, 2), "peak": PEAK["fp8"], "unit": "TFLOP/s", "frac": round(a8 / PEAK["fp8"], 4),
-                               "traffic": None, "launches_per_step": f8["launches"] // args.steps,
-                               "avg_launch_us": round(f8["ms"] * 1e3 / f8["launches"], 2),
-                               "share_of_step": round(f8["ms"] / args.steps / ms, 3)}
-    if world == 1 and not multi and not args.no_extra_paths:
+                      "hip_graph_segments": (len(tr._graph[1]) if (use_graph and tr._graph is not None) else 0)}}
+    if launches_per_step is not None:
+        # kernel launches of libvaegan_hip.so per iteration (vg_launch_count over the eager pass that follows the timed
+        # region; the replayed graph holds the same launches).  Round 3: 193 by rocprofv3.
+        out["kernel_launches_per_step"] = launches_per_step
+    out["losses"] = {k: round(v, 5) for k, v in ld.items()}
+    if timer is not None:
+        out.update(kernel_family_figures(timer, args.dtype, S, B, args.steps, ms, eager_pass))
+    if args.full and world == 1 and not multi and not args.no_extra_paths:
         del tr, e, g, d, oE, oG, oD
         out["denoise_path"] = denoise_path(V, S, B, dev, args.dtype, resident)
         out["parity_path"] = parity_path(V, S, B, dev, resident, ops)
@@ -525,7 +572,7 @@ def main():
             out["dropin_path"]["torchops_binding"] = {"error": str(ex)[:200]}
         finally:
             ops.set_binding("ctypes")
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(S, B)
     print(json.dumps(out), file=result_out, flush=True)
     if multi:
