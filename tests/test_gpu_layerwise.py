@@ -13,9 +13,15 @@ the tensors the engine itself stored as a stage's inputs, its stored outputs mus
 rounding, up to rare one-ulp flips.  An indexing or scheduling defect that corrupts even 1 % of one stage's output in the
 benchmarked dtype, batch and tile shapes fails these bounds by orders of magnitude.
 
-vaegan_code.py:74-135 (one iteration, S=64, B=128, bf16, eager launches with injected noise)."""
+vaegan_code.py:74-135 (one iteration, eager launches with injected noise) at S=64 B=128, S=128 B=64 and S=256 B=32 in bf16,
+S=256 B=32 with the fp8 forward, and at S=64 B=128 (and S=256 B=32 for split-K) with the opt-in and fallback switches.
+The f64 reference runs on the device (torch's native f64 convolutions: im2col + rocBLAS dgemm), one trace record at a
+time, so that the S=256 checks stay within seconds and no whole trace is ever held in f64.  Graph replay of the
+benchmarked configurations is shown to equal these eager iterations bit for bit at the end of the file."""
+import functools
 import importlib
 import os
+import time
 
 import pytest
 import torch
@@ -24,13 +30,17 @@ import torch.nn.functional as F
 from _inputs import make_inputs
 
 import vaegan_amd as V
+from test_gpu_kernels import FP8_MFMA_REL
 from test_gpu_parity import DEV, build
 
 pytestmark = pytest.mark.gpu
-torch.set_num_threads(min(32, os.cpu_count() or 1))
+torch.set_num_threads(min(16, os.cpu_count() or 1))
 
+PKG = "vae-gan-based-model-for-image-generation-and-denoising_amd"
 FLIP_TOL = 3e-4         # relative Frobenius distance of a bf16 tensor from bf16(exact): one-ulp flips of <= ~0.5 % of the elements
 F32_TOL = 2e-4          # f32 results (weight gradients, the reconstruction): f32 accumulation against f64
+ACC_TOL = 5e-4          # f32 gradients accumulated over several passes (the Discriminator's): the previous value + the new sum
+REF = DEV               # where the f64 reference arithmetic runs
 
 
 def q(t):
@@ -41,9 +51,22 @@ def frob(a, r):
     return float((a.double() - r.double()).norm() / r.double().norm().clamp_min(1e-30))
 
 
+def f64(t):
+    return t.to(REF, torch.float64)
+
+
 def nchw(t, C):
-    """[B,H,W,CP] engine tensor -> [B,C,H,W] float64 on the CPU."""
-    return t[..., :C].permute(0, 3, 1, 2).double().cpu().contiguous()
+    """[B,H,W,CP] engine tensor -> [B,C,H,W] float64 on the reference device."""
+    return f64(t[..., :C].permute(0, 3, 1, 2)).contiguous()
+
+
+def e4m3_bits(t):
+    """torch's float8_e4m3fn cast (round to nearest even) of a bf16 / f32 tensor, as the bytes the kernels exchange."""
+    return t.float().to(torch.float8_e4m3fn).view(torch.uint8)
+
+
+def e4m3_value(bits):
+    return bits.view(torch.float8_e4m3fn).float().to(torch.float64)
 
 
 def stage_fn(st, w, b, x):
@@ -63,133 +86,358 @@ def stage_weights(st):
     if st.kind == "linear2":
         w = torch.cat([st.conv.weight.detach(), st.conv2.weight.detach()], 0)
         b = torch.cat([st.conv.bias.detach(), st.conv2.bias.detach()], 0)
-        return q(w.cpu()), b.double().cpu()
-    b = st.conv.bias.detach().double().cpu() if getattr(st.conv, "bias", None) is not None else None
-    return q(st.conv.weight.detach().cpu()), b
+        return q(f64(w)), f64(b)
+    b = f64(st.conv.bias.detach()) if getattr(st.conv, "bias", None) is not None else None
+    return q(f64(st.conv.weight.detach())), b
 
 
-def check_engine(name, eng, report):
-    from_fwd = {}
-    prev_gw = {}
-    for rec in eng.trace:
+class LayerCheck:
+    """Checks one engine's trace records one at a time (each record is converted to f64, checked and dropped).  What
+    carries over between records: the previous value of every gradient that a later pass accumulates onto."""
+
+    def __init__(self, name, eng, report, tail_noise):
+        self.name, self.eng, self.report = name, eng, report
+        self.tail_noise = tail_noise            # (eps_recon, sigma) the trainer's fused Generator tail adds
+        self.prev = {}                          # (stage, what) -> the engine's previous f32 gradient
+        self.w8_checked = set()
+
+    def run(self, trace):
+        trace.reverse()
+        while trace:
+            self.check(trace.pop())
+
+    def grad(self, i, what, ge, gr, acc, tag):
+        """f32 gradient `ge` of stage i against its exact value `gr` (+ the engine's previous value when accumulated)."""
+        if acc:
+            gr = gr + self.prev[(i, what)]
+        self.prev[(i, what)] = f64(ge)
+        self.report(tag, frob(f64(ge), gr), ACC_TOL if acc else F32_TOL)
+
+    def check(self, rec):
         i, what = rec["stage"], rec["what"]
-        st = eng.stages[i]
-        tag = f"{name}.{i} {what}"
-        if what == "fwd":
-            w, b = stage_weights(st)
-            if st.kind == "linear2":
-                x = nchw(rec["x"], st.cin).flatten(1)
-                yr = F.linear(x, w, b)
-                ye = rec["Y"].double().cpu().reshape(x.shape[0], -1)[:, :st.cout]
-            else:
-                x = nchw(rec["x"], st.cin)
-                yr = stage_fn(st, w, b, x)
-                ye = nchw(rec["Y"], st.cout)
-            if rec["fused_act"]:
-                yr = act(yr, st)
-            report(tag + " Y", frob(ye, q(yr)), FLIP_TOL)
-            if rec["coeffs"] is not None and st.bn is not None:
-                co = rec["coeffs"].double().cpu()                       # [groups][4][C]
-                G_ = co.shape[0]
-                yg = yr.reshape(G_, -1, *yr.shape[1:])                  # statistics: from the UNROUNDED conv output, per group
-                mean = yg.mean(dim=(1, 3, 4)) if yg.dim() == 5 else yg.mean(dim=1)
-                var = yg.var(dim=(1, 3, 4), unbiased=False) if yg.dim() == 5 else yg.var(dim=1, unbiased=False)
-                if eng.spec(i, rec["B"], "fprop")[1].tap_in_n:          # (1x1-input layer: statistics of the STORED tensor)
-                    yq = ye.reshape(G_, -1, *ye.shape[1:])
-                    mean, var = yq.mean(dim=(1, 3, 4)), yq.var(dim=(1, 3, 4), unbiased=False)
-                report(tag + " mean", float((co[:, 0] - mean).abs().max() / mean.abs().max().clamp_min(1e-6)), 1e-4)
-                report(tag + " invstd", frob(co[:, 1], torch.rsqrt(var + 1e-5)), 1e-4)
-                # normalise + activation, teacher-forced on the engine's stored Y and published coefficients
-                sc = co[:, 2].reshape(G_, 1, -1, 1, 1)
-                sh = co[:, 3].reshape(G_, 1, -1, 1, 1)
-                ar = act(sc * ye.reshape(G_, -1, *ye.shape[1:]) + sh, st).reshape(ye.shape)
-                report(tag + " A", frob(nchw(rec["A"], st.cout), q(ar)), FLIP_TOL)
-        elif what == "fwd_tn":
-            w, _ = stage_weights(st)
+        st = self.eng.stages[i]
+        tag = f"{self.name}.{i} {what}"
+        getattr(self, "check_" + what)(i, st, rec, tag)
+
+    def check_fwd(self, i, st, rec, tag):
+        w, b = stage_weights(st)
+        if rec["x8"] is not None:
+            # fp8 forward: the e4m3 operands the GEMM read are the elementwise casts of the stored bf16 input and of the
+            # packed bf16 weights scaled by 2^VG_FP8_WSHIFT; the output is exact arithmetic on their decoded values
+            shift = importlib.import_module(PKG + "._lib").VG_FP8_WSHIFT
+            x8 = rec["x8"].view(rec["x"].shape)
+            self.report(tag + " x8 bits differing", float((x8 != e4m3_bits(rec["x"])).sum()), 0.0)
+            if i not in self.w8_checked:
+                pk = self.eng._packs[i]
+                self.report(tag + " w8 bits differing",
+                            float((pk["fprop8"] != e4m3_bits(pk["fprop"].float() * 2.0 ** shift)).sum()), 0.0)
+                self.w8_checked.add(i)
+            x = e4m3_value(x8)[..., :st.cin].permute(0, 3, 1, 2).contiguous()
+            w = e4m3_value(e4m3_bits(w * 2.0 ** shift)) / 2.0 ** shift
+            yr = stage_fn(st, w, b, x)
+            ye = nchw(rec["Y"], st.cout)
+            # The block-scaled MFMA does not sum its e4m3 products exactly (tests/test_gpu_kernels.py
+            # test_fp8_mfma_one_k128_tile_deviation_from_exact_sum pins it to FP8_MFMA_REL * sum |x w| per 128-long dot
+            # product), so every element is held to that budget plus its one bf16 rounding (half an ulp <= 2^-8 |y|),
+            # the K slices' budgets adding up to FP8_MFMA_REL * (|x| conv |w|)
+            mag = stage_fn(st, w.abs(), None, x.abs())
+            yq = act(yr, st) if rec["fused_act"] else yr
+            budget = 1.01 * FP8_MFMA_REL * mag + 2.0 ** -8 * yq.abs() + 1e-30
+            self.report(tag + " Y / fp8 budget", float(((ye - yq).abs() / budget).max()), 1.0)
+        elif st.kind == "linear2":
+            x = nchw(rec["x"], st.cin).flatten(1)
+            yr = F.linear(x, w, b)
+            ye = f64(rec["Y"]).reshape(x.shape[0], -1)[:, :st.cout]
+        else:
             x = nchw(rec["x"], st.cin)
-            yr = stage_fn(st, w, None, x)
-            if rec["A"].dim() == 4 and rec["A"].shape[1] == st.cout and rec["A"].dtype == torch.float32:
-                report(tag + " tanh image", frob(rec["A"].double().cpu(), torch.tanh(yr)), F32_TOL)
-        elif what == "bn_bwd" and st.bn is not None:
-            co = rec["coeffs"].double().cpu()
+            yr = stage_fn(st, w, b, x)
+            ye = nchw(rec["Y"], st.cout)
+        if rec["fused_act"]:
+            yr = act(yr, st)
+        if rec["x8"] is None:
+            self.report(tag + " Y", frob(ye, q(yr)), FLIP_TOL)
+        if rec["coeffs"] is not None and st.bn is not None:
+            co = f64(rec["coeffs"])                                     # [groups][4][C]
             G_ = co.shape[0]
-            Y = nchw(rec["Y"], st.cout)
-            dA = nchw(rec["dA"], st.cout)
-            Yg, dAg = Y.reshape(G_, -1, *Y.shape[1:]), dA.reshape(G_, -1, *Y.shape[1:])
-            mean, invstd = co[:, 0].reshape(G_, 1, -1, 1, 1), co[:, 1].reshape(G_, 1, -1, 1, 1)
-            z = co[:, 2].reshape(G_, 1, -1, 1, 1) * Yg + co[:, 3].reshape(G_, 1, -1, 1, 1)
-            slope = st.slope if st.act == 2 else (0.0 if st.act == 1 else 1.0)
-            dz = torch.where(z > 0, dAg, dAg * slope)
-            xh = (Yg - mean) * invstd
-            n = Yg.shape[1] * Yg.shape[3] * Yg.shape[4]
-            s1 = dz.sum(dim=(1, 3, 4), keepdim=True)
-            s2 = (dz * xh).sum(dim=(1, 3, 4), keepdim=True)
-            a = st.bn.weight.detach().double().cpu().reshape(1, 1, -1, 1, 1) * invstd
-            dyr = (a * (dz - s1 / n - xh * s2 / n)).reshape(Y.shape)
-            report(tag + " dY", frob(nchw(rec["dY"], st.cout), q(dyr)), FLIP_TOL)
-            from_fwd[(i, "dgamma")] = s2.sum(0).flatten()
-            from_fwd[(i, "dbeta")] = s1.sum(0).flatten()
-        elif what in ("wgrad", "dgrad"):
-            w, _ = stage_weights(st)
-            if what == "wgrad":
-                if st.kind == "linear2":
-                    x = nchw(rec["x"], st.cin).flatten(1)
-                    dy = rec["dY"].double().cpu().reshape(x.shape[0], -1)[:, :st.cout]
-                    gr = dy.t() @ x
-                    ge = torch.cat([rec["gw"], rec["gw2"]], 0).double().cpu()
-                else:
-                    x = nchw(rec["x"], st.cin).requires_grad_(False)
-                    wv = w.clone().requires_grad_(True)
-                    out = stage_fn(st, wv, None, x)
-                    out.backward(nchw(rec["dY"], st.cout))
-                    gr, ge = wv.grad, rec["gw"].double().cpu()
-                if rec["acc"]:
-                    gr = gr + prev_gw[i]
-                prev_gw[i] = ge
-                report(tag + " dW", frob(ge, gr), F32_TOL if not rec["acc"] else 5e-4)
-                if (i, "dgamma") in from_fwd and st.bn is not None and not rec["acc"] and name != "D":
-                    report(tag + " dgamma", frob(st.bn.weight.grad.double().cpu(), from_fwd[(i, "dgamma")]), F32_TOL)
-                    report(tag + " dbeta", frob(st.bn.bias.grad.double().cpu(), from_fwd[(i, "dbeta")]), F32_TOL)
+            yg = yr.reshape(G_, -1, *yr.shape[1:])                      # statistics: from the UNROUNDED conv output, per group
+            mean = yg.mean(dim=(1, 3, 4)) if yg.dim() == 5 else yg.mean(dim=1)
+            var = yg.var(dim=(1, 3, 4), unbiased=False) if yg.dim() == 5 else yg.var(dim=1, unbiased=False)
+            if self.eng.spec(i, rec["B"], "fprop")[1].tap_in_n:         # (1x1-input layer: statistics of the STORED tensor)
+                yq = ye.reshape(G_, -1, *ye.shape[1:])
+                mean, var = yq.mean(dim=(1, 3, 4)), yq.var(dim=(1, 3, 4), unbiased=False)
+            self.report(tag + " mean", float((co[:, 0] - mean).abs().max() / mean.abs().max().clamp_min(1e-6)), 1e-4)
+            self.report(tag + " invstd", frob(co[:, 1], torch.rsqrt(var + 1e-5)), 1e-4)
+            # normalise + activation, teacher-forced on the engine's stored Y and published coefficients
+            sc = co[:, 2].reshape(G_, 1, -1, 1, 1)
+            sh = co[:, 3].reshape(G_, 1, -1, 1, 1)
+            ar = act(sc * ye.reshape(G_, -1, *ye.shape[1:]) + sh, st).reshape(ye.shape)
+            self.report(tag + " A", frob(nchw(rec["A"], st.cout), q(ar)), FLIP_TOL)
+
+    def check_fwd_tn(self, i, st, rec, tag):
+        w, _ = stage_weights(st)
+        yr = stage_fn(st, w, None, nchw(rec["x"], st.cin))
+        if rec["A"].dim() == 4 and rec["A"].shape[1] == st.cout and rec["A"].dtype == torch.float32:
+            self.report(tag + " tanh image", frob(f64(rec["A"]), torch.tanh(yr)), F32_TOL)
+        if rec["noisy"] is not None:
+            # the instance-noised copy the Discriminator reads (vaegan_code.py:92): bf16(tanh(y) + sigma * eps)
+            eps, sigma = self.tail_noise
+            self.report(tag + " noisy image", frob(nchw(rec["noisy"], st.cout), q(torch.tanh(yr) + sigma * f64(eps))),
+                        FLIP_TOL)
+
+    def check_tail(self, i, st, rec, tag):
+        # the Generator's output through the separate tail kernel (the edge-layer kernel off): tanh of the stored
+        # pre-activation as the f32 NCHW image and bf16(tanh + sigma * eps) in the Discriminator's layout
+        pre = nchw(rec["pre"], st.cout)
+        eps, sigma = self.tail_noise
+        self.report(tag + " tanh image", frob(f64(rec["img"]), torch.tanh(pre)), F32_TOL)
+        self.report(tag + " noisy image", frob(nchw(rec["noisy"], st.cout), q(torch.tanh(pre) + sigma * f64(eps))), FLIP_TOL)
+
+    def check_head_fwd(self, i, st, rec, tag):
+        w, _ = stage_weights(st)
+        logit = (nchw(rec["x"], st.cin) * w).sum(dim=(1, 2, 3))
+        self.report(tag + " p", frob(f64(rec["p"]), torch.sigmoid(logit)), F32_TOL)
+
+    def check_head_bwd(self, i, st, rec, tag):
+        p = f64(rec["p"])
+        if rec["dp"] is not None:
+            dl = f64(rec["dp"]) * p * (1 - p)
+        else:                                   # BCE(p, target) + sigmoid backward, fused: d logit = gscale (p - t) / B
+            t0, t1, grp, gscale = rec["bce"]
+            Bg = p.numel() // grp
+            t = torch.full_like(p, t0)
+            t[Bg:] = t1
+            dl = gscale * (p - t) / Bg
+        w, _ = stage_weights(st)
+        x = nchw(rec["x"], st.cin)
+        if rec["dX"] is not None:
+            self.report(tag + " dX", frob(nchw(rec["dX"], st.cin), q(dl.reshape(-1, 1, 1, 1) * w)), FLIP_TOL)
+        if rec["gw"] is not None:
+            self.grad(i, "w", rec["gw"], (dl.reshape(-1, 1, 1, 1) * x).sum(0, keepdim=True), rec["acc"], tag + " dW")
+
+    def check_bn_bwd(self, i, st, rec, tag):
+        if st.bn is None:
+            return
+        co = f64(rec["coeffs"])
+        G_ = co.shape[0]
+        Y = nchw(rec["Y"], st.cout)
+        dA = nchw(rec["dA"], st.cout)
+        Yg, dAg = Y.reshape(G_, -1, *Y.shape[1:]), dA.reshape(G_, -1, *Y.shape[1:])
+        mean, invstd = co[:, 0].reshape(G_, 1, -1, 1, 1), co[:, 1].reshape(G_, 1, -1, 1, 1)
+        z = co[:, 2].reshape(G_, 1, -1, 1, 1) * Yg + co[:, 3].reshape(G_, 1, -1, 1, 1)
+        slope = st.slope if st.act == 2 else (0.0 if st.act == 1 else 1.0)
+        dz = torch.where(z > 0, dAg, dAg * slope)
+        xh = (Yg - mean) * invstd
+        n = Yg.shape[1] * Yg.shape[3] * Yg.shape[4]
+        s1 = dz.sum(dim=(1, 3, 4), keepdim=True)
+        s2 = (dz * xh).sum(dim=(1, 3, 4), keepdim=True)
+        a = f64(st.bn.weight.detach()).reshape(1, 1, -1, 1, 1) * invstd
+        dyr = (a * (dz - s1 / n - xh * s2 / n)).reshape(Y.shape)
+        self.report(tag + " dY", frob(nchw(rec["dY"], st.cout), q(dyr)), FLIP_TOL)
+        if rec["dgamma"] is not None:           # summed over the groups of a grouped pass, accumulated over passes
+            self.grad(i, "dgamma", rec["dgamma"], s2.sum(0).flatten(), rec["acc_bn"], tag + " dgamma")
+            self.grad(i, "dbeta", rec["dbeta"], s1.sum(0).flatten(), rec["acc_bn"], tag + " dbeta")
+
+    def check_wgrad(self, i, st, rec, tag):
+        w, _ = stage_weights(st)
+        if st.kind == "linear2":
+            x = nchw(rec["x"], st.cin).flatten(1)
+            dy = f64(rec["dY"]).reshape(x.shape[0], -1)[:, :st.cout]
+            self.grad(i, "w", torch.cat([rec["gw"], rec["gw2"]], 0), dy.t() @ x, rec["acc"], tag + " dW")
+            # the fused [fc_mu | fc_logvar] bias gradient: column sums of the stored dY
+            self.grad(i, "b", torch.cat([rec["gb"], rec["gb2"]], 0), dy.sum(0), rec["acc"], tag + " db")
+            return
+        x = nchw(rec["x"], st.cin)
+        wv = w.clone().requires_grad_(True)
+        dy = nchw(rec["dY"], st.cout)
+        stage_fn(st, wv, None, x).backward(dy)
+        self.grad(i, "w", rec["gw"], wv.grad, rec["acc"], tag + " dW")
+        if rec["gb"] is not None:
+            if st.bn is not None:
+                # a conv bias in front of a train-mode BatchNorm has the exact gradient 0 (engine.py _param_grads)
+                self.report(tag + " db (exact 0)", float(rec["gb"].abs().max()), 0.0)
             else:
-                if st.kind == "linear2":
-                    dy = rec["dY"].double().cpu().reshape(rec["dY"].shape[0], -1)[:, :st.cout]
-                    dxr = (dy @ w).reshape(dy.shape[0], st.cin, st.hin, st.hin)
-                else:
-                    xz = torch.zeros(rec["dX"].shape[0], st.cin, st.hin, st.hin, dtype=torch.float64, requires_grad=True)
-                    out = stage_fn(st, w, None, xz)
-                    out.backward(nchw(rec["dY"], st.cout))
-                    dxr = xz.grad
-                if rec["mask"] is not None:
-                    # the activation backward of the BatchNorm-less stage below, fused into this launch's epilogue: it
-                    # multiplies the tile AFTER its bf16 rounding (conv_gemm.hip mask_segment) -- two roundings where the slope applies
-                    ym, mact, mslope = rec["mask"]
-                    ymf = nchw(ym, st.cin)
-                    dxr = q(dxr)
-                    dxr = torch.where(ymf > 0, dxr, dxr * (mslope if mact == 2 else 0.0))
-                report(tag + " dX", frob(nchw(rec["dX"], st.cin), q(dxr)), FLIP_TOL)
+                self.grad(i, "b", rec["gb"], dy.sum(dim=(0, 2, 3)), rec["acc"], tag + " db")
+
+    def check_dgrad(self, i, st, rec, tag):
+        w, _ = stage_weights(st)
+        if st.kind == "linear2":
+            dy = f64(rec["dY"]).reshape(rec["dY"].shape[0], -1)[:, :st.cout]
+            dxr = (dy @ w).reshape(dy.shape[0], st.cin, st.hin, st.hin)
+        else:
+            xz = torch.zeros(rec["dX"].shape[0], st.cin, st.hin, st.hin, dtype=torch.float64, device=REF,
+                             requires_grad=True)
+            stage_fn(st, w, None, xz).backward(nchw(rec["dY"], st.cout))
+            dxr = xz.grad
+        if rec["mask"] is not None:
+            # the activation backward of the BatchNorm-less stage below, fused into this launch's epilogue: it
+            # multiplies the tile AFTER its bf16 rounding (conv_gemm.hip mask_segment) -- two roundings where the slope
+            # applies (DESIGN.md section 5)
+            ym, mact, mslope = rec["mask"]
+            ymf = nchw(ym, st.cin)
+            dxr = q(dxr)
+            dxr = torch.where(ymf > 0, dxr, dxr * (mslope if mact == 2 else 0.0))
+        self.report(tag + " dX", frob(nchw(rec["dX"], st.cin), q(dxr)), FLIP_TOL)
 
 
-def test_every_stage_of_the_bf16_iteration_equals_exact_arithmetic_on_its_own_stored_inputs():
-    S, B = 64, 128
-    e, g, d, tr = build(S, dtype="bf16", lr=0.0)       # lr = 0: the weights every pass used are the ones read back below
-    for m in (e, g, d):
+def selections(nets, B):
+    """Kernel selections visible from the host, per stage and pass -> (printable lines, shape-independent keys).
+    Keys: ('gg', pass, kind, tile rows, output columns <= 32) for the gather-GEMM launches (<= 32 columns: the
+    four-phase kernels of conv_phase4.hpp), ('tn', pass, channels) for the edge-layer GEMM + col2im kernel,
+    ('edge_wg', channel tiles of 16) for the edge weight gradient (edge_wgrad_kernel<CT>), ('fp8', kind) for
+    forward GEMMs on e4m3 operands."""
+    Gm = importlib.import_module(PKG + ".geometry")
+    ops = importlib.import_module(PKG + ".ops")
+    lines, keys = [], set()
+    for name, m in nets:
+        eng = m._engine
+        packs = eng._ensure_packed()
+        for i, st in enumerate(eng.stages):
+            if st.kind == "head":
+                continue
+            for what in ("fprop", "dgrad"):
+                tn = eng.tn(i, B, what)
+                if tn is not None:
+                    lines.append(f"{name}.{i} {what}: tnconv C={tn[0].C} N={tn[0].N}")
+                    keys.add(("tn", what, tn[0].C))
+                    continue
+                gg, _ = eng.spec(i, B, what)
+                fp8 = what == "fprop" and eng.fp8_ok(i)
+                kdt = Gm.FP8 if fp8 else eng.dtype
+                xin = torch.empty(gg.B * gg.IH * gg.IW * gg.IC, dtype=ops.TORCH_DT[kdt], device=DEV)
+                bm = ops.gather_gemm_tile_m(gg, xin, packs[i]["fprop8" if fp8 else what], kdt)
+                lines.append(f"{name}.{i} {what}: gather-GEMM {'fp8' if fp8 else 'bf16'} tile rows {bm} N={gg.N} "
+                             f"phases={gg.nphase}")
+                keys.add(("gg", what, st.kind, bm, gg.N <= 32))
+                if fp8:
+                    keys.add(("fp8", st.kind))
+            ew = eng.edge_wg(i, B)
+            if ew is not None:
+                lines.append(f"{name}.{i} wgrad: edge_wgrad C={ew.C} (channel tiles {ew.C // 16})")
+                keys.add(("edge_wg", ew.C // 16))
+    return lines, keys
+
+
+def run_layerwise(S, B, dtype, min_lines, onepass=False, before=None):
+    """One eager iteration with tracing on, every stage checked; returns the shape-independent selection keys.
+    before(nets): called with the freshly built networks before the iteration runs."""
+    e, g, d, tr = build(S, dtype=dtype, lr=0.0)        # lr = 0: the weights every pass used are the ones read back below
+    nets = (("E", e), ("G", g), ("D", d))
+    if before is not None:
+        before(nets)
+    for _, m in nets:
         m._engine.trace = []
     dev_in = [t.to(DEV) for t in make_inputs(B, S, 1234)]
     tr.train_step(dev_in[0], 60, *dev_in[1:])
     torch.cuda.synchronize()
-    lines, worst = [], []
+    if onepass:
+        assert not importlib.import_module(PKG + ".ops").grid_sync_error(DEV), "a grid-wide wait of bn_onepass gave up"
+    lines, worst, nparts = [], [], []
 
     def report(tag, err, tol):
         lines.append(f"{tag:34s} {err:.2e} (bound {tol:.0e})")
         if not err <= tol:
             worst.append(lines[-1])
 
+    t0 = time.time()
     try:
-        for name, m in (("E", e), ("G", g), ("D", d)):
-            check_engine(name, m._engine, report)
+        for name, m in nets:
+            trace, m._engine.trace = m._engine.trace, None
+            nparts += [f"{name}.{r['stage']} nparts={r['nparts']}" for r in trace if r["what"] == "fwd" and r["nparts"]]
+            LayerCheck(name, m._engine, report, (dev_in[3], tr.sigma)).run(trace)
+            del trace
     finally:
-        for m in (e, g, d):
+        for _, m in nets:
             m._engine.trace = None
+    sel_lines, keys = selections(nets, B)
+    print(f"\nS={S} B={B} {dtype}: {len(lines)} checks in {time.time() - t0:.1f} s")
     print("\n".join(lines))
-    assert len(lines) >= 120, len(lines)
+    print("\n".join(sel_lines + sorted(set(nparts))))
+    assert len(lines) >= min_lines, len(lines)
+    assert any(" noisy image " in ln for ln in lines), "the Generator's noisy output was not checked"
     assert not worst, "stages outside their bound:\n" + "\n".join(worst)
+    return keys
+
+
+@functools.lru_cache(maxsize=None)
+def _s64_keys():
+    e, g, d, _ = build(64, dtype="bf16", lr=0.0)
+    return frozenset(selections((("E", e), ("G", g), ("D", d)), 128)[1])
+
+
+def test_every_stage_of_the_bf16_iteration_equals_exact_arithmetic_on_its_own_stored_inputs():
+    run_layerwise(64, 128, "bf16", 189)
+
+
+@pytest.mark.parametrize("S,B,dtype,min_lines", [(128, 64, "bf16", 225), (256, 32, "bf16", 261), (256, 32, "fp8", 291)],
+                         ids=["S128-B64-bf16", "S256-B32-bf16", "S256-B32-fp8"])
+def test_layerwise_at_the_larger_benchmarked_configurations(S, B, dtype, min_lines):
+    """BASELINE configs C3 / C5: tile shapes, four-phase kernels, edge-layer kernels and (fp8) e4m3 operands that S=64
+    never selects, each checked inside the real iteration."""
+    keys = run_layerwise(S, B, dtype, min_lines)
+    new = keys - _s64_keys()
+    print("selections S=64 never makes:", sorted(new))
+    assert new, "this configuration selects nothing that S=64, B=128 does not"
+    if dtype == "fp8":
+        assert any(k[0] == "fp8" for k in keys)
+
+
+GENERIC = {"VG_GG_PATCH": 0, "VG_GG_DMA": 0, "VG_GG_PHASE4": 0, "VG_WG_SPEC": 0, "VG_EDGE": 0, "VG_BN_FUSED_FWD": 0,
+           "VG_SPLITK_BIGK": 0}
+
+
+@pytest.mark.parametrize("S,B,switches,min_lines", [
+    pytest.param(64, 128, {"VG_SPLITK_GENERAL": 1}, 189, id="splitk-general-S64"),
+    pytest.param(256, 32, {"VG_SPLITK_GENERAL": 1}, 261, id="splitk-general-S256"),
+    pytest.param(64, 128, {"VG_BN_ONEPASS": 1}, 189, id="bn-onepass-S64"),
+    pytest.param(64, 128, GENERIC, 190, id="generic-paths-S64"),
+])
+def test_layerwise_through_switched_paths(S, B, switches, min_lines, vg_switch, monkeypatch):
+    """The opt-in kernels (split K for phased / statistics launches, the one-launch BatchNorm backward with its grid-wide
+    exchange) and the fallbacks (register-staged and non-patch gather-GEMM, no four-phase kernel, one-role wgrad, no
+    edge-layer kernels, separate BatchNorm finalize, 64 x 64 long-K data gradients) through a whole eager iteration."""
+    eng_mod = importlib.import_module(PKG + ".engine")
+    for k, v in switches.items():
+        vg_switch(k, v)
+    if switches.get("VG_EDGE", 1) == 0:                 # engine.py reads VG_EDGE once, at import
+        monkeypatch.setattr(eng_mod, "_EDGE", False)
+        monkeypatch.setattr(eng_mod, "_EDGE_WGRAD", False)
+    def onepass_taken(nets):
+        lib = importlib.import_module(PKG + "._lib").load()
+        Gm = importlib.import_module(PKG + ".geometry")
+        taken = [lib.vg_bn_backward_onepass_supported(B * grp * st.hout * st.hout, st.cout, grp, Gm.BF16)
+                 for name, m in nets if name != "E" for grp in ((2,) if name == "D" else (1,))
+                 for st in m._engine.stages if st.bn is not None]
+        assert any(t == 1 for t in taken), "no BatchNorm backward of this iteration takes the one-launch kernel"
+
+    onepass = "VG_BN_ONEPASS" in switches
+    keys = run_layerwise(S, B, "bf16", min_lines, onepass=onepass, before=onepass_taken if onepass else None)
+    if switches.get("VG_EDGE", 1) == 0:
+        assert not any(k[0] in ("tn", "edge_wg") for k in keys)
+
+
+@pytest.mark.parametrize("S,B,dtype", [(64, 128, "bf16"), (128, 64, "bf16"), (256, 32, "fp8")],
+                         ids=["S64-B128-bf16", "S128-B64-bf16", "S256-B32-fp8"])
+def test_graph_replay_equals_eager_at_the_benchmarked_configurations(S, B, dtype):
+    """train_step_graphed (eager warm-up, capture + replay, replay) == train_step at lr > 0, bit for bit: losses, the three
+    flat parameter buffers, BatchNorm running statistics.  The eager layerwise checks above then hold for the replayed
+    iteration bench.py times."""
+    res = []
+    for graphed in (False, True):
+        e, g, d, tr = build(S, dtype=dtype, lr=2e-4)
+        fn = tr.train_step_graphed if graphed else tr.train_step
+        losses = []
+        for step in range(3):
+            real, ez, er, ec = (t.to(DEV) for t in make_inputs(B, S, 9100 + step))
+            losses.append(fn(real, 60, ez, er, ec)[:5].clone())
+        torch.cuda.synchronize()
+        bn = {f"{n}.{k}": v.clone() for n, m in (("E", e), ("G", g), ("D", d))
+              for k, v in m.state_dict().items() if "running" in k or "num_batches" in k}
+        res.append((torch.stack(losses), tr.opt_E.flat_p.clone(), tr.opt_G.flat_p.clone(), tr.opt_D.flat_p.clone(), bn))
+        if graphed:
+            assert tr._graph is not None and len(tr._graph[1]) == 1
+        del e, g, d, tr
+    for what, a, b in zip(("losses", "E params", "G params", "D params"), res[0][:4], res[1][:4]):
+        assert torch.equal(a, b), what
+    assert res[0][4].keys() == res[1][4].keys() and len(res[0][4]) > 0
+    for k in res[0][4]:
+        assert torch.equal(res[0][4][k], res[1][4][k]), k

@@ -365,6 +365,8 @@ class StackEngine:
                 K = st.hin * st.hin * G.padc(st.cin, dt)
                 p = ops.dot_sigmoid_forward(a, packs[i]["fprop"], B, K, dt)
                 ctx.append({"x": a, "p": p})
+                if self.trace is not None:
+                    self.trace.append(dict(stage=i, what="head_fwd", x=a.clone(), p=p.clone(), B=B))
                 a = p
                 continue
             if self.tn(i, B, "fprop") is not None:
@@ -397,9 +399,11 @@ class StackEngine:
             # a layer without BatchNorm gets its (Leaky)ReLU in the conv epilogue: "Y" is then the ACTIVATED output,
             # which carries the same sign information the activation's backward needs (slope >= 0)
             fuse_act = st.bn is None and st.act != VG_ACT_NONE
+            x8 = None
             if self.fp8_ok(i):
                 # e4m3 copy of the input activation (elementwise, same NHWC layout), block-scaled fp8 MFMA, bf16 output
-                Y, stats, nparts = ops.gather_gemm(gg, a8 if a8 is not None else ops.cast_fp8(a), packs[i]["fprop8"], G.FP8,
+                x8 = a8 if a8 is not None else ops.cast_fp8(a)
+                Y, stats, nparts = ops.gather_gemm(gg, x8, packs[i]["fprop8"], G.FP8,
                                                    bias=packs[i]["bias"],
                                                    want_stats=epilogue_stats, alg=st.alg(B, dt),
                                                    act=(st.act, st.slope) if fuse_act else None)
@@ -443,7 +447,8 @@ class StackEngine:
                 ctx.append({"x": a, "Y": Y, "coeffs": coeffs, "rows": rows, "OC": OC})
             if self.trace is not None:
                 self.trace.append(dict(stage=i, what="fwd", x=a.clone(), Y=Y.clone(), A=out.clone(), groups=groups, B=B,
-                                       coeffs=None if coeffs is None else coeffs.clone(), fused_act=fuse_act))
+                                       coeffs=None if coeffs is None else coeffs.clone(), fused_act=fuse_act,
+                                       x8=None if x8 is None else x8.clone(), nparts=nparts))
             a, a8 = out, out8
         if train and any(st.bn is not None for st in self.stages):
             self.pending_bn_ticks += groups
@@ -489,29 +494,37 @@ class StackEngine:
                 gw, acc = sink.get(st.conv.weight) if param_grads else (None, False)
                 dA = ops.head_backward(c["p"], c["x"], packs[i]["fprop"], B // grp, grp, t0, t1, gscale, slot, acc_loss, gw,
                                        acc, K, G.padc(st.cin, dt), st.hin * st.hin, dt, want_dx)
+                if self.trace is not None:
+                    self.trace.append(dict(stage=i, what="head_bwd", p=c["p"].clone(), x=c["x"].clone(), dp=None,
+                                           bce=(t0, t1, grp, gscale), dX=None if dA is None else dA.clone(), acc=acc,
+                                           gw=None if gw is None else gw.clone()))
                 if param_grads and on_grads is not None:
                     on_grads(i)
                 continue
             if st.kind == "head":
                 K = st.hin * st.hin * G.padc(st.cin, dt)
                 dx, dlogit = ops.dot_sigmoid_backward(c["p"], dA, packs[i]["fprop"], B, K, dt, want_dx, c["x"])
+                gw, acc = None, False
                 if param_grads:
                     gw, acc = sink.get(st.conv.weight)
                     ops.dot_wgrad(c["x"], dlogit, gw, B, K, G.padc(st.cin, dt), st.hin * st.hin, acc, dt)
                     if on_grads is not None:
                         on_grads(i)
+                if self.trace is not None:
+                    self.trace.append(dict(stage=i, what="head_bwd", p=c["p"].clone(), x=c["x"].clone(), dp=dA.clone(),
+                                           bce=None, dX=None if dx is None else dx.clone(), acc=acc,
+                                           gw=None if gw is None else gw.clone()))
                 dA = dx
                 continue
             Y, rows, OC = c["Y"], c["rows"], c["OC"]
             yshape = c["Yshape"] if Y is None else Y.shape
             dA = dA.view(yshape) if dA.shape != yshape else dA
+            gg_, gb_, acc_g = None, None, False
             if st.bn is not None:
                 if param_grads:
                     gg_, acc_g = sink.get(st.bn.weight)
                     gb_, acc_b = sink.get(st.bn.bias)
                     assert acc_g == acc_b
-                else:
-                    gg_, gb_, acc_g = None, None, False
                 dY = ops.bn_act_backward(Y, dA, c["coeffs"], rows, OC, rows, st.bn.weight.detach(), st.act, st.slope,
                                          gg_, gb_, acc_g, dt, sync=self.bn_sync)
             elif st.act != VG_ACT_NONE and not masked:
@@ -520,7 +533,9 @@ class StackEngine:
                 dY = dA                                     # no activation, or its backward was fused into the dgrad above
             if self.trace is not None:
                 self.trace.append(dict(stage=i, what="bn_bwd", dA=dA.clone(), dY=dY.clone(), Y=None if Y is None else Y.clone(),
-                                       coeffs=None if c["coeffs"] is None else c["coeffs"].clone(), masked_in=masked))
+                                       coeffs=None if c["coeffs"] is None else c["coeffs"].clone(), masked_in=masked,
+                                       dgamma=None if gg_ is None else gg_.clone(), dbeta=None if gb_ is None else gb_.clone(),
+                                       acc_bn=acc_g))
             masked = False
             if param_grads:
                 acc_before = st.conv.weight.grad is not None and not getattr(st.conv.weight, "_vg_fresh", False)
@@ -530,7 +545,9 @@ class StackEngine:
                 if self.trace is not None:
                     self.trace.append(dict(stage=i, what="wgrad", dY=dY.clone(), x=c["x"].clone(), acc=acc_before,
                                            gw=None if st.conv.weight.grad is None else st.conv.weight.grad.detach().clone(),
-                                           gw2=None if (st.conv2 is None or st.conv2.weight.grad is None) else st.conv2.weight.grad.detach().clone()))
+                                           gw2=None if (st.conv2 is None or st.conv2.weight.grad is None) else st.conv2.weight.grad.detach().clone(),
+                                           gb=None if not st.has_bias or st.conv.bias.grad is None else st.conv.bias.grad.detach().clone(),
+                                           gb2=None if (st.conv2 is None or st.conv2.bias.grad is None) else st.conv2.bias.grad.detach().clone()))
             if want_dx and self.tn(i, B, "dgrad") is not None:
                 tnsp, _ = self.tn(i, B, "dgrad")            # image gradient below a narrow first Conv2d (edge layer)
                 dX, _ = ops.tnconv(tnsp, dY, packs[i]["tn_dgrad"], alg=st.alg(B, dt))
