@@ -48,13 +48,14 @@ extern "C" {
 #define VG_ACT_LRELU   2   /* nn.LeakyReLU(slope)    main_vae.py:25, gan_code.py:62-82 */
 #define VG_ACT_TANH    3   /* nn.Tanh()              gan_code.py:50 (vg_tnconv epilogue only) */
 
-#define VG_ABI_VERSION 10  /* 2: vg_pack_desc.tile_start, SyncBN / WGAN / data-path entry points; 3: in-kernel noise (vg_*_rng);
+#define VG_ABI_VERSION 11  /* 2: vg_pack_desc.tile_start, SyncBN / WGAN / data-path entry points; 3: in-kernel noise (vg_*_rng);
                              4: vg_bn_finalize_act_forward, vg_bn_backward_finalize_apply;
                              7: vg_bce_pair_forward_backward;
                              8: vg_head_backward; round-3 prune -- the opt-in experiments of ABI 5 / 6 that measured slower (input prologue of
                                 vg_tn_desc / vg_ew_desc, vg_gg_desc.bnb_*) are gone from the descriptors; vg_reload_switches;
                              9: vg_step_prologue, vg_adam_step(lr < 0);
-                             10 (round 4): vg_adam_apply replaces the lr < 0 overload of vg_adam_step (which now rejects it) */
+                             10 (round 4): vg_adam_apply replaces the lr < 0 overload of vg_adam_step (which now rejects it);
+                             11: degraded-pair data path: vg_gather_degrade_u8, vg_degrade_params, vg_rand_u01 */
 int vg_abi_version(void);
 /* The library reads its optional kernel-selection switches (VG_* environment variables, DESIGN.md "Runtime switches")
  * ONCE, when it is loaded; nothing on a launch path calls getenv.  A process that changes one of them afterwards
@@ -438,6 +439,49 @@ int vg_reparam_forward_rng(const void* mulv, const uint64_t* rng, int draw, void
 int vg_reparam_kl_backward_rng(const void* mulv, const float* lv_clamped, const uint64_t* rng, int draw,
                                const void* dz, float kl_scale, void* dmulv, int B, int L, int MP, int ZP,
                                int dtype, void* stream);
+/* ------------------------------------------------------------------------------------------
+ * Degraded pairs (dataset_code.py:13-65, CelebADatasetV0 with noise_max_std set: `return noisy_img, clean_img`).
+ * vg_gather_degrade_u8 assembles, in ONE pass over the resident u8 [N][H][W][C] set and idx[B]:
+ *   clean  f32 [B][C][H][W]: normalize != 0: (u/255 - 0.5)/0.5, bit-identical to vg_gather_normalize_u8;
+ *                            normalize == 0: u/255 (V0's ToTensor without Normalize);
+ *   noisy  f32 [B][C][H][W]: add_noise (:35-42) of clean, see below;
+ *   nhwc   (optional, NULL to skip) noisy again as the engine input [B][H][W][CP] in dtype (VG_F32 / VG_BF16, pad channels
+ *          zero, 16-byte aligned), bit-identical to vg_nchw_to_nhwc(noisy).
+ * Per image, in the reference's order, every f32 product / sum rounded on its own:
+ *   base  = (rect and the pixel lies in the image's rectangle) ? 2*f - 1 : clean      (f: fill uniform of that element)
+ *   noisy = min(max(base + (n * s) * noise_max_std, -1), 1)         (n ~ N(0,1) per element, ONE s ~ U[0,1) per image)
+ * The rectangle covers rows y .. y + rect_h - 1 and columns x .. x + rect_w - 1 in every channel; rect_h or rect_w == 0
+ * is an empty rectangle.  Its integer ranges are fixed on the host (data.degrade_bounds: python round(), as the
+ * reference): rect_h, rect_w in [min_size, max_size], x in [x0, x1 - rect_w), y in [y0, y1 - rect_h).  rect == 0: no
+ * rectangle, the six bounds are ignored.
+ *
+ * Random draws.  Philox4x32-10 exactly as for the in-kernel N(0,1) noise below: key = seed, and the counter word that
+ * carries the iteration there carries pos = pos0 + b here, the sample's POSITION IN THE EPOCH'S ORDER (not its batch slot):
+ * a sample's degradation does not depend on batch size, rank or world size.  seed and pos0 (< 2^56) travel by value.
+ * With e = c*H*W + h*W + w, the element's index within its image, and word(draw, i) = output word i & 3 of Philox block
+ * i >> 2 of that draw at (seed, pos):
+ *   draw VG_DRAW_DEGRADE_NORMAL: n = element e of what vg_randn(out, C*H*W, {seed, pos}, draw) materialises;
+ *   draw VG_DRAW_DEGRADE_FILL:   f = u01(word(draw, e)) -- a rectangle pixel uses the uniform AT ITS OWN index
+ *                                (vg_rand_u01(out, C*H*W, {seed, pos}, draw) materialises all of them);
+ *   draw VG_DRAW_DEGRADE_PARAMS: s = u01(word 0), rect_h = rint(word 1, min_size, max_size + 1),
+ *                                rect_w = rint(word 2, min_size, max_size + 1), x = rint(word 3, x0, x1 - rect_w),
+ *                                y = rint(word 4, y0, y1 - rect_h);
+ *   u01(w) = (w >> 8) * 2^-24 in [0, 1);   rint(w, lo, hi) = lo + (((uint64)(w >> 8) * (hi - lo)) >> 24) in [lo, hi).
+ * The three ids are outside 0..2, the draws of a training iteration.
+ * vg_rand_u01: the uniform twin of vg_randn: out[i] = u01(word(draw, i)) at rng = {seed, counter} (device memory).
+ * vg_degrade_params: out f32 [B][8] = {s, sigma = s * noise_max_std, rect_h, rect_w, x, y, 0, 0} of positions
+ * pos0 .. pos0 + B - 1 (rect == 0: the four geometry entries are 0); for inspection, plots and tests.
+ * idx outside [0, N) is clamped to 0 (the host validates).  VG_EINVAL for empty ranges or a rectangle outside the image.
+ * ---------------------------------------------------------------------------------------- */
+#define VG_DRAW_DEGRADE_NORMAL 16
+#define VG_DRAW_DEGRADE_FILL   17
+#define VG_DRAW_DEGRADE_PARAMS 18
+int vg_gather_degrade_u8(const uint8_t* images, int64_t N, const int64_t* idx, int B, int C, int H, int W, uint64_t seed,
+                         uint64_t pos0, float noise_max_std, int rect, int normalize, int min_size, int max_size, int x0,
+                         int x1, int y0, int y1, float* clean, float* noisy, void* nhwc, int CP, int dtype, void* stream);
+int vg_degrade_params(uint64_t seed, uint64_t pos0, int B, float noise_max_std, int rect, int H, int W, int min_size,
+                      int max_size, int x0, int x1, int y0, int y1, float* out, void* stream);
+int vg_rand_u01(float* out, int64_t n, const uint64_t* rng, int draw, void* stream);
 /* hipMemsetAsync(p, 0, nbytes) on the stream: optimizer.zero_grad() (vaegan_code.py:103,131-132) over a flat buffer. */
 int vg_memset_zero(void* p, int64_t nbytes, void* stream);
 /* bf16 -> OCP e4m3fn, elementwise: y[i] = fp8(x[i] * 2^shift).  The fp8 copies of activations (shift 0) and of the

@@ -10,7 +10,7 @@ reference-shaped step function).
 from . import data  # noqa: F401
 from . import geometry  # noqa: F401
 from .ddp import GradReducer
-from .denoise import denoise_eval, validation_epoch
+from .denoise import denoise_eval, paired_test_epoch, validation_epoch
 from .graphed import graphed
 from .losses import BCELoss, MSELoss
 from .nets import ConvBlock, Discriminator, Encoder, Generator, weights_init
@@ -20,4 +20,4 @@ from .trainer import LOSS_NAMES, VAEGANTrainer
 from .utils import configure_seed
 
 __all__ = ["ConvBlock", "Encoder", "Generator", "Discriminator", "weights_init", "Adam", "BCELoss", "MSELoss",
-           "VAEGANTrainer", "LOSS_NAMES", "configure_seed", "geometry", "denoise_eval", "validation_epoch", "GradReducer", "data", "VAETrainer", "DCGANTrainer", "WGANTrainer", "graphed"]
+           "VAEGANTrainer", "LOSS_NAMES", "configure_seed", "geometry", "denoise_eval", "validation_epoch", "paired_test_epoch", "GradReducer", "data", "VAETrainer", "DCGANTrainer", "WGANTrainer", "graphed"]

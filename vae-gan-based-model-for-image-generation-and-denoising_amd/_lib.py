@@ -16,7 +16,7 @@ VG_F32, VG_BF16, VG_FP8 = 0, 1, 2
 VG_FP8_WSHIFT = 6
 VG_ACT_NONE, VG_ACT_RELU, VG_ACT_LRELU, VG_ACT_TANH = 0, 1, 2, 3
 VG_MAX_PHASE = 4
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 VG_ENOSUP = -3
 _ERR = {-1: "VG_EINVAL (bad shape/size/flag)", -2: "VG_EALIGN (16-byte contract violated)",
@@ -79,7 +79,7 @@ class PackDesc(Structure):
 
 
 # name -> (restype, argtypes); every symbol include/vaegan_hip.h declares
-_P, _F, _I, _L, _D = c_void_p, c_float, c_int, c_int64, c_double
+_P, _F, _I, _L, _D, _U = c_void_p, c_float, c_int, c_int64, c_double, ctypes.c_uint64
 SIGNATURES = {
     "vg_abi_version": (c_int, []),
     "vg_launch_count": (ctypes.c_uint64, []),
@@ -149,6 +149,10 @@ SIGNATURES = {
     "vg_mse_partial": (c_int, [_P, _P, _L, _F, _P, _P, _I, POINTER(c_int), _P]),
     "vg_kl_forward_mse_final": (c_int, [_P, _P, _I, _I, _I, _F, _P, _P, _I, _L, _P, _I, _P]),
     "vg_randn": (c_int, [_P, _L, _P, _I, _P]),
+    "vg_rand_u01": (c_int, [_P, _L, _P, _I, _P]),
+    "vg_gather_degrade_u8": (c_int, [_P, _L, _P, _I, _I, _I, _I, _U, _U, _F, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I,
+                                     _I, _P]),
+    "vg_degrade_params": (c_int, [_U, _U, _I, _F, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "vg_nchw_to_nhwc_rng": (c_int, [_P, _P, _I, _F, _P, _I, _I, _I, _I, _I, _I, _P]),
     "vg_nhwc_tanh_to_nchw_noisy_rng": (c_int, [_P, _P, _P, _I, _F, _P, _I, _I, _I, _I, _I, _I, _P]),
     "vg_reparam_forward_rng": (c_int, [_P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P]),

@@ -15,9 +15,12 @@ from . import ops
 
 @torch.no_grad()
 def denoise_eval(encoder, decoder, img: torch.Tensor, sigma: float = 0.05, eps: Optional[torch.Tensor] = None,
-                 eps_z: Optional[torch.Tensor] = None, alpha_kl: float = 0.1) -> Dict[str, object]:
+                 eps_z: Optional[torch.Tensor] = None, alpha_kl: float = 0.1,
+                 noisy: Optional[torch.Tensor] = None) -> Dict[str, object]:
     """img: [B,C,S,S] float32 on the MI355X in [-1,1].  Returns the noisy input, the reconstruction (both NCHW
     f32) and a dict of device scalars + host floats: recon_loss, kl_loss (sum), val_loss, psnr, ssim.
+    noisy: an already degraded input batch (the ``noisy`` half of a data.DeviceLoader pair) used INSTEAD of
+    clamp(img + sigma*eps): sigma / eps are then ignored, img is the clean target.
     The caller puts encoder / decoder in eval mode (vaegan_code.py:147-148) -- or not: BatchNorm follows
     module.training exactly as in the reference."""
     if not img.is_cuda:
@@ -26,12 +29,18 @@ def denoise_eval(encoder, decoder, img: torch.Tensor, sigma: float = 0.05, eps: 
     B, C = img.shape[0], img.shape[1]
     L = encoder.latent_dim
     img = img.contiguous()
-    if eps is None or eps_z is None:
+    if (eps is None and noisy is None) or eps_z is None:
         ns = ops.default_noise(img.device)                   # HIP Philox draws keyed by torch's device seed
         ns.advance()
-        eps = ns.randn(tuple(img.shape), 0) if eps is None else eps
+        eps = ns.randn(tuple(img.shape), 0) if eps is None and noisy is None else eps
         eps_z = ns.randn((B, L), 1) if eps_z is None else eps_z
-    noisy_h, noisy = ops.noisy_clamp_to_nhwc(img, eps, sigma, G.padc(C, dt), dt)
+    if noisy is not None:
+        if not noisy.is_cuda or noisy.shape != img.shape:
+            raise RuntimeError("denoise_eval: noisy must be a device batch of img's shape")
+        noisy = noisy.contiguous()
+        noisy_h = ops.nchw_to_nhwc(noisy, G.padc(C, dt), dt)
+    else:
+        noisy_h, noisy = ops.noisy_clamp_to_nhwc(img, eps, sigma, G.padc(C, dt), dt)
     mulv, _ = encoder._engine.forward(noisy_h, B, encoder.training, keep=False)
     mulv = mulv.view(B, -1)
     z, lvc = ops.reparam_forward(mulv, eps_z, L, G.padc(decoder.nz, dt), dt)
@@ -109,3 +118,79 @@ def validation_epoch(encoder, decoder, loader: Iterable[torch.Tensor], n_samples
     return {"val_loss": val_sum / n, "ssim": ssim_sum / seen,
             "psnr": float("inf") if mse01 == 0 else 10.0 * math.log10(1.0 / mse01),
             "recon_loss": mse_sum / seen, "kl_loss": kl_sum / batches, "samples": seen, "batches": batches}
+
+
+@torch.no_grad()
+def paired_test_epoch(encoder, decoder, loader: Iterable, n_samples: Optional[int] = None, noise_fn=None) -> Dict[str, float]:
+    """The reference's test pass over (noisy, clean) pairs, main_vae.py:251-266:
+
+        encoder.eval(); decoder.eval()                                                 (:251-252)
+        for noisy, clean in test_loader:   mu, logvar = E(noisy); z = mu + exp(logvar/2) * randn; recon = G(z)
+            test_loss += mse_SUM(recon, clean) + KL_sum                                 (:262-264)
+        test_loss /= len(test_loader.dataset)                                          (:266)
+
+    and, beyond the reference, SSIM and PSNR (on the [0,1]-rescaled images, as validation_epoch) of ``recon`` vs ``clean``
+    AND of ``noisy`` vs ``clean``, so the caller sees what the model gained over its input.  The metrics assume images
+    in [-1, 1] (``Degrade(normalize=True)``).
+    loader yields device pairs (data.DeviceLoader with a ``Degrade``).  A loader that offers ``want_nhwc`` is asked to
+    write ``noisy`` in the Encoder's input layout in the same kernel pass (no separate layout pass per batch).
+    noise_fn(i, noisy) -> eps_z [b, L] injects the reparameterisation draw of batch i (parity tests); by default it is
+    generated on the device.  n_samples defaults to the number of images seen.
+    Deviation: the engine's reparameterisation clamps logvar to [-10, 10] (as the training path, vaegan_code.py:76);
+    :258-259 do not.  Inert for |logvar| < 10.
+    Accumulation stays on the device; ONE host sync at the end.  Returns python floats: test_loss, recon_loss (mean
+    squared error per element), kl_loss (mean KL sum per sample), ssim, psnr, ssim_noisy, psnr_noisy, samples, batches."""
+    encoder.eval(), decoder.eval()                                                   # :251-252
+    dev = next(encoder.parameters()).device
+    dt, L = encoder._dt, encoder.latent_dim
+    # [sum(mse_sum + kl), sum(b * ssim(recon)), sum(b * mse_mean(recon)), sum(kl), sum(b * ssim(noisy)), sum(b * mse_mean(noisy))]
+    acc = ops.zeros_f32(6, dev)
+    seen = batches = numel = 0
+    offers = hasattr(loader, "want_nhwc") and getattr(loader, "degrade", None) is not None and loader.degrade.pairs
+    if offers:
+        loader.want_nhwc(G.padc(loader.dataset.image_shape[0], dt), dt)
+    try:
+        for i, (noisy, clean) in enumerate(loader):
+            if not (noisy.is_cuda and clean.is_cuda):
+                raise RuntimeError("paired_test_epoch needs device pairs (data.DeviceLoader); there is no CPU path")
+            noisy, clean = noisy.contiguous(), clean.contiguous()
+            b, C = clean.shape[0], clean.shape[1]
+            noisy_h = loader.last_nhwc if offers else ops.nchw_to_nhwc(noisy, G.padc(C, dt), dt)
+            eps_z = noise_fn(i, noisy) if noise_fn is not None else None
+            if eps_z is None:
+                ns = ops.default_noise(dev)
+                ns.advance()
+                eps_z = ns.randn((b, L), 1)
+            mulv, _ = encoder._engine.forward(noisy_h, b, False, keep=False)         # :258
+            mulv = mulv.view(b, -1)
+            z, lvc = ops.reparam_forward(mulv, eps_z, L, G.padc(decoder.nz, dt), dt)  # :259
+            pre, _ = decoder._engine.forward(z, b, False, keep=False)
+            recon = ops.nhwc_to_nchw(pre, decoder.nc, dt, apply_tanh=True)           # :260
+            scal = torch.empty(3, dtype=torch.float32, device=dev)
+            ops.mse_forward_backward(recon, clean, 1.0, scal[0:1], False)            # mean; * numel = :262's sum
+            ops.kl_forward(mulv, lvc, L, 1.0, dt, out=scal[1:2])                     # :263
+            ops.mse_forward_backward(noisy, clean, 1.0, scal[2:3], False)
+            ssim_r, ssim_n = ops.ssim(recon, clean), ops.ssim(noisy, clean)
+            ops.axpy(acc[0:1], scal[0:1], float(clean.numel()), out=acc[0:1])
+            ops.axpy(acc[0:1], scal[1:2], 1.0, out=acc[0:1])                         # :264
+            ops.axpy(acc[1:2], ssim_r, float(b), out=acc[1:2])
+            ops.axpy(acc[2:3], scal[0:1], float(b), out=acc[2:3])
+            ops.axpy(acc[3:4], scal[1:2], 1.0, out=acc[3:4])
+            ops.axpy(acc[4:5], ssim_n, float(b), out=acc[4:5])
+            ops.axpy(acc[5:6], scal[2:3], float(b), out=acc[5:6])
+            seen += b
+            batches += 1
+    finally:
+        if offers:
+            loader.want_nhwc(None)
+    if batches == 0:
+        raise RuntimeError("paired_test_epoch: the loader yielded no batch")
+    tot, ssim_sum, mse_sum, kl_sum, ssim_n_sum, mse_n_sum = (float(v) for v in acc.tolist())   # the one host sync
+    n = seen if n_samples is None else int(n_samples)
+
+    def psnr(mse):
+        mse01 = mse / 4.0                                                  # ((a+1)/2 - (b+1)/2)^2 = (a-b)^2 / 4
+        return float("inf") if mse01 == 0 else 10.0 * math.log10(1.0 / mse01)
+    return {"test_loss": tot / n, "recon_loss": mse_sum / seen, "kl_loss": kl_sum / seen, "ssim": ssim_sum / seen,
+            "psnr": psnr(mse_sum / seen), "ssim_noisy": ssim_n_sum / seen, "psnr_noisy": psnr(mse_n_sum / seen),
+            "samples": seen, "batches": batches}

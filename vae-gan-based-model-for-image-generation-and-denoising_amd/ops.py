@@ -679,6 +679,80 @@ def gather_normalize_u8(images_u8, idx, out=None):
     return y
 
 
+# draw ids of the degraded-pair data path (include/vaegan_hip.h "Degraded pairs"; 0..2 belong to the training iteration)
+DRAW_DEGRADE_NORMAL, DRAW_DEGRADE_FILL, DRAW_DEGRADE_PARAMS = 16, 17, 18
+_NO_BOUNDS = (0, 0, 0, 0, 0, 0)
+
+
+def rand_u01(n: int, state: torch.Tensor, draw: int, out=None) -> torch.Tensor:
+    """U[0,1) twin of NoiseStream.randn: element i = (word i & 3 of Philox block i >> 2) >> 8, times 2^-24.
+    state: int64[2] on the device = {seed, counter}."""
+    _need_cuda(state, out)
+    y = out if out is not None else torch.empty(n, dtype=torch.float32, device=state.device)
+    L.check(L.load().vg_rand_u01(y.data_ptr(), n, state.data_ptr(), draw, L.stream_ptr()), "vg_rand_u01")
+    return y
+
+
+def _degrade_key(seed, pos0) -> None:
+    if not 0 <= int(seed) < 1 << 63 or not 0 <= int(pos0) < 1 << 56:
+        raise RuntimeError("degrade: seed must be in [0, 2^63) (an int64 {seed, position} state addresses the same draws) "
+                           "and pos0 in [0, 2^56)")
+
+
+def _degrade_bounds(rect, bounds):
+    if not rect:
+        return _NO_BOUNDS
+    if bounds is None or len(bounds) != 6:
+        raise RuntimeError("rect=True needs bounds = (min_size, max_size, x0, x1, y0, y1), see data.degrade_bounds")
+    return tuple(int(v) for v in bounds)
+
+
+def gather_degrade_u8(images_u8, idx, seed, pos0, noise_max_std, rect, normalize, bounds=None, out_clean=None,
+                      out_noisy=None, nhwc=None):
+    """(noisy, clean) pair batch in one pass over the resident u8 set (vg_gather_degrade_u8; dataset_code.py:35-65).
+    images_u8 [N,H,W,C] uint8, idx [B] int64, both on the device; seed / pos0: python ints, pos0 = position of idx[0]
+    in the epoch's order.  nhwc: None, or (CP, dtype) / a preallocated [B,H,W,CP] engine tensor that also receives
+    `noisy` in the Encoder's input layout.  -> (noisy NCHW f32, clean NCHW f32, nhwc tensor or None)."""
+    _need_cuda(images_u8, idx, out_clean, out_noisy, nhwc if isinstance(nhwc, torch.Tensor) else None)
+    if images_u8.dtype != torch.uint8 or idx.dtype != torch.int64 or images_u8.dim() != 4:
+        raise RuntimeError("gather_degrade_u8: images must be uint8 [N,H,W,C], idx int64 [B]")
+    N, H, W, C = images_u8.shape
+    B = idx.numel()
+    dev = images_u8.device
+    _degrade_key(seed, pos0)
+    clean = out_clean if out_clean is not None else torch.empty(B, C, H, W, dtype=torch.float32, device=dev)
+    noisy = out_noisy if out_noisy is not None else torch.empty(B, C, H, W, dtype=torch.float32, device=dev)
+    CP, dtype, y = 0, F32, None
+    if isinstance(nhwc, torch.Tensor):
+        y = nhwc
+        CP = y.shape[-1]
+        dtype = {v: k for k, v in TORCH_DT.items()}[y.dtype]
+        if tuple(y.shape) != (B, H, W, CP):
+            raise RuntimeError("gather_degrade_u8: nhwc must be [B,H,W,CP]")
+    elif nhwc is not None:
+        CP, dtype = nhwc
+        y = empty_act((B, H, W, CP), dtype, dev)
+    for t in (clean, noisy):
+        if tuple(t.shape) != (B, C, H, W) or t.dtype != torch.float32:
+            raise RuntimeError("gather_degrade_u8: outputs must be f32 [B,C,H,W]")
+    L.check(L.load().vg_gather_degrade_u8(images_u8.data_ptr(), N, idx.data_ptr(), B, C, H, W, int(seed), int(pos0),
+                                          float(noise_max_std), 1 if rect else 0, 1 if normalize else 0,
+                                          *_degrade_bounds(rect, bounds), clean.data_ptr(), noisy.data_ptr(), L.ptr(y), CP,
+                                          dtype, L.stream_ptr()), "vg_gather_degrade_u8")
+    return noisy, clean, y
+
+
+def degrade_params(seed, pos0, B, noise_max_std, rect, H, W, bounds=None, device="cuda") -> torch.Tensor:
+    """-> f32 [B,8] on the device: s, sigma = s*noise_max_std, rect_h, rect_w, x, y, 0, 0 of epoch positions
+    pos0 .. pos0+B-1 (vg_degrade_params): what gather_degrade_u8 uses for the same seed and positions."""
+    out = torch.empty(B, 8, dtype=torch.float32, device=device)
+    _need_cuda(out)
+    _degrade_key(seed, pos0)
+    L.check(L.load().vg_degrade_params(int(seed), int(pos0), B, float(noise_max_std), 1 if rect else 0, H, W,
+                                       *_degrade_bounds(rect, bounds), out.data_ptr(), L.stream_ptr()), "vg_degrade_params")
+    return out
+
+
 def noisy_clamp_to_nhwc(x, eps, sigma, CP, dtype, lo=-1.0, hi=1.0):
     """-> (noisy NHWC engine tensor, noisy NCHW f32)."""
     _need_cuda(x, eps)
