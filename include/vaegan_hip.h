@@ -48,14 +48,15 @@ extern "C" {
 #define VG_ACT_LRELU   2   /* nn.LeakyReLU(slope)    main_vae.py:25, gan_code.py:62-82 */
 #define VG_ACT_TANH    3   /* nn.Tanh()              gan_code.py:50 (vg_tnconv epilogue only) */
 
-#define VG_ABI_VERSION 11  /* 2: vg_pack_desc.tile_start, SyncBN / WGAN / data-path entry points; 3: in-kernel noise (vg_*_rng);
+#define VG_ABI_VERSION 12  /* 2: vg_pack_desc.tile_start, SyncBN / WGAN / data-path entry points; 3: in-kernel noise (vg_*_rng);
                              4: vg_bn_finalize_act_forward, vg_bn_backward_finalize_apply;
                              7: vg_bce_pair_forward_backward;
                              8: vg_head_backward; round-3 prune -- the opt-in experiments of ABI 5 / 6 that measured slower (input prologue of
                                 vg_tn_desc / vg_ew_desc, vg_gg_desc.bnb_*) are gone from the descriptors; vg_reload_switches;
                              9: vg_step_prologue, vg_adam_step(lr < 0);
                              10 (round 4): vg_adam_apply replaces the lr < 0 overload of vg_adam_step (which now rejects it);
-                             11: degraded-pair data path: vg_gather_degrade_u8, vg_degrade_params, vg_rand_u01 */
+                             11: degraded-pair data path: vg_gather_degrade_u8, vg_degrade_params, vg_rand_u01;
+                             12: latent prior: vg_latent_hist (+ _ws_bytes), vg_latent_sample, vg_to_u8 */
 int vg_abi_version(void);
 /* The library reads its optional kernel-selection switches (VG_* environment variables, DESIGN.md "Runtime switches")
  * ONCE, when it is loaded; nothing on a launch path calls getenv.  A process that changes one of them afterwards
@@ -482,6 +483,59 @@ int vg_gather_degrade_u8(const uint8_t* images, int64_t N, const int64_t* idx, i
 int vg_degrade_params(uint64_t seed, uint64_t pos0, int B, float noise_max_std, int rect, int H, int W, int min_size,
                       int max_size, int x0, int x1, int y0, int y1, float* out, void* stream);
 int vg_rand_u01(float* out, int64_t n, const uint64_t* rng, int draw, void* stream);
+/* ------------------------------------------------------------------------------------------
+ * Latent prior (main_vae.py:415-436 vals_to_hist / sample_distribution, used by evaluate_vae :452-512 and sample_vae
+ * :594-626): the aggregate-posterior histogram prior.  The Encoder's (mu | logvar) rows of the whole data set stay on
+ * the device; their per-column histograms are fitted there and latent draws come out in the Generator's input layout.
+ *
+ * vg_latent_hist: per-column np.histogram(x[:, c], bins=n_bins) + np.cumsum(counts / N) of x f32 [N][D], rows
+ * `row_stride` elements apart (row_stride >= D; the [N][2L] mu | logvar matrix is fitted in one call, D = 2L).
+ *   range   lo_c = min_n x[n][c], hi_c = max_n x[n][c]; lo_c == hi_c: lo_c -= 0.5f, hi_c += 0.5f (numpy _get_outer_edges).
+ *   edges   f32 [D][n_bins + 1] (numpy >= 2 keeps float32 input in float32), every operation rounded on its own, no
+ *           fused multiply-add: step = (hi - lo) / n_bins; e_k = fl(fl(k * step) + lo) for k < n_bins; e_{n_bins} = hi.
+ *   counts  int32 [D][n_bins]: x falls in the bin b with e_b <= x < e_{b+1}, the last bin closed on the right.
+ *   cdf     f64 [D][n_bins]: cdf_b = cdf_{b-1} + (double)counts_b / (double)N, summed SEQUENTIALLY in bin order -- what
+ *           np.cumsum(freqs / n) computes; its last entry is often 1 - 1 ulp, and the sampler has to see the doubles the
+ *           reference sees.
+ *   status  int32 [1]: non-zero if some column's range (or its width) is not finite (numpy raises ValueError there);
+ *           the other outputs are then unspecified, but every access stays in bounds.
+ * Four launches: column min / max partials, edges (+ zeroed counts), binning into an LDS histogram flushed with integer
+ * atomics (order-independent: the result is deterministic), one-workgroup cdf.  1 <= N <= 2^31 - 1, D >= 1,
+ * 1 <= n_bins <= 1024, else VG_EINVAL.  ws: vg_latent_hist_ws_bytes() bytes of scratch, 4-byte aligned.
+ *
+ * vg_latent_sample: n draws from a fitted prior with L latent dimensions: histogram columns [0, L) are mu, [L, 2L) logvar.
+ * Per output element (j, c), j < n, c < 2L, with u, v in [0, 1):
+ *   idx = first b with cdf[c][b] >= u (np.searchsorted, side left), CLAMPED to n_bins - 1;
+ *   out = (float)(x0 + (x1 - x0) * v), x0 = (double)edges[c][idx], x1 = (double)edges[c][idx + 1], in f64, every
+ *         operation rounded on its own (legacy np.random.uniform is low + (high - low) * d), ONE final rounding to f32.
+ * Draws: injected -- u and v f64 [n][2L] (both or neither; the reference's draws are 53-bit doubles), eps f32 [n][L] --
+ * or, where the pointer is NULL, generated from rng = {seed, counter} (device memory) like every other in-kernel draw:
+ *   u = u01(word(VG_DRAW_LATENT_U, j*2L + c)), v = u01(word(VG_DRAW_LATENT_V, j*2L + c))   (u01, word: "Degraded pairs" above;
+ *       what vg_rand_u01(out, n*2L, rng, draw) materialises, 24 bits, exact in f64),
+ *   eps = element j*L + i of what vg_randn(out, n*L, rng, VG_DRAW_LATENT_EPS) materialises.
+ * Outputs, each optional (NULL), at least one:
+ *   mulv f32 [n][2L]: the sampled mu | logvar;
+ *   z    [n][ZP] in dtype (VG_F32 / VG_BF16, pad columns zero, 16-byte aligned): the Generator's input,
+ *        z = mu + exp(0.5 * clamp(logvar, -10, 10)) * eps (main_vae.py:487), eps needed only for z.
+ * Deviations from the reference, both inert in its own use: (a) the clamp of idx -- sample_distribution indexes
+ * bins[i, idx + 1] unclamped and raises IndexError if u > cdf[-1]; that needs u > 1 - ~1e-14, which a 24-bit device
+ * uniform (at most 1 - 2^-24) never is; (b) the logvar clamp -- main_vae.py:487 has none, the engine's reparameterisation
+ * clamps as vaegan_code.py:75 does; inert for |logvar| < 10.
+ *
+ * vg_to_u8: how generated images leave the device (main_vae.py:492,498-499): x f32 [B][C][H][W] in [-1, 1] ->
+ * t = fl(fl(fl(x + 1) / 2) * 255), clamped to [0, 255], truncated toward zero (a NaN gives 0).  grid_cols == 0: y u8
+ * [B][C][H][W]; grid_cols > 0: ONE picture y u8 [rows*H][grid_cols*W][C], rows = ceil(B / grid_cols), image i at tile
+ * (i / grid_cols, i % grid_cols), unused tiles zero (the vaegan_fake_epoch_*.jpg grid of vaegan_code.py:209-216).
+ * ---------------------------------------------------------------------------------------- */
+#define VG_DRAW_LATENT_U   32
+#define VG_DRAW_LATENT_V   33
+#define VG_DRAW_LATENT_EPS 34
+int64_t vg_latent_hist_ws_bytes(int64_t N, int D, int n_bins);     /* VG_EINVAL (negative) for sizes outside the contract */
+int vg_latent_hist(const float* x, int64_t N, int D, int64_t row_stride, int n_bins, float* edges, int32_t* counts,
+                   double* cdf, int32_t* status, void* ws, int64_t ws_bytes, void* stream);
+int vg_latent_sample(const float* edges, const double* cdf, int n_bins, int L, int64_t n, const double* u, const double* v,
+                     const float* eps, const uint64_t* rng, float* mulv, void* z, int ZP, int dtype, void* stream);
+int vg_to_u8(const float* x, uint8_t* y, int B, int C, int H, int W, int grid_cols, void* stream);
 /* hipMemsetAsync(p, 0, nbytes) on the stream: optimizer.zero_grad() (vaegan_code.py:103,131-132) over a flat buffer. */
 int vg_memset_zero(void* p, int64_t nbytes, void* stream);
 /* bf16 -> OCP e4m3fn, elementwise: y[i] = fp8(x[i] * 2^shift).  The fp8 copies of activations (shift 0) and of the

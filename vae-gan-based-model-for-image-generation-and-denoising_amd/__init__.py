@@ -5,13 +5,16 @@ Drop-in surface (INTEGRATION.md): ``Encoder``, ``ConvBlock`` (main_vae.py:20-58)
 ``Discriminator``, ``weights_init`` (gan_code.py:16-97), ``Adam`` (torch.optim.Adam as used at
 vaegan_code.py:42-44), ``BCELoss`` / ``MSELoss`` (vaegan_code.py:46-47), ``configure_seed``
 (utils.py:6-14), ``VAEGANTrainer`` (the loop body of vaegan_code.py:65-135) and ``graphed`` (hipGraph replay of a
-reference-shaped step function).
+reference-shaped step function).  Generation (main_vae.py:415-641): ``latent`` -- ``encode_dataset``, ``LatentPrior``,
+``evaluate_generation``, ``sample_images``.
 """
 from . import data  # noqa: F401
 from . import geometry  # noqa: F401
+from . import latent  # noqa: F401
 from .ddp import GradReducer
 from .denoise import denoise_eval, paired_test_epoch, validation_epoch
 from .graphed import graphed
+from .latent import LatentPrior, encode_dataset, evaluate_generation, sample_images
 from .losses import BCELoss, MSELoss
 from .nets import ConvBlock, Discriminator, Encoder, Generator, weights_init
 from .optim import Adam
@@ -20,4 +23,5 @@ from .trainer import LOSS_NAMES, VAEGANTrainer
 from .utils import configure_seed
 
 __all__ = ["ConvBlock", "Encoder", "Generator", "Discriminator", "weights_init", "Adam", "BCELoss", "MSELoss",
-           "VAEGANTrainer", "LOSS_NAMES", "configure_seed", "geometry", "denoise_eval", "validation_epoch", "paired_test_epoch", "GradReducer", "data", "VAETrainer", "DCGANTrainer", "WGANTrainer", "graphed"]
+           "VAEGANTrainer", "LOSS_NAMES", "configure_seed", "geometry", "denoise_eval", "validation_epoch", "paired_test_epoch", "GradReducer", "data", "VAETrainer", "DCGANTrainer", "WGANTrainer", "graphed",
+           "latent", "LatentPrior", "encode_dataset", "evaluate_generation", "sample_images"]

@@ -753,6 +753,82 @@ def degrade_params(seed, pos0, B, noise_max_std, rect, H, W, bounds=None, device
     return out
 
 
+# draw ids of the latent prior (include/vaegan_hip.h "Latent prior"): outside 0..2 and 16..18
+DRAW_LATENT_U, DRAW_LATENT_V, DRAW_LATENT_EPS = 32, 33, 34
+
+
+def latent_hist(x, n_bins=100):
+    """Per-column np.histogram + np.cumsum(counts / N) of x f32 [N,D] on the device (vg_latent_hist); x may be a view
+    whose rows are further apart than D (stride(1) == 1).  -> (edges f32 [D,n_bins+1], counts int32 [D,n_bins],
+    cdf f64 [D,n_bins], status int32 [1]: non-zero where a column's range is not finite).  No host sync."""
+    if not x.is_cuda:
+        raise RuntimeError("vaegan_amd ops need tensors on the MI355X (cuda) device; there is no CPU path")
+    if x.dtype != torch.float32 or x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1:
+        raise RuntimeError("latent_hist: x must be a non-empty f32 [N,D] tensor")
+    N, D = x.shape
+    stride = x.stride(0) if N > 1 else D
+    if (D > 1 and x.stride(1) != 1) or stride < D:
+        raise RuntimeError("latent_hist: the columns of x must be adjacent in memory (stride(1) == 1, stride(0) >= D)")
+    lib = L.load()
+    nbytes = lib.vg_latent_hist_ws_bytes(N, D, int(n_bins))
+    if nbytes < 0:
+        L.check(int(nbytes), "vg_latent_hist_ws_bytes")
+    dev = x.device
+    edges = torch.empty(D, n_bins + 1, dtype=torch.float32, device=dev)
+    counts = torch.empty(D, n_bins, dtype=torch.int32, device=dev)
+    cdf = torch.empty(D, n_bins, dtype=torch.float64, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    ws = WS.get("latent", nbytes, dev)
+    L.check(lib.vg_latent_hist(x.data_ptr(), N, D, stride, int(n_bins), edges.data_ptr(), counts.data_ptr(), cdf.data_ptr(),
+                               status.data_ptr(), ws.data_ptr(), ws.numel() * 4, L.stream_ptr()), "vg_latent_hist")
+    return edges, counts, cdf, status
+
+
+def latent_sample(edges, cdf, L_dim, n, u=None, v=None, eps=None, state=None, want_mulv=True, z=None):
+    """n draws from a fitted prior (vg_latent_sample).  edges f32 [2L,n_bins+1], cdf f64 [2L,n_bins].  u, v: f64 [n,2L]
+    (both or neither), eps: f32 [n,L]; whatever is None is drawn in the kernel from state = int64[2] {seed, counter}.
+    z: None or (ZP, dtype) -> also the Generator's input [n,1,1,ZP].  -> (mulv f32 [n,2L] or None, z or None)."""
+    _need_cuda(edges, cdf, u, v, eps, state)
+    n, L_dim = int(n), int(L_dim)
+    n_bins = cdf.shape[-1]
+    if (edges.dtype != torch.float32 or cdf.dtype != torch.float64 or tuple(edges.shape) != (2 * L_dim, n_bins + 1)
+            or tuple(cdf.shape) != (2 * L_dim, n_bins)):
+        raise RuntimeError("latent_sample: edges must be f32 [2L,n_bins+1] and cdf f64 [2L,n_bins]")
+    if n < 1:
+        raise RuntimeError("latent_sample: n must be >= 1")
+    for t, name in ((u, "u"), (v, "v")):
+        if t is not None and (t.dtype != torch.float64 or t.numel() != n * 2 * L_dim):
+            raise RuntimeError(f"latent_sample: {name} must be f64 [n,2L]")
+    if eps is not None and (eps.dtype != torch.float32 or eps.numel() != n * L_dim):
+        raise RuntimeError("latent_sample: eps must be f32 [n,L]")
+    if state is not None and (state.dtype != torch.int64 or state.numel() != 2):
+        raise RuntimeError("latent_sample: state must be int64[2] = {seed, counter}")
+    dev = edges.device
+    mulv = torch.empty(n, 2 * L_dim, dtype=torch.float32, device=dev) if want_mulv else None
+    ZP, dtype, zt = 0, F32, None
+    if z is not None:
+        ZP, dtype = z
+        zt = empty_act((n, 1, 1, ZP), dtype, dev)
+    L.check(L.load().vg_latent_sample(edges.data_ptr(), cdf.data_ptr(), n_bins, L_dim, n, L.ptr(u), L.ptr(v), L.ptr(eps),
+                                      L.ptr(state), L.ptr(mulv), L.ptr(zt), ZP, dtype, L.stream_ptr()), "vg_latent_sample")
+    return mulv, zt
+
+
+def to_u8(x, grid_cols=0):
+    """[-1,1] f32 [B,C,H,W] -> uint8 ((x + 1) / 2 * 255, clamp, truncate; main_vae.py:492,498-499) on the device:
+    [B,C,H,W], or with grid_cols > 0 ONE [rows*H, grid_cols*W, C] picture, image i at tile (i // grid_cols, i % grid_cols)."""
+    _need_cuda(x)
+    if x.dtype != torch.float32 or x.dim() != 4 or x.numel() == 0 or grid_cols < 0:
+        raise RuntimeError("to_u8: x must be a non-empty f32 [B,C,H,W] tensor and grid_cols >= 0")
+    B, C, H, W = x.shape
+    if grid_cols:
+        y = torch.empty((B + grid_cols - 1) // grid_cols * H, grid_cols * W, C, dtype=torch.uint8, device=x.device)
+    else:
+        y = torch.empty(B, C, H, W, dtype=torch.uint8, device=x.device)
+    L.check(L.load().vg_to_u8(x.data_ptr(), y.data_ptr(), B, C, H, W, int(grid_cols), L.stream_ptr()), "vg_to_u8")
+    return y
+
+
 def noisy_clamp_to_nhwc(x, eps, sigma, CP, dtype, lo=-1.0, hi=1.0):
     """-> (noisy NHWC engine tensor, noisy NCHW f32)."""
     _need_cuda(x, eps)
