@@ -48,7 +48,7 @@ extern "C" {
 #define VG_ACT_LRELU   2   /* nn.LeakyReLU(slope)    main_vae.py:25, gan_code.py:62-82 */
 #define VG_ACT_TANH    3   /* nn.Tanh()              gan_code.py:50 (vg_tnconv epilogue only) */
 
-#define VG_ABI_VERSION 12  /* 2: vg_pack_desc.tile_start, SyncBN / WGAN / data-path entry points; 3: in-kernel noise (vg_*_rng);
+#define VG_ABI_VERSION 13  /* 2: vg_pack_desc.tile_start, SyncBN / WGAN / data-path entry points; 3: in-kernel noise (vg_*_rng);
                              4: vg_bn_finalize_act_forward, vg_bn_backward_finalize_apply;
                              7: vg_bce_pair_forward_backward;
                              8: vg_head_backward; round-3 prune -- the opt-in experiments of ABI 5 / 6 that measured slower (input prologue of
@@ -56,7 +56,8 @@ extern "C" {
                              9: vg_step_prologue, vg_adam_step(lr < 0);
                              10 (round 4): vg_adam_apply replaces the lr < 0 overload of vg_adam_step (which now rejects it);
                              11: degraded-pair data path: vg_gather_degrade_u8, vg_degrade_params, vg_rand_u01;
-                             12: latent prior: vg_latent_hist (+ _ws_bytes), vg_latent_sample, vg_to_u8 */
+                             12: latent prior: vg_latent_hist (+ _ws_bytes), vg_latent_sample, vg_to_u8;
+                             13: Resize + CenterCrop on the device: vg_resize_u8 (+ _lds_bytes, _band) */
 int vg_abi_version(void);
 /* The library reads its optional kernel-selection switches (VG_* environment variables, DESIGN.md "Runtime switches")
  * ONCE, when it is loaded; nothing on a launch path calls getenv.  A process that changes one of them afterwards
@@ -536,6 +537,65 @@ int vg_latent_hist(const float* x, int64_t N, int D, int64_t row_stride, int n_b
 int vg_latent_sample(const float* edges, const double* cdf, int n_bins, int L, int64_t n, const double* u, const double* v,
                      const float* eps, const uint64_t* rng, float* mulv, void* z, int ZP, int dtype, void* stream);
 int vg_to_u8(const float* x, uint8_t* y, int B, int C, int H, int W, int grid_cols, void* stream);
+/* ------------------------------------------------------------------------------------------
+ * Resize (dataset_code.py:26-30, CelebADatasetV0's transforms.Resize(image_size) + transforms.CenterCrop(image_size) on
+ * the PIL image default_loader hands them): PIL's ImagingResample for 8-bit images with the triangle (BILINEAR) filter,
+ * restated as integer arithmetic.  The output equals Image.resize((w, h), Image.BILINEAR) + crop byte for byte.
+ * PB = 22 (PIL's PRECISION_BITS = 32 - 8 - 2).
+ *
+ * Coefficient table of one axis, in_size -> out_size, computed ON THE HOST in IEEE double, in exactly this order of
+ * operations ((int) truncates toward zero):
+ *   scale = in_size / out_size;  fs = max(scale, 1.0);  support = 1.0 * fs;  ksize = 2 * ceil(support) + 1;  ss = 1.0 / fs
+ *   for each output index xx:
+ *     center = (xx + 0.5) * scale
+ *     xmin = max((int)(center - support + 0.5), 0)
+ *     n    = min((int)(center + support + 0.5), in_size) - xmin
+ *     w_x  = max(0, 1 - |(x + xmin - center + 0.5) * ss|)  for x < n
+ *     ww   = sum of w_x, summed left to right
+ *     p_x  = w_x / ww  (left as w_x if ww == 0)
+ *     k_x  = (int)(0.5 + p_x * 2^PB);  for p_x < 0 it is (int)(-0.5 + p_x * 2^PB) (cannot occur for this filter, part of the rule)
+ *     taps beyond n are 0;  bounds[xx] = (xmin, n)
+ * One pass along an axis, on u8 data, per channel, int32 accumulator:
+ *   out = clamp((2^(PB-1) + sum_{x<n} in[xmin + x] * k_x) >> PB, 0, 255)
+ * (the largest accumulator is 255 * (2^22 + a few ulps) + 2^21 < 2^31).
+ * Resize (Hin, Win) -> (Hr, Wr): the horizontal pass first, then the vertical pass on the U8 result of the horizontal one;
+ * a pass whose size does not change is skipped; an unchanged image is a copy.
+ * CenterCrop to (ch, cw): top = int(round((Hr - ch) / 2.0)), left = int(round((Wr - cw) / 2.0)) with python's round
+ * (ties to even); dst[y][x] = resized[top + y][left + x].  ch > Hr or cw > Wr is an error (torchvision would pad).
+ * image_size -> geometry (data.resize_geometry): an int resizes the SHORTER edge to it, the longer edge becomes
+ * int(size * long / short), crop size x size; an (h, w) pair resizes to exactly that and the crop is a no-op.
+ * RGBA is outside the contract (PIL resizes it with premultiplied alpha); L, RGB, CMYK are channels treated alike.
+ *
+ * vg_resize_u8: src u8 [N][Hin][Win][C], C <= 4, 4-byte aligned -> dst u8 [B][ch][cw][C] (the resident layout).
+ *   idx    int64 [B] source image of each output image, or NULL: images 0 .. B-1 in order (B <= N).  idx outside [0, N)
+ *          reads image 0 (the host validates).
+ *   kh/bh  int32 [cw][ksize_h] and [cw][2]: the horizontal table ALREADY RESTRICTED to the crop window (rows left ..
+ *          left + cw - 1 of the Win -> Wr table), 16-byte aligned device memory; bh_host: the same bounds in HOST memory,
+ *          read by this call before the launch: every (xmin, n) is checked against the input (0 <= xmin, 1 <= n <=
+ *          ksize, xmin + n <= in_size, windows moving forward) -- a table that reaches outside the image is VG_EINVAL,
+ *          nothing is launched.  All three NULL: the pass is skipped and `left` is the first source column.
+ *   kv/bv/bv_host, ksize_v, top: the same for rows (rows top .. top + ch - 1 of the Hin -> Hr table).
+ *   top, left: used only by a skipped pass (a table carries its own offsets).
+ *   band   output rows per workgroup; 0: chosen by the library.  The result does not depend on it.
+ * One launch: a workgroup owns one image and a band of output rows; it stages the input rows [bv[y0].xmin,
+ * bv[y1-1].xmin + bv[y1-1].n) that band reads -- only the columns [bh[0].xmin, bh[cw-1].xmin + bh[cw-1].n) -- through
+ * LDS, keeps the horizontal result there as u8 and stores the band as whole contiguous rows; no intermediate in HBM.
+ * Columns and rows of the resized image outside the crop window are never computed.  All byte offsets are 64-bit.
+ * vg_resize_u8_lds_bytes: the LDS bytes a launch of this geometry takes (host arguments only), or VG_EINVAL where
+ * vg_resize_u8 would return it -- which includes a geometry that cannot be served: an LDS image of one output row's
+ * input rows plus four staged input rows beyond 64 KiB (e.g. C * (3 * cw + 4 * cols_read) > 65536 for an enlargement).
+ * There is no second path.
+ * ---------------------------------------------------------------------------------------- */
+int64_t vg_resize_u8_lds_bytes(int Hin, int Win, int C, const int32_t* bh_host, int ksize_h, const int32_t* bv_host,
+                               int ksize_v, int top, int left, int ch, int cw, int B, int band);
+/* The band height (output rows per workgroup) that launch uses -- `band` itself where it is given and fits; VG_EINVAL as above.
+ * With it a caller can count the bytes a launch really reads: adjacent bands re-read about 2 * support input rows. */
+int vg_resize_u8_band(int Hin, int Win, int C, const int32_t* bh_host, int ksize_h, const int32_t* bv_host, int ksize_v,
+                      int top, int left, int ch, int cw, int B, int band);
+int vg_resize_u8(const uint8_t* src, int64_t N, int Hin, int Win, int C, const int64_t* idx, int B, const int32_t* kh,
+                 const int32_t* bh, const int32_t* bh_host, int ksize_h, const int32_t* kv, const int32_t* bv,
+                 const int32_t* bv_host, int ksize_v, int top, int left, uint8_t* dst, int ch, int cw, int band,
+                 void* stream);
 /* hipMemsetAsync(p, 0, nbytes) on the stream: optimizer.zero_grad() (vaegan_code.py:103,131-132) over a flat buffer. */
 int vg_memset_zero(void* p, int64_t nbytes, void* stream);
 /* bf16 -> OCP e4m3fn, elementwise: y[i] = fp8(x[i] * 2^shift).  The fp8 copies of activations (shift 0) and of the

@@ -28,11 +28,18 @@ size.  They cannot equal torch's CPU generator; the distribution and the arithme
 (tests/test_gpu_degrade.py).  The epoch seed is the int64 base seed that ``iter(DataLoader)`` draws from the default
 generator -- the number a real DataLoader hands its workers as their RNG seed -- so ``utils.configure_seed`` governs
 the noise, every epoch differs, and no default-RNG state is consumed beyond what the plain loader consumes.
-``image_size`` (``decode_folder`` / ``from_folder`` / 'LQ'): V0's ``Resize`` + ``CenterCrop`` (:26-30) at decode time on
-the host with PIL, so the resident set is already at the training size.
+``image_size`` (``decode_folder`` / ``from_folder`` / 'LQ'): V0's ``Resize`` + ``CenterCrop`` (:26-30).  ``resize_on="host"``
+(the default): at decode time with PIL, so the resident set is frozen at the size asked for.  ``resize_on="device"``: the
+files are decoded ONCE at their own size and uploaded; ``ResidentImages.resized(image_size)`` then makes any member of
+the size family from that raw set with one HIP kernel (ops.resize_u8) whose output equals PIL's byte for byte -- PIL's
+8-bit bilinear resampler is integer arithmetic over a small coefficient table, which ``resample_coeffs`` builds on the
+host in double exactly as PIL does (include/vaegan_hip.h "Resize"; tests/test_resize_cpu.py holds the restated contract
+against recorded PIL output, tests/test_gpu_resize.py the kernel).  ``resize_geometry`` is the one place that turns an
+``image_size`` into (Hr, Wr, top, left, ch, cw) for both routes.
 """
 from functools import partial
 import glob
+import math
 import os
 from multiprocessing import Pool, cpu_count
 from typing import Iterator, Optional, Tuple
@@ -43,27 +50,69 @@ import torch
 from . import ops
 
 
-def _resize_center_crop(img, image_size):
-    """transforms.Resize(image_size) + transforms.CenterCrop(image_size) (dataset_code.py:27-28) on a PIL image, restated
-    from torchvision's PIL path: an int resizes the SHORTER edge to it (longer edge int(size * long / short)), an (h, w)
-    pair resizes to exactly that; ``img.resize((w, h), BILINEAR)``; the crop window starts at int(round((H - h) / 2)).
-    Parity unpinned against torchvision (the package is not installed here)."""
-    from PIL import Image
-    w, h = img.size
+def resize_geometry(H: int, W: int, image_size) -> Tuple[int, int, int, int, int, int]:
+    """transforms.Resize(image_size) + transforms.CenterCrop(image_size) (dataset_code.py:27-28) of an H x W image ->
+    (Hr, Wr, top, left, ch, cw), restated from torchvision's PIL path: an int resizes the SHORTER edge to it (longer edge
+    int(size * long / short)) and crops size x size, an (h, w) pair resizes to exactly that (the crop is a no-op); the crop
+    window starts at int(round((Hr - ch) / 2)), python's round.  A crop larger than the resized image (torchvision would
+    pad) raises.  Parity unpinned against torchvision (the package is not installed here)."""
+    H, W = int(H), int(W)
     if isinstance(image_size, int):
-        short, long = (w, h) if w <= h else (h, w)
+        short, long = (W, H) if W <= H else (H, W)
         new_short, new_long = image_size, int(image_size * long / short)
-        new_w, new_h = (new_short, new_long) if w <= h else (new_long, new_short)
+        new_w, new_h = (new_short, new_long) if W <= H else (new_long, new_short)
         ch = cw = image_size
     else:
         ch, cw = (int(v) for v in image_size)
         new_h, new_w = ch, cw
-    if (new_w, new_h) != (w, h):
-        img = img.resize((new_w, new_h), Image.BILINEAR)
     if new_h < ch or new_w < cw:
         raise RuntimeError("CenterCrop larger than the resized image (padding) is not supported")
     top, left = int(round((new_h - ch) / 2.0)), int(round((new_w - cw) / 2.0))
+    return new_h, new_w, top, left, ch, cw
+
+
+def _resize_center_crop(img, image_size):
+    """resize_geometry on a PIL image: ``img.resize((Wr, Hr), BILINEAR)`` where the size changes, then the crop."""
+    from PIL import Image
+    w, h = img.size
+    new_h, new_w, top, left, ch, cw = resize_geometry(h, w, image_size)
+    if (new_w, new_h) != (w, h):
+        img = img.resize((new_w, new_h), Image.BILINEAR)
     return img.crop((left, top, left + cw, top + ch))
+
+
+RESAMPLE_PRECISION_BITS = 22                 # PIL's PRECISION_BITS = 32 - 8 - 2
+
+
+def resample_coeffs(in_size: int, out_size: int) -> Tuple[np.ndarray, np.ndarray]:
+    """Coefficient table of one axis of PIL's 8-bit bilinear resampler, in_size -> out_size (include/vaegan_hip.h
+    "Resize"; PIL's precompute_coeffs + normalize_coeffs_8bpc with the triangle filter): python floats are IEEE doubles
+    and every line below is one of the contract's operations, in its order.
+    -> (k int32 [out_size, ksize], bounds int32 [out_size, 2] = (xmin, n))."""
+    in_size, out_size = int(in_size), int(out_size)
+    if in_size < 1 or out_size < 1:
+        raise ValueError("resample_coeffs: sizes must be >= 1")
+    scale = in_size / out_size
+    fs = max(scale, 1.0)
+    support = 1.0 * fs
+    ksize = 2 * int(math.ceil(support)) + 1
+    ss = 1.0 / fs
+    one = float(1 << RESAMPLE_PRECISION_BITS)
+    k = np.zeros((out_size, ksize), np.int32)
+    bounds = np.zeros((out_size, 2), np.int32)
+    for xx in range(out_size):
+        center = (xx + 0.5) * scale
+        xmin = max(int(center - support + 0.5), 0)
+        n = min(int(center + support + 0.5), in_size) - xmin
+        w = [max(0.0, 1.0 - abs((x + xmin - center + 0.5) * ss)) for x in range(n)]
+        ww = 0.0
+        for v in w:
+            ww += v
+        for x in range(n):
+            p = w[x] / ww if ww != 0.0 else w[x]
+            k[xx, x] = int(-0.5 + p * one) if p < 0 else int(0.5 + p * one)
+        bounds[xx] = (xmin, n)
+    return k, bounds
 
 
 def _decode(path: str, image_size=None) -> np.ndarray:
@@ -82,11 +131,21 @@ def list_images(image_folder: str, dataset_size: Optional[int] = None):
     return paths
 
 
+def _check_resize_on(resize_on: str) -> bool:
+    if resize_on not in ("host", "device"):
+        raise ValueError("resize_on must be 'host' or 'device'")
+    return resize_on == "device"
+
+
 def decode_folder(image_folder: str, dataset_size: Optional[int] = None, workers: Optional[int] = None,
-                  image_size=None) -> torch.Tensor:
+                  image_size=None, resize_on: str = "host") -> torch.Tensor:
     """-> uint8 tensor [N, H, W, 3] on the host (all images must share one size, as CelebA-HQ does).
     image_size (int or (h, w)): CelebADatasetV0's Resize + CenterCrop at decode time (_resize_center_crop), e.g. a folder
-    of 178 x 218 CelebA files becomes a 64 x 64 set; None: the files as they are."""
+    of 178 x 218 CelebA files becomes a 64 x 64 set; None: the files as they are.
+    resize_on="device": the files as they are whatever image_size says -- the caller resizes the uploaded set
+    (ResidentImages.resized; from_folder does both)."""
+    if _check_resize_on(resize_on):
+        image_size = None
     paths = list_images(image_folder, dataset_size)
     if not paths:
         raise RuntimeError(f"no *.jpg files in {image_folder}")
@@ -131,6 +190,9 @@ class Degrade:
         return f"Degrade(noise_max_std={self.noise_max_std}, rect={self.rect}, normalize={self.normalize})"
 
 
+RESIZE_CHUNK = 8192          # images per resize launch / per upload of a raw set (218 x 178 x 3: 0.95 GB)
+
+
 class ResidentImages:
     """The decoded image set in HBM: u8 [N, H, W, C].  ``ds[i]`` returns what ``CelebAHQDataset[i]`` returns
     (f32 [C,H,W] in [-1,1]) -- as a device tensor."""
@@ -141,11 +203,51 @@ class ResidentImages:
         self.images = images_u8.to(device).contiguous()
         if not self.images.is_cuda:
             raise RuntimeError("ResidentImages lives in MI355X HBM ('cuda'); there is no CPU path")
+        self.raw: Optional["ResidentImages"] = None                # from_folder(resize_on="device", keep_raw=True)
 
     @classmethod
     def from_folder(cls, image_folder: str, dataset_size: Optional[int] = None, device="cuda", workers=None,
-                    image_size=None):
-        return cls(decode_folder(image_folder, dataset_size, workers, image_size), device)
+                    image_size=None, resize_on: str = "host", keep_raw: bool = False, chunk: int = RESIZE_CHUNK):
+        """resize_on="host": Resize + CenterCrop inside the decode pool (PIL), the set is uploaded at image_size.
+        resize_on="device": the files are decoded at their own size, uploaded `chunk` images at a time and resized on the
+        device (the same bytes); keep_raw=True keeps the uploaded raw set as ``.raw`` for further ``resized()`` calls,
+        otherwise only one chunk of it is on the device at a time."""
+        if not _check_resize_on(resize_on) or image_size is None:
+            return cls(decode_folder(image_folder, dataset_size, workers, image_size), device)
+        raw = decode_folder(image_folder, dataset_size, workers, None)
+        N, H, W, C = raw.shape
+        chunk = max(1, int(chunk))
+        if keep_raw:
+            up = torch.empty(raw.shape, dtype=torch.uint8, device=device)
+            for lo in range(0, N, chunk):
+                up[lo:lo + chunk].copy_(raw[lo:lo + chunk])
+            rawset = cls(up, device)
+            ds = rawset.resized(image_size, chunk)
+            ds.raw = rawset
+            return ds
+        geom = resize_geometry(H, W, image_size)
+        out = torch.empty(N, geom[4], geom[5], C, dtype=torch.uint8, device=device)
+        for lo in range(0, N, chunk):
+            ops.resize_u8(raw[lo:lo + chunk].to(device), geom, out=out[lo:lo + chunk])
+        return cls(out, device)
+
+    def resized(self, image_size, chunk: int = RESIZE_CHUNK) -> "ResidentImages":
+        """A new resident set: every image of this one through Resize(image_size) + CenterCrop(image_size) on the device
+        (ops.resize_u8; equals the host route's PIL bytes).  chunk: images per launch -- it bounds the launch size only."""
+        if not self.images.is_cuda:
+            raise RuntimeError("ResidentImages lives in MI355X HBM ('cuda'); there is no CPU path")
+        N, H, W, C = self.images.shape
+        geom = resize_geometry(H, W, image_size)
+        dev = self.images.device
+        out = torch.empty(N, geom[4], geom[5], C, dtype=torch.uint8, device=dev)
+        chunk = max(1, int(chunk))
+        if chunk >= N:
+            ops.resize_u8(self.images, geom, out=out)
+        else:
+            order = torch.arange(N, dtype=torch.int64, device=dev)
+            for lo in range(0, N, chunk):
+                ops.resize_u8(self.images, geom, idx=order[lo:lo + chunk], out=out[lo:lo + chunk])
+        return ResidentImages(out, dev)
 
     def __len__(self) -> int:
         return self.images.shape[0]
@@ -280,20 +382,24 @@ class DeviceLoader:
 
 def get_dataset_loaders(path, batch_size=64, train_p=0.9, dataset_size=None, device="cuda", rank=0, world=1,
                         workers=None, dataset_type="HQ", image_size=(64, 64), noise_max_std=None, rect=True,
-                        normalize=None):
+                        normalize=None, resize_on="host"):
     """dataset_code.py:167-178 -> (train_loader, test_loader, image_shape).
     dataset_type 'HQ' (:168-169): the files as they are, values (u/255 - 0.5)/0.5.  'LQ' (:170-171, CelebADatasetV0):
-    Resize + CenterCrop to image_size at decode time, values u/255 (a ResidentImages passed as `path` is used as it is).
+    Resize + CenterCrop to image_size, values u/255; resize_on="host": at decode time with PIL, "device": the files are
+    decoded at their own size and resized on the device (same bytes).  A ResidentImages passed as `path` is used as it is,
+    unless dataset_type is 'LQ' and resize_on="device": then it is taken as a raw set and ``path.resized(image_size)`` is
+    what the loaders serve -- one raw resident set feeds every member of the size family.
     normalize overrides the value mapping (default: True for 'HQ', False for 'LQ').  noise_max_std set: both loaders
     yield (noisy, clean) pairs with `rect` (the call the reference's own test script asks for, main_vae.py:240).
     The defaults are the 'HQ' clean-batch loaders."""
     if dataset_type not in ("HQ", "LQ"):
         raise ValueError("dataset_type must be 'HQ' or 'LQ'")
     lq = dataset_type == "LQ"
+    on_device = _check_resize_on(resize_on)
     if isinstance(path, ResidentImages):
-        ds = path
+        ds = path.resized(image_size) if (lq and on_device) else path
     else:
-        ds = ResidentImages.from_folder(path, dataset_size, device, workers, image_size if lq else None)
+        ds = ResidentImages.from_folder(path, dataset_size, device, workers, image_size if lq else None, resize_on)
     normalize = (not lq) if normalize is None else bool(normalize)
     degrade = None if (noise_max_std is None and normalize) else Degrade(noise_max_std, rect, normalize)
     train_idx, test_idx = random_split_indices(len(ds), train_p)

@@ -679,6 +679,99 @@ def gather_normalize_u8(images_u8, idx, out=None):
     return y
 
 
+class _ResizeTables:
+    """Device coefficient tables of one resize geometry, restricted to the crop window, plus the host copy of the
+    bounds that vg_resize_u8 validates before every launch (kept alive here)."""
+
+    def __init__(self, Hin, Win, geometry, device):
+        from .data import resample_coeffs                               # data imports ops
+        Hr, Wr, top, left, ch, cw = geometry
+        if ch > Hr or cw > Wr:
+            raise RuntimeError("CenterCrop larger than the resized image (padding) is not supported")
+        if min(Hr, Wr, ch, cw) < 1 or top < 0 or left < 0 or top + ch > Hr or left + cw > Wr:
+            raise RuntimeError(f"resize_u8: bad geometry {geometry}")
+        self.top, self.left, self.ch, self.cw = top, left, ch, cw
+        self.kh = self.bh = self.bh_host = self.kv = self.bv = self.bv_host = None
+        self.ksh = self.ksv = 0
+        if Wr != Win:
+            k, b = resample_coeffs(Win, Wr)
+            self.ksh = k.shape[1]
+            self.bh_host = b[left:left + cw].copy()
+            self.kh = torch.from_numpy(k[left:left + cw].copy()).to(device)
+            self.bh = torch.from_numpy(self.bh_host).to(device)
+        if Hr != Hin:
+            k, b = resample_coeffs(Hin, Hr)
+            self.ksv = k.shape[1]
+            self.bv_host = b[top:top + ch].copy()
+            self.kv = torch.from_numpy(k[top:top + ch].copy()).to(device)
+            self.bv = torch.from_numpy(self.bv_host).to(device)
+
+    def host(self, b):
+        return 0 if b is None else b.ctypes.data
+
+
+_RESIZE_TABLES = {}          # (Hin, Win, Hr, Wr, top, left, ch, cw, device) -> _ResizeTables; a few hundred bytes to a few KB each
+
+
+def resize_tables(Hin, Win, geometry, device) -> _ResizeTables:
+    key = (int(Hin), int(Win)) + tuple(int(v) for v in geometry) + (str(device),)
+    t = _RESIZE_TABLES.get(key)
+    if t is None:
+        if len(_RESIZE_TABLES) >= 64:
+            _RESIZE_TABLES.clear()
+        t = _RESIZE_TABLES[key] = _ResizeTables(int(Hin), int(Win), key[2:8], device)
+    return t
+
+
+def resize_u8_lds_bytes(Hin, Win, C, geometry, B=1, band=0) -> int:
+    """LDS bytes per workgroup of resize_u8 for this geometry, or -1 where the library does not serve it (host only)."""
+    t = _ResizeTables(Hin, Win, tuple(int(v) for v in geometry), "cpu")
+    return int(L.load().vg_resize_u8_lds_bytes(Hin, Win, C, t.host(t.bh_host), t.ksh, t.host(t.bv_host), t.ksv, t.top, t.left,
+                                               t.ch, t.cw, B, band))
+
+
+def resize_u8_traffic(Hin, Win, C, geometry, B=1, band=0) -> dict:
+    """Bytes per image of a resize_u8 launch (host only): `algorithmic` = rows_read * cols_read * C + ch * cw * C, and
+    `actual` with the input rows that adjacent bands read twice; plus the band height and the LDS bytes of the launch."""
+    t = _ResizeTables(Hin, Win, tuple(int(v) for v in geometry), "cpu")
+    args = (Hin, Win, C, t.host(t.bh_host), t.ksh, t.host(t.bv_host), t.ksv, t.top, t.left, t.ch, t.cw, B, band)
+    bd = int(L.load().vg_resize_u8_band(*args))
+    if bd < 0:
+        L.check(bd, "vg_resize_u8_band")
+    cols = t.cw if t.bh_host is None else int(t.bh_host[-1].sum() - t.bh_host[0, 0])
+    lo = [t.top + y for y in range(t.ch)] if t.bv_host is None else [int(v) for v in t.bv_host[:, 0]]
+    hi = [v + 1 for v in lo] if t.bv_host is None else [int(v) for v in t.bv_host.sum(1)]
+    rows = hi[-1] - lo[0]
+    rows_banded = sum(hi[min(y0 + bd, t.ch) - 1] - lo[y0] for y0 in range(0, t.ch, bd))
+    out = t.ch * t.cw * C
+    return {"band": bd, "lds_bytes": int(L.load().vg_resize_u8_lds_bytes(*args)), "rows_read": rows, "cols_read": cols,
+            "algorithmic": rows * cols * C + out, "actual": rows_banded * cols * C + out}
+
+
+def resize_u8(images_u8, geometry, idx=None, out=None, band=0):
+    """Resize + CenterCrop on the device (vg_resize_u8, include/vaegan_hip.h "Resize"): images_u8 [N,Hin,Win,C] uint8 ->
+    uint8 [B,ch,cw,C], equal to PIL's ``resize((Wr, Hr), BILINEAR)`` + crop byte for byte.  geometry = (Hr, Wr, top, left,
+    ch, cw), see data.resize_geometry.  idx: int64 [B] on the device (source image of each output image) or None: all N
+    images in order.  band: output rows per workgroup (0: chosen by the library; the result does not depend on it).
+    The coefficient tables are built on the host once per geometry and cached on the device; a launch whose tables are
+    cached does no host-to-device copy (graph capture)."""
+    _need_cuda(images_u8, idx, out)
+    if images_u8.dtype != torch.uint8 or images_u8.dim() != 4 or images_u8.numel() == 0:
+        raise RuntimeError("resize_u8: images must be a non-empty uint8 [N,H,W,C] tensor")
+    if idx is not None and (idx.dtype != torch.int64 or idx.dim() != 1 or idx.numel() == 0):
+        raise RuntimeError("resize_u8: idx must be a non-empty int64 [B] tensor")
+    N, Hin, Win, C = images_u8.shape
+    B = N if idx is None else idx.numel()
+    t = resize_tables(Hin, Win, geometry, images_u8.device)
+    y = out if out is not None else torch.empty(B, t.ch, t.cw, C, dtype=torch.uint8, device=images_u8.device)
+    if tuple(y.shape) != (B, t.ch, t.cw, C) or y.dtype != torch.uint8:
+        raise RuntimeError("resize_u8: out must be uint8 [B,ch,cw,C]")
+    L.check(L.load().vg_resize_u8(images_u8.data_ptr(), N, Hin, Win, C, L.ptr(idx), B, L.ptr(t.kh), L.ptr(t.bh),
+                                  t.host(t.bh_host), t.ksh, L.ptr(t.kv), L.ptr(t.bv), t.host(t.bv_host), t.ksv, t.top, t.left,
+                                  y.data_ptr(), t.ch, t.cw, int(band), L.stream_ptr()), "vg_resize_u8")
+    return y
+
+
 # draw ids of the degraded-pair data path (include/vaegan_hip.h "Degraded pairs"; 0..2 belong to the training iteration)
 DRAW_DEGRADE_NORMAL, DRAW_DEGRADE_FILL, DRAW_DEGRADE_PARAMS = 16, 17, 18
 _NO_BOUNDS = (0, 0, 0, 0, 0, 0)
