@@ -48,7 +48,7 @@ extern "C" {
 #define VG_ACT_LRELU   2   /* nn.LeakyReLU(slope)    main_vae.py:25, gan_code.py:62-82 */
 #define VG_ACT_TANH    3   /* nn.Tanh()              gan_code.py:50 (vg_tnconv epilogue only) */
 
-#define VG_ABI_VERSION 13  /* 2: vg_pack_desc.tile_start, SyncBN / WGAN / data-path entry points; 3: in-kernel noise (vg_*_rng);
+#define VG_ABI_VERSION 14  /* 2: vg_pack_desc.tile_start, SyncBN / WGAN / data-path entry points; 3: in-kernel noise (vg_*_rng);
                              4: vg_bn_finalize_act_forward, vg_bn_backward_finalize_apply;
                              7: vg_bce_pair_forward_backward;
                              8: vg_head_backward; round-3 prune -- the opt-in experiments of ABI 5 / 6 that measured slower (input prologue of
@@ -57,7 +57,8 @@ extern "C" {
                              10 (round 4): vg_adam_apply replaces the lr < 0 overload of vg_adam_step (which now rejects it);
                              11: degraded-pair data path: vg_gather_degrade_u8, vg_degrade_params, vg_rand_u01;
                              12: latent prior: vg_latent_hist (+ _ws_bytes), vg_latent_sample, vg_to_u8;
-                             13: Resize + CenterCrop on the device: vg_resize_u8 (+ _lds_bytes, _band) */
+                             13: Resize + CenterCrop on the device: vg_resize_u8 (+ _lds_bytes, _band);
+                             14: feature-space metrics: vg_feat_stats_accum, vg_knn_radius2, vg_manifold_cover (+ _ws_bytes each) */
 int vg_abi_version(void);
 /* The library reads its optional kernel-selection switches (VG_* environment variables, DESIGN.md "Runtime switches")
  * ONCE, when it is loaded; nothing on a launch path calls getenv.  A process that changes one of them afterwards
@@ -596,6 +597,53 @@ int vg_resize_u8(const uint8_t* src, int64_t N, int Hin, int Win, int C, const i
                  const int32_t* bh, const int32_t* bh_host, int ksize_h, const int32_t* kv, const int32_t* bv,
                  const int32_t* bv_host, int ksize_v, int top, int left, uint8_t* dst, int ch, int cw, int band,
                  void* stream);
+/* ------------------------------------------------------------------------------------------
+ * Feature-space metrics (vaegan_code.py:143-185, gan_code.py:111-145, main_vae.py:472-512, :540-574: fid.update /
+ * fid.compute; README.md:22: Precision / Recall / F1 "computed via manifold distances", Kynkaanniemi et al. 2019).  What
+ * comes AFTER a feature vector exists; the feature extractor is the caller's (metrics.py: the project's own Encoder, or
+ * any callable).  All three entry points are deterministic: no floating-point atomics, partial results are combined in a
+ * fixed order, two calls on the same input give the same bits.
+ *
+ * vg_feat_stats_accum: the running sums behind FID (torchmetrics keeps features.double() sums): x f32 [n][D], rows
+ * `row_stride` elements apart (row_stride >= D, no alignment asked of x), sum f64 [D], outer f64 [D][D] (8-byte aligned):
+ *     sum[j] += sum_r x[r][j]          outer[i][j] += sum_r x[r][i] * x[r][j]
+ * every product and every addition in f64 on the exactly converted f32 inputs (the product of two f32 is exact in f64, so
+ * only the order of the additions is the kernel's: rows in ascending order inside a row split, the splits' partials in
+ * split order, then ONE addition to the value already in sum / outer).  outer on v_mfma_f64_16x16x4_f64, 64 x 64 column
+ * tiles of the upper triangle, mirrored when the partials are combined: the result is the full symmetric matrix.
+ * 0 <= n <= 2^31 - 1 (n == 0: nothing is launched, 0 is returned), 1 <= D <= 2048, any D; else VG_EINVAL.
+ * ws: vg_feat_stats_accum_ws_bytes(n, D) bytes, 8-byte aligned = splits * (P * 4096 + T * 64) * 8 with T = ceil(D / 64),
+ * P = T (T + 1) / 2, splits = min(max(1, 512 / P), ceil(n / 64)): 17.3 MB at D = 2048 and never more than that.
+ * Two launches.
+ *
+ * Distances, for both functions below: f32 inputs, the GEMM form
+ *     d2(a, b) = max(0, (|a|^2 + |b|^2) - 2 * dot(a, b))
+ * dot accumulated in f32 on the exact-f32 MFMA (v_mfma_f32_16x16x4_f32, columns of the feature vector in ascending
+ * order), |.|^2 in f32 by a pass of its own (per lane a fused multiply-add chain over columns lane, lane + 64, ..., then
+ * the wavefront's xor tree); no bf16 anywhere.  Error against exact arithmetic: at most 2 (D + 4) 2^-24 (|a|^2 + |b|^2).
+ * Where every intermediate is an integer below 2^24 the result is exact.  The Nq x Nr matrix is never written to memory:
+ * a workgroup owns 128 query rows and walks the reference rows 64 at a time with the running result in registers; the
+ * reference rows are split over up to 16 workgroups per row tile and the partial results are merged by a second, small
+ * launch.  1 <= D <= 2048, at most 2^24 rows; x / q / ref contiguous ([N][D], no row stride) and 16-byte aligned.
+ *
+ * vg_knn_radius2: x f32 [N][D], 1 <= k <= 8, k < N -> r2 f32 [N]: the k-th smallest d2 from row i to the OTHER rows of
+ * x.  Row i is excluded by INDEX, not by value: a duplicate of row i at distance 0 counts.
+ * ws: vg_knn_radius2_ws_bytes(N, D, k) = 4 N (rounded up to 256) + 4 N k splits bytes, 16-byte aligned.  Three launches.
+ *
+ * vg_manifold_cover: q f32 [Nq][D], ref f32 [Nr][D], r2_ref f32 [Nr] -> inside int32 [Nq]: 1 where some j has
+ * d2(q_i, ref_j) <= r2_ref[j], else 0; count int64 [1] (device, 8-byte aligned): the number of ones (an integer sum).
+ * ws: vg_manifold_cover_ws_bytes(Nq, Nr, D) = 4 Nq + 4 Nr (each rounded up to 256) + 4 Nq splits bytes.  Four launches
+ * and one 8-byte memset.
+ * The _ws_bytes queries return VG_EINVAL (negative) for sizes outside the contract.
+ * ---------------------------------------------------------------------------------------- */
+int64_t vg_feat_stats_accum_ws_bytes(int64_t n, int D);
+int vg_feat_stats_accum(const float* x, int64_t n, int D, int64_t row_stride, double* sum, double* outer, void* ws,
+                        int64_t ws_bytes, void* stream);
+int64_t vg_knn_radius2_ws_bytes(int64_t N, int D, int k);
+int vg_knn_radius2(const float* x, int64_t N, int D, int k, float* r2, void* ws, int64_t ws_bytes, void* stream);
+int64_t vg_manifold_cover_ws_bytes(int64_t Nq, int64_t Nr, int D);
+int vg_manifold_cover(const float* q, int64_t Nq, const float* ref, int64_t Nr, int D, const float* r2_ref, int32_t* inside,
+                      int64_t* count, void* ws, int64_t ws_bytes, void* stream);
 /* hipMemsetAsync(p, 0, nbytes) on the stream: optimizer.zero_grad() (vaegan_code.py:103,131-132) over a flat buffer. */
 int vg_memset_zero(void* p, int64_t nbytes, void* stream);
 /* bf16 -> OCP e4m3fn, elementwise: y[i] = fp8(x[i] * 2^shift).  The fp8 copies of activations (shift 0) and of the

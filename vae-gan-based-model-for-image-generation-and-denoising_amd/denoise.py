@@ -2,7 +2,8 @@
 reparameterisation -> Generator on ``clamp(img + sigma*eps, -1, 1)``, reconstruction MSE + KL (not divided by
 the batch, :166), and image-quality metrics on the [0,1]-rescaled images: SSIM (torchmetrics recipe, parity
 unpinned: the package is not installed) and PSNR (listed as intended in the reference README.md:22, implemented
-nowhere in it).  All compute is HIP kernels; Inception-based IS/FID need downloaded weights and are out of scope.
+nowhere in it).  All compute is HIP kernels.  FID (vaegan_code.py:182-183) is computed in the feature space of a pluggable
+``feature_fn`` (metrics.py); InceptionV3 itself needs downloaded weights, so Inception Score is out of scope.
 """
 import math
 from typing import Dict, Iterable, Optional
@@ -11,6 +12,7 @@ import torch
 
 from . import geometry as G
 from . import ops
+from .metrics import FeaturePass
 
 
 @torch.no_grad()
@@ -59,7 +61,7 @@ def denoise_eval(encoder, decoder, img: torch.Tensor, sigma: float = 0.05, eps: 
 
 @torch.no_grad()
 def validation_epoch(encoder, decoder, loader: Iterable[torch.Tensor], n_samples: Optional[int] = None,
-                     sigma: float = 0.05, alpha_kl: float = 0.1, noise_fn=None) -> Dict[str, float]:
+                     sigma: float = 0.05, alpha_kl: float = 0.1, noise_fn=None, feature_fn=None) -> Dict[str, float]:
     """The per-epoch validation loop of the reference trainer, vaegan_code.py:147-191:
 
         encoder.eval(); decoder.eval()                                   (:147-148; the discriminator is not used)
@@ -73,15 +75,20 @@ def validation_epoch(encoder, decoder, loader: Iterable[torch.Tensor], n_samples
     size, as torchmetrics' running sums do).  n_samples defaults to the number of images seen (= len(dataset) for a
     full pass).  noise_fn(i, img) -> (eps, eps_z) injects the two draws of batch i (parity tests); by default they are
     generated on the device.  PSNR (not in the reference, README.md:22 lists it as intended) is that of the mean
-    squared error over every pixel of the pass.  Inception Score / FID need downloaded InceptionV3 weights: not
-    available offline, left out.  Accumulation stays on the device; ONE host sync at the end of the pass.
+    squared error over every pixel of the pass.  Accumulation stays on the device; ONE host sync at the end of the pass.
     Returns python floats: val_loss, ssim, psnr, recon_loss (mean of the batch MSEs), kl_loss (mean of the batch KL
-    sums), samples, batches."""
+    sums), samples, batches.
+    feature_fn (default None: nothing changes): ``images_u8 [b,C,S,S] uint8 device -> f32 [b, D] device``
+    (``metrics.encoder_features(encoder)`` or a network of the caller's): the reconstructions and the clean images go
+    through ``ops.to_u8`` and feature_fn, their f64 running statistics are accumulated on the device per batch
+    (fid.update, :182-183) and the result gains ``fid`` (fid.compute, :185; its last D x D step runs on the host, see
+    ``metrics.frechet_distance``).  Inception Score needs InceptionV3's classifier head: out of scope."""
     encoder.eval(), decoder.eval()                                                   # :147-148
     dev = next(encoder.parameters()).device
     acc = ops.zeros_f32(4, dev)                # [sum(recon + a*kl), sum(b * ssim_b), sum(b * mse_b), sum(kl)]
     seen = batches = 0
     dt, L = encoder._dt, encoder.latent_dim
+    feats = FeaturePass(feature_fn, False) if feature_fn is not None else None
     for i, img in enumerate(loader):
         if not img.is_cuda:
             raise RuntimeError("validation_epoch needs device batches (data.DeviceLoader); there is no CPU path")
@@ -108,6 +115,8 @@ def validation_epoch(encoder, decoder, loader: Iterable[torch.Tensor], n_samples
         ops.axpy(acc[1:2], ssim_b, float(b), out=acc[1:2])
         ops.axpy(acc[2:3], scal[0:1], float(b), out=acc[2:3])
         ops.axpy(acc[3:4], scal[1:2], 1.0, out=acc[3:4])
+        if feats is not None:
+            feats.update(img, recon)
         seen += b
         batches += 1
     if batches == 0:
@@ -115,9 +124,12 @@ def validation_epoch(encoder, decoder, loader: Iterable[torch.Tensor], n_samples
     val_sum, ssim_sum, mse_sum, kl_sum = (float(v) for v in acc.tolist())           # the one host sync
     n = seen if n_samples is None else int(n_samples)
     mse01 = mse_sum / seen / 4.0
-    return {"val_loss": val_sum / n, "ssim": ssim_sum / seen,
-            "psnr": float("inf") if mse01 == 0 else 10.0 * math.log10(1.0 / mse01),
-            "recon_loss": mse_sum / seen, "kl_loss": kl_sum / batches, "samples": seen, "batches": batches}
+    out = {"val_loss": val_sum / n, "ssim": ssim_sum / seen,
+           "psnr": float("inf") if mse01 == 0 else 10.0 * math.log10(1.0 / mse01),
+           "recon_loss": mse_sum / seen, "kl_loss": kl_sum / batches, "samples": seen, "batches": batches}
+    if feats is not None:
+        out["fid"] = feats.fid()
+    return out
 
 
 @torch.no_grad()

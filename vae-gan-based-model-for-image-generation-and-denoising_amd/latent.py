@@ -8,8 +8,9 @@ it reparameterises and decodes.  Here the Encoder's outputs never leave the devi
 one [N, 2L] buffer, ``LatentPrior.fit`` fits the 2L histograms with one HIP call (vg_latent_hist), ``sample_z`` draws
 straight into the Generator's input layout (vg_latent_sample) and ``sample_images`` / ``evaluate_generation`` decode and
 score.  The contracts -- f32 edges as numpy >= 2 computes them, the f64 cdf summed in bin order, the two stated
-deviations -- are in include/vaegan_hip.h, "Latent prior".  All compute is HIP kernels; Inception-based IS/FID need
-downloaded weights and are out of scope.
+deviations -- are in include/vaegan_hip.h, "Latent prior".  All compute is HIP kernels.  FID and precision / recall / F1
+are computed in the feature space of a pluggable ``feature_fn`` (metrics.py; the project's own Encoder by default);
+InceptionV3 itself needs downloaded weights, so Inception Score is out of scope.
 """
 from typing import Dict, Iterable, Optional, Tuple
 
@@ -17,6 +18,7 @@ import torch
 
 from . import geometry as G
 from . import ops
+from .metrics import FeaturePass, _pr_result
 
 
 def _loader_samples(loader) -> int:
@@ -174,7 +176,7 @@ def _normal_z(decoder, b: int, eps: Optional[torch.Tensor]) -> torch.Tensor:
 
 @torch.no_grad()
 def evaluate_generation(decoder, val_loader: Iterable[torch.Tensor], prior: Optional[LatentPrior] = None,
-                        noise_fn=None) -> Dict[str, float]:
+                        noise_fn=None, feature_fn=None, k: int = 3, real_stats=None) -> Dict[str, float]:
     """The generation-evaluation loops of the reference:
 
         decoder.eval()                                                                  (main_vae.py:476 / :546)
@@ -187,13 +189,24 @@ def evaluate_generation(decoder, val_loader: Iterable[torch.Tensor], prior: Opti
     val_loader yields device batches [b,C,S,S] in [-1,1] (data.DeviceLoader).  noise_fn(i, b) injects the draws of batch
     i (parity tests): with a prior it returns (u, v, eps) -- f64 [b,2L], f64 [b,2L], f32 [b,L], see LatentPrior.sample_z --
     and without one the f32 [b, nz] z itself; by default everything is drawn on the device.  SSIM: torchmetrics recipe,
-    parity unpinned (the package is not installed), as in denoise.py.  Inception Score / FID need downloaded InceptionV3
-    weights: not available offline, left out.  Deviation: the logvar clamp of sample_z.  Accumulation stays on the
-    device; ONE host sync at the end of the pass.  Returns python numbers: ssim, samples, batches."""
+    parity unpinned (the package is not installed), as in denoise.py.  Deviation: the logvar clamp of sample_z.
+    Accumulation stays on the device; ONE host sync at the end of the pass.  Returns python numbers: ssim, samples,
+    batches.
+
+    feature_fn (default None: nothing below happens and exactly the three keys above come back): a callable
+    ``images_u8 [b,C,S,S] uint8 device -> f32 [b, D] device`` -- ``metrics.encoder_features(encoder)`` or a network of
+    the caller's (the reference's InceptionV3, :472-473).  Each batch's real and fake images go through ``ops.to_u8``
+    (:492, :498-499) and feature_fn; ``fid.update`` (:500-501) becomes two f64 running-sum kernels per batch, the
+    features stay on the device for the pass, and the result gains ``fid`` (:507), ``precision``, ``recall``, ``f1``
+    (README.md:22, k-th-neighbour manifolds with ``k``) and ``feature_dim``.  real_stats: a ``metrics.FeatureStats`` of the
+    real side computed earlier (the reference recomputes it on every call): the real half of the FID update is skipped.
+    Inception Score needs InceptionV3's classifier head: out of scope.  Still one host sync for everything accumulated on
+    the device, plus the final D x D step of ``metrics.frechet_distance`` on the host."""
     decoder.eval()
     dev = _device_of(decoder, "evaluate_generation")
     acc = ops.zeros_f32(1, dev)
     seen = batches = 0
+    feats = FeaturePass(feature_fn, True, real_stats) if feature_fn is not None else None
     for i, real in enumerate(val_loader):
         if not real.is_cuda:
             raise RuntimeError("evaluate_generation needs device batches (data.DeviceLoader); there is no CPU path")
@@ -207,11 +220,20 @@ def evaluate_generation(decoder, val_loader: Iterable[torch.Tensor], prior: Opti
             z = _normal_z(decoder, b, inj)
         fake = _decode(decoder, z, b)
         ops.axpy(acc, ops.ssim(fake, real), float(b), out=acc)
+        if feats is not None:
+            feats.update(real, fake)
         seen += b
         batches += 1
     if batches == 0:
         raise RuntimeError("evaluate_generation: the loader yielded no batch")
-    return {"ssim": float(acc.item()) / seen, "samples": seen, "batches": batches}   # the one host sync
+    if feats is None:
+        return {"ssim": float(acc.item()) / seen, "samples": seen, "batches": batches}   # the one host sync
+    counts = feats.pr_counts(int(k))
+    ssim_sum, fake_in_real, real_in_fake = torch.cat([acc.double(), counts.double()]).tolist()   # the one host sync
+    out = {"ssim": ssim_sum / seen, "samples": seen, "batches": batches, "fid": feats.fid(), "feature_dim": feats.D}
+    pr = _pr_result(int(fake_in_real), int(real_in_fake), seen, seen, int(k))
+    out.update(precision=pr["precision"], recall=pr["recall"], f1=pr["f1"])
+    return out
 
 
 @torch.no_grad()

@@ -1,0 +1,227 @@
+"""Feature-space generation metrics on the device: FID and the k-nearest-neighbour precision / recall / F1.
+
+Every evaluation loop of the reference ends in ``fid.update(real, real=True); fid.update(fake, real=False); fid.compute()``
+(vaegan_code.py:143-185, gan_code.py:111-145, main_vae.py:472-512, :540-574), and its README.md:22 lists Precision /
+Recall / F1 "computed via manifold distances" (Kynkaanniemi et al. 2019, "Improved Precision and Recall Metric for
+Assessing Generative Models"), which the reference implements nowhere.  This module is everything AFTER a feature vector
+exists; the three kernels behind it are stated in include/vaegan_hip.h, "Feature-space metrics":
+
+    FeatureStats.update      vg_feat_stats_accum   f64 running sums (sum x, sum x x^T) on the f64 MFMA
+    precision_recall         vg_knn_radius2        k-th neighbour radius of every sample, exact-f32 MFMA
+                             vg_manifold_cover     is a sample inside some ball of the other set
+
+The feature extractor is pluggable: ``feature_fn(images_u8 [b,C,S,S] uint8 device) -> f32 [b, D] device``.
+``encoder_features`` wraps the project's own Encoder (no download); a user who has InceptionV3 weights passes a callable of
+their own and gets the reference's FID.  This module never imports a network, so Inception Score stays out of scope.
+Parity with the torchmetrics package itself is unpinned (the package is not installed), as for SSIM: the formulas are
+torchmetrics' ``_compute_fid`` and running sums, checked against an f64 numpy restatement (tests/_metrics_ref.py).
+Precision / recall is single-process: ``FeatureStats.merge`` makes the FID side additive over ranks, the k-NN part needs
+all features in one place.
+"""
+from typing import Callable, Dict, Optional
+
+import numpy as np
+import torch
+
+from . import ops
+
+
+def _check_feats(f, D: Optional[int], what: str) -> None:
+    if not isinstance(f, torch.Tensor) or not f.is_cuda:
+        raise RuntimeError(f"{what} needs features on the MI355X ('cuda'); there is no CPU path")
+    if f.dtype != torch.float32 or f.dim() != 2 or (D is not None and f.shape[1] != D):
+        raise RuntimeError(f"{what}: features must be f32 [b, {'D' if D is None else D}], got {f.dtype} {tuple(f.shape)}")
+
+
+class FeatureStats:
+    """Running first and second moments of a feature stream, as torchmetrics' FrechetInceptionDistance keeps them:
+    ``sum`` f64 [D] (features.double().sum(0)), ``outer`` f64 [D, D] (features.double().T @ features.double()) and the
+    row count ``n`` (a python int: batch sizes are known on the host, no sync).  ``update`` runs on the device and is
+    deterministic; a FeatureStats on the CPU only HOLDS state (``load_state_dict`` of a saved one, ``frechet_distance``)."""
+
+    def __init__(self, D: int, device="cuda"):
+        D = int(D)
+        if not 1 <= D <= 2048:
+            raise RuntimeError(f"FeatureStats: the feature dimension must be in [1, 2048], got {D}")
+        self.D, self.n = D, 0
+        self.sum = torch.zeros(D, dtype=torch.float64, device=device)
+        self.outer = torch.zeros(D, D, dtype=torch.float64, device=device)
+
+    def update(self, feats: torch.Tensor) -> "FeatureStats":
+        """feats f32 [b, D] on the device, any b >= 0 (ragged batches).  No host sync."""
+        if not self.sum.is_cuda:
+            raise RuntimeError("FeatureStats.update needs the statistics on the MI355X ('cuda'); there is no CPU path")
+        _check_feats(feats, self.D, "FeatureStats.update")
+        ops.feat_stats_accum(feats, self.sum, self.outer)
+        self.n += int(feats.shape[0])
+        return self
+
+    def merge(self, other: "FeatureStats") -> "FeatureStats":
+        """Add another stream's sums (another rank's, another shard's): the statistics are additive."""
+        if other.D != self.D:
+            raise RuntimeError(f"FeatureStats.merge: feature dimensions differ ({self.D} vs {other.D})")
+        self.sum += other.sum.to(self.sum.device)
+        self.outer += other.outer.to(self.outer.device)
+        self.n += other.n
+        return self
+
+    def _host(self):
+        return self.sum.cpu().numpy(), self.outer.cpu().numpy()
+
+    def mean(self) -> np.ndarray:
+        """sum / n as a host f64 array [D] (one copy of D doubles)."""
+        if self.n < 1:
+            raise RuntimeError("FeatureStats.mean: no sample yet")
+        return self.sum.cpu().numpy() / self.n
+
+    def cov(self) -> np.ndarray:
+        """(outer - n m m^T) / (n - 1), f64, as torchmetrics; a host array [D, D] (one copy of D + D^2 doubles)."""
+        if self.n < 2:
+            raise RuntimeError("FeatureStats.cov needs at least two samples")
+        s, o = self._host()
+        m = s / self.n
+        return (o - self.n * np.outer(m, m)) / (self.n - 1)
+
+    def state_dict(self) -> Dict[str, torch.Tensor]:
+        """Plain tensors: compute the real side once per data set, save it, reuse it for every checkpoint."""
+        return {"sum": self.sum, "outer": self.outer, "n": torch.tensor(self.n, dtype=torch.int64)}
+
+    def load_state_dict(self, sd: Dict[str, torch.Tensor]) -> "FeatureStats":
+        s, o = sd["sum"], sd["outer"]
+        if (s.dtype != torch.float64 or o.dtype != torch.float64 or tuple(s.shape) != (self.D,)
+                or tuple(o.shape) != (self.D, self.D)):
+            raise RuntimeError(f"FeatureStats: sum must be f64 [{self.D}] and outer f64 [{self.D},{self.D}]")
+        dev = self.sum.device
+        self.sum, self.outer, self.n = s.to(dev).contiguous().clone(), o.to(dev).contiguous().clone(), int(sd["n"])
+        return self
+
+
+def frechet_distance(real: FeatureStats, fake: FeatureStats) -> float:
+    """torchmetrics' ``_compute_fid`` on two sets of running statistics:
+
+        |m1 - m2|^2 + tr S1 + tr S2 - 2 sum Re sqrt(eigvals(S1 S2))
+
+    The sums were accumulated on the device in f64; this last D x D step (mean, covariance, the eigenvalues of a
+    non-symmetric product) runs on the HOST in numpy f64: one copy of 2 (D + D^2) doubles per evaluation pass and the only
+    host work of the metric.  A device eigensolver is deliberately out of scope."""
+    if real.D != fake.D:
+        raise RuntimeError(f"frechet_distance: feature dimensions differ ({real.D} vs {fake.D})")
+    if real.n < 2 or fake.n < 2:
+        raise RuntimeError("frechet_distance needs at least two samples on each side")
+    m1, m2 = real.mean(), fake.mean()
+    s1, s2 = real.cov(), fake.cov()
+    d = m1 - m2
+    c = np.sqrt(np.linalg.eigvals(s1 @ s2).astype(np.complex128)).real.sum()
+    return float(d @ d + np.trace(s1) + np.trace(s2) - 2.0 * c)
+
+
+def _pr_counts(real_feats: torch.Tensor, fake_feats: torch.Tensor, k: int) -> torch.Tensor:
+    """int64 [2] on the device: (fake rows inside the real manifold, real rows inside the fake manifold)."""
+    _check_feats(real_feats, None, "precision_recall")
+    _check_feats(fake_feats, real_feats.shape[1], "precision_recall")
+    counts = torch.empty(2, dtype=torch.int64, device=real_feats.device)
+    r2_real = ops.knn_radius2(real_feats, k)
+    r2_fake = ops.knn_radius2(fake_feats, k)
+    ops.manifold_cover(fake_feats, real_feats, r2_real, count=counts[0:1])
+    ops.manifold_cover(real_feats, fake_feats, r2_fake, count=counts[1:2])
+    return counts
+
+
+def _pr_result(fake_in_real: int, real_in_fake: int, n_real: int, n_fake: int, k: int) -> Dict[str, float]:
+    p, r = fake_in_real / n_fake, real_in_fake / n_real
+    return {"precision": p, "recall": r, "f1": 0.0 if p + r == 0 else 2.0 * p * r / (p + r),
+            "n_real": n_real, "n_fake": n_fake, "k": k}
+
+
+def precision_recall(real_feats: torch.Tensor, fake_feats: torch.Tensor, k: int = 3) -> Dict[str, float]:
+    """Improved precision and recall (Kynkaanniemi et al. 2019): the manifold of a set is the union of the balls around
+    its samples that reach to each sample's k-th nearest neighbour in the set.
+        precision = share of fake rows inside the real manifold,  recall = share of real rows inside the fake manifold,
+        f1 = their harmonic mean (0 when both are 0);  plus n_real, n_fake, k.
+    real_feats f32 [Nr, D], fake_feats f32 [Nf, D] on the device, k < min(Nr, Nf), k <= 8.  Distances in exact f32 on the
+    MFMA (include/vaegan_hip.h states the form and its error bound); no N x N matrix is ever allocated.  Single process;
+    ONE host sync at the end (two integers)."""
+    k = int(k)
+    c = _pr_counts(real_feats, fake_feats, k).tolist()                                 # the one host sync
+    return _pr_result(c[0], c[1], real_feats.shape[0], fake_feats.shape[0], k)
+
+
+_ARANGE = {}
+
+
+def _arange(n: int, device) -> torch.Tensor:
+    key = (n, str(device))
+    t = _ARANGE.get(key)
+    if t is None:
+        t = _ARANGE[key] = torch.arange(n, dtype=torch.int64, device=device)
+    return t
+
+
+def encoder_features(encoder, part: str = "mu") -> Callable[[torch.Tensor], torch.Tensor]:
+    """-> ``feature_fn(images_u8) -> f32 [b, L]`` (``part="mu"``) or ``[b, 2L]`` (``part="mulv"``: mu | logvar): uint8
+    [b,C,S,S] device images -> x / 255 * 2 - 1 (the data path's ToTensor + Normalize arithmetic, (u/255 - 0.5)/0.5) ->
+    the eval-mode Encoder through the engine.  uint8 in, because that is what the reference hands to its metrics
+    (vaegan_code.py:176-183) and what ``ops.to_u8`` produces.  The features are the project's own: an FID in this space
+    is comparable between checkpoints scored with the SAME encoder, not with published Inception FIDs."""
+    if part not in ("mu", "mulv"):
+        raise RuntimeError(f"encoder_features: part must be 'mu' or 'mulv', got {part!r}")
+    width = encoder.latent_dim * (1 if part == "mu" else 2)
+
+    @torch.no_grad()
+    def feature_fn(images_u8: torch.Tensor) -> torch.Tensor:
+        if not images_u8.is_cuda:
+            raise RuntimeError("encoder_features needs device images ('cuda'); there is no CPU path")
+        if images_u8.dtype != torch.uint8 or images_u8.dim() != 4:
+            raise RuntimeError("encoder_features: images must be uint8 [b,C,S,S]")
+        encoder.eval()
+        b, C, H, W = images_u8.shape
+        planes = images_u8.contiguous().view(b * C, H, W, 1)               # every channel plane as a 1-channel image
+        x = ops.gather_normalize_u8(planes, _arange(b * C, images_u8.device)).view(b, C, H, W)
+        mulv, _ = encoder.engine_forward(x, keep=False)
+        out = torch.empty(b, width, dtype=torch.float32, device=images_u8.device)
+        out.copy_(mulv[:, :width])                                          # widening copy of the real columns
+        return out
+
+    return feature_fn
+
+
+class FeaturePass:
+    """What an evaluation loop keeps while it runs with a ``feature_fn``: per-batch FID statistics of both sides and,
+    with ``keep=True``, the features themselves (on the device) for precision / recall at the end of the pass."""
+
+    def __init__(self, feature_fn, keep: bool, real_stats: Optional[FeatureStats] = None):
+        self.fn, self.keep, self.given_real = feature_fn, keep, real_stats
+        self.real, self.fake = real_stats, None
+        self.real_feats, self.fake_feats = [], []
+        self.D = real_stats.D if real_stats is not None else None
+
+    def _features(self, img: torch.Tensor) -> torch.Tensor:
+        f = self.fn(ops.to_u8(img))
+        _check_feats(f, self.D, "feature_fn")
+        if f.shape[0] != img.shape[0]:
+            raise RuntimeError(f"feature_fn returned {f.shape[0]} rows for {img.shape[0]} images")
+        if self.D is None:
+            self.D = int(f.shape[1])
+        return f.contiguous()
+
+    def update(self, real: torch.Tensor, fake: torch.Tensor) -> None:
+        """real, fake: f32 [b,C,S,S] device images in [-1, 1]."""
+        need_real = self.given_real is None or self.keep
+        fr = self._features(real) if need_real else None
+        ff = self._features(fake)
+        if self.fake is None:
+            self.fake = FeatureStats(self.D, ff.device)
+            if self.real is None:
+                self.real = FeatureStats(self.D, ff.device)
+        if self.given_real is None:
+            self.real.update(fr)
+        self.fake.update(ff)
+        if self.keep:
+            self.real_feats.append(fr)
+            self.fake_feats.append(ff)
+
+    def pr_counts(self, k: int) -> torch.Tensor:
+        return _pr_counts(torch.cat(self.real_feats), torch.cat(self.fake_feats), k)
+
+    def fid(self) -> float:
+        return frechet_distance(self.real, self.fake)

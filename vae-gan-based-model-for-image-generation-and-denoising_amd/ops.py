@@ -922,6 +922,98 @@ def to_u8(x, grid_cols=0):
     return y
 
 
+def _ws_query(nbytes: int, what: str) -> int:
+    if nbytes < 0:
+        L.check(int(nbytes), what)
+    return int(nbytes)
+
+
+def _feature_rows(x, what: str, name: str = "x"):
+    """f32 [N,D] device matrix whose columns are adjacent in memory -> (N, D, row stride in elements)."""
+    if not x.is_cuda:
+        raise RuntimeError("vaegan_amd ops need tensors on the MI355X (cuda) device; there is no CPU path")
+    if x.dtype != torch.float32 or x.dim() != 2 or x.shape[1] < 1:
+        raise RuntimeError(f"{what}: {name} must be an f32 [N,D] tensor with D >= 1")
+    N, D = x.shape
+    stride = x.stride(0) if N > 1 else D
+    if (D > 1 and N > 0 and x.stride(1) != 1) or (N > 1 and stride < D):
+        raise RuntimeError(f"{what}: the columns of {name} must be adjacent in memory (stride(1) == 1, stride(0) >= D)")
+    return N, D, stride
+
+
+def feat_stats_accum(x, sum, outer):
+    """FID's running statistics on the device (vg_feat_stats_accum): sum f64 [D] += column sums of x, outer f64 [D,D] +=
+    x^T x, every product and addition in f64 on the exactly converted f32 rows of x f32 [n,D] (n >= 0; x may be a view
+    whose rows are further apart than D).  Deterministic; in place; no host sync.  -> (sum, outer)."""
+    n, D, stride = _feature_rows(x, "feat_stats_accum")
+    _need_cuda(sum, outer)
+    if (sum.dtype != torch.float64 or outer.dtype != torch.float64 or tuple(sum.shape) != (D,)
+            or tuple(outer.shape) != (D, D)):
+        raise RuntimeError(f"feat_stats_accum: sum must be f64 [{D}] and outer f64 [{D},{D}]")
+    if n == 0:
+        return sum, outer
+    lib = L.load()
+    nbytes = _ws_query(lib.vg_feat_stats_accum_ws_bytes(n, D), "vg_feat_stats_accum_ws_bytes")
+    ws = WS.get("metrics", nbytes, x.device)
+    L.check(lib.vg_feat_stats_accum(x.data_ptr(), n, D, stride, sum.data_ptr(), outer.data_ptr(), ws.data_ptr(),
+                                    ws.numel() * 4, L.stream_ptr()), "vg_feat_stats_accum")
+    return sum, outer
+
+
+def knn_radius2(x, k=3):
+    """r2 f32 [N]: the k-th smallest squared Euclidean distance from row i of x f32 [N,D] to the OTHER rows (row i is left
+    out by index; a duplicate row counts with distance 0).  vg_knn_radius2: exact-f32 MFMA, the N x N matrix is never
+    written.  1 <= k <= 8, k < N.  No host sync."""
+    N, D, stride = _feature_rows(x, "knn_radius2")
+    k = int(k)
+    if not 1 <= k <= 8 or k >= N:
+        raise RuntimeError(f"knn_radius2: k must be in [1, 8] and below the number of rows ({N}), got {k}")
+    if N > 1 and stride != D:
+        x = x.contiguous()
+    x = _aligned16(x)
+    lib = L.load()
+    nbytes = _ws_query(lib.vg_knn_radius2_ws_bytes(N, D, k), "vg_knn_radius2_ws_bytes")
+    ws = WS.get("metrics", nbytes, x.device)
+    r2 = torch.empty(N, dtype=torch.float32, device=x.device)
+    L.check(lib.vg_knn_radius2(x.data_ptr(), N, D, k, r2.data_ptr(), ws.data_ptr(), ws.numel() * 4, L.stream_ptr()),
+            "vg_knn_radius2")
+    return r2
+
+
+def _aligned16(x):
+    """The distance kernels read rows as 16-byte vectors: a view that starts off that grid is copied once."""
+    return x if x.data_ptr() % 16 == 0 else x.clone()
+
+
+def manifold_cover(q, ref, r2_ref, count=None):
+    """inside int32 [Nq]: 1 where row i of q f32 [Nq,D] lies in the ball of radius^2 r2_ref[j] around some row j of ref
+    f32 [Nr,D] (d2 <= r2_ref[j]); count int64 [1] (allocated unless given): the number of ones, on the device
+    (vg_manifold_cover).  -> (inside, count).  No host sync."""
+    Nq, D, sq = _feature_rows(q, "manifold_cover", "q")
+    Nr, Dr, sr = _feature_rows(ref, "manifold_cover", "ref")
+    _need_cuda(r2_ref)
+    if Nq < 1 or Nr < 1 or D != Dr:
+        raise RuntimeError("manifold_cover: q [Nq,D] and ref [Nr,D] must be non-empty and share D")
+    if r2_ref.dtype != torch.float32 or tuple(r2_ref.shape) != (Nr,):
+        raise RuntimeError(f"manifold_cover: r2_ref must be f32 [{Nr}]")
+    if Nq > 1 and sq != D:
+        q = q.contiguous()
+    if Nr > 1 and sr != D:
+        ref = ref.contiguous()
+    q, ref = _aligned16(q), _aligned16(ref)
+    if count is None:
+        count = torch.empty(1, dtype=torch.int64, device=q.device)
+    elif not count.is_cuda or count.dtype != torch.int64 or count.numel() != 1:
+        raise RuntimeError("manifold_cover: count must be an int64 [1] device tensor")
+    lib = L.load()
+    nbytes = _ws_query(lib.vg_manifold_cover_ws_bytes(Nq, Nr, D), "vg_manifold_cover_ws_bytes")
+    ws = WS.get("metrics", nbytes, q.device)
+    inside = torch.empty(Nq, dtype=torch.int32, device=q.device)
+    L.check(lib.vg_manifold_cover(q.data_ptr(), Nq, ref.data_ptr(), Nr, D, r2_ref.data_ptr(), inside.data_ptr(),
+                                  count.data_ptr(), ws.data_ptr(), ws.numel() * 4, L.stream_ptr()), "vg_manifold_cover")
+    return inside, count
+
+
 def noisy_clamp_to_nhwc(x, eps, sigma, CP, dtype, lo=-1.0, hi=1.0):
     """-> (noisy NHWC engine tensor, noisy NCHW f32)."""
     _need_cuda(x, eps)
