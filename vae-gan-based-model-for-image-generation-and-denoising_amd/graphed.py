@@ -37,7 +37,7 @@ from typing import Callable, Optional, Sequence
 
 import torch
 
-from .engine import no_gc_while_capturing
+from .capture import HostMirrors, capture, replay
 
 
 def _flatten(out):
@@ -62,7 +62,7 @@ class GraphedStep:
         self.fn, self.modules, self.optimizers, self.warmup = fn, tuple(modules), tuple(optimizers), max(1, int(warmup))
         self.max_graphs = max(1, int(max_graphs))
         self.scalar_key = scalar_key
-        # key -> (graph, static inputs, outputs, bn-tick deltas, step-count deltas); least recently used first
+        # key -> capture.Captured; least recently used first
         self._graphs = OrderedDict()
         self._seen = OrderedDict()  # key -> eager calls so far (bounded like _graphs)
         self._pool = None           # one memory pool for every capture of this step (created with the first one)
@@ -81,13 +81,11 @@ class GraphedStep:
         hit = self._graphs.get(key)
         if hit is not None:
             self._graphs.move_to_end(key)
-            graph, sin, out, dticks, dsteps = hit
-            for s, t in zip(sin, tensors):
+            for s, t in zip(hit.sin, tensors):
                 if s.data_ptr() != t.data_ptr():
                     s.copy_(t)
-            graph.replay()
-            self._bump(dticks, dsteps)
-            return out
+            replay(hit)
+            return hit.out
         n = self._seen.get(key, 0)
         if n < self.warmup:
             self._seen[key] = n + 1
@@ -100,54 +98,16 @@ class GraphedStep:
             self._graphs.popitem(last=False)
         if self._pool is None:
             self._pool = torch.cuda.graph_pool_handle()
-        # ---- capture ----
         sin = [t.clone() for t in tensors]
-        engines = self._engines()
-        for e in engines:
-            e.invalidate()                              # the captured sequence must contain the operand re-packs
-        torch.cuda.synchronize()
-        ticks = [e.pending_bn_ticks for e in engines]
-        steps = [o.steps for o in self.optimizers]
-        graph = torch.cuda.CUDAGraph()
-        cap = torch.cuda.Stream(device=sin[0].device if sin else None)
-        cap.wait_stream(torch.cuda.current_stream())
-        try:
-            with no_gc_while_capturing(), torch.cuda.stream(cap):
-                # global capture mode (the default): the autograd engine runs the backward nodes on its own device thread,
-                # which launches into this stream -- their work is captured with the rest
-                graph.capture_begin(pool=self._pool)
-                try:
-                    out = self.fn(*sin, **scalars)
-                finally:
-                    graph.capture_end()
-        except BaseException:
-            # nothing was executed: put the host-side mirrors back and let the caller run eagerly / try again
-            for e, t in zip(engines, ticks):
-                e.pending_bn_ticks = t
-                e.invalidate()
-            for o, s in zip(self.optimizers, steps):
-                o.steps = s
-            raise
-        torch.cuda.current_stream().wait_stream(cap)
-        if any(not t.is_cuda for t in _flatten(out)):
+        # global capture mode (torch's default): the autograd engine runs the backward nodes on its own device thread,
+        # which launches into the capturing stream -- their work is captured with the rest (capture.capture)
+        cap = capture(lambda *s: self.fn(*s, **scalars), sin, HostMirrors(self._engines(), self.optimizers),
+                      sin[0].device if sin else None, pool=self._pool, error_mode="global")
+        if any(not t.is_cuda for t in _flatten(cap.out)):
             raise RuntimeError("graphed step: the step function must return device tensors")
-        # capture only records: undo the host-side counter changes it made, then replay for real
-        dticks = [e.pending_bn_ticks - t for e, t in zip(engines, ticks)]
-        dsteps = [o.steps - s for o, s in zip(self.optimizers, steps)]
-        for e, t in zip(engines, ticks):
-            e.pending_bn_ticks = t
-        for o, s in zip(self.optimizers, steps):
-            o.steps = s
-        self._graphs[key] = (graph, sin, out, dticks, dsteps)
-        graph.replay()
-        self._bump(dticks, dsteps)
-        return out
-
-    def _bump(self, dticks, dsteps) -> None:
-        for e, d in zip(self._engines(), dticks):
-            e.pending_bn_ticks += d
-        for o, d in zip(self.optimizers, dsteps):
-            o.steps += d
+        self._graphs[key] = cap
+        replay(cap)
+        return cap.out
 
 
 def graphed(fn, modules: Sequence = (), optimizers: Sequence = (), warmup: int = 2, max_graphs: int = 2,

@@ -16,7 +16,8 @@ import torch
 
 from . import geometry as G
 from . import ops
-from .engine import GradSink, bump_weights_epoch, no_gc_while_capturing
+from .capture import HostMirrors, capture, replay
+from .engine import GradSink, bump_weights_epoch
 
 
 class _Graphed:
@@ -40,48 +41,26 @@ class _Graphed:
                tuple(n.training for n in self._nets), None if noise is None else noise.state.data_ptr())
         self._gnoise = noise
         st = getattr(self, "_gstate", None)
-        if st is not None and st[0] == key:
-            _, graph, sin, sout, dticks, dsteps = st[:6]
-            for s, t in zip(sin, tensors):
+        if st is not None and st.key == key:
+            for s, t in zip(st.sin, tensors):
                 if s is not None:
                     s.copy_(t)
-            graph.replay()
-            self._bump(dticks, dsteps)
-            return sout
+            replay(st)
+            return st.out
         if getattr(self, "_gwarm", None) != key:
             self._gwarm, self._gstate = key, None
             return self.train_step(*tensors, **scalars)
         sin = [None if t is None else t.clone() for t in tensors]      # None: drawn on the device inside the graph
-        for n in self._nets:
-            n._engine.invalidate()                     # the captured sequence must contain the operand re-packs
-        torch.cuda.synchronize()
-        ticks = [n._engine.pending_bn_ticks for n in self._nets]
-        steps = [o.steps for o in self._opts]
-        graph = torch.cuda.CUDAGraph()
-        cap = torch.cuda.Stream(device=sin[0].device)
-        cap.wait_stream(torch.cuda.current_stream())
-        with no_gc_while_capturing(), torch.cuda.stream(cap):
-            graph.capture_begin(capture_error_mode="thread_local")   # see trainer.py: other threads (c10d watchdog) may poll events
-            sout = self.train_step(*sin, **scalars)
-            graph.capture_end()
-        torch.cuda.current_stream().wait_stream(cap)
-        # capture only records: undo the host-side counter changes it made, then replay for real
-        dticks = [n._engine.pending_bn_ticks - t for n, t in zip(self._nets, ticks)]
-        dsteps = [o.steps - s for o, s in zip(self._opts, steps)]
-        for n, t in zip(self._nets, ticks):
-            n._engine.pending_bn_ticks = t
-        for o, s in zip(self._opts, steps):
-            o.steps = s
-        self._gstate = (key, graph, sin, sout, dticks, dsteps, noise)   # noise: keeps the captured state buffer alive
-        graph.replay()
-        self._bump(dticks, dsteps)
-        return sout
-
-    def _bump(self, dticks, dsteps) -> None:
-        for n, d in zip(self._nets, dticks):
-            n._engine.pending_bn_ticks += d
-        for o, d in zip(self._opts, dsteps):
-            o.steps += d
+        try:
+            # thread_local: see capture.capture (the c10d watchdog may poll events); keep: the captured state buffer
+            st = self._gstate = capture(lambda *s: self.train_step(*s, **scalars), sin,
+                                        HostMirrors([n._engine for n in self._nets], self._opts), sin[0].device,
+                                        key=key, error_mode="thread_local", keep=noise)
+        except BaseException:
+            self._gwarm = self._gstate = None          # nothing ran: the next call warms up again
+            raise
+        replay(st)
+        return st.out
 
 
 def _need_cuda(t: torch.Tensor, what: str) -> None:

@@ -14,7 +14,8 @@ import torch
 
 from . import geometry as G
 from . import ops
-from .engine import GradSink, no_gc_while_capturing
+from .capture import CaptureRefused, HostMirrors, capture, replay
+from .engine import GradSink
 
 LOSS_NAMES = ("recon_loss", "kl_loss", "g_loss_adv", "d_loss_1", "d_loss_2")
 
@@ -75,7 +76,7 @@ class VAEGANTrainer:
         self.noise = None               # ops.NoiseStream for the in-kernel randn_like draws (created on first use)
         self._noise_pinned_seed = None  # torch device seed at the time a checkpoint's noise stream was restored
         self._bucket_plans = {}
-        self._graph = None              # (key, [hipGraph segments], [collectives between them], static in, static out)
+        self._graph = None              # capture.Captured: key, [hipGraph segments], [collectives between them], static in, ...
         self._warm_key = None
         self._cut_hook = None           # set while capturing: splits the iteration into graph segments
         self._inline_failed = False     # capturing the collectives inside the graph failed once: use the segmented form
@@ -305,7 +306,7 @@ class VAEGANTrainer:
         """The static image buffer the captured iteration reads ([B, C, H, W] f32), or None before a capture.  A loader
         that assembles its batches straight into it (data.DeviceLoader.bind_output) hands them to train_step_graphed
         without the device-to-device copy; pass the SAME tensor as `real`."""
-        return None if self._graph is None else self._graph[3][0]
+        return None if self._graph is None else self._graph.sin[0]
 
     def train_step_graphed(self, real: torch.Tensor, epoch: int, eps_z: Optional[torch.Tensor] = None,
                            eps_real: Optional[torch.Tensor] = None,
@@ -325,16 +326,16 @@ class VAEGANTrainer:
         if not inject:
             self._noise_stream(real.device)         # exists (and is keyed on the current seed) before the key is formed
         key = self._capture_key(real, epoch, inject)
-        if self._graph is not None and self._graph[0] == key:
-            _, graphs, cuts, sin, sout = self._graph[:5]
+        g = self._graph
+        if g is not None and g.key == key:
+            sin = g.sin
             if real.data_ptr() != sin[0].data_ptr():    # a batch assembled in graph_input() needs no copy
                 sin[0].copy_(real)
             if inject:
                 sin[1].copy_(eps_z), sin[2].copy_(eps_real), sin[3].copy_(eps_recon)
-            self._replay(graphs, cuts)
-            self._advance_host_counters()
-            self.losses = sout
-            return sout
+            replay(g)
+            self.losses = g.out
+            return g.out
         if self._warm_key != key:
             self._warm_key = key
             self._graph = None
@@ -347,7 +348,7 @@ class VAEGANTrainer:
         # work) keep the segmented form; if the inline capture fails on some stack the segmented one is tried next.
         inline = self.reducer is not None and bool(getattr(self.reducer, "capturable", False)) and not self._inline_failed
         try:
-            graphs, cuts, sout, dcount = self._capture(sin, epoch, inline)
+            g = self._capture(key, sin, epoch, inline)
         except Exception as ex:                     # noqa: BLE001
             if not inline:
                 raise
@@ -355,117 +356,43 @@ class VAEGANTrainer:
             print(f"[vaegan_amd] capturing the gradient collectives inside the hipGraph failed ({ex!r}); "
                   f"falling back to graph segments cut at the collectives", file=sys.stderr)
             self._inline_failed = True
-            graphs, cuts, sout, dcount = self._capture(sin, epoch, False)
-        self._graph = (key, graphs, cuts, sin, sout, dcount)
-        self._replay(graphs, cuts)
-        self._advance_host_counters()
-        self.losses = sout
-        return sout
+            g = self._capture(key, sin, epoch, False)
+        self._graph = g
+        replay(g)
+        self.losses = g.out
+        return g.out
 
-    def _capture(self, sin, epoch, inline):
-        """Capture one iteration on the static inputs `sin`.  inline: the reducer's collectives are recorded into the graph
-        (one segment); else the graph is cut at every hand-off to the reducer and the collectives run between the segment
-        replays.  Returns (graphs, cuts, static output, per-iteration deltas of the reducer's counters).  Executes nothing;
-        on failure the trainer is exactly where it was."""
-        for eng in (self.E._engine, self.G._engine, self.D._engine):
-            eng.invalidate()                       # the captured sequence must contain the operand re-packs
-        # Nothing of torch.distributed may be in flight while a stream is capturing: c10d's watchdog thread polls
-        # unfinished collectives with hipEventQuery, which is illegal next to a capture (the abort recorded in round 1).
-        # Structural guard rather than luck: wait for every collective this trainer launched, drain the device, and
-        # REFUSE to capture if the reducer still reports outstanding work.
-        if self.reducer is not None and hasattr(self.reducer, "drain"):
-            self.reducer.drain()
-        torch.cuda.synchronize()
-        if self.reducer is not None and getattr(self.reducer, "outstanding", lambda: 0)() != 0:
-            raise RuntimeError("hipGraph capture refused: the gradient reducer still has collectives in flight")
-        ticks = [m._engine.pending_bn_ticks for m in (self.E, self.G, self.D)]
-        steps = [o.steps for o in (self.opt_E, self.opt_G, self.opt_D)]
-        cnames = ("collectives", "bytes_reduced", "stat_collectives")
-        counts = [getattr(self.reducer, n, 0) for n in cnames] if self.reducer is not None else None
-        graphs, cuts = [], []
-        pool = torch.cuda.graph_pool_handle()
-        cap = torch.cuda.Stream(device=sin[0].device)
-        cap.wait_stream(torch.cuda.current_stream())
+    def _capture(self, key, sin, epoch, inline):
+        """Capture one iteration on the static inputs `sin` (capture.capture).  inline: the reducer's collectives are
+        recorded into the graph (one segment, and a replay advances the reducer's counters with the other host mirrors);
+        else the graph is cut at every hand-off to the reducer and the collectives run between the segment replays.
+        Executes nothing; on failure the trainer is exactly where it was."""
+        def quiesce():
+            # Nothing of torch.distributed may be in flight while a stream is capturing: c10d's watchdog thread polls
+            # unfinished collectives with hipEventQuery, which is illegal next to a capture (the abort recorded in round
+            # 1).  Structural guard rather than luck: wait for every collective this trainer launched and REFUSE to
+            # capture if the reducer still reports outstanding work (capture.capture then drains the device).
+            if self.reducer is not None and hasattr(self.reducer, "drain"):
+                self.reducer.drain()
+            if self.reducer is not None and getattr(self.reducer, "outstanding", lambda: 0)() != 0:
+                raise CaptureRefused("hipGraph capture refused: the gradient reducer still has collectives in flight")
 
-        def begin():
-            g = torch.cuda.CUDAGraph()
-            # thread-local capture mode: torch.distributed's watchdog thread polls finished collectives with
-            # hipEventQuery at its own pace; under the default (global) mode such a call from ANOTHER thread while
-            # this one captures is an error that takes the process down (seen once in four runs with RCCL)
-            g.capture_begin(pool=pool, capture_error_mode="thread_local")
-            graphs.append(g)
+        def set_cut_hook(cut):                     # inline: _cut runs the collective at once, i.e. records it
+            self._cut_hook = None if inline else cut
 
-        def cut(collective):
-            if inline:
-                collective()                       # recorded: a fork onto / a join from RCCL's stream inside the graph
-                return
-            graphs[-1].capture_end()               # close this segment, remember the collective, open the next
-            cuts.append(collective)
-            begin()
-
-        def restore_host_counters():               # capture only records: undo the host-side counter changes it made
-            for m, t in zip((self.E, self.G, self.D), ticks):
-                m._engine.pending_bn_ticks = t
-            for o, st in zip((self.opt_E, self.opt_G, self.opt_D), steps):
-                o.steps = st
-            deltas = None
-            if counts is not None:
-                deltas = [getattr(self.reducer, n, 0) - c for n, c in zip(cnames, counts)]
-                for n, c in zip(cnames, counts):
-                    if hasattr(self.reducer, n):
-                        setattr(self.reducer, n, c)
-            return deltas
-
-        with no_gc_while_capturing(), torch.cuda.stream(cap):
-            self._cut_hook = cut
-            try:
-                begin()
-                sout = self.train_step(sin[0], epoch, sin[1], sin[2], sin[3])
-                graphs[-1].capture_end()
-            except BaseException:
-                # leave no stream behind in capture mode and no half-built state: nothing was executed, so after
-                # this the trainer is exactly where it was before the call and can run eagerly (or capture again)
-                try:
-                    graphs[-1].capture_end()
-                except Exception:
-                    pass
-                restore_host_counters()
-                if self.reducer is not None and hasattr(self.reducer, "forget_pending"):
-                    self.reducer.forget_pending()
-                self._graph, self._warm_key = None, None
-                for eng in (self.E._engine, self.G._engine, self.D._engine):
-                    eng.invalidate()
-                raise
-            finally:
-                self._cut_hook = None
-        torch.cuda.current_stream().wait_stream(cap)
-        deltas = restore_host_counters()           # then replay for real
-        dcount = dict(zip(cnames, deltas)) if (inline and deltas is not None) else None
-        return graphs, cuts, sout, dcount
-
-    @staticmethod
-    def _replay(graphs, cuts) -> None:
-        for i, g in enumerate(graphs):
-            g.replay()
-            if i < len(cuts):
-                cuts[i]()                       # the collective that separates segment i from segment i + 1
-
-    def _advance_host_counters(self) -> None:
-        """What one iteration does to host-side mirrors: BatchNorm forward counts (E 1, G 1, D 2*d_iters+1) and
-        optimizer step counts (the authoritative Adam step counter lives on the device); with collectives captured
-        inside the graph also the reducer's statistics counters (a replay runs no Python of the reducer)."""
-        dcount = self._graph[5] if (self._graph is not None and len(self._graph) > 5) else None
-        if dcount and self.reducer is not None:
-            for n, d in dcount.items():
-                if hasattr(self.reducer, n):
-                    setattr(self.reducer, n, getattr(self.reducer, n) + d)
-        if self.E.training:
-            self.E._engine.pending_bn_ticks += 1
-            self.G._engine.pending_bn_ticks += 1
-            self.D._engine.pending_bn_ticks += 2 * self.d_iters + 1
-        self.opt_E.steps += 1
-        self.opt_G.steps += 1
-        self.opt_D.steps += self.d_iters
+        mirrors = HostMirrors([m._engine for m in (self.E, self.G, self.D)], (self.opt_E, self.opt_G, self.opt_D),
+                              self.reducer, replay_reducer=inline)
+        try:
+            return capture(lambda *s: self.train_step(s[0], epoch, *s[1:]), sin, mirrors, sin[0].device, key=key,
+                           pool=torch.cuda.graph_pool_handle(), error_mode="thread_local", pre_capture=quiesce,
+                           install_cut=set_cut_hook)
+        except CaptureRefused:
+            raise
+        except BaseException:
+            if self.reducer is not None and hasattr(self.reducer, "forget_pending"):
+                self.reducer.forget_pending()
+            self._graph, self._warm_key = None, None
+            raise
 
     # ---- checkpoint / resume ----------------------------------------------------------------------------------
     # The reference only ever writes `decoder.state_dict()` (vaegan_code.py:193; main_vae.py:204-205 also the
