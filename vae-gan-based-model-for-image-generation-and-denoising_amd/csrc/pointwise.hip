@@ -597,8 +597,12 @@ __global__ void mse_final_kernel(const float* __restrict__ ws, int nparts, doubl
     if (threadIdx.x == 0) loss[0] = (float)(s / n);
 }
 
+// out = a + alpha * b as the f32 expression reads: the product rounded, then the sum.  Contraction OFF: hipcc otherwise
+// forms one fma (through __fmul_rn / __fadd_rn too, which are plain operators to it), whose result differs from the
+// host's `a + alpha * b` in the last bit for about a fifth of the elements.
 __global__ __launch_bounds__(256) void axpy_kernel(const float* __restrict__ a, const float* __restrict__ b,
                                                    float alpha, float* __restrict__ out, int64_t n) {
+#pragma clang fp contract(off)
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
         out[i] = a[i] + alpha * b[i];
 }
@@ -626,7 +630,11 @@ __global__ __launch_bounds__(256) void ssim_kernel(const float* __restrict__ a, 
         const int64_t pl = i / ((int64_t)IW * IH);
         const float* pa = a + pl * H * W;
         const float* pb = b + pl * H * W;
-        float ma = 0.f, mb = 0.f, saa = 0.f, sbb = 0.f, sab = 0.f;
+        // Second moments about the window's centre pixel (a variance does not move with the origin): E[x^2] - E[x]^2 of
+        // the raw values cancels ~1e-7 against c2 = 9e-4 and put flat windows 1.2e-4 off in f32; about the centre a flat
+        // window has exactly zero variance and a smooth one a small cancellation.
+        const float ca = (pa[y * W + x] + 1.f) * 0.5f, cb = (pb[y * W + x] + 1.f) * 0.5f;
+        float ma = 0.f, mb = 0.f, da = 0.f, db = 0.f, saa = 0.f, sbb = 0.f, sab = 0.f;
         for (int dy = -5; dy <= 5; ++dy) {
             const int yy = y + dy;                              // interior pixels never need the reflect
             const float gy = g[dy + 5];
@@ -634,10 +642,12 @@ __global__ __launch_bounds__(256) void ssim_kernel(const float* __restrict__ a, 
                 const float w = gy * g[dx + 5];
                 const float va = (pa[yy * W + x + dx] + 1.f) * 0.5f;
                 const float vb = (pb[yy * W + x + dx] + 1.f) * 0.5f;
-                ma += w * va; mb += w * vb; saa += w * va * va; sbb += w * vb * vb; sab += w * va * vb;
+                const float ua = va - ca, ub = vb - cb;
+                ma += w * va; mb += w * vb; da += w * ua; db += w * ub;
+                saa += w * ua * ua; sbb += w * ub * ub; sab += w * ua * ub;
             }
         }
-        const float vaa = saa - ma * ma, vbb = sbb - mb * mb, vab = sab - ma * mb;
+        const float vaa = saa - da * da, vbb = sbb - db * db, vab = sab - da * db;
         acc += (double)(((2.f * ma * mb + c1) * (2.f * vab + c2)) / ((ma * ma + mb * mb + c1) * (vaa + vbb + c2)));
     }
     acc = wave_sum_d(acc);
