@@ -6,7 +6,8 @@
 // sum: a workgroup owns a contiguous block of rows, each thread a fixed 4-channel column
 // (16-byte loads, fully coalesced), partial sums go wave -> LDS -> one slab row per
 // workgroup, and a one-thread-per-channel finalize kernel adds the slab rows in fixed order
-// in double precision.  HBM-bound: ideal traffic is one read (+ one write) of the tensor.
+// in double precision.  Ideal traffic is one read (+ one write) of the tensor; the elementwise passes (normalise +
+// activation, backward apply) use the same thread -> column mapping and reach 0.75 of the HBM rate on the largest tensors.
 #include "common.hpp"
 
 namespace {
@@ -302,48 +303,174 @@ __global__ void bn_eval_kernel(const float* gamma, const float* beta, const floa
     shift[c] = (beta ? beta[c] : 0.f) - rmean[c] * sc;
 }
 
-template <int DT>
+// ---- streaming passes over a [rows][C] tensor (normalise + activation, backward apply) -------------------------------
+// A thread owns VW consecutive channels -- 16 bytes: 8 channels of bf16 when C % 8 == 0, 4 channels of f32; 8 bytes (4
+// channels of bf16) otherwise -- and walks rows, with col_reduce_kernel's thread -> (row slot, channel column) mapping:
+// min(C / VW, 256) threads per row, 256 / that rows per pass (leftover threads idle), blockIdx.y the block of 256 columns.
+// blockIdx = (row block, column block, group): a workgroup never straddles a group, so the per-channel coefficients of its
+// group are loaded ONCE into registers before the row loop, and the loop has no division: the offset advances by
+// rows-per-pass * C.  Four rows (4 x 16 bytes per tensor) are in flight per thread; a row block's last trip may be short.
+constexpr int EW_UNROLL = 4;
+// Grid cap = the workgroups that are resident at once on the 256 CUs, so that larger tensors give each thread several trips
+// of EW_UNROLL rows and no second, partly filled round of workgroups follows: 4 per CU for the forward pass; 3 per CU for
+// the backward apply, whose 7 coefficient vectors + 8 packed vectors in flight take 164 VGPRs with 8 channels per thread.
+constexpr int EW_FWD_WGS = 1024, EW_BWD_WGS = 768;
+// Below 4 MiB (VG_BN_WIDE_MIN) a bf16 tensor keeps 4 channels (8 bytes) per thread: such a launch is one pass per workgroup
+// and one round trip long, and what it waits for is its coefficients (seven vectors per thread in the backward apply) --
+// half as many bytes per thread on twice as many CUs is 0.2-0.3 us quicker there; from 4 MiB on the 16-byte form wins
+// (DESIGN.md 4.3).
+inline bool stream_wide(int dtype, int64_t rows, int C) {
+    return dtype == VG_BF16 && C % 8 == 0 && rows * C * 2 >= (int64_t)vg_sw().bn_wide_min;
+}
+
+struct StreamPlan { int rows_per_block, blocks_per_group, ncolblk; };
+
+inline StreamPlan plan_stream(int64_t rows_per_group, int cols, int groups, int max_wgs) {
+    const int ncol = cols < 256 ? cols : 256;
+    const int rpp = 256 / ncol;
+    StreamPlan p;
+    p.ncolblk = (cols + 255) / 256;
+    const int64_t passes = (rows_per_group + rpp - 1) / rpp;
+    int64_t cap = max_wgs / ((int64_t)groups * p.ncolblk);
+    if (cap < 1) cap = 1;
+    const int64_t blocks = passes < cap ? passes : cap;            // small tensors: one pass per workgroup
+    const int64_t rpb = (passes + blocks - 1) / blocks * rpp;
+    p.rows_per_block = (int)rpb;
+    p.blocks_per_group = (int)((rows_per_group + rpb - 1) / rpb);
+    return p;
+}
+
+// VW consecutive elements: loaded as one vector (kept packed while in flight), unpacked to floats where they are used
+template <int DT, int VW> struct RawVec { typedef __attribute__((ext_vector_type(VW / 2))) uint32_t type; };
+template <int VW> struct RawVec<VG_F32, VW> { typedef float4 type; };
+template <int DT, int VW>
+__device__ __forceinline__ typename RawVec<DT, VW>::type loadv(const void* base, int64_t idx) {
+    typedef typename RawVec<DT, VW>::type W;
+    return *reinterpret_cast<const W*>(reinterpret_cast<const typename ElemT<DT>::type*>(base) + idx);
+}
+template <int DT, int VW>
+__device__ __forceinline__ void unpackv(const typename RawVec<DT, VW>::type& r, float (&v)[VW]) {
+    if constexpr (DT == VG_F32) {
+        static_assert(VW == 4, "f32: one 16-byte vector");
+        v[0] = r.x; v[1] = r.y; v[2] = r.z; v[3] = r.w;
+    } else {
+#pragma unroll
+        for (int k = 0; k < VW / 2; ++k) {
+            v[2 * k] = __uint_as_float(r[k] << 16);
+            v[2 * k + 1] = __uint_as_float(r[k] & 0xffff0000u);
+        }
+    }
+}
+template <int DT, int VW> __device__ __forceinline__ void storev(void* base, int64_t idx, const float (&v)[VW]) {
+    typename RawVec<DT, VW>::type r;
+    if constexpr (DT == VG_F32) {
+        r = float4{v[0], v[1], v[2], v[3]};
+    } else {
+#pragma unroll
+        for (int k = 0; k < VW / 2; ++k)
+            r[k] = (uint32_t)ElemT<VG_BF16>::from_f32(v[2 * k]) | ((uint32_t)ElemT<VG_BF16>::from_f32(v[2 * k + 1]) << 16);
+    }
+    *reinterpret_cast<typename RawVec<DT, VW>::type*>(reinterpret_cast<typename ElemT<DT>::type*>(base) + idx) = r;
+}
+template <int V> struct IntC { static constexpr int value = V; };      // a uniform run-time choice made compile-time
+
+template <int VW> __device__ __forceinline__ void load_coef(const float* __restrict__ p, float (&c)[VW]) {
+#pragma unroll
+    for (int k = 0; k < VW; k += 4) {
+        const float4 r = *reinterpret_cast<const float4*>(p + k);
+        c[k] = r.x; c[k + 1] = r.y; c[k + 2] = r.z; c[k + 3] = r.w;
+    }
+}
+
+// the rows r0, r0 + rpp, ... < r1 and the channel offset of this thread (blockIdx: row block, column block, group); an idle
+// thread gets an empty range and a valid channel offset -- no early exit, so that the kernel arguments arrive in one batch
+template <int VW>
+__device__ __forceinline__ void stream_range(int64_t rows, int C, int64_t rows_per_group, int rows_per_block, int& c,
+                                             int& rpp, int64_t& r0, int64_t& r1) {
+    const int cols = C / VW;
+    const int cb = blockIdx.y * 256;
+    const int ncol = min(256, cols - cb);
+    rpp = 256 / ncol;
+    const int tr = threadIdx.x / ncol, tc = threadIdx.x - tr * ncol;
+    c = (cb + tc) * VW;
+    const int64_t gbase = (int64_t)blockIdx.z * rows_per_group;
+    const int64_t b0 = gbase + (int64_t)blockIdx.x * rows_per_block;
+    r1 = min(min(rows, gbase + rows_per_group), b0 + (int64_t)rows_per_block);
+    r0 = tr < rpp ? b0 + tr : r1;
+}
+
+template <int DT, int VW>
 __global__ __launch_bounds__(256) void bn_act_fwd_kernel(const void* __restrict__ x, void* __restrict__ y,
                                                          const float* __restrict__ scale,
-                                                         const float* __restrict__ shift, int64_t nvec, int cols,
-                                                         int act, float slope, int64_t nvec_per_group,
-                                                         int64_t gstride, uint32_t* __restrict__ y8) {
-    auto one = [&](int64_t i, float4 v) {
-        const int c4 = (int)(i % cols) * 4;
-        if (scale) {
-            const int64_t go = (i / nvec_per_group) * gstride;
-            const float4 sc = *reinterpret_cast<const float4*>(scale + go + c4);
-            const float4 sh = *reinterpret_cast<const float4*>(shift + go + c4);
-            v.x = sc.x * v.x + sh.x; v.y = sc.y * v.y + sh.y; v.z = sc.z * v.z + sh.z; v.w = sc.w * v.w + sh.w;
-        }
-        v.x = act_fwd(v.x, act, slope); v.y = act_fwd(v.y, act, slope);
-        v.z = act_fwd(v.z, act, slope); v.w = act_fwd(v.w, act, slope);
-        store4<DT>(y, i * 4, v);
-        if (y8) {                   // e4m3 twin of the activated tensor for an fp8 forward GEMM (same NHWC layout)
-            // cast from the STORED value, as vg_cast_fp8 does: casting the f32 value directly rounds differently
-            // wherever the bf16 rounding lands on an e4m3 midpoint (about 2 % of the elements)
-            if constexpr (DT == VG_BF16) {
-                v.x = ElemT<VG_BF16>::to_f32(ElemT<VG_BF16>::from_f32(v.x));
-                v.y = ElemT<VG_BF16>::to_f32(ElemT<VG_BF16>::from_f32(v.y));
-                v.z = ElemT<VG_BF16>::to_f32(ElemT<VG_BF16>::from_f32(v.z));
-                v.w = ElemT<VG_BF16>::to_f32(ElemT<VG_BF16>::from_f32(v.w));
+                                                         const float* __restrict__ shift, int64_t rows, int C, int act,
+                                                         float slope, int64_t rows_per_group, int rows_per_block,
+                                                         int64_t gstride, uint8_t* __restrict__ y8) {
+    int c, rpp;
+    int64_t r, r1;
+    stream_range<VW>(rows, C, rows_per_group, rows_per_block, c, rpp, r, r1);
+    typedef typename RawVec<DT, VW>::type Raw;
+    const int64_t step = (int64_t)rpp * C;
+    int64_t off = r * C + c;
+    float sc[VW], sh[VW];
+    if (scale) {
+        load_coef<VW>(scale + (int64_t)blockIdx.z * gstride + c, sc);
+        load_coef<VW>(shift + (int64_t)blockIdx.z * gstride + c, sh);
+    }
+    // the activation and the activation-only mode are uniform: chosen once, outside the row loop
+    auto run = [&](auto act_c, auto affine_c) {
+        constexpr int ACT = decltype(act_c)::value;
+        constexpr bool AFFINE = decltype(affine_c)::value;
+        auto one = [&](int64_t o, const Raw& raw) {
+            float f[VW];
+            unpackv<DT, VW>(raw, f);
+            if (AFFINE) {                                       // sc * x + sh, contracted: spelled out, see bn_act_bwd_apply_kernel
+#pragma unroll
+                for (int k = 0; k < VW; ++k) f[k] = __builtin_fmaf(sc[k], f[k], sh[k]);
             }
-            int w = __builtin_amdgcn_cvt_pk_fp8_f32(v.x, v.y, 0, false);
-            w = __builtin_amdgcn_cvt_pk_fp8_f32(v.z, v.w, w, true);
-            y8[i] = (uint32_t)w;
+#pragma unroll
+            for (int k = 0; k < VW; ++k) f[k] = act_fwd(f[k], ACT, slope);
+            storev<DT, VW>(y, o, f);
+            if (y8) {               // e4m3 twin of the activated tensor for an fp8 forward GEMM (same NHWC layout)
+                // cast from the STORED value, as vg_cast_fp8 does: casting the f32 value directly rounds differently
+                // wherever the bf16 rounding lands on an e4m3 midpoint (about 2 % of the elements)
+                if constexpr (DT == VG_BF16) {
+#pragma unroll
+                    for (int k = 0; k < VW; ++k) f[k] = ElemT<VG_BF16>::to_f32(ElemT<VG_BF16>::from_f32(f[k]));
+                }
+                typedef __attribute__((ext_vector_type(VW / 4))) uint32_t W8;
+                W8 w8;
+#pragma unroll
+                for (int k = 0; k < VW / 4; ++k) {
+                    int w = __builtin_amdgcn_cvt_pk_fp8_f32(f[4 * k], f[4 * k + 1], 0, false);
+                    w = __builtin_amdgcn_cvt_pk_fp8_f32(f[4 * k + 2], f[4 * k + 3], w, true);
+                    w8[k] = (uint32_t)w;
+                }
+                *reinterpret_cast<W8*>(y8 + o) = w8;
+            }
+        };
+        for (; r + (EW_UNROLL - 1) * rpp < r1; r += EW_UNROLL * rpp, off += EW_UNROLL * step) {
+            Raw v[EW_UNROLL];
+#pragma unroll
+            for (int u = 0; u < EW_UNROLL; ++u) v[u] = loadv<DT, VW>(x, off + u * step);
+#pragma unroll
+            for (int u = 0; u < EW_UNROLL; ++u) one(off + u * step, v[u]);
+        }
+        if (r < r1) {                                           // the last one to three rows of the row block, together as well
+            Raw v[EW_UNROLL - 1];
+#pragma unroll
+            for (int u = 0; u < EW_UNROLL - 1; ++u)
+                if (r + u * rpp < r1) v[u] = loadv<DT, VW>(x, off + u * step);
+#pragma unroll
+            for (int u = 0; u < EW_UNROLL - 1; ++u)
+                if (r + u * rpp < r1) one(off + u * step, v[u]);
         }
     };
-    // four vectors in flight per thread (the grid is capped: big tensors give each thread several iterations)
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    for (; i + 3 * stride < nvec; i += 4 * stride) {
-        float4 v[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) v[u] = load4<DT>(x, (i + u * stride) * 4);
-#pragma unroll
-        for (int u = 0; u < 4; ++u) one(i + u * stride, v[u]);
-    }
-    for (; i < nvec; i += stride) one(i, load4<DT>(x, i * 4));
+    auto with_act = [&](auto affine_c) {
+        if (act == VG_ACT_RELU) run(IntC<VG_ACT_RELU>{}, affine_c);
+        else if (act == VG_ACT_LRELU) run(IntC<VG_ACT_LRELU>{}, affine_c);
+        else run(IntC<VG_ACT_NONE>{}, affine_c);
+    };
+    if (scale) with_act(IntC<1>{}); else with_act(IntC<0>{});
 }
 
 __global__ __launch_bounds__(FIN_CH * FIN_PL) void bn_bwd_finalize_kernel(
@@ -362,45 +489,69 @@ __global__ __launch_bounds__(FIN_CH * FIN_PL) void bn_bwd_finalize_kernel(
     coef[2 * C + c] = (float)((double)a * s1 / count);
 }
 
-template <int DT>
+template <int DT, int VW>
 __global__ __launch_bounds__(256) void bn_act_bwd_apply_kernel(const void* __restrict__ x, const void* __restrict__ dy,
                                                                void* __restrict__ dx,
                                                                const float* __restrict__ scale,
                                                                const float* __restrict__ shift,
                                                                const float* __restrict__ mean,
                                                                const float* __restrict__ invstd,
-                                                               const float* __restrict__ coef, int64_t nvec, int cols,
-                                                               int C, int act, float slope, int64_t nvec_per_group,
-                                                               int64_t gstride, int64_t cstride) {
-    auto one = [&](int64_t i, const float4& v, const float4& g) {
-        const int c4 = (int)(i % cols) * 4;
-        const int64_t grp = i / nvec_per_group;
-        const int64_t go = grp * gstride;
-        const float* cf = coef + grp * cstride;
-        const float4 sc = *reinterpret_cast<const float4*>(scale + go + c4);
-        const float4 sh = *reinterpret_cast<const float4*>(shift + go + c4);
-        const float4 mu = *reinterpret_cast<const float4*>(mean + go + c4);
-        const float4 is = *reinterpret_cast<const float4*>(invstd + go + c4);
-        const float4 ca = *reinterpret_cast<const float4*>(cf + c4);
-        const float4 cbv = *reinterpret_cast<const float4*>(cf + C + c4);
-        const float4 cc = *reinterpret_cast<const float4*>(cf + 2 * C + c4);
-        float4 o;
-        o.x = ca.x * act_bwd(sc.x * v.x + sh.x, g.x, act, slope) - cbv.x * ((v.x - mu.x) * is.x) - cc.x;
-        o.y = ca.y * act_bwd(sc.y * v.y + sh.y, g.y, act, slope) - cbv.y * ((v.y - mu.y) * is.y) - cc.y;
-        o.z = ca.z * act_bwd(sc.z * v.z + sh.z, g.z, act, slope) - cbv.z * ((v.z - mu.z) * is.z) - cc.z;
-        o.w = ca.w * act_bwd(sc.w * v.w + sh.w, g.w, act, slope) - cbv.w * ((v.w - mu.w) * is.w) - cc.w;
-        store4<DT>(dx, i * 4, o);
+                                                               const float* __restrict__ coef, int64_t rows, int C,
+                                                               int act, float slope, int64_t rows_per_group,
+                                                               int rows_per_block, int64_t gstride, int64_t cstride) {
+    int c, rpp;
+    int64_t r, r1;
+    stream_range<VW>(rows, C, rows_per_group, rows_per_block, c, rpp, r, r1);
+    typedef typename RawVec<DT, VW>::type Raw;
+    const int64_t step = (int64_t)rpp * C;
+    int64_t off = r * C + c;
+    float sc[VW], sh[VW], mu[VW], is[VW], ca[VW], cbv[VW], cc[VW];
+    const int64_t go = (int64_t)blockIdx.z * gstride + c;
+    const float* cf = coef + (int64_t)blockIdx.z * cstride + c;
+    load_coef<VW>(scale + go, sc);
+    load_coef<VW>(shift + go, sh);
+    load_coef<VW>(mean + go, mu);
+    load_coef<VW>(invstd + go, is);
+    load_coef<VW>(cf, ca);
+    load_coef<VW>(cf + C, cbv);
+    load_coef<VW>(cf + 2 * C, cc);
+    auto run = [&](auto act_c) {                                // the activation is uniform: chosen once, outside the row loop
+        constexpr int ACT = decltype(act_c)::value;
+        auto one = [&](int64_t o, const Raw& rx, const Raw& rg) {
+            float f[VW], d[VW], q[VW];
+            unpackv<DT, VW>(rx, f);
+            unpackv<DT, VW>(rg, d);
+            // ca * act_bwd(sc * x + sh, dy) - cb * ((x - mu) * is) - cc with the two contractions the compiler has always made
+            // here spelled out: left to -ffp-contract it fused the second one in the full trips and not in every lane of the
+            // short last trip, and the same element came out one ulp apart depending on where its row fell in a row block
+#pragma unroll
+            for (int k = 0; k < VW; ++k) {
+                const float dz = act_bwd(__builtin_fmaf(sc[k], f[k], sh[k]), d[k], ACT, slope);
+                const float xh = cbv[k] * ((f[k] - mu[k]) * is[k]);
+                q[k] = __builtin_fmaf(ca[k], dz, -xh) - cc[k];
+            }
+            storev<DT, VW>(dx, o, q);
+        };
+        for (; r + (EW_UNROLL - 1) * rpp < r1; r += EW_UNROLL * rpp, off += EW_UNROLL * step) {
+            Raw v[EW_UNROLL], g[EW_UNROLL];
+#pragma unroll
+            for (int u = 0; u < EW_UNROLL; ++u) { v[u] = loadv<DT, VW>(x, off + u * step); g[u] = loadv<DT, VW>(dy, off + u * step); }
+#pragma unroll
+            for (int u = 0; u < EW_UNROLL; ++u) one(off + u * step, v[u], g[u]);
+        }
+        if (r < r1) {                                           // the last one to three rows of the row block, together as well
+            Raw v[EW_UNROLL - 1], g[EW_UNROLL - 1];
+#pragma unroll
+            for (int u = 0; u < EW_UNROLL - 1; ++u)
+                if (r + u * rpp < r1) { v[u] = loadv<DT, VW>(x, off + u * step); g[u] = loadv<DT, VW>(dy, off + u * step); }
+#pragma unroll
+            for (int u = 0; u < EW_UNROLL - 1; ++u)
+                if (r + u * rpp < r1) one(off + u * step, v[u], g[u]);
+        }
     };
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    for (; i + 3 * stride < nvec; i += 4 * stride) {          // eight loads in flight per thread
-        float4 v[4], g[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) { v[u] = load4<DT>(x, (i + u * stride) * 4); g[u] = load4<DT>(dy, (i + u * stride) * 4); }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) one(i + u * stride, v[u], g[u]);
-    }
-    for (; i < nvec; i += stride) one(i, load4<DT>(x, i * 4), load4<DT>(dy, i * 4));
+    if (act == VG_ACT_RELU) run(IntC<VG_ACT_RELU>{});
+    else if (act == VG_ACT_LRELU) run(IntC<VG_ACT_LRELU>{});
+    else run(IntC<VG_ACT_NONE>{});
 }
 
 // ---- train-mode BatchNorm finalize + normalise + activation in ONE launch (bf16, small statistics slabs) ----------
@@ -801,14 +952,23 @@ extern "C" int vg_bn_act_forward_fp8(const void* x, void* y, void* y8, const flo
     VG_CHECK_ARG(y != nullptr && (scale == nullptr) == (shift == nullptr), VG_EINVAL);
     VG_CHECK_ARG(groups >= 1 && rows % groups == 0, VG_EINVAL);
     VG_CHECK_ARG(y8 == nullptr || (dtype == VG_BF16 && (reinterpret_cast<uintptr_t>(y8) & 3u) == 0), VG_EINVAL);
-    const int64_t nvec = rows * C / 4;
-    const int64_t nvg = nvec / groups;
+    const int64_t rpg = rows / groups;
+    const hipStream_t s = vg_stream(stream);
+    uint8_t* twin = reinterpret_cast<uint8_t*>(y8);
+    // 16-byte vectors of bf16 need 8 | C and 16-byte aligned tensors (8-byte aligned twin); otherwise 8-byte vectors
+    const bool wide = stream_wide(dtype, rows, C) && vg_aligned16(x) &&
+                      vg_aligned16(y) && (reinterpret_cast<uintptr_t>(y8) & 7u) == 0;
+    const StreamPlan p = plan_stream(rpg, C / (wide ? 8 : 4), groups, EW_FWD_WGS);
+    const dim3 grid(p.blocks_per_group, p.ncolblk, groups);
     if (dtype == VG_F32)
-        vg_launch_timed(4, bn_act_fwd_kernel<VG_F32>, dim3(ew_blocks(nvec)), dim3(256), 0, vg_stream(stream), x, y,
-                           scale, shift, nvec, C / 4, act, slope, nvg, gstride, (uint32_t*)nullptr);
+        vg_launch_timed(4, (bn_act_fwd_kernel<VG_F32, 4>), grid, dim3(256), 0, s, x, y, scale, shift, rows, C, act, slope,
+                           rpg, p.rows_per_block, gstride, twin);
+    else if (wide)
+        vg_launch_timed(4, (bn_act_fwd_kernel<VG_BF16, 8>), grid, dim3(256), 0, s, x, y, scale, shift, rows, C, act, slope,
+                           rpg, p.rows_per_block, gstride, twin);
     else
-        vg_launch_timed(4, bn_act_fwd_kernel<VG_BF16>, dim3(ew_blocks(nvec)), dim3(256), 0, vg_stream(stream), x, y,
-                           scale, shift, nvec, C / 4, act, slope, nvg, gstride, reinterpret_cast<uint32_t*>(y8));
+        vg_launch_timed(4, (bn_act_fwd_kernel<VG_BF16, 4>), grid, dim3(256), 0, s, x, y, scale, shift, rows, C, act, slope,
+                           rpg, p.rows_per_block, gstride, twin);
     return VG_LAUNCH_RC();
 }
 
@@ -848,14 +1008,21 @@ extern "C" int vg_bn_act_backward_apply(const void* x, const void* dy, void* dx,
     if (rc) return rc;
     VG_CHECK_ARG(dy && dx && scale && shift && mean && invstd && coef, VG_EINVAL);
     VG_CHECK_ARG(groups >= 1 && rows % groups == 0, VG_EINVAL);
-    const int64_t nvec = rows * C / 4;
-    const int64_t nvg = nvec / groups;
+    const int64_t rpg = rows / groups;
+    const hipStream_t s = vg_stream(stream);
+    const bool wide = stream_wide(dtype, rows, C) && vg_aligned16(x) &&
+                      vg_aligned16(dy) && vg_aligned16(dx);
+    const StreamPlan p = plan_stream(rpg, C / (wide ? 8 : 4), groups, EW_BWD_WGS);
+    const dim3 grid(p.blocks_per_group, p.ncolblk, groups);
     if (dtype == VG_F32)
-        vg_launch_timed(4, bn_act_bwd_apply_kernel<VG_F32>, dim3(ew_blocks(nvec)), dim3(256), 0, vg_stream(stream), x,
-                           dy, dx, scale, shift, mean, invstd, coef, nvec, C / 4, C, act, slope, nvg, gstride, cstride);
+        vg_launch_timed(4, (bn_act_bwd_apply_kernel<VG_F32, 4>), grid, dim3(256), 0, s, x, dy, dx, scale, shift, mean, invstd,
+                           coef, rows, C, act, slope, rpg, p.rows_per_block, gstride, cstride);
+    else if (wide)
+        vg_launch_timed(4, (bn_act_bwd_apply_kernel<VG_BF16, 8>), grid, dim3(256), 0, s, x, dy, dx, scale, shift, mean, invstd,
+                           coef, rows, C, act, slope, rpg, p.rows_per_block, gstride, cstride);
     else
-        vg_launch_timed(4, bn_act_bwd_apply_kernel<VG_BF16>, dim3(ew_blocks(nvec)), dim3(256), 0, vg_stream(stream), x,
-                           dy, dx, scale, shift, mean, invstd, coef, nvec, C / 4, C, act, slope, nvg, gstride, cstride);
+        vg_launch_timed(4, (bn_act_bwd_apply_kernel<VG_BF16, 4>), grid, dim3(256), 0, s, x, dy, dx, scale, shift, mean, invstd,
+                           coef, rows, C, act, slope, rpg, p.rows_per_block, gstride, cstride);
     return VG_LAUNCH_RC();
 }
 

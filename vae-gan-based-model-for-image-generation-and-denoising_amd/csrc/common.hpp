@@ -172,5 +172,6 @@ struct VgSwitches {
     int wg_xcd;            // VG_WG_XCD            1: XCD-aware workgroup order in wgrad (2: always)
     int bn_fused_fwd;      // VG_BN_FUSED_FWD      1: BatchNorm finalize folded into the elementwise passes of small layers
     int bn_onepass;        // VG_BN_ONEPASS        0: (1: BatchNorm backward in one launch with a grid-wide exchange, bn_onepass.hip -- measured slower)
+    int bn_wide_min;       // VG_BN_WIDE_MIN       4194304: bytes from which a bf16 tensor's streaming BatchNorm passes take 16-byte vectors per thread (smaller: 8-byte)
 };
 const VgSwitches& vg_sw();

@@ -1017,6 +1017,7 @@ void read_switches() {
     g_sw.wg_xcd = env_int("VG_WG_XCD", 1);
     g_sw.bn_fused_fwd = env_int("VG_BN_FUSED_FWD", 1);
     g_sw.bn_onepass = env_int("VG_BN_ONEPASS", 0);
+    g_sw.bn_wide_min = env_int("VG_BN_WIDE_MIN", 4 << 20);
 }
 struct SwitchInit { SwitchInit() { read_switches(); } } g_switch_init;
 }  // namespace
