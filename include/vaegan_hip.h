@@ -48,7 +48,7 @@ extern "C" {
 #define VG_ACT_LRELU   2   /* nn.LeakyReLU(slope)    main_vae.py:25, gan_code.py:62-82 */
 #define VG_ACT_TANH    3   /* nn.Tanh()              gan_code.py:50 (vg_tnconv epilogue only) */
 
-#define VG_ABI_VERSION 14  /* 2: vg_pack_desc.tile_start, SyncBN / WGAN / data-path entry points; 3: in-kernel noise (vg_*_rng);
+#define VG_ABI_VERSION 15  /* 2: vg_pack_desc.tile_start, SyncBN / WGAN / data-path entry points; 3: in-kernel noise (vg_*_rng);
                              4: vg_bn_finalize_act_forward, vg_bn_backward_finalize_apply;
                              7: vg_bce_pair_forward_backward;
                              8: vg_head_backward; round-3 prune -- the opt-in experiments of ABI 5 / 6 that measured slower (input prologue of
@@ -635,7 +635,41 @@ int vg_resize_u8(const uint8_t* src, int64_t N, int Hin, int Win, int C, const i
  * ws: vg_manifold_cover_ws_bytes(Nq, Nr, D) = 4 Nq + 4 Nr (each rounded up to 256) + 4 Nq splits bytes.  Four launches
  * and one 8-byte memset.
  * The _ws_bytes queries return VG_EINVAL (negative) for sizes outside the contract.
+ *
+ * vg_kid_scores: the Kernel Inception Distance (Binkowski et al. 2018), an unbiased polynomial-kernel MMD^2 estimate per
+ * subset pair.  The reference computes no KID: like precision / recall this goes beyond its code.  real f32 [Nr][D], fake
+ * f32 [Nf][D], contiguous and 16-byte aligned; idx_real, idx_fake int32 [S][m] on the device: subset s is the rows
+ * x_i = real[idx_real[s][i]] and y_j = fake[idx_fake[s][j]].  A table is just a list of rows: repeated indices are
+ * allowed, and every index is clamped into [0, N), so a corrupt table cannot read outside the buffers (callers validate
+ * tables before upload; the subsets are the CALLER's draw, metrics.kid_subsets draws them on the host).  With
+ * b(a, c) = gamma * dot(a, c) + coef and k = b^degree, per subset s:
+ *     sums[s][0] = sum_{i != j} k(x_i, x_j)      i, j are POSITIONS in the subset: the pair is left out by position, not
+ *     sums[s][1] = sum_{i != j} k(y_i, y_j)      by value and not by row index (a repeated row still counts)
+ *     sums[s][2] = sum_{i, j}   k(x_i, y_j)
+ *     scores[s]  = (sums0 + sums1) / (m (m - 1)) - 2 * sums2 / (m * m)          in f64, in exactly that order
+ *     stat[0] = (sum_s scores[s], ascending s) / S      stat[1] = sqrt(sum_s (scores[s] - stat[0])^2 / S), the
+ *     POPULATION standard deviation; exactly 0 for S == 1.
+ * Arithmetic: everything in f64.  dot on v_mfma_f64_16x16x4_f64 over the exactly converted f32 inputs, columns in
+ * ascending order (f32 x f32 is exact in f64: only the order of the additions is the kernel's); the affine step in f64;
+ * the power as degree - 1 left-to-right multiplications, no pow().  Why f64: the score is a small difference of three
+ * large sums, and an f32 dot-product bound (3 D 2^-24 relative per kernel value) is of the size of the score at D = 2048.
+ * Deterministic: no floating-point atomics.  One workgroup owns one 64 x 64 tile of one family (xx, yy, xy) of one
+ * subset; xx and yy take only the tiles on or above the diagonal, an off-diagonal tile counts twice, a diagonal tile
+ * masks i == j.  Positions >= m and columns >= D are staged as zeros and masked, never multiplied in.  Each workgroup
+ * writes its one partial into ws; a second launch adds them per family in ascending tile order (xx and yy: pairs
+ * (ti, tj), ti <= tj, ti-major; xy: ti * T + tj) and forms scores and stat.  Two calls give the same bits.  The m x m
+ * Gram matrix is never written to memory.
+ * Range: 1 <= D <= 2048, 2 <= m <= min(Nr, Nf, 32768), 1 <= S <= 4096, 1 <= degree <= 8, gamma and coef finite,
+ * S * (2 P + T * T) <= 2^31 - 1 workgroups; else (or for a NULL pointer, or ws_bytes too small) VG_EINVAL.  sums f64
+ * [S][3], scores f64 [S], stat f64 [2] and ws 8-byte aligned, the tables 4-byte aligned; else VG_EALIGN.
+ * ws: vg_kid_scores_ws_bytes(m, S) = 8 * S * (2 P + T * T) bytes with T = ceil(m / 64), P = T (T + 1) / 2: 422 400 bytes
+ * at m = 1000, S = 100.  Exactly two launches; nothing is allocated, nothing synchronises.
  * ---------------------------------------------------------------------------------------- */
+int64_t vg_kid_scores_ws_bytes(int64_t m, int S);
+int vg_kid_scores(const float* real, int64_t Nr, const float* fake, int64_t Nf, int D, const int32_t* idx_real,
+                  const int32_t* idx_fake, int S, int64_t m, int degree, double gamma, double coef,
+                  double* sums /* [S][3] */, double* scores /* [S] */, double* stat /* [2] */, void* ws, int64_t ws_bytes,
+                  void* stream);
 int64_t vg_feat_stats_accum_ws_bytes(int64_t n, int D);
 int vg_feat_stats_accum(const float* x, int64_t n, int D, int64_t row_stride, double* sum, double* outer, void* ws,
                         int64_t ws_bytes, void* stream);

@@ -8,7 +8,7 @@ vaegan_code.py:42-44), ``BCELoss`` / ``MSELoss`` (vaegan_code.py:46-47), ``confi
 reference-shaped step function).  Generation (main_vae.py:415-641): ``latent`` -- ``encode_dataset``, ``LatentPrior``,
 ``evaluate_generation``, ``sample_images``.  Feature-space metrics (fid.update / fid.compute of every evaluation loop,
 README.md:22 precision / recall): ``metrics`` -- ``FeatureStats``, ``frechet_distance``, ``precision_recall``,
-``encoder_features``.  Data path (dataset_code.py): ``data`` -- ``ResidentImages`` (``resized``: Resize +
+``encoder_features``, ``kernel_distance`` (KID).  Data path (dataset_code.py): ``data`` -- ``ResidentImages`` (``resized``: Resize +
 CenterCrop on the device), ``resample_coeffs``, ``resize_geometry``.
 """
 from . import data  # noqa: F401
@@ -20,7 +20,7 @@ from .ddp import GradReducer
 from .denoise import denoise_eval, paired_test_epoch, validation_epoch
 from .graphed import graphed
 from .latent import LatentPrior, encode_dataset, evaluate_generation, sample_images
-from .metrics import FeatureStats, encoder_features, frechet_distance, precision_recall
+from .metrics import FeatureStats, encoder_features, frechet_distance, kernel_distance, precision_recall
 from .losses import BCELoss, MSELoss
 from .nets import ConvBlock, Discriminator, Encoder, Generator, weights_init
 from .optim import Adam
@@ -32,4 +32,4 @@ __all__ = ["ConvBlock", "Encoder", "Generator", "Discriminator", "weights_init",
            "VAEGANTrainer", "LOSS_NAMES", "configure_seed", "geometry", "denoise_eval", "validation_epoch", "paired_test_epoch", "GradReducer", "data", "VAETrainer", "DCGANTrainer", "WGANTrainer", "graphed",
            "latent", "LatentPrior", "encode_dataset", "evaluate_generation", "sample_images",
            "ResidentImages", "resample_coeffs", "resize_geometry",
-           "metrics", "FeatureStats", "frechet_distance", "precision_recall", "encoder_features"]
+           "metrics", "FeatureStats", "frechet_distance", "precision_recall", "encoder_features", "kernel_distance"]

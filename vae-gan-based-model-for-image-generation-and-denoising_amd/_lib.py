@@ -16,7 +16,7 @@ VG_F32, VG_BF16, VG_FP8 = 0, 1, 2
 VG_FP8_WSHIFT = 6
 VG_ACT_NONE, VG_ACT_RELU, VG_ACT_LRELU, VG_ACT_TANH = 0, 1, 2, 3
 VG_MAX_PHASE = 4
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 VG_ENOSUP = -3
 _ERR = {-1: "VG_EINVAL (bad shape/size/flag)", -2: "VG_EALIGN (16-byte contract violated)",
@@ -166,6 +166,8 @@ SIGNATURES = {
     "vg_knn_radius2": (c_int, [_P, _L, _I, _I, _P, _P, _L, _P]),
     "vg_manifold_cover_ws_bytes": (c_int64, [_L, _L, _I]),
     "vg_manifold_cover": (c_int, [_P, _L, _P, _L, _I, _P, _P, _P, _P, _L, _P]),
+    "vg_kid_scores_ws_bytes": (c_int64, [_L, _I]),
+    "vg_kid_scores": (c_int, [_P, _L, _P, _L, _I, _P, _P, _I, _L, _I, _D, _D, _P, _P, _P, _P, _L, _P]),
     "vg_nchw_to_nhwc_rng": (c_int, [_P, _P, _I, _F, _P, _I, _I, _I, _I, _I, _I, _P]),
     "vg_nhwc_tanh_to_nchw_noisy_rng": (c_int, [_P, _P, _P, _I, _F, _P, _I, _I, _I, _I, _I, _I, _P]),
     "vg_reparam_forward_rng": (c_int, [_P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P]),

@@ -61,7 +61,8 @@ def denoise_eval(encoder, decoder, img: torch.Tensor, sigma: float = 0.05, eps: 
 
 @torch.no_grad()
 def validation_epoch(encoder, decoder, loader: Iterable[torch.Tensor], n_samples: Optional[int] = None,
-                     sigma: float = 0.05, alpha_kl: float = 0.1, noise_fn=None, feature_fn=None) -> Dict[str, float]:
+                     sigma: float = 0.05, alpha_kl: float = 0.1, noise_fn=None, feature_fn=None,
+                     kid_subsets: Optional[int] = None, kid_subset_size: int = 1000, kid_seed: int = 0) -> Dict[str, float]:
     """The per-epoch validation loop of the reference trainer, vaegan_code.py:147-191:
 
         encoder.eval(); decoder.eval()                                   (:147-148; the discriminator is not used)
@@ -82,13 +83,20 @@ def validation_epoch(encoder, decoder, loader: Iterable[torch.Tensor], n_samples
     (``metrics.encoder_features(encoder)`` or a network of the caller's): the reconstructions and the clean images go
     through ``ops.to_u8`` and feature_fn, their f64 running statistics are accumulated on the device per batch
     (fid.update, :182-183) and the result gains ``fid`` (fid.compute, :185; its last D x D step runs on the host, see
-    ``metrics.frechet_distance``).  Inception Score needs InceptionV3's classifier head: out of scope."""
+    ``metrics.frechet_distance``).  Inception Score needs InceptionV3's classifier head: out of scope.
+    kid_subsets (default None: nothing changes; needs feature_fn, else RuntimeError): the pass keeps its features on the
+    device and the result gains ``kid_mean`` and ``kid_std``, the Kernel Inception Distance between the clean images and
+    the reconstructions (``metrics.kernel_distance``: ``kid_subsets`` subset pairs of ``kid_subset_size`` rows drawn on the
+    host with ``kid_seed``; population standard deviation).  Not in the reference; single process; one more host read of
+    two doubles."""
+    if kid_subsets is not None and feature_fn is None:
+        raise RuntimeError("validation_epoch: kid_subsets needs a feature_fn (KID is a feature-space metric)")
     encoder.eval(), decoder.eval()                                                   # :147-148
     dev = next(encoder.parameters()).device
     acc = ops.zeros_f32(4, dev)                # [sum(recon + a*kl), sum(b * ssim_b), sum(b * mse_b), sum(kl)]
     seen = batches = 0
     dt, L = encoder._dt, encoder.latent_dim
-    feats = FeaturePass(feature_fn, False) if feature_fn is not None else None
+    feats = FeaturePass(feature_fn, kid_subsets is not None) if feature_fn is not None else None
     for i, img in enumerate(loader):
         if not img.is_cuda:
             raise RuntimeError("validation_epoch needs device batches (data.DeviceLoader); there is no CPU path")
@@ -121,6 +129,7 @@ def validation_epoch(encoder, decoder, loader: Iterable[torch.Tensor], n_samples
         batches += 1
     if batches == 0:
         raise RuntimeError("validation_epoch: the loader yielded no batch")
+    kid = feats.kid(int(kid_subsets), int(kid_subset_size), int(kid_seed)) if kid_subsets is not None else None
     val_sum, ssim_sum, mse_sum, kl_sum = (float(v) for v in acc.tolist())           # the one host sync
     n = seen if n_samples is None else int(n_samples)
     mse01 = mse_sum / seen / 4.0
@@ -129,6 +138,8 @@ def validation_epoch(encoder, decoder, loader: Iterable[torch.Tensor], n_samples
            "recon_loss": mse_sum / seen, "kl_loss": kl_sum / batches, "samples": seen, "batches": batches}
     if feats is not None:
         out["fid"] = feats.fid()
+    if kid is not None:
+        out["kid_mean"], out["kid_std"] = kid.tolist()
     return out
 
 

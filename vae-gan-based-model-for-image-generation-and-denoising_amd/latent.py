@@ -176,7 +176,8 @@ def _normal_z(decoder, b: int, eps: Optional[torch.Tensor]) -> torch.Tensor:
 
 @torch.no_grad()
 def evaluate_generation(decoder, val_loader: Iterable[torch.Tensor], prior: Optional[LatentPrior] = None,
-                        noise_fn=None, feature_fn=None, k: int = 3, real_stats=None) -> Dict[str, float]:
+                        noise_fn=None, feature_fn=None, k: int = 3, real_stats=None, kid_subsets: Optional[int] = None,
+                        kid_subset_size: int = 1000, kid_seed: int = 0) -> Dict[str, float]:
     """The generation-evaluation loops of the reference:
 
         decoder.eval()                                                                  (main_vae.py:476 / :546)
@@ -201,7 +202,14 @@ def evaluate_generation(decoder, val_loader: Iterable[torch.Tensor], prior: Opti
     (README.md:22, k-th-neighbour manifolds with ``k``) and ``feature_dim``.  real_stats: a ``metrics.FeatureStats`` of the
     real side computed earlier (the reference recomputes it on every call): the real half of the FID update is skipped.
     Inception Score needs InceptionV3's classifier head: out of scope.  Still one host sync for everything accumulated on
-    the device, plus the final D x D step of ``metrics.frechet_distance`` on the host."""
+    the device, plus the final D x D step of ``metrics.frechet_distance`` on the host.
+
+    kid_subsets (default None: nothing changes; needs feature_fn, else RuntimeError): the Kernel Inception Distance of the
+    pass's features (``metrics.kernel_distance``: ``kid_subsets`` subset pairs of ``kid_subset_size`` rows drawn on the host
+    with ``kid_seed``, degree 3, gamma 1 / D, coef 1); the result gains ``kid_mean`` and ``kid_std`` (population standard
+    deviation), read in the same host sync.  Not in the reference; single process, like precision / recall."""
+    if kid_subsets is not None and feature_fn is None:
+        raise RuntimeError("evaluate_generation: kid_subsets needs a feature_fn (KID is a feature-space metric)")
     decoder.eval()
     dev = _device_of(decoder, "evaluate_generation")
     acc = ops.zeros_f32(1, dev)
@@ -229,10 +237,15 @@ def evaluate_generation(decoder, val_loader: Iterable[torch.Tensor], prior: Opti
     if feats is None:
         return {"ssim": float(acc.item()) / seen, "samples": seen, "batches": batches}   # the one host sync
     counts = feats.pr_counts(int(k))
-    ssim_sum, fake_in_real, real_in_fake = torch.cat([acc.double(), counts.double()]).tolist()   # the one host sync
+    parts = [acc.double(), counts.double()]
+    if kid_subsets is not None:
+        parts.append(feats.kid(int(kid_subsets), int(kid_subset_size), int(kid_seed)))
+    ssim_sum, fake_in_real, real_in_fake, *kid = torch.cat(parts).tolist()             # the one host sync
     out = {"ssim": ssim_sum / seen, "samples": seen, "batches": batches, "fid": feats.fid(), "feature_dim": feats.D}
     pr = _pr_result(int(fake_in_real), int(real_in_fake), seen, seen, int(k))
     out.update(precision=pr["precision"], recall=pr["recall"], f1=pr["f1"])
+    if kid:
+        out.update(kid_mean=kid[0], kid_std=kid[1])
     return out
 
 

@@ -1,4 +1,4 @@
-"""Feature-space generation metrics on the device: FID and the k-nearest-neighbour precision / recall / F1.
+"""Feature-space generation metrics on the device: FID, the k-nearest-neighbour precision / recall / F1 and KID.
 
 Every evaluation loop of the reference ends in ``fid.update(real, real=True); fid.update(fake, real=False); fid.compute()``
 (vaegan_code.py:143-185, gan_code.py:111-145, main_vae.py:472-512, :540-574), and its README.md:22 lists Precision /
@@ -9,6 +9,7 @@ exists; the three kernels behind it are stated in include/vaegan_hip.h, "Feature
     FeatureStats.update      vg_feat_stats_accum   f64 running sums (sum x, sum x x^T) on the f64 MFMA
     precision_recall         vg_knn_radius2        k-th neighbour radius of every sample, exact-f32 MFMA
                              vg_manifold_cover     is a sample inside some ball of the other set
+    kernel_distance          vg_kid_scores         polynomial-kernel MMD^2 over random subsets (KID), f64 MFMA
 
 The feature extractor is pluggable: ``feature_fn(images_u8 [b,C,S,S] uint8 device) -> f32 [b, D] device``.
 ``encoder_features`` wraps the project's own Encoder (no download); a user who has InceptionV3 weights passes a callable of
@@ -16,7 +17,11 @@ their own and gets the reference's FID.  This module never imports a network, so
 Parity with the torchmetrics package itself is unpinned (the package is not installed), as for SSIM: the formulas are
 torchmetrics' ``_compute_fid`` and running sums, checked against an f64 numpy restatement (tests/_metrics_ref.py).
 Precision / recall is single-process: ``FeatureStats.merge`` makes the FID side additive over ranks, the k-NN part needs
-all features in one place.
+all features in one place.  So is the Kernel Inception Distance (Binkowski et al. 2018, "Demystifying MMD GANs"), which
+the reference computes nowhere either: it is the unbiased companion of FID for small validation sets (FID's estimator is
+biased in N).  Deviations from torchmetrics' KernelInceptionDistance, whose parity is unpinned for the
+same reason: the subsets are drawn on the HOST by numpy's PCG64 (``kid_subsets``), the arithmetic is f64 and ``kid_std``
+is the population standard deviation (torch.std's default is the sample one).
 """
 from typing import Callable, Dict, Optional
 
@@ -146,6 +151,87 @@ def precision_recall(real_feats: torch.Tensor, fake_feats: torch.Tensor, k: int 
     return _pr_result(c[0], c[1], real_feats.shape[0], fake_feats.shape[0], k)
 
 
+def kid_subsets(Nr: int, Nf: int, subsets: int, subset_size: int, seed: int = 0):
+    """The subset tables of ``kernel_distance``, drawn on the host: -> (idx_real, idx_fake), int32 numpy [subsets,
+    subset_size].  One ``numpy.random.Generator(numpy.random.PCG64(seed))``; for each subset in turn
+    ``permutation(Nr)[:m]`` first, then ``permutation(Nf)[:m]``: rows without repetition, as torchmetrics draws them."""
+    Nr, Nf, S, m = int(Nr), int(Nf), int(subsets), int(subset_size)
+    if S < 1 or m < 2:
+        raise ValueError(f"kid_subsets: need subsets >= 1 and subset_size >= 2, got {S} and {m}")
+    if m > min(Nr, Nf):
+        raise ValueError(f"kid_subsets: subset_size {m} exceeds the smaller feature set ({min(Nr, Nf)} rows)")
+    g = np.random.Generator(np.random.PCG64(int(seed)))
+    ir, jf = np.empty((S, m), np.int32), np.empty((S, m), np.int32)
+    for s in range(S):
+        ir[s] = g.permutation(Nr)[:m]
+        jf[s] = g.permutation(Nf)[:m]
+    return ir, jf
+
+
+def _check_table(t, S: int, m: int, N: int, name: str) -> np.ndarray:
+    """An injected subset table on the host: integer [S, m] with every entry in [0, N) -> int32 numpy."""
+    if isinstance(t, torch.Tensor):
+        t = t.cpu().numpy()
+    t = np.asarray(t)
+    if t.ndim != 2 or t.shape != (S, m) or not np.issubdtype(t.dtype, np.integer):
+        raise ValueError(f"kernel_distance: {name} must be an integer [{S}, {m}] table, got {t.dtype} {t.shape}")
+    lo, hi = int(t.min()), int(t.max())
+    if lo < 0 or hi >= N:
+        raise ValueError(f"kernel_distance: {name} holds row indices in [{lo}, {hi}], the set has {N} rows")
+    return np.ascontiguousarray(t, dtype=np.int32)
+
+
+def _kid_device(real_feats, fake_feats, subsets, subset_size, degree, gamma, coef, seed, idx_real, idx_fake):
+    """-> (scores f64 [S] and stat f64 [2] on the device, S, m, D); no host sync unless an injected table lives on the
+    device (the tables are made or checked on the host)."""
+    _check_feats(real_feats, None, "kernel_distance")
+    _check_feats(fake_feats, real_feats.shape[1], "kernel_distance")
+    Nr, Nf, D = int(real_feats.shape[0]), int(fake_feats.shape[0]), int(real_feats.shape[1])
+    if (idx_real is None) != (idx_fake is None):
+        raise ValueError("kernel_distance: give both idx_real and idx_fake, or neither")
+    if idx_real is not None:
+        shape = tuple(idx_real.shape)
+        S, m = (int(shape[0]), int(shape[1])) if len(shape) == 2 else (int(subsets), int(subset_size))
+    else:
+        S, m = int(subsets), int(subset_size)
+    if m > min(Nr, Nf):
+        raise ValueError(f"kernel_distance: subset_size {m} exceeds the smaller feature set ({min(Nr, Nf)} rows)")
+    if not (1 <= S <= 4096 and 2 <= m <= 32768):
+        raise ValueError(f"kernel_distance: need 1 <= subsets <= 4096 and 2 <= subset_size <= 32768, got {S} and {m}")
+    if idx_real is None:
+        ir, jf = kid_subsets(Nr, Nf, S, m, seed)
+    else:
+        ir, jf = _check_table(idx_real, S, m, Nr, "idx_real"), _check_table(idx_fake, S, m, Nf, "idx_fake")
+    dev = real_feats.device
+    g = 1.0 / D if gamma is None else float(gamma)
+    scores, stat, _ = ops.kid_scores(real_feats, fake_feats, torch.from_numpy(ir).to(dev), torch.from_numpy(jf).to(dev),
+                                     int(degree), g, float(coef))
+    return scores, stat, S, m, D
+
+
+def kernel_distance(real_feats: torch.Tensor, fake_feats: torch.Tensor, subsets: int = 100, subset_size: int = 1000,
+                    degree: int = 3, gamma: Optional[float] = None, coef: float = 1.0, seed: int = 0, idx_real=None,
+                    idx_fake=None, return_scores: bool = False):
+    """Kernel Inception Distance (Binkowski et al. 2018): for each of ``subsets`` random subset pairs of ``subset_size``
+    rows, the unbiased MMD^2 estimate under k(a, c) = (gamma a.c + coef)^degree (``gamma=None``: 1 / D),
+
+        score = (sum_{i != j} k(x_i, x_j) + sum_{i != j} k(y_i, y_j)) / (m (m - 1)) - 2 sum_{i, j} k(x_i, y_j) / m^2
+
+    -> {"kid_mean", "kid_std" (POPULATION standard deviation over the subsets), "subsets", "subset_size",
+    "feature_dim"}; with ``return_scores=True`` -> (that dict, the f64 [subsets] scores on the device).
+    real_feats f32 [Nr, D], fake_feats f32 [Nf, D] on the device; ``subset_size > min(Nr, Nf)`` is a ValueError.
+    The subsets are drawn on the host (``kid_subsets(Nr, Nf, subsets, subset_size, seed)``) and uploaded once as int32;
+    ``idx_real`` / ``idx_fake`` inject tables instead (integer [S, m], numpy or torch; checked on the host for shape, dtype
+    and range, which is a sync if they live on the device).  All arithmetic in f64 on the f64 MFMA, deterministic
+    (include/vaegan_hip.h, vg_kid_scores); the m x m Gram matrix is never written.  Single process; ONE host sync at the
+    end (two doubles).  The reference computes no KID; parity with torchmetrics is unpinned (not installed)."""
+    scores, stat, S, m, D = _kid_device(real_feats, fake_feats, subsets, subset_size, degree, gamma, coef, seed, idx_real,
+                                        idx_fake)
+    mean, std = stat.tolist()                                                          # the one host sync
+    out = {"kid_mean": mean, "kid_std": std, "subsets": S, "subset_size": m, "feature_dim": D}
+    return (out, scores) if return_scores else out
+
+
 _ARANGE = {}
 
 
@@ -225,3 +311,10 @@ class FeaturePass:
 
     def fid(self) -> float:
         return frechet_distance(self.real, self.fake)
+
+    def kid(self, subsets: int, subset_size: int = 1000, seed: int = 0) -> torch.Tensor:
+        """f64 [2] on the device: mean and population standard deviation of the pass's KID scores (``keep=True``)."""
+        if not self.keep:
+            raise RuntimeError("FeaturePass.kid needs the features of the pass: construct it with keep=True")
+        return _kid_device(torch.cat(self.real_feats), torch.cat(self.fake_feats), subsets, subset_size, 3, None, 1.0, seed,
+                           None, None)[1]

@@ -4,6 +4,7 @@ Each function takes torch CUDA tensors (used only as device-memory handles), fil
 descriptor struct, and launches on torch's current HIP stream.  No computation happens in
 Python/ATen here.  All functions raise RuntimeError when the library rejects the arguments.
 """
+import math
 import os
 from ctypes import byref, c_int
 
@@ -1012,6 +1013,43 @@ def manifold_cover(q, ref, r2_ref, count=None):
     L.check(lib.vg_manifold_cover(q.data_ptr(), Nq, ref.data_ptr(), Nr, D, r2_ref.data_ptr(), inside.data_ptr(),
                                   count.data_ptr(), ws.data_ptr(), ws.numel() * 4, L.stream_ptr()), "vg_manifold_cover")
     return inside, count
+
+
+def kid_scores(real, fake, idx_real, idx_fake, degree=3, gamma=1.0, coef=1.0):
+    """Kernel Inception Distance per subset pair (vg_kid_scores): real f32 [Nr,D], fake f32 [Nf,D]; idx_real, idx_fake int32
+    [S,m] device tables of row indices (subset s = real[idx_real[s]], fake[idx_fake[s]]; the kernel clamps indices, callers
+    validate them).  k(a, c) = (gamma dot(a, c) + coef)^degree, everything in f64 on the f64 MFMA.  -> (scores f64 [S],
+    stat f64 [2] = mean and population standard deviation of the scores, sums f64 [S,3] = the xx and yy sums over
+    positions i != j and the xy sum over all pairs).  Deterministic; two launches; no host sync."""
+    Nr, D, sr = _feature_rows(real, "kid_scores", "real")
+    Nf, Df, sf = _feature_rows(fake, "kid_scores", "fake")
+    _need_cuda(idx_real, idx_fake)
+    if D != Df:
+        raise RuntimeError(f"kid_scores: real [Nr,{D}] and fake [Nf,{Df}] must share D")
+    if (idx_real.dtype != torch.int32 or idx_fake.dtype != torch.int32 or idx_real.dim() != 2
+            or idx_real.shape != idx_fake.shape):
+        raise RuntimeError("kid_scores: idx_real and idx_fake must be int32 [S, m] tensors of one shape")
+    S, m = idx_real.shape
+    degree, gamma, coef = int(degree), float(gamma), float(coef)
+    if not (1 <= D <= 2048 and 1 <= S <= 4096 and 2 <= m <= min(Nr, Nf, 32768) and 1 <= degree <= 8
+            and math.isfinite(gamma) and math.isfinite(coef)):
+        raise RuntimeError(f"kid_scores: need 1 <= D <= 2048, 1 <= S <= 4096, 2 <= m <= min(Nr, Nf, 32768), 1 <= degree <= 8 "
+                           f"and finite gamma, coef; got D={D} S={S} m={m} Nr={Nr} Nf={Nf} degree={degree} gamma={gamma} "
+                           f"coef={coef}")
+    if Nr > 1 and sr != D:
+        real = real.contiguous()
+    if Nf > 1 and sf != D:
+        fake = fake.contiguous()
+    real, fake = _aligned16(real), _aligned16(fake)
+    lib = L.load()
+    nbytes = _ws_query(lib.vg_kid_scores_ws_bytes(m, S), "vg_kid_scores_ws_bytes")
+    ws = WS.get("metrics", nbytes, real.device)
+    out = torch.empty(4 * S + 2, dtype=torch.float64, device=real.device)
+    sums, scores, stat = out[:3 * S].view(S, 3), out[3 * S:4 * S], out[4 * S:]
+    L.check(lib.vg_kid_scores(real.data_ptr(), Nr, fake.data_ptr(), Nf, D, idx_real.data_ptr(), idx_fake.data_ptr(), S, m,
+                              degree, gamma, coef, sums.data_ptr(), scores.data_ptr(), stat.data_ptr(), ws.data_ptr(),
+                              ws.numel() * 4, L.stream_ptr()), "vg_kid_scores")
+    return scores, stat, sums
 
 
 def noisy_clamp_to_nhwc(x, eps, sigma, CP, dtype, lo=-1.0, hi=1.0):
