@@ -48,7 +48,7 @@ extern "C" {
 #define VG_ACT_LRELU   2   /* nn.LeakyReLU(slope)    main_vae.py:25, gan_code.py:62-82 */
 #define VG_ACT_TANH    3   /* nn.Tanh()              gan_code.py:50 (vg_tnconv epilogue only) */
 
-#define VG_ABI_VERSION 15  /* 2: vg_pack_desc.tile_start, SyncBN / WGAN / data-path entry points; 3: in-kernel noise (vg_*_rng);
+#define VG_ABI_VERSION 16  /* 2: vg_pack_desc.tile_start, SyncBN / WGAN / data-path entry points; 3: in-kernel noise (vg_*_rng);
                              4: vg_bn_finalize_act_forward, vg_bn_backward_finalize_apply;
                              7: vg_bce_pair_forward_backward;
                              8: vg_head_backward; round-3 prune -- the opt-in experiments of ABI 5 / 6 that measured slower (input prologue of
@@ -58,7 +58,9 @@ extern "C" {
                              11: degraded-pair data path: vg_gather_degrade_u8, vg_degrade_params, vg_rand_u01;
                              12: latent prior: vg_latent_hist (+ _ws_bytes), vg_latent_sample, vg_to_u8;
                              13: Resize + CenterCrop on the device: vg_resize_u8 (+ _lds_bytes, _band);
-                             14: feature-space metrics: vg_feat_stats_accum, vg_knn_radius2, vg_manifold_cover (+ _ws_bytes each) */
+                             14: feature-space metrics: vg_feat_stats_accum, vg_knn_radius2, vg_manifold_cover (+ _ws_bytes each);
+                             15: KID: vg_kid_scores (+ _ws_bytes);
+                             16: Discriminator-feature reconstruction loss: vg_feat_mse_forward_backward */
 int vg_abi_version(void);
 /* The library reads its optional kernel-selection switches (VG_* environment variables, DESIGN.md "Runtime switches")
  * ONCE, when it is loaded; nothing on a launch path calls getenv.  A process that changes one of them afterwards
@@ -401,6 +403,16 @@ int vg_clamp(float* p, int64_t n, float lo, float hi, void* stream);
 /* nn.MSELoss(mean) (vaegan_code.py:47) on NCHW f32 tensors; d_a = gscale*2*(a-b)/n (NULL ok). */
 int vg_mse_forward_backward(const float* a, const float* b, int64_t n, float gscale,
                             float* loss, float* d_a, float* ws, int ws_capacity, void* stream);
+/* Discriminator-feature reconstruction loss (Larsen et al. 2016, eq. 2; ABI 16; csrc/featloss.hip) on two flat engine-layout
+ * activations of `dtype` (VG_F32 / VG_BF16), f_real being a constant:
+ *   loss[0] (+)= (1/n) sum_i (a_i - b_i)^2                  (accumulate_loss != 0: added to what the slot holds)
+ *   d_inout[i] = round_dtype(float(d_inout[i]) + f32(gscale 2 / n) (a_i - b_i))   (d_inout NULL: loss only)
+ * i.e. the loss gradient is ADDED onto the gradient already standing in d_inout, in the pass that reads a and b; f32
+ * arithmetic, one rounding on the store.  Two launches (partials + gradient; one wave for the final sum), fixed summation
+ * order, no atomics, capturable.  ws: ws_capacity f32 partial sums (1024 are used at most).  Pointers 16-byte aligned
+ * (VG_EALIGN).  Padded channel rows are the caller's business: pass only activations without padding. */
+int vg_feat_mse_forward_backward(const void* f_fake, const void* f_real, void* d_inout, int64_t n, float gscale, float* loss,
+                                 int accumulate_loss, float* ws, int ws_capacity, int dtype, void* stream);
 /* Mean SSIM of two NCHW f32 image batches in [-1,1] (rescaled to [0,1] as vaegan_code.py:170-174 does):
  * gaussian 11x11, sigma 1.5, k1 .01, k2 .03, data_range 1, 5-pixel border cropped.  out[0] = mean. */
 int vg_ssim(const float* a, const float* b, int B, int C, int H, int W, float* out, float* ws, int ws_capacity,

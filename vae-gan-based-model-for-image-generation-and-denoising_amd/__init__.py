@@ -5,7 +5,9 @@ Drop-in surface (INTEGRATION.md): ``Encoder``, ``ConvBlock`` (main_vae.py:20-58)
 ``Discriminator``, ``weights_init`` (gan_code.py:16-97), ``Adam`` (torch.optim.Adam as used at
 vaegan_code.py:42-44), ``BCELoss`` / ``MSELoss`` (vaegan_code.py:46-47), ``configure_seed``
 (utils.py:6-14), ``VAEGANTrainer`` (the loop body of vaegan_code.py:65-135) and ``graphed`` (hipGraph replay of a
-reference-shaped step function).  Generation (main_vae.py:415-641): ``latent`` -- ``encode_dataset``, ``LatentPrior``,
+reference-shaped step function).  The learned-similarity term of Larsen et al. (the reference README's eq. 2, absent from
+its code): ``VAEGANTrainer(..., feat_layer=, alpha_feat=, alpha_pix=)`` and ``Discriminator.features(x, layer)`` /
+``Discriminator.feature_layers()``.  Generation (main_vae.py:415-641): ``latent`` -- ``encode_dataset``, ``LatentPrior``,
 ``evaluate_generation``, ``sample_images``.  Feature-space metrics (fid.update / fid.compute of every evaluation loop,
 README.md:22 precision / recall): ``metrics`` -- ``FeatureStats``, ``frechet_distance``, ``precision_recall``,
 ``encoder_features``, ``kernel_distance`` (KID).  Data path (dataset_code.py): ``data`` -- ``ResidentImages`` (``resized``: Resize +

@@ -329,11 +329,33 @@ class StackEngine:
             self._specs[key] = ok
         return self._specs[key]
 
-    def forward(self, x: torch.Tensor, B: int, train: bool, keep: bool = True, groups: int = 1, tail=None):
+    def check_feat_stage(self, l) -> int:
+        """Stage index `l` as a legal tap / feature-loss stage, else ValueError: a stage WITH BatchNorm (a stage without one
+        has its activation backward folded into the next stage's dgrad mask, which a gradient added at its output would
+        bypass), followed by another stage, whose channel rows carry no padding (the feature loss reads them flat)."""
+        if isinstance(l, bool) or not isinstance(l, int) or not 0 <= l < len(self.stages) - 1:
+            raise ValueError(f"feature stage must be an integer in [0, {len(self.stages) - 1}) naming a BatchNorm stage, got {l!r}")
+        st = self.stages[l]
+        if st.kind == "head" or st.bn is None:
+            raise ValueError(f"feature stage {l} has no BatchNorm: only BatchNorm stages can be tapped")
+        if st.cout != G.padc(st.cout, self.dtype):
+            raise ValueError(f"feature stage {l}: {st.cout} channels are padded to {G.padc(st.cout, self.dtype)} in the "
+                             f"engine layout, which the feature loss does not handle")
+        return l
+
+    def forward(self, x: torch.Tensor, B: int, train: bool, keep: bool = True, groups: int = 1, tail=None, tap=None):
         """x: NHWC activation of the first stage.  Returns (output, ctx).  For a 'head' last stage the
         output is p [B] (f32); otherwise the (activated) NHWC output of the last stage.
         groups > 1: x holds `groups` independent batches of B images (see can_group); BatchNorm statistics,
-        running-stat updates and coefficients are per group, in group order."""
+        running-stat updates and coefficients are per group, in group order.
+        tap = l (see check_feat_stage): returns (output, ctx, A_l) with A_l the ACTIVATED output of stage l (after BatchNorm
+        and the activation; with keep=True it is ctx[l + 1]["x"]), also when keep=False.  The launches are those of the
+        untapped call."""
+        if tap is not None:
+            self.check_feat_stage(tap)
+            if groups != 1:
+                raise ValueError("tap needs groups == 1")
+        tapped = None
         packs = self._ensure_packed()
         dt = self.dtype
         ctx = []
@@ -430,8 +452,12 @@ class StackEngine:
                                        coeffs=None if coeffs is None else coeffs.clone(), fused_act=fuse_act,
                                        x8=None if x8 is None else x8.clone(), nparts=nparts))
             a, a8 = out, out8
+            if i == tap:
+                tapped = out
         if train and any(st.bn is not None for st in self.stages):
             self.pending_bn_ticks += groups
+        if tap is not None:
+            return a, (ctx, B, train), tapped
         return a, (ctx, B, train)
 
     # ---- backward ---------------------------------------------------------------------------------
@@ -446,7 +472,7 @@ class StackEngine:
         return out
 
     def backward(self, ctxpack, dout: torch.Tensor, need_dx: bool, sink: GradSink, param_grads: bool = True,
-                 on_grads=None, head_loss=None):
+                 on_grads=None, head_loss=None, feat=None):
         """dout: gradient w.r.t. forward()'s output.  Returns the gradient w.r.t. the NHWC input (or None).
         param_grads=False skips every weight/bias/BN-parameter gradient (legal when the caller discards
         them, e.g. the generator-loss pass through the discriminator).
@@ -456,11 +482,17 @@ class StackEngine:
         in the Discriminator's head -- the BCE of its output probabilities against target0 (first group of rows) / target1
         (second group), its gradient, the sigmoid backward and the head's data / weight gradients run as ONE launch
         (ops.head_backward; vaegan_code.py:99-104, :115); loss_slot[0] (+)= the loss.
+        feat = (l, f_real, gscale, loss_slot): the Discriminator-feature reconstruction loss at stage l (check_feat_stage):
+        when the loop reaches stage l, BEFORE its BatchNorm backward, ops.feat_mse_forward_backward writes
+        loss_slot[0] = mean((A_l - f_real)^2) and adds gscale * 2 (A_l - f_real) / n onto dA in place (A_l = ctx[l + 1]["x"],
+        the activation this pass stored; f_real a constant of the same shape) -- dA then carries both branches.
         Everything runs on the current stream: forking weight gradients onto a second stream (three schedules, rounds 1
         and 2) measured slower every time and is gone ("Concurrency does not pay")."""
         ctx, B, train = ctxpack
         if not train:
             raise RuntimeError("backward through an eval-mode network is not supported (the reference never does it)")
+        if feat is not None:
+            self.check_feat_stage(feat[0])
         packs = self._ensure_packed()
         dt = self.dtype
         dA = dout
@@ -499,6 +531,14 @@ class StackEngine:
             Y, rows, OC = c["Y"], c["rows"], c["OC"]
             yshape = c["Yshape"] if Y is None else Y.shape
             dA = dA.view(yshape) if dA.shape != yshape else dA
+            if feat is not None and i == feat[0]:
+                _, f_real, fscale, fslot = feat
+                f_fake = ctx[i + 1]["x"]
+                dA_in = dA.clone() if self.trace is not None else None
+                ops.feat_mse_forward_backward(f_fake, f_real.view(f_fake.shape), dA, fscale, fslot, False, dt)
+                if self.trace is not None:
+                    self.trace.append(dict(stage=i, what="feat", f_fake=f_fake.clone(), f_real=f_real.clone(), dA_in=dA_in,
+                                           dA=dA.clone(), gscale=fscale, loss=fslot.clone()))
             gg_, gb_, acc_g = None, None, False
             if st.bn is not None:
                 if param_grads:

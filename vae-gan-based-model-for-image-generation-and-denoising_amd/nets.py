@@ -389,8 +389,28 @@ class Discriminator(_EngineNet):
         stages.append(Stage("head", chans[-1], 1, 4, 1, 0, 4, 1, conv=self.main[3 * len(chans) - 1]))
         self._engine = StackEngine(stages, self._dt, nc, fp8_fprop=_is_fp8(dtype))
 
-    def engine_forward(self, x_nhwc, B, keep=True, groups=1):
-        return self._engine.forward(x_nhwc, B, self.training, keep, groups=groups)
+    def engine_forward(self, x_nhwc, B, keep=True, groups=1, tap=None):
+        """tap = l: -> (p, ctx, activated output of engine stage l) (engine.StackEngine.forward)."""
+        return self._engine.forward(x_nhwc, B, self.training, keep, groups=groups, tap=tap)
+
+    def feature_layers(self):
+        """Engine stages whose activation `features` / the trainer's feat_layer accept: those with a BatchNorm
+        (img_size 64: 1, 2, 3 = 128 @ 16^2, 256 @ 8^2, 512 @ 4^2; img_size 256: 1..5)."""
+        return [i for i, st in enumerate(self._engine.stages) if st.bn is not None]
+
+    def features(self, x, layer):
+        """Dis_l(x) of Larsen et al. (eq. 2): the ACTIVATED output (after BatchNorm and LeakyReLU) of engine stage `layer`
+        for images x [B,nc,S,S] f32 on the device, as NCHW f32.  No autograd; BatchNorm follows self.training (a train-mode
+        call updates the running statistics and num_batches_tracked like any other train-mode forward -- the whole stack
+        runs).  ValueError for a stage without BatchNorm (stage 0), the head, or an index out of range."""
+        self._engine.check_feat_stage(layer)
+        _check_input(x, "Discriminator.features")
+        B, C, H, W = x.shape
+        if C != self.nc or H != self.img_size or W != self.img_size:
+            raise RuntimeError(f"Discriminator was built for {self.nc}x{self.img_size}x{self.img_size} images, got {C}x{H}x{W}")
+        xh = ops.nchw_to_nhwc(x.detach().contiguous(), G.padc(C, self._dt), self._dt)
+        _, _, f = self.engine_forward(xh, B, keep=False, tap=layer)
+        return ops.nhwc_to_nchw(f, self._engine.stages[layer].cout, self._dt)
 
     def _forward_impl(self, x, keep):
         B, C, H, W = x.shape

@@ -1258,6 +1258,23 @@ def mse_forward_backward(a, b, gscale, loss, want_grad, defer_final=False):
     return da
 
 
+def feat_mse_forward_backward(f_fake, f_real, d_inout, gscale, loss, accumulate, dtype):
+    """Discriminator-feature reconstruction loss (vg_feat_mse_forward_backward): loss[0] (+)= mean((f_fake - f_real)^2) and,
+    when d_inout is given, d_inout += gscale * 2 (f_fake - f_real) / n IN PLACE (the gradient w.r.t. f_fake joins the one
+    already there; f_real is a constant).  Engine-layout activations of `dtype` whose channel rows carry no padding."""
+    _need_cuda(f_fake, f_real, d_inout, loss)
+    tdt = TORCH_DT[dtype]
+    if f_fake.dtype != tdt or f_real.dtype != tdt or (d_inout is not None and d_inout.dtype != tdt):
+        raise RuntimeError(f"feat_mse_forward_backward: tensors must all be {tdt}")
+    if f_fake.shape != f_real.shape or (d_inout is not None and d_inout.numel() != f_fake.numel()):
+        raise RuntimeError("feat_mse_forward_backward: f_fake, f_real and d_inout must have the same number of elements")
+    ws = WS.get("featloss", 1024 * 4, f_fake.device)
+    L.check(L.load().vg_feat_mse_forward_backward(f_fake.data_ptr(), f_real.data_ptr(), L.ptr(d_inout), f_fake.numel(), gscale,
+                                                  loss.data_ptr(), 1 if accumulate else 0, ws.data_ptr(), 1024, dtype,
+                                                  L.stream_ptr()), "vg_feat_mse_forward_backward")
+    return d_inout
+
+
 def axpy(a, b, alpha, out=None):
     out = out if out is not None else torch.empty_like(a)
     L.check(L.load().vg_axpy(a.data_ptr(), b.data_ptr(), alpha, out.data_ptr(), a.numel(), L.stream_ptr()), "vg_axpy")

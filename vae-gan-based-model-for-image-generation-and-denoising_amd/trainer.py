@@ -40,7 +40,7 @@ class VAEGANTrainer:
     def __init__(self, encoder, decoder, discriminator, opt_E, opt_Dec, opt_Dis, alpha_kl: float = 0.1,
                  alpha_adv: float = 0.1, noise_sigma: float = 0.05, real_label: float = 0.9, fake_label: float = 0.1,
                  d_iters: int = 2, elide_dead_grads: bool = False, reducer=None, group_d_passes: bool = True,
-                 sync_bn: bool = False):
+                 sync_bn: bool = False, feat_layer: Optional[int] = None, alpha_feat: float = 0.0, alpha_pix: float = 1.0):
         self.E, self.G, self.D = encoder, decoder, discriminator
         self.opt_E, self.opt_G, self.opt_D = opt_E, opt_Dec, opt_Dis
         self.alpha_kl, self.alpha_adv, self.sigma = alpha_kl, alpha_adv, noise_sigma          # :49-50, :91-92
@@ -48,6 +48,16 @@ class VAEGANTrainer:
         # The generator-loss pass through D (vaegan_code.py:110,133) also produces D weight gradients that the
         # next opt_Dis.zero_grad() discards unread.  False = compute them anyway (what the reference executes).
         self.elide_dead_grads = elide_dead_grads
+        # Discriminator-feature reconstruction loss (Larsen et al. 2016, eq. 2): total +=
+        # alpha_feat * mean((D_l(recon_noisy) - D_l(real_noisy))^2), D_l = the activated output of the Discriminator's engine
+        # stage feat_layer, D_l(real_noisy) a constant.  alpha_pix weighs the pixel MSE (alpha_pix = 0, alpha_feat > 0 is
+        # Larsen's form).  Off (alpha_feat = 0, the default): the iteration launches exactly what it launched without it.
+        self.alpha_feat, self.alpha_pix = float(alpha_feat), float(alpha_pix)
+        if feat_layer is not None:
+            discriminator._engine.check_feat_stage(feat_layer)
+        elif self.alpha_feat != 0.0:
+            raise ValueError("alpha_feat != 0 needs feat_layer (a BatchNorm stage of the Discriminator)")
+        self.feat_layer = feat_layer
         self.group_d_passes = group_d_passes       # run a D iteration's real+fake passes as one 2B-row launch chain
         # BCE + its gradient + the sigmoid / head backward as ONE launch per Discriminator pass (ops.head_backward;
         # bit-identical to the three separate launches, which False selects)
@@ -105,7 +115,8 @@ class VAEGANTrainer:
         launches point at.  A change in any of them re-captures instead of silently replaying stale values."""
         opts = tuple((o.lr, o.betas, o.eps, o.grad_scale, o.flat_p.data_ptr()) for o in (self.opt_E, self.opt_G, self.opt_D))
         return (tuple(real.shape), float(self.alpha_kl * min(1.0, epoch / 50)), inject, self.E.training, self.G.training,
-                self.D.training, self.alpha_adv, self.sigma, self.real_label, self.fake_label, self.d_iters,
+                self.D.training, self.alpha_adv, self.alpha_feat, self.alpha_pix, self.feat_layer, self.sigma, self.real_label,
+                self.fake_label, self.d_iters,
                 self.elide_dead_grads, self.group_d_passes, self.fuse_head_backward, self.fuse_step_prologue,
                 self.merge_small_launches,
                 id(self.reducer), self.sync_bn, opts,
@@ -165,7 +176,9 @@ class VAEGANTrainer:
 
     def train_step(self, real: torch.Tensor, epoch: int, eps_z: Optional[torch.Tensor] = None,
                    eps_real: Optional[torch.Tensor] = None, eps_recon: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """One iteration.  Returns a device tensor [recon_loss, kl_loss, g_loss_adv, d_loss_1, d_loss_2]."""
+        """One iteration.  Returns a device tensor [recon_loss, kl_loss, g_loss_adv, d_loss_1, d_loss_2, feat_loss, 0, 0]:
+        slot 5 holds the Discriminator-feature reconstruction loss (unweighted, like recon_loss) when alpha_feat != 0 and
+        reads 0 when the feature is off."""
         steps = [o.steps for o in (self.opt_E, self.opt_G, self.opt_D)]
         try:
             return self._train_step(real, epoch, eps_z, eps_real, eps_recon)
@@ -268,23 +281,31 @@ class VAEGANTrainer:
             self.opt_D.step(prepared=prep and it == 0)
 
         # ---- Generator + VAE loss (:110-117) ----
+        feat = None
+        if self.alpha_feat != 0.0:
+            # Dis_l(x): one more ordinary train-mode pass of D on the noisy real batch, after the d_iters updates and BEFORE
+            # the pass on the reconstruction (BatchNorm buffers see real, then fake); nothing kept but the tapped activation
+            _, _, f_real = D.engine_forward(real_noisy, B, keep=False, tap=self.feat_layer)
+            feat = (self.feat_layer, f_real, self.alpha_feat, losses[5:6])
         p_adv, c_adv = D.engine_forward(recon_noisy, B)
         if self.merge_small_launches:
             # :113-114: the MSE's final sum rides on the KL launch (same arithmetic as its own one-wave launch)
-            d_recon, mse_tail = ops.mse_forward_backward(recon, real, 1.0, losses[0:1], True, defer_final=True)
+            d_recon, mse_tail = ops.mse_forward_backward(recon, real, self.alpha_pix, losses[0:1], True, defer_final=True)
             ops.kl_forward(mulv, lvc, L, float(B), dt, out=losses[1:2], mse=mse_tail)
         else:
-            d_recon = ops.mse_forward_backward(recon, real, 1.0, losses[0:1], True)           # :113
+            d_recon = ops.mse_forward_backward(recon, real, self.alpha_pix, losses[0:1], True)    # :113
             ops.kl_forward(mulv, lvc, L, float(B), dt, out=losses[1:2])                       # :114
         dp_adv = None
         if not fused_head:
             dp_adv = ops.bce_forward_backward(p_adv, self.real_label, self.alpha_adv, losses[2:3], False, True)  # :115
 
-        # ---- backward of total = recon + a_kl*min(1,epoch/50)*kl + a_adv*adv, then E and G steps (:131-135) ----
+        # ---- backward of total = a_pix*recon + a_kl*min(1,epoch/50)*kl + a_adv*adv (+ a_feat*feat), then E and G steps
+        # (:131-135) ----
         self.opt_E.zero_grad(memset=False)
         self.opt_G.zero_grad(memset=False)
         d_noisy = D._engine.backward(c_adv, dp_adv, True, sink, param_grads=not self.elide_dead_grads,
-                                     head_loss=(self.real_label, 0.0, 1, self.alpha_adv, losses[2:3], False) if fused_head else None)
+                                     head_loss=(self.real_label, 0.0, 1, self.alpha_adv, losses[2:3], False) if fused_head else None,
+                                     feat=feat)
         # d total / d recon = d MSE + d adv through the instance-noise add (:92), then through tanh: one pass
         d_pre = ops.nchw_grad_add_to_nhwc(d_recon, d_noisy, recon, G.padc(Gn.nc, dt), dt)
         dz = Gn._engine.backward(ctxG, d_pre, True, sink, on_grads=self._grad_hook(self.opt_G, Gn))
@@ -442,9 +463,12 @@ class VAEGANTrainer:
 
     def loss_dict(self, losses: Optional[torch.Tensor] = None, epoch: Optional[int] = None) -> Dict[str, float]:
         """Host copy of the last step's losses (one device sync, like the reference's .item() calls :125-127)."""
-        v = (losses if losses is not None else self.losses)[:5].tolist()
+        v = (losses if losses is not None else self.losses)[:6].tolist()
+        v += [0.0] * (6 - len(v))                # a caller's five-slot slice
         out = dict(zip(LOSS_NAMES, v))
+        if self.alpha_feat != 0.0:
+            out["feat_loss"] = v[5]
         if epoch is not None:
-            out["total"] = out["recon_loss"] + self.alpha_kl * min(1.0, epoch / 50) * out["kl_loss"] \
-                + self.alpha_adv * out["g_loss_adv"]
+            out["total"] = self.alpha_pix * out["recon_loss"] + self.alpha_kl * min(1.0, epoch / 50) * out["kl_loss"] \
+                + self.alpha_adv * out["g_loss_adv"] + self.alpha_feat * v[5]
         return out
