@@ -229,6 +229,22 @@ __global__ void step_prologue_kernel(const PrologueArgs a) {
     }
 }
 
+// g * grad_scale as a ROUNDED f32 product -- the gradient torch's Adam is handed after the all-reduce and the division by
+// the world size.  Contraction off (the pragma binds lexically): hipcc otherwise folds the product into the fma of
+// (g * scale - m), which moves exp_avg in the last bits of g for every scale that is no power of two.
+__device__ __forceinline__ float adam_grad(float g, float gscale) {
+#pragma clang fp contract(off)
+    return g * gscale;
+}
+
+// exp_avg.lerp_(grad, w) as ATen evaluates it (Lerp.h): the form anchored at the nearer end -- m + w (g - m) for w < 0.5,
+// g - (g - m)(1 - w) otherwise.  The two differ by the rounding of (g - m): where g ~ -m that is a relative error of 1e-5
+// in the new moment.  torch's defaults (beta1 = 0.9, w = 0.1) take the first form, the DCGAN trainer's beta1 = 0.5 the second.
+__device__ __forceinline__ float adam_lerp(float m, float g, float w) {
+    const float d = g - m;
+    return w < 0.5f ? m + w * d : g - d * (1.0f - w);
+}
+
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                    float* __restrict__ m, float* __restrict__ v, int64_t n4,
                                                    int64_t n, float w1, float beta2, float w2, float eps,
@@ -243,8 +259,8 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
         float* P = &pp.x; float* G = &gg.x; float* Mv = &mm.x; float* V = &vv.x;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            const float gr = G[k] * gscale;
-            Mv[k] = Mv[k] + w1 * (gr - Mv[k]);                 // exp_avg.lerp_(grad, 1-beta1)
+            const float gr = adam_grad(G[k], gscale);
+            Mv[k] = adam_lerp(Mv[k], gr, w1);                  // exp_avg.lerp_(grad, 1-beta1)
             V[k] = V[k] * beta2 + w2 * (gr * gr);              // mul_(beta2).addcmul_(g, g, 1-beta2)
             const float denom = sqrtf(V[k]) / bc2_sqrt + eps;
             P[k] = P[k] - step_size * (Mv[k] / denom);         // addcdiv_(exp_avg, denom, -step_size)
@@ -256,9 +272,9 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
     // tail (n not a multiple of 4)
     if (blockIdx.x == 0) {
         for (int64_t i = n4 * 4 + threadIdx.x; i < n; i += blockDim.x) {
-            const float gr = g[i] * gscale;
+            const float gr = adam_grad(g[i], gscale);
             float mi = m[i], vi = v[i];
-            mi = mi + w1 * (gr - mi);
+            mi = adam_lerp(mi, gr, w1);
             vi = vi * beta2 + w2 * (gr * gr);
             const float denom = sqrtf(vi) / bc2_sqrt + eps;
             p[i] = p[i] - step_size * (mi / denom);
@@ -294,8 +310,8 @@ __global__ __launch_bounds__(256) void adam2_kernel(const Adam2Args a) {
         float* P = &pp.x; float* G = &gg.x; float* Mv = &mm.x; float* V = &vv.x;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            const float gr = G[k] * gscale;
-            Mv[k] = Mv[k] + w1 * (gr - Mv[k]);
+            const float gr = adam_grad(G[k], gscale);
+            Mv[k] = adam_lerp(Mv[k], gr, w1);
             V[k] = V[k] * beta2 + w2 * (gr * gr);
             const float denom = sqrtf(V[k]) / bc2_sqrt + eps;
             P[k] = P[k] - step_size * (Mv[k] / denom);
@@ -306,9 +322,9 @@ __global__ __launch_bounds__(256) void adam2_kernel(const Adam2Args a) {
     }
     if (bid == 0) {
         for (int64_t i = n4 * 4 + threadIdx.x; i < n; i += blockDim.x) {
-            const float gr = g[i] * gscale;
+            const float gr = adam_grad(g[i], gscale);
             float mi = m[i], vi = v[i];
-            mi = mi + w1 * (gr - mi);
+            mi = adam_lerp(mi, gr, w1);
             vi = vi * beta2 + w2 * (gr * gr);
             const float denom = sqrtf(vi) / bc2_sqrt + eps;
             p[i] = p[i] - step_size * (mi / denom);

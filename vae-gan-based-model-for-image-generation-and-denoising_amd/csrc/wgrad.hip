@@ -502,7 +502,8 @@ __global__ __launch_bounds__(256) void wgrad_bf16_dma_kernel(const vg_wg_desc d,
 // global_load_lds only), a ring of three 48 KB stages with two stages in flight across the single s_barrier per
 // stage, counted vmcnt in the producers.  A producer wave owns row groups pw and pw + 8 of every operand tile:
 // (row & 7), the swizzle key, is the same for both, so a lane still fetches one fixed source unit all kernel long.
-// Why it wins where its parts lose (S=64 B=128, tools/ab_wgrad_spec.sh, all wgrad tests pass in every mode):
+// Why it wins where its parts lose (S=64 B=128, tools/ab_wgrad_spec.sh; every mode gives the same bits on integer operands:
+// tests/test_gpu_wgrad.py, test_every_build_of_the_weight_gradient_gives_the_same_bits):
 //   * one role per wave, 2 workgroups per CU (kernel above):            G1-G4 57 / 55 / 54 / 54 us, step 2.845 ms
 //   * 128 x 256 tile, one role per wave, 1 workgroup per CU:            3-10 % slower (all waves in the same phase)
 //   * 128 x 128 tile, 4 consumers + 8 producers (VG_WG_SPEC=1):         61 / 56 / 56 / 55 us (one consumer per SIMD
