@@ -48,7 +48,7 @@ extern "C" {
 #define VG_ACT_LRELU   2   /* nn.LeakyReLU(slope)    main_vae.py:25, gan_code.py:62-82 */
 #define VG_ACT_TANH    3   /* nn.Tanh()              gan_code.py:50 (vg_tnconv epilogue only) */
 
-#define VG_ABI_VERSION 16  /* 2: vg_pack_desc.tile_start, SyncBN / WGAN / data-path entry points; 3: in-kernel noise (vg_*_rng);
+#define VG_ABI_VERSION 17  /* 2: vg_pack_desc.tile_start, SyncBN / WGAN / data-path entry points; 3: in-kernel noise (vg_*_rng);
                              4: vg_bn_finalize_act_forward, vg_bn_backward_finalize_apply;
                              7: vg_bce_pair_forward_backward;
                              8: vg_head_backward; round-3 prune -- the opt-in experiments of ABI 5 / 6 that measured slower (input prologue of
@@ -60,7 +60,8 @@ extern "C" {
                              13: Resize + CenterCrop on the device: vg_resize_u8 (+ _lds_bytes, _band);
                              14: feature-space metrics: vg_feat_stats_accum, vg_knn_radius2, vg_manifold_cover (+ _ws_bytes each);
                              15: KID: vg_kid_scores (+ _ws_bytes);
-                             16: Discriminator-feature reconstruction loss: vg_feat_mse_forward_backward */
+                             16: Discriminator-feature reconstruction loss: vg_feat_mse_forward_backward;
+                             17: SSIM reconstruction loss: vg_ssim_loss_forward_backward (+ _ws_floats) */
 int vg_abi_version(void);
 /* The library reads its optional kernel-selection switches (VG_* environment variables, DESIGN.md "Runtime switches")
  * ONCE, when it is loaded; nothing on a launch path calls getenv.  A process that changes one of them afterwards
@@ -413,6 +414,22 @@ int vg_mse_forward_backward(const float* a, const float* b, int64_t n, float gsc
  * (VG_EALIGN).  Padded channel rows are the caller's business: pass only activations without padding. */
 int vg_feat_mse_forward_backward(const void* f_fake, const void* f_real, void* d_inout, int64_t n, float gscale, float* loss,
                                  int accumulate_loss, float* ws, int ws_capacity, int dtype, void* stream);
+/* SSIM reconstruction loss (ABI 17; csrc/ssimloss.hip): the contract of vg_ssim below made differentiable.  a (reconstruction)
+ * and b (target, a constant) are NCHW f32 in [-1, 1], u = (a + 1) / 2, v = (b + 1) / 2; g = the normalised 11-tap Gaussian
+ * (sigma 1.5), w = g (x) g; over the interior pixels p in [5, H - 5) x [5, W - 5) (what the metric keeps after its crop; no
+ * padding is ever read), with c1 = 1e-4, c2 = 9e-4:
+ *   mu_u = sum w u, mu_v = sum w v, s_uu = sum w u^2 - mu_u^2, s_vv likewise, s_uv = sum w u v - mu_u mu_v
+ *   S = (2 mu_u mu_v + c1)(2 s_uv + c2) / ((mu_u^2 + mu_v^2 + c1)(s_uu + s_vv + c2))
+ *   loss[0] (+)= 1 - (1 / n) sum_p S(p),  n = B C (H - 10)(W - 10)      (accumulate_loss != 0: added to what the slot holds)
+ *   d[q] += gscale * d(1 - mean S) / d a[q]     for every pixel q of the H x W plane            (d NULL: forward only)
+ * i.e. the loss gradient is ADDED onto the gradient already standing in d (same shape as a).  Two launches (tiles: forward
+ * and backward, one read-modify-write of d per element by its one owner; one wave for the final sum), fixed summation
+ * order, no atomics, capturable.  ws: vg_ssim_loss_ws_floats(B, C, H, W) f32 partial sums (one per 32 x 32 tile of every
+ * plane); ws_capacity in floats.  VG_EINVAL: a, b or loss NULL, B or C < 1, H or W < 11, ws NULL or too small.  No alignment
+ * beyond that of a float is required. */
+int vg_ssim_loss_forward_backward(const float* a, const float* b, float* d, int B, int C, int H, int W, float gscale,
+                                  float* loss, int accumulate_loss, float* ws, int ws_capacity, void* stream);
+int64_t vg_ssim_loss_ws_floats(int B, int C, int H, int W);      /* VG_EINVAL (negative) for sizes outside the contract */
 /* Mean SSIM of two NCHW f32 image batches in [-1,1] (rescaled to [0,1] as vaegan_code.py:170-174 does):
  * gaussian 11x11, sigma 1.5, k1 .01, k2 .03, data_range 1, 5-pixel border cropped.  out[0] = mean. */
 int vg_ssim(const float* a, const float* b, int B, int C, int H, int W, float* out, float* ws, int ws_capacity,

@@ -7,7 +7,8 @@ vaegan_code.py:42-44), ``BCELoss`` / ``MSELoss`` (vaegan_code.py:46-47), ``confi
 (utils.py:6-14), ``VAEGANTrainer`` (the loop body of vaegan_code.py:65-135) and ``graphed`` (hipGraph replay of a
 reference-shaped step function).  The learned-similarity term of Larsen et al. (the reference README's eq. 2, absent from
 its code): ``VAEGANTrainer(..., feat_layer=, alpha_feat=, alpha_pix=)`` and ``Discriminator.features(x, layer)`` /
-``Discriminator.feature_layers()``.  Generation (main_vae.py:415-641): ``latent`` -- ``encode_dataset``, ``LatentPrior``,
+``Discriminator.feature_layers()``.  The SSIM reconstruction loss (1 - the SSIM the denoising passes report; not in the
+reference): ``SSIMLoss`` and ``VAEGANTrainer(..., alpha_ssim=)`` / ``VAETrainer(..., alpha_ssim=)``.  Generation (main_vae.py:415-641): ``latent`` -- ``encode_dataset``, ``LatentPrior``,
 ``evaluate_generation``, ``sample_images``.  Feature-space metrics (fid.update / fid.compute of every evaluation loop,
 README.md:22 precision / recall): ``metrics`` -- ``FeatureStats``, ``frechet_distance``, ``precision_recall``,
 ``encoder_features``, ``kernel_distance`` (KID).  Data path (dataset_code.py): ``data`` -- ``ResidentImages`` (``resized``: Resize +
@@ -23,14 +24,14 @@ from .denoise import denoise_eval, paired_test_epoch, validation_epoch
 from .graphed import graphed
 from .latent import LatentPrior, encode_dataset, evaluate_generation, sample_images
 from .metrics import FeatureStats, encoder_features, frechet_distance, kernel_distance, precision_recall
-from .losses import BCELoss, MSELoss
+from .losses import BCELoss, MSELoss, SSIMLoss
 from .nets import ConvBlock, Discriminator, Encoder, Generator, weights_init
 from .optim import Adam
 from .siblings import DCGANTrainer, VAETrainer, WGANTrainer
 from .trainer import LOSS_NAMES, VAEGANTrainer
 from .utils import configure_seed
 
-__all__ = ["ConvBlock", "Encoder", "Generator", "Discriminator", "weights_init", "Adam", "BCELoss", "MSELoss",
+__all__ = ["ConvBlock", "Encoder", "Generator", "Discriminator", "weights_init", "Adam", "BCELoss", "MSELoss", "SSIMLoss",
            "VAEGANTrainer", "LOSS_NAMES", "configure_seed", "geometry", "denoise_eval", "validation_epoch", "paired_test_epoch", "GradReducer", "data", "VAETrainer", "DCGANTrainer", "WGANTrainer", "graphed",
            "latent", "LatentPrior", "encode_dataset", "evaluate_generation", "sample_images",
            "ResidentImages", "resample_coeffs", "resize_geometry",

@@ -1275,6 +1275,25 @@ def feat_mse_forward_backward(f_fake, f_real, d_inout, gscale, loss, accumulate,
     return d_inout
 
 
+def ssim_loss_forward_backward(a, b, gscale, loss, accumulate, d=None):
+    """SSIM reconstruction loss (vg_ssim_loss_forward_backward): loss[0] (+)= 1 - mean SSIM(a, b) over the interior pixels
+    (NCHW f32 in [-1, 1], the metric's 11 x 11 Gaussian window) and, when d is given (same shape as a), d += gscale *
+    d(1 - mean SSIM) / da IN PLACE: the gradient joins the one already there; b is a constant.  Returns d."""
+    _need_cuda(a, b, loss, d)
+    if a.dtype != torch.float32 or b.dtype != torch.float32 or (d is not None and d.dtype != torch.float32):
+        raise RuntimeError("ssim_loss_forward_backward: tensors must all be torch.float32")
+    if a.dim() != 4 or a.shape != b.shape or (d is not None and d.shape != a.shape):
+        raise RuntimeError("ssim_loss_forward_backward: a, b and d must be [B,C,H,W] tensors of one shape")
+    B, C, H, W = a.shape
+    lib = L.load()
+    nws = _ws_query(lib.vg_ssim_loss_ws_floats(B, C, H, W), "vg_ssim_loss_ws_floats (needs B, C >= 1 and H, W >= 11)")
+    ws = WS.get("ssimloss", nws * 4, a.device)
+    L.check(lib.vg_ssim_loss_forward_backward(a.data_ptr(), b.data_ptr(), L.ptr(d), B, C, H, W, gscale, loss.data_ptr(),
+                                              1 if accumulate else 0, ws.data_ptr(), nws, L.stream_ptr()),
+            "vg_ssim_loss_forward_backward")
+    return d
+
+
 def axpy(a, b, alpha, out=None):
     out = out if out is not None else torch.empty_like(a)
     L.check(L.load().vg_axpy(a.data_ptr(), b.data_ptr(), alpha, out.data_ptr(), a.numel(), L.stream_ptr()), "vg_axpy")

@@ -81,9 +81,13 @@ class VAETrainer(_Graphed):
     ``list(encoder.parameters()) + list(decoder.parameters())`` (main_vae.py:84-87)."""
     LOSS_NAMES = ("recon_loss", "kl_loss", "total")
 
-    def __init__(self, encoder, decoder, optimizer, noise_max_std: float = 0.5, kl_weight: float = 1e-5):
+    def __init__(self, encoder, decoder, optimizer, noise_max_std: float = 0.5, kl_weight: float = 1e-5,
+                 alpha_ssim: float = 0.0):
         self.E, self.G, self.opt = encoder, decoder, optimizer
         self.sigma, self.kl_weight = noise_max_std, kl_weight                       # :66, :121
+        # SSIM reconstruction loss (not in the reference; DESIGN.md section 4.4f): total += alpha_ssim * (1 - SSIM(recon,
+        # img)), the gradient added onto the MSE's.  Off (0, the default): the iteration launches what it launched before.
+        self.alpha_ssim = float(alpha_ssim)
         self.dt = _same_dtype(encoder, decoder)
         self._nets, self._opts = (encoder, decoder), (optimizer,)
 
@@ -92,7 +96,8 @@ class VAETrainer(_Graphed):
 
     def train_step(self, img: torch.Tensor, eps_img: Optional[torch.Tensor] = None,
                    eps_z: Optional[torch.Tensor] = None, epoch: int = 0) -> torch.Tensor:
-        """-> device tensor [recon_loss, kl_loss (sum, not /B), total]."""
+        """-> device tensor [recon_loss, kl_loss (sum, not /B), total, ssim_loss]: slot 3 holds 1 - SSIM(recon, img)
+        (unweighted; total includes alpha_ssim times it) when alpha_ssim != 0 and reads 0 otherwise."""
         _need_cuda(img, "VAETrainer.train_step")
         E, Gn, dt = self.E, self.G, self.dt
         B, dev, L = img.shape[0], img.device, E.latent_dim
@@ -118,6 +123,9 @@ class VAETrainer(_Graphed):
         ops.kl_forward(mulv, lvc, L, 1.0, dt, out=losses[1:2])                     # :120
         w = min(epoch / 50, 1.0) * self.kl_weight                                  # :121
         torch.add(losses[0:1], losses[1:2], alpha=w, out=losses[2:3])
+        if self.alpha_ssim != 0.0:
+            ops.ssim_loss_forward_backward(recon, img, self.alpha_ssim, losses[3:4], False, d_recon)
+            torch.add(losses[2:3], losses[3:4], alpha=self.alpha_ssim, out=losses[2:3])
         self.opt.zero_grad(memset=False)                                           # :124
         d_pre = ops.nchw_grad_to_nhwc(d_recon, recon, G.padc(Gn.nc, dt), dt)
         dz = Gn._engine.backward(ctxG, d_pre, True, sink)

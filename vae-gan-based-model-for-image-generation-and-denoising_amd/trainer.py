@@ -40,7 +40,8 @@ class VAEGANTrainer:
     def __init__(self, encoder, decoder, discriminator, opt_E, opt_Dec, opt_Dis, alpha_kl: float = 0.1,
                  alpha_adv: float = 0.1, noise_sigma: float = 0.05, real_label: float = 0.9, fake_label: float = 0.1,
                  d_iters: int = 2, elide_dead_grads: bool = False, reducer=None, group_d_passes: bool = True,
-                 sync_bn: bool = False, feat_layer: Optional[int] = None, alpha_feat: float = 0.0, alpha_pix: float = 1.0):
+                 sync_bn: bool = False, feat_layer: Optional[int] = None, alpha_feat: float = 0.0, alpha_pix: float = 1.0,
+                 alpha_ssim: float = 0.0):
         self.E, self.G, self.D = encoder, decoder, discriminator
         self.opt_E, self.opt_G, self.opt_D = opt_E, opt_Dec, opt_Dis
         self.alpha_kl, self.alpha_adv, self.sigma = alpha_kl, alpha_adv, noise_sigma          # :49-50, :91-92
@@ -58,6 +59,11 @@ class VAEGANTrainer:
         elif self.alpha_feat != 0.0:
             raise ValueError("alpha_feat != 0 needs feat_layer (a BatchNorm stage of the Discriminator)")
         self.feat_layer = feat_layer
+        # SSIM reconstruction loss: total += alpha_ssim * (1 - SSIM(recon, real)), the metric of
+        # denoise.py (11 x 11 Gaussian window, interior pixels) as a training term; its gradient is added onto the pixel
+        # MSE's in the buffer that launch wrote (csrc/ssimloss.hip, one launch for forward and backward).  Off (0, the
+        # default): the iteration launches exactly what it launched without it.
+        self.alpha_ssim = float(alpha_ssim)
         self.group_d_passes = group_d_passes       # run a D iteration's real+fake passes as one 2B-row launch chain
         # BCE + its gradient + the sigmoid / head backward as ONE launch per Discriminator pass (ops.head_backward;
         # bit-identical to the three separate launches, which False selects)
@@ -115,7 +121,8 @@ class VAEGANTrainer:
         launches point at.  A change in any of them re-captures instead of silently replaying stale values."""
         opts = tuple((o.lr, o.betas, o.eps, o.grad_scale, o.flat_p.data_ptr()) for o in (self.opt_E, self.opt_G, self.opt_D))
         return (tuple(real.shape), float(self.alpha_kl * min(1.0, epoch / 50)), inject, self.E.training, self.G.training,
-                self.D.training, self.alpha_adv, self.alpha_feat, self.alpha_pix, self.feat_layer, self.sigma, self.real_label,
+                self.D.training, self.alpha_adv, self.alpha_feat, self.alpha_pix, self.alpha_ssim, self.feat_layer, self.sigma,
+                self.real_label,
                 self.fake_label, self.d_iters,
                 self.elide_dead_grads, self.group_d_passes, self.fuse_head_backward, self.fuse_step_prologue,
                 self.merge_small_launches,
@@ -176,9 +183,10 @@ class VAEGANTrainer:
 
     def train_step(self, real: torch.Tensor, epoch: int, eps_z: Optional[torch.Tensor] = None,
                    eps_real: Optional[torch.Tensor] = None, eps_recon: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """One iteration.  Returns a device tensor [recon_loss, kl_loss, g_loss_adv, d_loss_1, d_loss_2, feat_loss, 0, 0]:
-        slot 5 holds the Discriminator-feature reconstruction loss (unweighted, like recon_loss) when alpha_feat != 0 and
-        reads 0 when the feature is off."""
+        """One iteration.  Returns a device tensor [recon_loss, kl_loss, g_loss_adv, d_loss_1, d_loss_2, feat_loss, ssim_loss, 0]:
+        slot 5 holds the Discriminator-feature reconstruction loss (unweighted, like recon_loss) when alpha_feat != 0,
+        slot 6 the SSIM reconstruction loss 1 - SSIM(recon, real) (unweighted) when alpha_ssim != 0; each reads 0 when its
+        term is off."""
         steps = [o.steps for o in (self.opt_E, self.opt_G, self.opt_D)]
         try:
             return self._train_step(real, epoch, eps_z, eps_real, eps_recon)
@@ -295,18 +303,22 @@ class VAEGANTrainer:
         else:
             d_recon = ops.mse_forward_backward(recon, real, self.alpha_pix, losses[0:1], True)    # :113
             ops.kl_forward(mulv, lvc, L, float(B), dt, out=losses[1:2])                       # :114
+        if self.alpha_ssim != 0.0:
+            # 1 - SSIM(recon, real) and its gradient, added onto the MSE's in d_recon (which that launch wrote in full, also
+            # with alpha_pix = 0)
+            ops.ssim_loss_forward_backward(recon, real, self.alpha_ssim, losses[6:7], False, d_recon)
         dp_adv = None
         if not fused_head:
             dp_adv = ops.bce_forward_backward(p_adv, self.real_label, self.alpha_adv, losses[2:3], False, True)  # :115
 
-        # ---- backward of total = a_pix*recon + a_kl*min(1,epoch/50)*kl + a_adv*adv (+ a_feat*feat), then E and G steps
+        # ---- backward of total = a_pix*recon + a_kl*min(1,epoch/50)*kl + a_adv*adv (+ a_feat*feat) (+ a_ssim*ssim), then E and G steps
         # (:131-135) ----
         self.opt_E.zero_grad(memset=False)
         self.opt_G.zero_grad(memset=False)
         d_noisy = D._engine.backward(c_adv, dp_adv, True, sink, param_grads=not self.elide_dead_grads,
                                      head_loss=(self.real_label, 0.0, 1, self.alpha_adv, losses[2:3], False) if fused_head else None,
                                      feat=feat)
-        # d total / d recon = d MSE + d adv through the instance-noise add (:92), then through tanh: one pass
+        # d total / d recon = d MSE (+ d SSIM) + d adv through the instance-noise add (:92), then through tanh: one pass
         d_pre = ops.nchw_grad_add_to_nhwc(d_recon, d_noisy, recon, G.padc(Gn.nc, dt), dt)
         dz = Gn._engine.backward(ctxG, d_pre, True, sink, on_grads=self._grad_hook(self.opt_G, Gn))
         self._finish_reduce(self.opt_G, Gn, wait=False)       # G's last bucket overlaps the encoder's backward
@@ -463,12 +475,14 @@ class VAEGANTrainer:
 
     def loss_dict(self, losses: Optional[torch.Tensor] = None, epoch: Optional[int] = None) -> Dict[str, float]:
         """Host copy of the last step's losses (one device sync, like the reference's .item() calls :125-127)."""
-        v = (losses if losses is not None else self.losses)[:6].tolist()
-        v += [0.0] * (6 - len(v))                # a caller's five-slot slice
+        v = (losses if losses is not None else self.losses)[:7].tolist()
+        v += [0.0] * (7 - len(v))                # a caller's five-slot slice
         out = dict(zip(LOSS_NAMES, v))
         if self.alpha_feat != 0.0:
             out["feat_loss"] = v[5]
+        if self.alpha_ssim != 0.0:
+            out["ssim_loss"] = v[6]
         if epoch is not None:
             out["total"] = self.alpha_pix * out["recon_loss"] + self.alpha_kl * min(1.0, epoch / 50) * out["kl_loss"] \
-                + self.alpha_adv * out["g_loss_adv"] + self.alpha_feat * v[5]
+                + self.alpha_adv * out["g_loss_adv"] + self.alpha_feat * v[5] + self.alpha_ssim * v[6]
         return out
