@@ -48,7 +48,7 @@ extern "C" {
 #define VG_ACT_LRELU   2   /* nn.LeakyReLU(slope)    main_vae.py:25, gan_code.py:62-82 */
 #define VG_ACT_TANH    3   /* nn.Tanh()              gan_code.py:50 (vg_tnconv epilogue only) */
 
-#define VG_ABI_VERSION 17  /* 2: vg_pack_desc.tile_start, SyncBN / WGAN / data-path entry points; 3: in-kernel noise (vg_*_rng);
+#define VG_ABI_VERSION 18  /* 2: vg_pack_desc.tile_start, SyncBN / WGAN / data-path entry points; 3: in-kernel noise (vg_*_rng);
                              4: vg_bn_finalize_act_forward, vg_bn_backward_finalize_apply;
                              7: vg_bce_pair_forward_backward;
                              8: vg_head_backward; round-3 prune -- the opt-in experiments of ABI 5 / 6 that measured slower (input prologue of
@@ -61,7 +61,8 @@ extern "C" {
                              14: feature-space metrics: vg_feat_stats_accum, vg_knn_radius2, vg_manifold_cover (+ _ws_bytes each);
                              15: KID: vg_kid_scores (+ _ws_bytes);
                              16: Discriminator-feature reconstruction loss: vg_feat_mse_forward_backward;
-                             17: SSIM reconstruction loss: vg_ssim_loss_forward_backward (+ _ws_floats) */
+                             17: SSIM reconstruction loss: vg_ssim_loss_forward_backward (+ _ws_floats);
+                             18: region-weighted MSE for degraded pairs: vg_region_mse_forward_backward (+ _ws_doubles) */
 int vg_abi_version(void);
 /* The library reads its optional kernel-selection switches (VG_* environment variables, DESIGN.md "Runtime switches")
  * ONCE, when it is loaded; nothing on a launch path calls getenv.  A process that changes one of them afterwards
@@ -430,6 +431,30 @@ int vg_feat_mse_forward_backward(const void* f_fake, const void* f_real, void* d
 int vg_ssim_loss_forward_backward(const float* a, const float* b, float* d, int B, int C, int H, int W, float gscale,
                                   float* loss, int accumulate_loss, float* ws, int ws_capacity, void* stream);
 int64_t vg_ssim_loss_ws_floats(int B, int C, int H, int W);      /* VG_EINVAL (negative) for sizes outside the contract */
+/* Region-weighted reconstruction MSE (ABI 18; csrc/regionloss.hip): the pixel MSE of a reconstruction a against the clean
+ * image b (a constant), both NCHW f32 [B][C][H][W], split by each image's occlusion rectangle, for training on and evaluating
+ * degraded pairs.  rects: f32 [B][8] in the layout vg_degrade_params writes; entries 2..5 = {rect_h, rect_w, x, y} are read;
+ * NULL: no image has a hole.  Pixel (h, w) of image i is in the hole iff y <= h < y + rect_h and x <= w < x + rect_w, in every
+ * channel; the comparisons are made in f32 (y + rect_h and x + rect_w are f32 sums).  rect_h == 0 or rect_w == 0: an empty
+ * hole; a rectangle reaching past the image is clipped by it; a NaN entry makes every comparison false (no hole).  The
+ * rectangle enters comparisons only: no address is formed from it, no content of rects can cause an out-of-range access.
+ * Arithmetic: d = a - b in f32, q = d d in f32, q accumulated in f64 into S_hole and S_valid; with n = B C H W:
+ *   loss[0]     = (float)((S_valid + (double)w_hole S_hole) / n)                 written, not accumulated; NULL skips it
+ *   hole_mse[0] = (float)(S_hole / n_hole), 0 when n_hole == 0                   NULL skips it
+ *   d_a[e]      = d * coef_region, coef_valid = (float)(2 (double)gscale / n),
+ *                 coef_hole = (float)(2 (double)gscale (double)w_hole / n)       written in full; NULL skips the gradient
+ *   stats[0..3] += {S_hole, S_valid, n_hole, n_valid}                            f64, ALWAYS accumulated (an evaluation pass
+ *                 keeps one f64[4] for a whole epoch); n_hole is the exact count of hole elements after clipping; NULL skips it
+ * Two launches (per-workgroup f64 partials of the two sums and the count in ws; one wave for the final pass), fixed summation
+ * order, no atomics: the same inputs give the same bits, eagerly and replayed from a graph.  16-byte loads along W with a
+ * per-lane mask where W % 4 == 0 and the pointers are 16-byte aligned, one element per lane otherwise.  ws: at least
+ * vg_region_mse_ws_doubles(B, C, H, W) doubles; ws_doubles is its capacity.  VG_EINVAL: a or b NULL, a size < 1, w_hole < 0 or
+ * not finite, ws NULL or too small, every output NULL.  VG_EALIGN: rects not 8-byte aligned (its rows are read as 8-byte
+ * pairs).  HBM-bound: 12 B per element with the gradient, 8 B without. */
+int vg_region_mse_forward_backward(const float* a, const float* b, const float* rects, int B, int C, int H, int W,
+                                   float w_hole, float gscale, float* loss, float* hole_mse, float* d_a, double* stats,
+                                   double* ws, int ws_doubles, void* stream);
+int vg_region_mse_ws_doubles(int B, int C, int H, int W);        /* <= 0 (VG_EINVAL) for B, C, H or W < 1 */
 /* Mean SSIM of two NCHW f32 image batches in [-1,1] (rescaled to [0,1] as vaegan_code.py:170-174 does):
  * gaussian 11x11, sigma 1.5, k1 .01, k2 .03, data_range 1, 5-pixel border cropped.  out[0] = mean. */
 int vg_ssim(const float* a, const float* b, int B, int C, int H, int W, float* out, float* ws, int ws_capacity,

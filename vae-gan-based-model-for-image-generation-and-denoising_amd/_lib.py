@@ -16,7 +16,7 @@ VG_F32, VG_BF16, VG_FP8 = 0, 1, 2
 VG_FP8_WSHIFT = 6
 VG_ACT_NONE, VG_ACT_RELU, VG_ACT_LRELU, VG_ACT_TANH = 0, 1, 2, 3
 VG_MAX_PHASE = 4
-ABI_VERSION = 17
+ABI_VERSION = 18
 
 VG_ENOSUP = -3
 _ERR = {-1: "VG_EINVAL (bad shape/size/flag)", -2: "VG_EALIGN (16-byte contract violated)",
@@ -138,6 +138,8 @@ SIGNATURES = {
     "vg_feat_mse_forward_backward": (c_int, [_P, _P, _P, _L, _F, _P, _I, _P, _I, _I, _P]),
     "vg_ssim_loss_forward_backward": (c_int, [_P, _P, _P, _I, _I, _I, _I, _F, _P, _I, _P, _I, _P]),
     "vg_ssim_loss_ws_floats": (c_int64, [_I, _I, _I, _I]),
+    "vg_region_mse_forward_backward": (c_int, [_P, _P, _P, _I, _I, _I, _I, _F, _F, _P, _P, _P, _P, _P, _I, _P]),
+    "vg_region_mse_ws_doubles": (c_int, [_I, _I, _I, _I]),
     "vg_ssim": (c_int, [_P, _P, _I, _I, _I, _I, _P, _P, _I, _P]),
     "vg_axpy": (c_int, [_P, _P, _F, _P, _L, _P]),
     "vg_bn_backward_onepass_supported": (c_int, [_L, _I, _I, _I]),

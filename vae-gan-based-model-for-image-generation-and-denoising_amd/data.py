@@ -261,16 +261,17 @@ class ResidentImages:
         return ops.gather_normalize_u8(self.images, idx, out)
 
     def pair(self, idx: torch.Tensor, seed: int, pos0: int, degrade: Degrade, out: Optional[torch.Tensor] = None,
-             nhwc=None) -> Tuple[torch.Tensor, torch.Tensor]:
+             nhwc=None, out_noisy: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """-> (noisy, clean), both [B,C,H,W] f32, what a batch of ``CelebADatasetV0[i]`` with noise_max_std set collates
         to (dataset_code.py:64-65).  seed: the epoch's seed; pos0: position of idx[0] in the epoch's order (sample k of
         the batch is keyed by pos0 + k).  out: receives ``clean``.  nhwc: a [B,H,W,CP] engine tensor that also receives
-        ``noisy`` in the Encoder's input layout.  degrade.noise_max_std None: sigma 0 and no rectangle (noisy == clean)."""
+        ``noisy`` in the Encoder's input layout.  out_noisy: receives ``noisy``.  degrade.noise_max_std None: sigma 0 and no
+        rectangle (noisy == clean)."""
         _, H, W, _ = self.images.shape
         rect = degrade.rect and degrade.pairs
         noisy, clean, _ = ops.gather_degrade_u8(self.images, idx, seed, pos0, degrade.noise_max_std or 0.0, rect,
                                                 degrade.normalize, degrade_bounds(H, W) if rect else None,
-                                                out_clean=out, nhwc=nhwc)
+                                                out_clean=out, out_noisy=out_noisy, nhwc=nhwc)
         return noisy, clean
 
     def __getitem__(self, i: int) -> torch.Tensor:
@@ -309,6 +310,9 @@ class DeviceLoader:
         self.degrade = degrade
         self.last_nhwc: Optional[torch.Tensor] = None            # see want_nhwc()
         self._nhwc = None
+        self.last_rects: Optional[torch.Tensor] = None           # see want_rects()
+        self._rects = False
+        self._out_noisy: Optional[torch.Tensor] = None           # see bind_noisy()
 
     def __len__(self) -> int:
         return sum(1 for _ in self.global_batches(self.indices.numel()))
@@ -350,8 +354,27 @@ class DeviceLoader:
         """Assemble every FULL batch into `out` ([B, C, H, W] f32 on the device, e.g. VAEGANTrainer.graph_input()) and
         yield that same tensor: the consumer must be done with a batch before asking for the next (a training loop
         is).  A ragged last batch gets its own tensor.  None unbinds.  A degraded loader binds the CLEAN half (the
-        training target and the trainer's input); ``noisy`` is always a fresh tensor."""
+        training target and the trainer's input); ``noisy`` is a fresh tensor unless bind_noisy() binds it too."""
         self._out = out
+
+    def bind_noisy(self, out: Optional[torch.Tensor]) -> None:
+        """Degraded loaders only: assemble the ``noisy`` half of every FULL batch into `out` ([B, C, H, W] f32 on the device,
+        e.g. VAEGANTrainer.graph_noisy_input()) and yield that same tensor, as bind_output does for the clean half.  A
+        ragged last batch gets its own tensor.  None unbinds."""
+        if out is not None and (self.degrade is None or not self.degrade.pairs):
+            raise RuntimeError("bind_noisy: this loader does not yield degraded pairs")
+        self._out_noisy = out
+
+    def want_rects(self, on: bool) -> None:
+        """Degraded loaders only: while on, ``last_rects`` holds the f32 [b, 8] device tensor of the batch just yielded --
+        ops.degrade_params(last_base_seed, lo, b, ...) with this loader's Degrade and bounds: the occlusion rectangle of
+        every image as the degradation kernel drew it (the region-weighted loss and the region metrics read it).  With
+        rect=False the four geometry entries are 0: no hole.  Off: ``last_rects`` is None."""
+        if on and (self.degrade is None or not self.degrade.pairs):
+            raise RuntimeError("want_rects: this loader does not yield degraded pairs")
+        self._rects = bool(on)
+        if not on:
+            self.last_rects = None
 
     def want_nhwc(self, CP: Optional[int], dtype: Optional[int] = None) -> None:
         """Degraded loaders only: also write every ``noisy`` batch in the Encoder's NHWC input layout ([b,H,W,CP] in the
@@ -375,8 +398,15 @@ class DeviceLoader:
             if self._nhwc is not None:
                 nhwc = ops.empty_act((idx.numel(),) + tuple(self.dataset.images.shape[1:3]) + (self._nhwc[0],),
                                      self._nhwc[1], idx.device)
-            noisy, clean = self.dataset.pair(idx, self.last_base_seed, lo, self.degrade, dst, nhwc)
+            bound = self._out_noisy
+            dst_noisy = bound if bound is not None and bound.shape[0] == idx.numel() else None
+            noisy, clean = self.dataset.pair(idx, self.last_base_seed, lo, self.degrade, dst, nhwc, dst_noisy)
             self.last_nhwc = nhwc
+            if self._rects:
+                H, W = self.dataset.images.shape[1:3]
+                rect = self.degrade.rect and self.degrade.pairs
+                self.last_rects = ops.degrade_params(self.last_base_seed, lo, idx.numel(), self.degrade.noise_max_std or 0.0,
+                                                     rect, H, W, degrade_bounds(H, W) if rect else None, idx.device)
             yield (noisy, clean) if self.degrade.pairs else clean
 
 

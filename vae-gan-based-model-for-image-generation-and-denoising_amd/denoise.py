@@ -144,7 +144,8 @@ def validation_epoch(encoder, decoder, loader: Iterable[torch.Tensor], n_samples
 
 
 @torch.no_grad()
-def paired_test_epoch(encoder, decoder, loader: Iterable, n_samples: Optional[int] = None, noise_fn=None) -> Dict[str, float]:
+def paired_test_epoch(encoder, decoder, loader: Iterable, n_samples: Optional[int] = None, noise_fn=None,
+                      regions: bool = False) -> Dict[str, float]:
     """The reference's test pass over (noisy, clean) pairs, main_vae.py:251-266:
 
         encoder.eval(); decoder.eval()                                                 (:251-252)
@@ -162,7 +163,15 @@ def paired_test_epoch(encoder, decoder, loader: Iterable, n_samples: Optional[in
     Deviation: the engine's reparameterisation clamps logvar to [-10, 10] (as the training path, vaegan_code.py:76);
     :258-259 do not.  Inert for |logvar| < 10.
     Accumulation stays on the device; ONE host sync at the end.  Returns python floats: test_loss, recon_loss (mean
-    squared error per element), kl_loss (mean KL sum per sample), ssim, psnr, ssim_noisy, psnr_noisy, samples, batches."""
+    squared error per element), kl_loss (mean KL sum per sample), ssim, psnr, ssim_noisy, psnr_noisy, samples, batches.
+    regions=True (default False: exactly the keys and the launches above): the loader must offer ``want_rects`` (a degraded
+    data.DeviceLoader); the pass turns it on and restores it.  The result gains mse_hole, mse_valid (mean squared error per
+    element inside / outside the occlusion rectangles), psnr_hole, psnr_valid and hole_fraction (hole elements / all
+    elements) of ``recon`` vs ``clean``, and the same five suffixed ``_noisy`` for the input, each set from one f64[4]
+    tensor that ops.region_mse_forward_backward accumulates over the pass (w_hole = 1, no gradient).  An empty region
+    reports mse 0.0 and psnr inf.  Still one host sync."""
+    if regions and not (hasattr(loader, "want_rects") and getattr(loader, "degrade", None) is not None and loader.degrade.pairs):
+        raise RuntimeError("paired_test_epoch: regions=True needs a degraded data.DeviceLoader (want_rects)")
     encoder.eval(), decoder.eval()                                                   # :251-252
     dev = next(encoder.parameters()).device
     dt, L = encoder._dt, encoder.latent_dim
@@ -172,6 +181,11 @@ def paired_test_epoch(encoder, decoder, loader: Iterable, n_samples: Optional[in
     offers = hasattr(loader, "want_nhwc") and getattr(loader, "degrade", None) is not None and loader.degrade.pairs
     if offers:
         loader.want_nhwc(G.padc(loader.dataset.image_shape[0], dt), dt)
+    stats = None
+    if regions:
+        rects_were_on = bool(getattr(loader, "_rects", False))
+        loader.want_rects(True)
+        stats = torch.zeros(2, 4, dtype=torch.float64, device=dev)                   # {S_hole, S_valid, n_hole, n_valid} of recon, noisy
     try:
         for i, (noisy, clean) in enumerate(loader):
             if not (noisy.is_cuda and clean.is_cuda):
@@ -194,6 +208,9 @@ def paired_test_epoch(encoder, decoder, loader: Iterable, n_samples: Optional[in
             ops.kl_forward(mulv, lvc, L, 1.0, dt, out=scal[1:2])                     # :263
             ops.mse_forward_backward(noisy, clean, 1.0, scal[2:3], False)
             ssim_r, ssim_n = ops.ssim(recon, clean), ops.ssim(noisy, clean)
+            if regions:
+                ops.region_mse_forward_backward(recon, clean, loader.last_rects, 1.0, 1.0, stats=stats[0])
+                ops.region_mse_forward_backward(noisy, clean, loader.last_rects, 1.0, 1.0, stats=stats[1])
             ops.axpy(acc[0:1], scal[0:1], float(clean.numel()), out=acc[0:1])
             ops.axpy(acc[0:1], scal[1:2], 1.0, out=acc[0:1])                         # :264
             ops.axpy(acc[1:2], ssim_r, float(b), out=acc[1:2])
@@ -206,14 +223,25 @@ def paired_test_epoch(encoder, decoder, loader: Iterable, n_samples: Optional[in
     finally:
         if offers:
             loader.want_nhwc(None)
+        if regions:
+            loader.want_rects(rects_were_on)
     if batches == 0:
         raise RuntimeError("paired_test_epoch: the loader yielded no batch")
-    tot, ssim_sum, mse_sum, kl_sum, ssim_n_sum, mse_n_sum = (float(v) for v in acc.tolist())   # the one host sync
+    host = torch.cat([acc.double(), stats.flatten()]).tolist() if regions else acc.tolist()   # the one host sync
+    tot, ssim_sum, mse_sum, kl_sum, ssim_n_sum, mse_n_sum = (float(v) for v in host[:6])
     n = seen if n_samples is None else int(n_samples)
 
     def psnr(mse):
         mse01 = mse / 4.0                                                  # ((a+1)/2 - (b+1)/2)^2 = (a-b)^2 / 4
         return float("inf") if mse01 == 0 else 10.0 * math.log10(1.0 / mse01)
-    return {"test_loss": tot / n, "recon_loss": mse_sum / seen, "kl_loss": kl_sum / seen, "ssim": ssim_sum / seen,
-            "psnr": psnr(mse_sum / seen), "ssim_noisy": ssim_n_sum / seen, "psnr_noisy": psnr(mse_n_sum / seen),
-            "samples": seen, "batches": batches}
+    out = {"test_loss": tot / n, "recon_loss": mse_sum / seen, "kl_loss": kl_sum / seen, "ssim": ssim_sum / seen,
+           "psnr": psnr(mse_sum / seen), "ssim_noisy": ssim_n_sum / seen, "psnr_noisy": psnr(mse_n_sum / seen),
+           "samples": seen, "batches": batches}
+    if regions:
+        for suffix, (s_hole, s_valid, n_hole, n_valid) in (("", host[6:10]), ("_noisy", host[10:14])):
+            m_hole = s_hole / n_hole if n_hole > 0 else 0.0
+            m_valid = s_valid / n_valid if n_valid > 0 else 0.0
+            out.update({"mse_hole" + suffix: m_hole, "mse_valid" + suffix: m_valid,
+                        "psnr_hole" + suffix: psnr(m_hole), "psnr_valid" + suffix: psnr(m_valid),
+                        "hole_fraction" + suffix: n_hole / (n_hole + n_valid)})
+    return out

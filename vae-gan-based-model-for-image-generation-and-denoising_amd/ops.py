@@ -1294,6 +1294,37 @@ def ssim_loss_forward_backward(a, b, gscale, loss, accumulate, d=None):
     return d
 
 
+def region_mse_forward_backward(a, b, rects, w_hole, gscale, loss=None, hole_mse=None, want_grad=False, stats=None):
+    """Region-weighted reconstruction MSE (vg_region_mse_forward_backward): a, b NCHW f32 of one shape (b a constant), rects
+    f32 [B, 8] in ops.degrade_params' layout (None: no image has a hole).  loss[0] = (S_valid + w_hole S_hole) / n (written),
+    hole_mse[0] = S_hole / n_hole (0 without a hole), stats f64 [4] += {S_hole, S_valid, n_hole, n_valid} (ALWAYS
+    accumulated), and with want_grad the gradient of gscale * loss w.r.t. a, written in full.  -> d_a or None."""
+    what = "region_mse_forward_backward"
+    _need_cuda(a, b, rects, loss, hole_mse, stats)
+    if a.dtype != torch.float32 or b.dtype != torch.float32 or a.dim() != 4 or a.shape != b.shape:
+        raise RuntimeError(f"{what}: a and b must be f32 [B,C,H,W] tensors of one shape")
+    B, C, H, W = a.shape
+    if rects is not None and (rects.dtype != torch.float32 or tuple(rects.shape) != (B, 8)):
+        raise RuntimeError(f"{what}: rects must be f32 [B, 8] (ops.degrade_params)")
+    if stats is not None and (stats.dtype != torch.float64 or tuple(stats.shape) != (4,)):
+        raise RuntimeError(f"{what}: stats must be f64 [4]")
+    for t in (loss, hole_mse):
+        if t is not None and (t.dtype != torch.float32 or t.numel() < 1):
+            raise RuntimeError(f"{what}: loss and hole_mse must be f32 slots")
+    if not (math.isfinite(w_hole) and w_hole >= 0):
+        raise RuntimeError(f"{what}: w_hole must be finite and >= 0")
+    if loss is None and hole_mse is None and stats is None and not want_grad:
+        raise RuntimeError(f"{what}: nothing to compute (every output is None)")
+    lib = L.load()
+    nws = _ws_query(lib.vg_region_mse_ws_doubles(B, C, H, W), "vg_region_mse_ws_doubles (needs B, C, H, W >= 1)")
+    ws = WS.get("regionloss", nws * 8, a.device)
+    da = torch.empty_like(a) if want_grad else None
+    L.check(lib.vg_region_mse_forward_backward(a.data_ptr(), b.data_ptr(), L.ptr(rects), B, C, H, W, float(w_hole),
+                                               float(gscale), L.ptr(loss), L.ptr(hole_mse), L.ptr(da), L.ptr(stats),
+                                               ws.data_ptr(), nws, L.stream_ptr()), "vg_region_mse_forward_backward")
+    return da
+
+
 def axpy(a, b, alpha, out=None):
     out = out if out is not None else torch.empty_like(a)
     L.check(L.load().vg_axpy(a.data_ptr(), b.data_ptr(), alpha, out.data_ptr(), a.numel(), L.stream_ptr()), "vg_axpy")

@@ -10,6 +10,7 @@ optimizers' flat buffers, every random draw of the reference loop can be injecte
 device, losses come back as one device tensor (no host sync), ``step_graphed`` replays the whole iteration from a
 captured hipGraph.  There is no CPU path.
 """
+import math
 from typing import List, Optional, Sequence
 
 import torch
@@ -29,6 +30,10 @@ class _Graphed:
     _opts: Sequence = ()
 
     def step_graphed(self, *tensors, **scalars):
+        return self._graphed_call(self.train_step, tensors, scalars)
+
+    def _graphed_call(self, step, tensors, scalars, tag=None):
+        """step(*tensors, **scalars) eagerly, then captured, then replayed; tag: whatever else the capture freezes."""
         # Draws that are not injected come from the per-device default NoiseStream, whose STATE BUFFER the captured
         # vg_rng_advance / vg_randn launches point at.  utils.configure_seed() (ops.reset_noise) drops that stream: the
         # graph must then be re-captured against the new one -- the buffer's address is part of the key, and the
@@ -38,7 +43,8 @@ class _Graphed:
             dev = next(t for t in tensors if t is not None).device
             noise = ops.default_noise(dev)
         key = (tuple(None if t is None else tuple(t.shape) for t in tensors), tuple(sorted(scalars.items())),
-               tuple(n.training for n in self._nets), None if noise is None else noise.state.data_ptr())
+               tuple(n.training for n in self._nets), None if noise is None else noise.state.data_ptr()) \
+            + (() if tag is None else (tag,))
         self._gnoise = noise
         st = getattr(self, "_gstate", None)
         if st is not None and st.key == key:
@@ -49,11 +55,11 @@ class _Graphed:
             return st.out
         if getattr(self, "_gwarm", None) != key:
             self._gwarm, self._gstate = key, None
-            return self.train_step(*tensors, **scalars)
+            return step(*tensors, **scalars)
         sin = [None if t is None else t.clone() for t in tensors]      # None: drawn on the device inside the graph
         try:
             # thread_local: see capture.capture (the c10d watchdog may poll events); keep: the captured state buffer
-            st = self._gstate = capture(lambda *s: self.train_step(*s, **scalars), sin,
+            st = self._gstate = capture(lambda *s: step(*s, **scalars), sin,
                                         HostMirrors([n._engine for n in self._nets], self._opts), sin[0].device,
                                         key=key, error_mode="thread_local", keep=noise)
         except BaseException:
@@ -82,12 +88,17 @@ class VAETrainer(_Graphed):
     LOSS_NAMES = ("recon_loss", "kl_loss", "total")
 
     def __init__(self, encoder, decoder, optimizer, noise_max_std: float = 0.5, kl_weight: float = 1e-5,
-                 alpha_ssim: float = 0.0):
+                 alpha_ssim: float = 0.0, hole_weight: float = 1.0):
         self.E, self.G, self.opt = encoder, decoder, optimizer
         self.sigma, self.kl_weight = noise_max_std, kl_weight                       # :66, :121
         # SSIM reconstruction loss (not in the reference): total += alpha_ssim * (1 - SSIM(recon,
         # img)), the gradient added onto the MSE's.  Off (0, the default): the iteration launches what it launched before.
         self.alpha_ssim = float(alpha_ssim)
+        # Training on degraded pairs: train_step(img, ..., noisy=, rects=) feeds `noisy` to the
+        # Encoder; with hole_weight != 1 and rects the reconstruction term is the region-weighted MSE (csrc/regionloss.hip).
+        self.hole_weight = float(hole_weight)
+        if not (math.isfinite(self.hole_weight) and self.hole_weight >= 0.0):
+            raise ValueError("hole_weight must be finite and >= 0")
         self.dt = _same_dtype(encoder, decoder)
         self._nets, self._opts = (encoder, decoder), (optimizer,)
 
@@ -95,31 +106,50 @@ class VAETrainer(_Graphed):
         self.E.train(), self.G.train()                                             # :98-99
 
     def train_step(self, img: torch.Tensor, eps_img: Optional[torch.Tensor] = None,
-                   eps_z: Optional[torch.Tensor] = None, epoch: int = 0) -> torch.Tensor:
+                   eps_z: Optional[torch.Tensor] = None, epoch: int = 0, noisy: Optional[torch.Tensor] = None,
+                   rects: Optional[torch.Tensor] = None) -> torch.Tensor:
         """-> device tensor [recon_loss, kl_loss (sum, not /B), total, ssim_loss]: slot 3 holds 1 - SSIM(recon, img)
-        (unweighted; total includes alpha_ssim times it) when alpha_ssim != 0 and reads 0 otherwise."""
+        (unweighted; total includes alpha_ssim times it) when alpha_ssim != 0 and reads 0 otherwise.
+        noisy (device f32 of img's shape): the PAIRED step -- the Encoder reads `noisy` in place of clamp(img + sigma *
+        eps_img); eps_img is neither drawn nor read (the noise stream advances as ever: eps_z stays draw 1).  rects (f32
+        [B, 8], data.DeviceLoader.last_rects) with hole_weight != 1: slot 0 holds the region-weighted MSE L_w, total uses
+        it, and the vector grows to 5 slots: slot 4 holds the mean squared error inside the holes."""
+        if noisy is None and rects is not None:
+            raise ValueError("rects belongs to the paired step: pass noisy= as well")
         _need_cuda(img, "VAETrainer.train_step")
         E, Gn, dt = self.E, self.G, self.dt
         B, dev, L = img.shape[0], img.device, E.latent_dim
         img = img.contiguous()
-        if eps_img is None or eps_z is None:
+        if noisy is not None:
+            _need_cuda(noisy, "VAETrainer.train_step")
+            if noisy.dtype != torch.float32 or noisy.shape != img.shape:
+                raise RuntimeError("VAETrainer.train_step: noisy must be a device f32 batch of img's shape")
+            noisy = noisy.contiguous()
+        weighted = noisy is not None and rects is not None and self.hole_weight != 1.0
+        if (eps_img is None and noisy is None) or eps_z is None:
             # the reference's randn_like draws, generated in HIP (Philox keyed by torch's device seed; the one-thread
             # advance kernel is captured with the iteration, so graph replays draw fresh noise)
             noise = ops.default_noise(dev)
             noise.advance()
-            if eps_img is None:
+            if eps_img is None and noisy is None:
                 eps_img = noise.randn(tuple(img.shape), 0)                         # :104
             if eps_z is None:
                 eps_z = noise.randn((B, L), 1)                                     # :114
-        losses = ops.zeros_f32(4, dev)
+        losses = ops.zeros_f32(5 if weighted else 4, dev)
         sink = GradSink(direct=True)
-        noisy_h, _ = ops.noisy_clamp_to_nhwc(img, eps_img, self.sigma, G.padc(img.shape[1], dt), dt)   # :104-105
+        if noisy is not None:
+            noisy_h = ops.nchw_to_nhwc(noisy, G.padc(img.shape[1], dt), dt)
+        else:
+            noisy_h, _ = ops.noisy_clamp_to_nhwc(img, eps_img, self.sigma, G.padc(img.shape[1], dt), dt)   # :104-105
         mulv, ctxE = E._engine.forward(noisy_h, B, E.training, True)               # :111
         mulv = mulv.view(B, -1)
         z, lvc = ops.reparam_forward(mulv, eps_z, L, G.padc(Gn.nz, dt), dt)        # :112-115
         pre, ctxG = Gn.engine_forward(z, B)                                        # :116
         recon = ops.nhwc_to_nchw(pre, Gn.nc, dt, apply_tanh=True)
-        d_recon = ops.mse_forward_backward(recon, img, 1.0, losses[0:1], True)     # :119
+        if weighted:
+            d_recon = ops.region_mse_forward_backward(recon, img, rects, self.hole_weight, 1.0, losses[0:1], losses[4:5], True)
+        else:
+            d_recon = ops.mse_forward_backward(recon, img, 1.0, losses[0:1], True)  # :119
         ops.kl_forward(mulv, lvc, L, 1.0, dt, out=losses[1:2])                     # :120
         w = min(epoch / 50, 1.0) * self.kl_weight                                  # :121
         torch.add(losses[0:1], losses[1:2], alpha=w, out=losses[2:3])
@@ -133,6 +163,17 @@ class VAETrainer(_Graphed):
         E._engine.backward(ctxE, dmulv.view(B, 1, 1, -1), False, sink)
         self.opt.step()                                                            # :126
         return losses
+
+    def step_graphed(self, img, eps_img=None, eps_z=None, noisy=None, rects=None, **scalars):
+        """_Graphed.step_graphed; noisy / rects (the paired step) are static inputs of their own capture."""
+        if noisy is None:
+            if rects is not None:
+                raise ValueError("rects belongs to the paired step: pass noisy= as well")
+            return self._graphed_call(self.train_step, (img, eps_img, eps_z), scalars)
+        return self._graphed_call(self._paired_step, (img, eps_z, noisy, rects), scalars, tag=("paired", self.hole_weight))
+
+    def _paired_step(self, img, eps_z, noisy, rects, **scalars):
+        return self.train_step(img, None, eps_z, noisy=noisy, rects=rects, **scalars)
 
 
 # ---------------------------------------------------------------------------------------------------------------

@@ -7,6 +7,7 @@ parity runs or are drawn on the device.
     trainer = VAEGANTrainer(encoder, decoder, discriminator, opt_E, opt_Dec, opt_Dis)
     losses = trainer.train_step(real_images, epoch)          # device tensor, no host sync
 """
+import math
 import os
 from typing import Dict, Optional
 
@@ -41,7 +42,7 @@ class VAEGANTrainer:
                  alpha_adv: float = 0.1, noise_sigma: float = 0.05, real_label: float = 0.9, fake_label: float = 0.1,
                  d_iters: int = 2, elide_dead_grads: bool = False, reducer=None, group_d_passes: bool = True,
                  sync_bn: bool = False, feat_layer: Optional[int] = None, alpha_feat: float = 0.0, alpha_pix: float = 1.0,
-                 alpha_ssim: float = 0.0):
+                 alpha_ssim: float = 0.0, hole_weight: float = 1.0):
         self.E, self.G, self.D = encoder, decoder, discriminator
         self.opt_E, self.opt_G, self.opt_D = opt_E, opt_Dec, opt_Dis
         self.alpha_kl, self.alpha_adv, self.sigma = alpha_kl, alpha_adv, noise_sigma          # :49-50, :91-92
@@ -64,6 +65,13 @@ class VAEGANTrainer:
         # MSE's in the buffer that launch wrote (csrc/ssimloss.hip, one launch for forward and backward).  Off (0, the
         # default): the iteration launches exactly what it launched without it.
         self.alpha_ssim = float(alpha_ssim)
+        # Training on degraded pairs: train_step(clean, ..., noisy=, rects=) feeds `noisy` to the
+        # Encoder and, with hole_weight != 1, replaces the pixel MSE by the region-weighted one (csrc/regionloss.hip): the
+        # squared error inside each image's occlusion rectangle counts hole_weight times.  1 (the default) or no rects:
+        # the pixel MSE launches of the unpaired step.
+        self.hole_weight = float(hole_weight)
+        if not (math.isfinite(self.hole_weight) and self.hole_weight >= 0.0):
+            raise ValueError("hole_weight must be finite and >= 0")
         self.group_d_passes = group_d_passes       # run a D iteration's real+fake passes as one 2B-row launch chain
         # BCE + its gradient + the sigmoid / head backward as ONE launch per Discriminator pass (ops.head_backward;
         # bit-identical to the three separate launches, which False selects)
@@ -96,6 +104,7 @@ class VAEGANTrainer:
         self._warm_key = None
         self._cut_hook = None           # set while capturing: splits the iteration into graph segments
         self._inline_failed = False     # capturing the collectives inside the graph failed once: use the segmented form
+        self.last_step_weighted = False # the last iteration used the region-weighted term (loss_dict reports hole_mse)
 
     def train(self):
         self.E.train(), self.G.train(), self.D.train()                                         # :56-58
@@ -115,7 +124,7 @@ class VAEGANTrainer:
             self._graph = None
         return self.noise
 
-    def _capture_key(self, real, epoch, inject):
+    def _capture_key(self, real, epoch, inject, paired=False, with_rects=False):
         """Everything a captured graph freezes: shapes, every scalar kernel argument (loss weights, labels, noise
         sigma, Adam hyper-parameters, the data-parallel gradient scale), the schedule switches and the buffers the
         launches point at.  A change in any of them re-captures instead of silently replaying stale values."""
@@ -127,7 +136,8 @@ class VAEGANTrainer:
                 self.elide_dead_grads, self.group_d_passes, self.fuse_head_backward, self.fuse_step_prologue,
                 self.merge_small_launches,
                 id(self.reducer), self.sync_bn, opts,
-                None if self.noise is None or inject else self.noise.state.data_ptr())
+                None if self.noise is None or inject else self.noise.state.data_ptr()) \
+            + ((True, with_rects, self.hole_weight) if paired else ())
 
     # ---- data-parallel gradient hand-off (ddp.GradReducer) -------------------------------------------------------
     def _buckets_for(self, opt, net):
@@ -181,15 +191,45 @@ class VAEGANTrainer:
         else:
             self._cut_hook(collective)
 
+    def _weighted(self, noisy, rects) -> bool:
+        """Whether a step with these arguments uses the region-weighted reconstruction term."""
+        return noisy is not None and rects is not None and self.hole_weight != 1.0
+
+    def _check_pair(self, real, noisy, noisy_nhwc, rects) -> None:
+        """The paired step's tensors against the clean batch: device, dtype and shape, before anything reads or copies them
+        (a copy into a captured step's static buffer would convert a wrong dtype or broadcast a wrong shape silently)."""
+        dt, B = self.dt, real.shape[0]
+        if not noisy.is_cuda or noisy.device != real.device or noisy.dtype != torch.float32 or noisy.shape != real.shape:
+            raise RuntimeError("train_step: noisy must be a device f32 batch of real's shape")
+        if noisy_nhwc is not None:
+            want = (B, real.shape[2], real.shape[3], G.padc(real.shape[1], dt))
+            if not noisy_nhwc.is_cuda or tuple(noisy_nhwc.shape) != want or noisy_nhwc.dtype != ops.TORCH_DT[dt] \
+                    or not noisy_nhwc.is_contiguous():
+                raise RuntimeError(f"train_step: noisy_nhwc must be a contiguous device {ops.TORCH_DT[dt]} tensor of "
+                                   f"shape {want} (data.DeviceLoader.want_nhwc)")
+        if rects is not None and (not rects.is_cuda or rects.device != real.device or rects.dtype != torch.float32
+                                  or tuple(rects.shape) != (B, 8) or not rects.is_contiguous()):
+            raise RuntimeError("train_step: rects must be a contiguous device f32 [B, 8] tensor (ops.degrade_params)")
+
     def train_step(self, real: torch.Tensor, epoch: int, eps_z: Optional[torch.Tensor] = None,
-                   eps_real: Optional[torch.Tensor] = None, eps_recon: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """One iteration.  Returns a device tensor [recon_loss, kl_loss, g_loss_adv, d_loss_1, d_loss_2, feat_loss, ssim_loss, 0]:
-        slot 5 holds the Discriminator-feature reconstruction loss (unweighted, like recon_loss) when alpha_feat != 0,
-        slot 6 the SSIM reconstruction loss 1 - SSIM(recon, real) (unweighted) when alpha_ssim != 0; each reads 0 when its
-        term is off."""
+                   eps_real: Optional[torch.Tensor] = None, eps_recon: Optional[torch.Tensor] = None, *,
+                   noisy: Optional[torch.Tensor] = None, noisy_nhwc: Optional[torch.Tensor] = None,
+                   rects: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """One iteration.  Returns a device tensor [recon_loss, kl_loss, g_loss_adv, d_loss_1, d_loss_2, feat_loss, ssim_loss,
+        hole_mse]: slot 5 holds the Discriminator-feature reconstruction loss (unweighted, like recon_loss) when alpha_feat
+        != 0, slot 6 the SSIM reconstruction loss 1 - SSIM(recon, real) (unweighted) when alpha_ssim != 0; each reads 0 when
+        its term is off.
+        noisy (device f32 of real's shape): the PAIRED step on a degraded pair -- the Encoder reads `noisy` as it is (no
+        clamp, no noise added); everything else (the Discriminator's real batch, the MSE / SSIM / Dis_l targets) reads
+        `real`, the clean image.  noisy_nhwc: the same batch already in the Encoder's input layout ([B, H, W, padc(C)] in
+        the engine dtype: data.DeviceLoader.last_nhwc), used instead of converting `noisy`.  rects (f32 [B, 8],
+        DeviceLoader.last_rects) with hole_weight != 1: the reconstruction term is alpha_pix * L_w, the region-weighted
+        MSE; slot 0 then holds L_w and slot 7 the mean squared error inside the holes (0 otherwise)."""
+        if noisy is None and (rects is not None or noisy_nhwc is not None):
+            raise ValueError("rects / noisy_nhwc belong to the paired step: pass noisy= as well")
         steps = [o.steps for o in (self.opt_E, self.opt_G, self.opt_D)]
         try:
-            return self._train_step(real, epoch, eps_z, eps_real, eps_recon)
+            return self._train_step(real, epoch, eps_z, eps_real, eps_recon, noisy, noisy_nhwc, rects)
         except BaseException:
             # The step prologue advances the DEVICE step counters / bias corrections of all three optimizers at the top of
             # the iteration, the host mirrors (opt.steps) move with the updates at its end.  An eager iteration that dies
@@ -205,13 +245,18 @@ class VAEGANTrainer:
                             pass
             raise
 
-    def _train_step(self, real, epoch, eps_z, eps_real, eps_recon) -> torch.Tensor:
+    def _train_step(self, real, epoch, eps_z, eps_real, eps_recon, noisy=None, noisy_nhwc=None, rects=None) -> torch.Tensor:
         if not real.is_cuda:
             raise RuntimeError("train_step needs the batch on the MI355X ('cuda'); there is no CPU path")
         E, Gn, D, dt = self.E, self.G, self.D, self.dt
         B, dev = real.shape[0], real.device
         L = self.latent
         real = real.contiguous()
+        if noisy is not None:
+            self._check_pair(real, noisy, noisy_nhwc, rects)
+            noisy = noisy.contiguous()
+        weighted = self._weighted(noisy, rects)
+        self.last_step_weighted = weighted
         noise = None
         if eps_z is None or eps_real is None or eps_recon is None:
             # the three randn_like draws (:77, :91, :92) are generated inside the kernels that consume them
@@ -240,9 +285,14 @@ class VAEGANTrainer:
         # Discriminator's noisy real batch are the same images: one pass over `real` writes both (round 4).
         CP = G.padc(D.nc, dt)
         both = ops.empty_act((2 * B, real.shape[2], real.shape[3], CP), dt, dev)
-        pair = ops.nchw_to_nhwc_pair(real, CP, dt, eps_real, self.sigma, both[:B]) \
-            if (self.merge_small_launches and G.padc(real.shape[1], dt) == CP) else None
-        mulv, ctxE = E.engine_forward(real, x_nhwc=None if pair is None else pair[0])
+        if noisy is None:
+            pair = ops.nchw_to_nhwc_pair(real, CP, dt, eps_real, self.sigma, both[:B]) \
+                if (self.merge_small_launches and G.padc(real.shape[1], dt) == CP) else None
+            mulv, ctxE = E.engine_forward(real, x_nhwc=None if pair is None else pair[0])
+        else:
+            # paired: the Encoder's input and the Discriminator's real batch are different images, one conversion each
+            pair = None
+            mulv, ctxE = E.engine_forward(noisy, x_nhwc=noisy_nhwc)
         ZP = G.padc(Gn.nz, dt)
         z, lvc = ops.reparam_forward(mulv, eps_z, L, ZP, dt)
         real_noisy = both[:B] if pair is not None else \
@@ -296,7 +346,12 @@ class VAEGANTrainer:
             _, _, f_real = D.engine_forward(real_noisy, B, keep=False, tap=self.feat_layer)
             feat = (self.feat_layer, f_real, self.alpha_feat, losses[5:6])
         p_adv, c_adv = D.engine_forward(recon_noisy, B)
-        if self.merge_small_launches:
+        if weighted:
+            # alpha_pix * L_w: the region-weighted MSE writes slot 0, the holes' own MSE (slot 7) and d_recon in full
+            d_recon = ops.region_mse_forward_backward(recon, real, rects, self.hole_weight, self.alpha_pix, losses[0:1],
+                                                      losses[7:8], True)
+            ops.kl_forward(mulv, lvc, L, float(B), dt, out=losses[1:2])                       # :114
+        elif self.merge_small_launches:
             # :113-114: the MSE's final sum rides on the KL launch (same arithmetic as its own one-wave launch)
             d_recon, mse_tail = ops.mse_forward_backward(recon, real, self.alpha_pix, losses[0:1], True, defer_final=True)
             ops.kl_forward(mulv, lvc, L, float(B), dt, out=losses[1:2], mse=mse_tail)
@@ -341,9 +396,20 @@ class VAEGANTrainer:
         without the device-to-device copy; pass the SAME tensor as `real`."""
         return None if self._graph is None else self._graph.sin[0]
 
+    def graph_noisy_input(self):
+        """The static `noisy` buffer of a captured PAIRED iteration ([B, C, H, W] f32), or None (no capture, or an unpaired
+        one).  data.DeviceLoader.bind_noisy assembles batches straight into it; pass the SAME tensor as `noisy`."""
+        return None if self._graph is None or len(self._graph.sin) < 6 else self._graph.sin[4]
+
+    def graph_rects_input(self):
+        """The static rectangle buffer of a captured paired iteration (f32 [B, 8]), or None; copy a batch's
+        DeviceLoader.last_rects into it (or pass it as it is: it is copied) and pass the SAME tensor as `rects`."""
+        return None if self._graph is None or len(self._graph.sin) < 6 else self._graph.sin[5]
+
     def train_step_graphed(self, real: torch.Tensor, epoch: int, eps_z: Optional[torch.Tensor] = None,
                            eps_real: Optional[torch.Tensor] = None,
-                           eps_recon: Optional[torch.Tensor] = None) -> torch.Tensor:
+                           eps_recon: Optional[torch.Tensor] = None, *, noisy: Optional[torch.Tensor] = None,
+                           noisy_nhwc: Optional[torch.Tensor] = None, rects: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Same iteration as train_step, replayed from captured hipGraphs (~220 kernel launches become one graph
         launch per segment).  The returned tensor is the graph's STATIC output buffer: the next call overwrites it
         (clone it to keep a history of losses).  Every call performs exactly one training iteration: the first call with a new
@@ -352,13 +418,23 @@ class VAEGANTrainer:
         call or drawn on the device inside the graph (torch's graph-safe Philox state).
         With a gradient reducer the iteration is captured as SEGMENTS that share one memory pool, cut at the points
         where gradients are handed to the reducer (one cut per gradient bucket, ddp.py) and, in SyncBN mode, at every
-        BatchNorm's statistics all-reduce; the collectives run eagerly between the segment replays."""
+        BatchNorm's statistics all-reduce; the collectives run eagerly between the segment replays.
+        noisy / rects: the paired step (train_step); both become static inputs (graph_noisy_input, graph_rects_input) and the
+        captured iteration converts the static NCHW `noisy` itself: noisy_nhwc is eager-only (ValueError)."""
+        if noisy_nhwc is not None:
+            raise ValueError("train_step_graphed: noisy_nhwc is eager-only (the captured step converts its static noisy input)")
+        if noisy is None and rects is not None:
+            raise ValueError("rects belongs to the paired step: pass noisy= as well")
+        if noisy is not None:
+            if not real.is_cuda or real.dtype != torch.float32:
+                raise RuntimeError("train_step_graphed: the paired step needs a device f32 batch")
+            self._check_pair(real, noisy, None, rects)          # also on a replay, whose copies would convert silently
         inject = eps_z is not None
         if inject and (eps_real is None or eps_recon is None):
             raise ValueError("inject all three noise tensors or none")
         if not inject:
             self._noise_stream(real.device)         # exists (and is keyed on the current seed) before the key is formed
-        key = self._capture_key(real, epoch, inject)
+        key = self._capture_key(real, epoch, inject, noisy is not None, rects is not None)
         g = self._graph
         if g is not None and g.key == key:
             sin = g.sin
@@ -366,14 +442,22 @@ class VAEGANTrainer:
                 sin[0].copy_(real)
             if inject:
                 sin[1].copy_(eps_z), sin[2].copy_(eps_real), sin[3].copy_(eps_recon)
+            if noisy is not None:
+                if noisy.data_ptr() != sin[4].data_ptr():
+                    sin[4].copy_(noisy)
+                if rects is not None and rects.data_ptr() != sin[5].data_ptr():
+                    sin[5].copy_(rects)
             replay(g)
+            self.last_step_weighted = self._weighted(noisy, rects)
             self.losses = g.out
             return g.out
         if self._warm_key != key:
             self._warm_key = key
             self._graph = None
-            return self.train_step(real, epoch, eps_z, eps_real, eps_recon)
+            return self.train_step(real, epoch, eps_z, eps_real, eps_recon, noisy=noisy, rects=rects)
         sin = [real.clone()] + ([eps_z.clone(), eps_real.clone(), eps_recon.clone()] if inject else [None] * 3)
+        if noisy is not None:
+            sin += [noisy.clone(), None if rects is None else rects.clone()]
         # Collectives INSIDE the graph (round 4): RCCL's all-reduces are capturable on this stack (PyTorch 2.10 / RCCL 2.26:
         # tools/rccl_capture_probe.py) -- the asynchronous bucket launches fork onto RCCL's stream and the waits join it
         # back, all as graph dependencies, so the iteration stays ONE graph and no hand-off costs a graph boundary (a cut
@@ -392,6 +476,7 @@ class VAEGANTrainer:
             g = self._capture(key, sin, epoch, False)
         self._graph = g
         replay(g)
+        self.last_step_weighted = self._weighted(noisy, rects)
         self.losses = g.out
         return g.out
 
@@ -416,7 +501,8 @@ class VAEGANTrainer:
         mirrors = HostMirrors([m._engine for m in (self.E, self.G, self.D)], (self.opt_E, self.opt_G, self.opt_D),
                               self.reducer, replay_reducer=inline)
         try:
-            return capture(lambda *s: self.train_step(s[0], epoch, *s[1:]), sin, mirrors, sin[0].device, key=key,
+            return capture(lambda *s: self.train_step(s[0], epoch, *s[1:4], noisy=s[4], rects=s[5]) if len(s) > 4
+                           else self.train_step(s[0], epoch, *s[1:]), sin, mirrors, sin[0].device, key=key,
                            pool=torch.cuda.graph_pool_handle(), error_mode="thread_local", pre_capture=quiesce,
                            install_cut=set_cut_hook)
         except CaptureRefused:
@@ -475,13 +561,16 @@ class VAEGANTrainer:
 
     def loss_dict(self, losses: Optional[torch.Tensor] = None, epoch: Optional[int] = None) -> Dict[str, float]:
         """Host copy of the last step's losses (one device sync, like the reference's .item() calls :125-127)."""
-        v = (losses if losses is not None else self.losses)[:7].tolist()
-        v += [0.0] * (7 - len(v))                # a caller's five-slot slice
+        v = (losses if losses is not None else self.losses)[:8].tolist()
+        v += [0.0] * (8 - len(v))                # a caller's five-slot slice
         out = dict(zip(LOSS_NAMES, v))
         if self.alpha_feat != 0.0:
             out["feat_loss"] = v[5]
         if self.alpha_ssim != 0.0:
             out["ssim_loss"] = v[6]
+        if self.last_step_weighted:
+            out["hole_mse"] = v[7]               # mean squared error inside the occlusion rectangles: only after a step that
+                                                 # used the weighted term (slot 7 reads 0 after any other)
         if epoch is not None:
             out["total"] = self.alpha_pix * out["recon_loss"] + self.alpha_kl * min(1.0, epoch / 50) * out["kl_loss"] \
                 + self.alpha_adv * out["g_loss_adv"] + self.alpha_feat * v[5] + self.alpha_ssim * v[6]
