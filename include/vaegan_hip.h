@@ -48,7 +48,7 @@ extern "C" {
 #define VG_ACT_LRELU   2   /* nn.LeakyReLU(slope)    main_vae.py:25, gan_code.py:62-82 */
 #define VG_ACT_TANH    3   /* nn.Tanh()              gan_code.py:50 (vg_tnconv epilogue only) */
 
-#define VG_ABI_VERSION 18  /* 2: vg_pack_desc.tile_start, SyncBN / WGAN / data-path entry points; 3: in-kernel noise (vg_*_rng);
+#define VG_ABI_VERSION 19  /* 2: vg_pack_desc.tile_start, SyncBN / WGAN / data-path entry points; 3: in-kernel noise (vg_*_rng);
                              4: vg_bn_finalize_act_forward, vg_bn_backward_finalize_apply;
                              7: vg_bce_pair_forward_backward;
                              8: vg_head_backward; round-3 prune -- the opt-in experiments of ABI 5 / 6 that measured slower (input prologue of
@@ -62,7 +62,8 @@ extern "C" {
                              15: KID: vg_kid_scores (+ _ws_bytes);
                              16: Discriminator-feature reconstruction loss: vg_feat_mse_forward_backward;
                              17: SSIM reconstruction loss: vg_ssim_loss_forward_backward (+ _ws_floats);
-                             18: region-weighted MSE for degraded pairs: vg_region_mse_forward_backward (+ _ws_doubles) */
+                             18: region-weighted MSE for degraded pairs: vg_region_mse_forward_backward (+ _ws_doubles);
+                             19: vg_gather_gemm_plan / vg_gg_plan: the launcher's kernel choice as a host-only query */
 int vg_abi_version(void);
 /* The library reads its optional kernel-selection switches (VG_* environment variables, DESIGN.md "Runtime switches")
  * ONCE, when it is loaded; nothing on a launch path calls getenv.  A process that changes one of them afterwards
@@ -135,6 +136,31 @@ int vg_gather_gemm_tile_m(const vg_gg_desc* d, int dtype);
  * split along K over gridDim.z; the f32 partial tiles are summed in fixed order by a second kernel. */
 int64_t vg_gather_gemm_ws_bytes(const vg_gg_desc* d, int dtype);
 int vg_gather_gemm(const vg_gg_desc* d, int dtype, void* stream);
+
+/* What vg_gather_gemm launches for a descriptor under the current switches (host-only query; needs no GPU).  The launcher
+ * builds this same record and launches from it, so the query cannot drift from the launch.  Pointers of the descriptor are
+ * only tested against NULL / for alignment (bias, stats, ws + ws_bytes, zeros and mask_x all take part in the choice). */
+#define VG_GG_GENERIC  0   /* gg_kernel  (conv_gemm.hip): bm x bn tile, one phase per workgroup                              */
+#define VG_GG_NARROWK  1   /* ggn_kernel (conv_narrowk.hpp): 3-channel input; detail = { NT = N / 16, KC = Kp / 32 }         */
+#define VG_GG_PHASE4   2   /* ggq_kernel (conv_phase4.hpp): four phases per workgroup; detail = { NR: patch DMA rounds, 0 }  */
+#define VG_GG_PATCH    3   /* ggp_kernel (conv_patch.hpp): input patch in LDS; detail = { NR: patch DMA rounds, NR_ argument } */
+#define VG_GG_REDUCE_NONE  0
+#define VG_GG_REDUCE_FLAT  1   /* splitk_reduce_kernel: elementwise over a flat output, no statistics */
+#define VG_GG_REDUCE_TILE  2   /* splitk_reduce2_kernel: per tile, with phases / statistics           */
+typedef struct vg_gg_plan {
+    int32_t family;            /* VG_GG_*                                                                              */
+    int32_t bm, bn;            /* output tile; one statistics slab covers bm rows                                      */
+    int32_t detail[2];         /* the template arguments beyond the tile (see the family)                              */
+    int32_t dma;               /* 1: operands staged by LDS-DMA (the ring of gg_kernel; always 1 for families 2, 3)    */
+    int32_t ksplit;            /* K slices (1: K is not split)                                                         */
+    int32_t stages_per_split;  /* main-loop stages per slice (0 when K is not split)                                   */
+    int32_t nstages;           /* main-loop stages of the whole K (generic family; 0 otherwise): the last slice holds
+                                  nstages - (ksplit - 1) * stages_per_split of them                                    */
+    int32_t reduce;            /* VG_GG_REDUCE_*: the second launch of a split                                          */
+    int32_t n_major;           /* 1: workgroups are dealt XCD-major over the n tiles                                   */
+    int32_t nparts;            /* statistics slabs the launch writes (0 without d->stats)                              */
+} vg_gg_plan;
+int vg_gather_gemm_plan(const vg_gg_desc* d, int dtype, vg_gg_plan* out);
 
 /* ------------------------------------------------------------------------------------------
  * Weight gradient (autograd convolution_backward wgrad; Linear weight grad):

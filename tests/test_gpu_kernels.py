@@ -145,14 +145,24 @@ def test_few_row_long_k_data_gradient_on_128x128_tiles_with_dma_k_slices(ops, vg
     gg, pk = G.convT_dgrad(B, H, H, Cin, Cout, k, s, p, dtype)
     Wd = ops.pack_weights(pk, w.to(DEV), dtype)
     DY = _dev(to_nhwc(dy, gg.IC), dtype, ops)
-    out = {}
+    out, plans = {}, {}
     for mode in ("0", "1"):
         vg_switch("VG_SPLITK_BIGK", mode)
+        plans[mode] = ops.gather_gemm_plan(gg, dtype)
         n0 = ops.launch_count()
         DX, _, _ = ops.gather_gemm(gg, DY, Wd, dtype)
         out[mode] = (DX.clone(), ops.launch_count() - n0)
     torch.cuda.synchronize()
     expect_split = (B * H * H) % 128 == 0 and (B * H * H // 128) * (Cin // 128) >= 64
+    # which kernel ran, from the record the launcher launches from: K slices of 128 x 128 tiles on the LDS-DMA ring + the flat
+    # reduce where the form applies; otherwise (and with the switch off) one un-split launch on a smaller generic tile
+    for mode in ("0", "1"):
+        pl = plans[mode]
+        assert pl["family"] == "generic" and pl["dma"] and out[mode][1] == (2 if pl["ksplit"] > 1 else 1)
+        if mode == "1" and expect_split:
+            assert (pl["bm"], pl["bn"], pl["reduce"]) == (128, 128, "flat") and pl["ksplit"] > 1
+        else:
+            assert pl["ksplit"] == 1 and (pl["bm"], pl["bn"]) != (128, 128)
     if expect_split:
         assert out["1"][1] == 2                                               # main launch + slab reduce
     for mode in ("0", "1"):
@@ -187,8 +197,13 @@ def test_split_k_with_batchnorm_statistics_and_subpixel_phases(ops, vg_switch, k
     out = {}
     for mode in ("0", "1"):
         vg_switch("VG_SPLITK_GENERAL", mode)                 # (opt-in: off by default)
+        pl = ops.gather_gemm_plan(gg, dtype, bias=b is not None, want_stats=True)
+        # the kernel that runs: 64 x 64 generic tiles on the LDS-DMA ring, K cut into slices + the per-tile slab reduce when on
+        assert (pl["family"], pl["bm"], pl["bn"], pl["dma"]) == ("generic", 64, 64, True)
+        assert (pl["ksplit"] > 1, pl["reduce"]) == ((True, "tile") if mode == "1" else (False, "none"))
         n0 = ops.launch_count()
         Y, stats, nparts = ops.gather_gemm(gg, X, Wp, dtype, bias=None if b is None else b.to(DEV), want_stats=True)
+        assert nparts == pl["nparts"]
         out[mode] = (Y.clone(), stats[: nparts * 2 * Cout].clone().view(nparts, 2, Cout), nparts, ops.launch_count() - n0)
     torch.cuda.synchronize()
     assert out["0"][3] == 1 and out["1"][3] == 2 and out["0"][2] == out["1"][2]      # split: main + slab reduce; same slab rows
@@ -686,8 +701,12 @@ def test_patch_gather_gemm_equals_reference_and_gather_path(ops, vg_switch, kind
         vg_switch("VG_GG_PATCH", "0" if mode == "gather" else "1")
         vg_switch("VG_PATCH256_MIN", "1" if mode == "patch256" else "2000000000")
         vg_switch("VG_PATCH256X64_MIN", "1" if mode == "patch256" else "2000000000")    # 256 x 64 for 33..64 channels
+        pl = ops.gather_gemm_plan(gg, dtype, want_stats=True)
         Y, st, nparts = ops.gather_gemm(gg, X, Wp, dtype, want_stats=True)
         M = gg.B * gg.GH * gg.GW
+        # the kernel that ran: the per-tap generic tile, or a patch kernel (every case of PATCH_CASES reaches one in both variants)
+        assert pl["family"] == ("generic" if mode == "gather" else "patch") and nparts == pl["nparts"]
+        assert pl["bm"] == 128 or (mode == "patch256" and pl["bm"] == 256)
         # 256-row tiles only where an 8-wave variant applies (N > 32 and a patch of <= 384 pixels), else 128-row tiles
         assert nparts in ((gg.nphase * (M // 128),) if mode != "patch256" else (gg.nphase * (M // 128), gg.nphase * (M // 256)))
         outs[mode] = (from_nhwc(Y.double().cpu(), nout), st[: nparts * 2 * nout].view(nparts, 2, nout).double().sum(0).cpu())
@@ -710,7 +729,8 @@ def test_narrow_transposed_layers_all_phases_per_workgroup(ops, vg_switch, kind,
     """The narrow layers of the S >= 128 stacks (ConvTranspose2d(64 -> 32), (32 -> 16) forward, the data gradients of
     Conv2d(16 -> 32), (32 -> 64); gan_code.py:21-49, :61-84 at img_size 128 / 256) on conv_phase4.hpp -- all four sub-pixel
     phases of 256 grid pixels in one workgroup, union patch fetched once, whole output rows written: against torch fp64 and
-    against the generic per-tap gather tiles (one phase per workgroup), BatchNorm partial sums included; 4- to 128-wide grids (multi-image tiles, a two-row tile of a 128-wide grid), 12 and 24 real columns."""
+    against the one-phase-per-workgroup kernels (the generic per-tap tiles; the 128 x 32 patch kernel for exactly 32 channels on grids
+    of <= 64 columns -- the plan says which), BatchNorm partial sums included; 4- to 128-wide grids (multi-image tiles, a two-row tile of a 128-wide grid), 12 and 24 real columns."""
     dtype = G.BF16
     g = torch.Generator().manual_seed(H * 5 + Cin)
     if kind == "convT":
@@ -734,7 +754,15 @@ def test_narrow_transposed_layers_all_phases_per_workgroup(ops, vg_switch, kind,
     vg_switch("VG_GG_PHASE4_MIN", "1")       # (by default only launches of >= 512 tiles come here)
     for name, ph4 in (("generic", "0"), ("phase4", "1")):
         vg_switch("VG_GG_PHASE4", ph4)
+        pl = ops.gather_gemm_plan(gg, dtype, bias=True, want_stats=True)
+        # the kernel that runs: ggq_kernel, against one phase per workgroup -- the generic tile, or the 128 x 32 patch kernel
+        # where the layer has exactly 32 output channels and a grid of at most 64 columns (conv_patch.hpp)
+        if name == "phase4":
+            assert (pl["family"], pl["bm"], pl["bn"]) == ("phase4", 256, 16 if nout <= 16 else 32)
+        else:
+            assert pl["family"] == ("patch" if gg.N == 32 and gg.GW <= 64 else "generic")
         Y, st, nparts = ops.gather_gemm(gg, X, Wp, dtype, bias=bias, want_stats=True)
+        assert nparts == pl["nparts"]
         if name != "generic":
             assert nparts == gg.nphase * (M // 256)
         assert (Y[..., nout:] == 0).all()
@@ -750,6 +778,8 @@ def test_narrow_transposed_layers_all_phases_per_workgroup(ops, vg_switch, kind,
     fused = {}
     for name, ph4 in (("generic", "0"), ("phase4", "1")):
         vg_switch("VG_GG_PHASE4", ph4)
+        for kw in (dict(bias=True, act=(2, 0.2)), dict(mask=(2, 0.2))):
+            assert (ops.gather_gemm_plan(gg, dtype, **kw)["family"] == "phase4") == (name == "phase4")
         Ya, _, _ = ops.gather_gemm(gg, X, Wp, dtype, bias=bias, act=(2, 0.2))
         Ym, _, _ = ops.gather_gemm(gg, X, Wp, dtype, mask=(mx, 2, 0.2))
         fused[name] = (Ya.float().cpu(), Ym.float().cpu())

@@ -171,6 +171,9 @@ def test_c_abi_rejects_bad_arguments_on_host():
     d = L.GGDesc()                                  # all zeros: NULL pointers, zero sizes
     assert lib.vg_gather_gemm(ctypes.byref(d), 0, None) == -1
     assert lib.vg_gather_gemm(ctypes.byref(d), 7, None) == -3
+    plan = L.GGPlan()                               # the launcher's plan as a host-only query: validated like a launch
+    assert lib.vg_gather_gemm_plan(ctypes.byref(d), 0, ctypes.byref(plan)) == -1
+    assert lib.vg_gather_gemm_plan(ctypes.byref(d), 7, ctypes.byref(plan)) == -3
     w = L.WGDesc()
     assert lib.vg_wgrad_ws_bytes(ctypes.byref(w), 0) == -1
     assert lib.vg_adam_step(None, None, None, None, 0, 1e-3, 0.9, 0.999, 1e-8, 1.0, None, None) == -1

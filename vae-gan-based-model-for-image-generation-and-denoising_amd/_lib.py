@@ -16,7 +16,7 @@ VG_F32, VG_BF16, VG_FP8 = 0, 1, 2
 VG_FP8_WSHIFT = 6
 VG_ACT_NONE, VG_ACT_RELU, VG_ACT_LRELU, VG_ACT_TANH = 0, 1, 2, 3
 VG_MAX_PHASE = 4
-ABI_VERSION = 18
+ABI_VERSION = 19
 
 VG_ENOSUP = -3
 _ERR = {-1: "VG_EINVAL (bad shape/size/flag)", -2: "VG_EALIGN (16-byte contract violated)",
@@ -38,6 +38,13 @@ class GGDesc(Structure):
                 ("nphase", c_int32), ("stats_capacity", c_int32), ("ws", c_void_p), ("ws_bytes", c_int64), ("zeros", c_void_p),
                 ("act", c_int32), ("act_slope", c_float),
                 ("mask_x", c_void_p), ("mask_act", c_int32), ("mask_slope", c_float)]
+
+
+class GGPlan(Structure):
+    """vg_gg_plan."""
+    _fields_ = [("family", c_int32), ("bm", c_int32), ("bn", c_int32), ("detail", c_int32 * 2), ("dma", c_int32),
+                ("ksplit", c_int32), ("stages_per_split", c_int32), ("nstages", c_int32), ("reduce", c_int32),
+                ("n_major", c_int32), ("nparts", c_int32)]
 
 
 class WGDesc(Structure):
@@ -92,6 +99,7 @@ SIGNATURES = {
     "vg_gather_gemm_family": (c_int, [POINTER(GGDesc), _I]),
     "vg_gather_gemm_ws_bytes": (c_int64, [POINTER(GGDesc), _I]),
     "vg_gather_gemm": (c_int, [POINTER(GGDesc), _I, _P]),
+    "vg_gather_gemm_plan": (c_int, [POINTER(GGDesc), _I, POINTER(GGPlan)]),
     "vg_wgrad_ws_bytes": (c_int64, [POINTER(WGDesc), _I]),
     "vg_wgrad": (c_int, [POINTER(WGDesc), _I, _P]),
     "vg_pack_weights": (c_int, [POINTER(PackDesc), _I, _P]),

@@ -911,32 +911,120 @@ inline bool n_major(const vg_gg_desc* d, int n_tiles, int esz) {
     return mode == 2 || wbytes > abytes;
 }
 
-template <int DT, int BM, int BN, int WM, int WN>
-int launch(const vg_gg_desc* d, hipStream_t s, SplitK sk) {
+// ---- the plan: EVERYTHING the launcher decides, in one place ------------------------------------------------------------
+// vg_gather_gemm_plan returns the public part, vg_gather_gemm launches from the same record (launch / dispatch / the patch,
+// four-phase and narrow-K launchers below only translate it into a template instantiation and a grid).
+struct GGPlan {
+    vg_gg_plan p;
+    SplitK sk;                      // as planned (p.ksplit is 1 where the workspace for it was not supplied)
+    PatchGeo pg;                    // family VG_GG_PATCH
+    Q4Geo qg;                       // family VG_GG_PHASE4
+};
+
+// 64-byte K chunks per main-loop stage of gg_kernel<DT, bm, bn, .., DMA>
+inline int stage_chunks(int dtype, int bm, int bn, bool dma) {
+    if (!dma) return dtype == VG_F32 ? 1 : 2;
+    if (bm == 128 && bn == 128) return DmaRing<128, 128>::KCH;
+    if (bm == 128 && bn == 64) return DmaRing<128, 64>::KCH;
+    return DmaRing<64, 64>::KCH;
+}
+
+inline void plan_generic(const vg_gg_desc* d, int dtype, GGPlan* P) {
+    vg_gg_plan& p = P->p;
+    const TileCfg t{p.bm, p.bn};
+    const int esz = dtype == VG_F32 ? 4 : (dtype == VG_BF16 ? 2 : 1);
+    const int n_tiles = (d->N + t.bn - 1) / t.bn;
+    const bool can_dma = (dtype == VG_BF16 || dtype == VG_FP8) && (t.bn % 64 == 0);
+    bool dma = can_dma && use_dma() && d->zeros != nullptr;
+    const bool split = dtype != VG_FP8 && P->sk.ksplit > 1 && d->ws != nullptr && d->ws_bytes >= P->sk.ws_bytes;
+    if (split) dma = dma && (t.bm == 64 || t.bm == 128) && split_dma_ok(d, dtype, t);    // K slices on the LDS-DMA ring too
+    p.family = VG_GG_GENERIC;
+    p.dma = dma ? 1 : 0;
+    const int kch = stage_chunks(dtype, t.bm, t.bn, dma);
+    p.nstages = ((d->Kp * esz) / 64 + kch - 1) / kch;
+    if (split) {
+        const bool flat = d->nphase == 1 && d->OSY == 1 && d->OSX == 1 && d->GH == d->OH && d->GW == d->OW;
+        p.ksplit = P->sk.ksplit;
+        p.stages_per_split = P->sk.sps;
+        // the round-1 reduce is elementwise over the flat output; phases and statistics need the tile form
+        p.reduce = (flat && d->stats == nullptr) ? VG_GG_REDUCE_FLAT : VG_GG_REDUCE_TILE;
+    } else {
+        p.n_major = n_major(d, n_tiles, esz) ? 1 : 0;
+    }
+}
+
+inline int make_plan(const vg_gg_desc* d, int dtype, GGPlan* P) {
+    *P = GGPlan{};
+    vg_gg_plan& p = P->p;
+    const TileCfg t = pick_tile(d, dtype == VG_BF16, dtype == VG_FP8);
+    P->sk = plan_splitk(d, dtype, t);
     const int M = d->B * d->GH * d->GW;
-    const bool split = sk.ksplit > 1 && d->ws != nullptr && d->ws_bytes >= sk.ws_bytes;
+    p.bm = t.bm; p.bn = t.bn;
+    p.ksplit = 1;
+    p.reduce = VG_GG_REDUCE_NONE;
+    p.nparts = d->stats ? d->nphase * ((M + t.bm - 1) / t.bm) : 0;
+    if (dtype != VG_BF16) { plan_generic(d, dtype, P); return 0; }
+    if (narrowk_ok(d, dtype)) {
+        p.family = VG_GG_NARROWK;
+        p.detail[0] = d->N / 16;
+        p.detail[1] = d->Kp / 32;
+        return 0;
+    }
+    {
+        int nr;
+        if (t.bm == 256 && t.bn <= 32 && use_dma() && P->sk.ksplit <= 1 && ggq_geometry(d, &P->qg, &nr)) {
+            p.family = VG_GG_PHASE4;
+            p.detail[0] = nr;
+            p.dma = 1;
+            return 0;
+        }
+        if (t.bm == 256 && t.bn == 32) return VG_EINVAL;       // (switch flipped between planning and launch)
+    }
+    if ((t.bm == 128 || t.bm == 256) && (t.bn == GP_BN || (t.bn == 64 && patch64()) || (t.bn == 32 && d->N == 32 && patch32())) &&
+        P->sk.ksplit <= 1 && use_patch() && use_dma() && d->zeros != nullptr && patch_geometry(d, t.bm, &P->pg)) {
+        const int n_tiles = (d->N + t.bn - 1) / t.bn;
+        P->pg.n_major = n_major(d, n_tiles, 2) ? 1 : 0;
+        p.family = VG_GG_PATCH;
+        p.dma = 1;
+        p.n_major = P->pg.n_major;
+        // patch DMA rounds = the NR of ggp_kernel: 3 for the 8-wave tiles and for the 128 x 64 tile whose patch has <= 192 pixels
+        const bool nr3 = t.bm == 128 && t.bn == 64 && P->pg.NPP <= 192 && patch_nr3();
+        p.detail[1] = nr3 ? 3 : 0;                             // the NR_ template argument (0: by tile shape)
+        p.detail[0] = (t.bm == 256 || nr3 || GP_TPS != 2) ? 3 : 4;
+        return 0;
+    }
+    if (t.bm == 256 && t.bn >= 64) return VG_EINVAL;           // (env flipped between planning and launch)
+    plan_generic(d, dtype, P);
+    return 0;
+}
+
+template <int DT, int BM, int BN, int WM, int WN>
+int launch(const vg_gg_desc* d, hipStream_t s, const GGPlan& P) {
+    const vg_gg_plan& p = P.p;
+    const int M = d->B * d->GH * d->GW;
+    const bool split = p.ksplit > 1;
     const int m_tiles = (M + BM - 1) / BM, n_tiles = (d->N + BN - 1) / BN;
     dim3 grid(((m_tiles + 7) / 8) * 8 * n_tiles, 1, d->nphase);
     const int nstages_all = 1 << 30;
-    const int one = 1 | (n_major(d, n_tiles, ElemT<DT>::size) ? GG_N_MAJOR : 0);
+    const int one = 1 | (p.n_major ? GG_N_MAJOR : 0);
     constexpr bool CAN_DMA = (DT == VG_BF16 || DT == VG_FP8) && (BN % 64 == 0);
-    const bool dma = CAN_DMA && use_dma() && d->zeros != nullptr;
+    const bool dma = CAN_DMA && p.dma;
     if constexpr (DT == VG_FP8) {
         // LDS-DMA ring as the bf16 kernel (the staging code is byte-generic: a 64-byte chunk holds 64 e4m3 channels)
         if (dma) vg_launch_timed(3, gg_kernel<DT, BM, BN, WM, WN, false, true>, grid, dim3(256), 0, s, *d, one, nstages_all);
         else vg_launch_timed(3, gg_kernel<DT, BM, BN, WM, WN, false, false>, grid, dim3(256), 0, s, *d, one, nstages_all);
         return VG_LAUNCH_RC();
     } else if (split) {
-        grid.z = d->nphase * sk.ksplit;
+        grid.z = d->nphase * p.ksplit;
         bool launched = false;
         if constexpr (CAN_DMA && (BM == 64 || BM == 128)) {     // round 4: K slices on the LDS-DMA ring too
-            if (dma && split_dma_ok(d, DT, TileCfg{BM, BN})) {
-                vg_launch_timed(0, gg_kernel<DT, BM, BN, WM, WN, true, true>, grid, dim3(256), 0, s, *d, sk.ksplit, sk.sps);
+            if (dma) {
+                vg_launch_timed(0, gg_kernel<DT, BM, BN, WM, WN, true, true>, grid, dim3(256), 0, s, *d, p.ksplit, p.stages_per_split);
                 launched = true;
             }
         }
         if (!launched)
-            vg_launch_timed(0, gg_kernel<DT, BM, BN, WM, WN, true, false>, grid, dim3(256), 0, s, *d, sk.ksplit, sk.sps);
+            vg_launch_timed(0, gg_kernel<DT, BM, BN, WM, WN, true, false>, grid, dim3(256), 0, s, *d, p.ksplit, p.stages_per_split);
     } else if constexpr (CAN_DMA) {
         if (dma) vg_launch_timed(0, gg_kernel<DT, BM, BN, WM, WN, false, true>, grid, dim3(256), 0, s, *d, one, nstages_all);
         else vg_launch_timed(0, gg_kernel<DT, BM, BN, WM, WN, false, false>, grid, dim3(256), 0, s, *d, one, nstages_all);
@@ -946,31 +1034,45 @@ int launch(const vg_gg_desc* d, hipStream_t s, SplitK sk) {
     int rc = VG_LAUNCH_RC();
     if (rc || !split) return rc;
     if constexpr (DT != VG_FP8) {
-        const bool flat = d->nphase == 1 && d->OSY == 1 && d->OSX == 1 && d->GH == d->OH && d->GW == d->OW;
-        if (flat && d->stats == nullptr) {                    // the round-1 reduce: elementwise over the flat output
+        if (p.reduce == VG_GG_REDUCE_FLAT) {                  // the round-1 reduce: elementwise over the flat output
             const int64_t total = (int64_t)M * d->OC;
             int blocks = (int)((total + 255) / 256);
             if (blocks > 2048) blocks = 2048;
-            hipLaunchKernelGGL(splitk_reduce_kernel<DT>, dim3(blocks), dim3(256), 0, s, d->ws, sk.ksplit, M, d->N, d->OC,
+            hipLaunchKernelGGL(splitk_reduce_kernel<DT>, dim3(blocks), dim3(256), 0, s, d->ws, p.ksplit, M, d->N, d->OC,
                                m_tiles * BM, n_tiles * BN, d->bias, d->Y);
         } else {
             // (the output's padding channels [N, OC) of a pixel are written as zeros by the 64-column blocks that cover them)
             hipLaunchKernelGGL(splitk_reduce2_kernel<DT>, dim3(m_tiles, (d->OC + 63) / 64, d->nphase), dim3(256), 0, s, *d,
-                               sk.ksplit, BM, m_tiles * BM, n_tiles * BN);
+                               p.ksplit, BM, m_tiles * BM, n_tiles * BN);
         }
     }
     return VG_LAUNCH_RC();
 }
 
 template <int DT>
-int dispatch(const vg_gg_desc* d, TileCfg t, hipStream_t s, SplitK sk) {
+int dispatch(const vg_gg_desc* d, hipStream_t s, const GGPlan& P) {
+    const vg_gg_plan& t = P.p;
     if constexpr (DT != VG_FP8) {
-        if (t.bm == 256 && t.bn == 16) return launch<DT, 256, 16, 4, 1>(d, s, sk);
-        if (t.bm == 128 && t.bn == 32) return launch<DT, 128, 32, 4, 1>(d, s, sk);
+        if (t.bm == 256 && t.bn == 16) return launch<DT, 256, 16, 4, 1>(d, s, P);
+        if (t.bm == 128 && t.bn == 32) return launch<DT, 128, 32, 4, 1>(d, s, P);
     }
-    if (t.bm == 128 && t.bn == 128) return launch<DT, 128, 128, 2, 2>(d, s, sk);
-    if (t.bm == 128 && t.bn == 64) return launch<DT, 128, 64, 2, 2>(d, s, sk);
-    return launch<DT, 64, 64, 2, 2>(d, s, sk);
+    if (t.bm == 128 && t.bn == 128) return launch<DT, 128, 128, 2, 2>(d, s, P);
+    if (t.bm == 128 && t.bn == 64) return launch<DT, 128, 64, 2, 2>(d, s, P);
+    return launch<DT, 64, 64, 2, 2>(d, s, P);
+}
+
+inline int launch_patch(const vg_gg_desc* d, hipStream_t s, const GGPlan& P) {
+    const vg_gg_plan& t = P.p;
+    const PatchGeo& pg = P.pg;
+    const int m_tiles = (d->B * d->GH * d->GW) / t.bm, n_tiles = (d->N + t.bn - 1) / t.bn;
+    dim3 grid(((m_tiles + 7) / 8) * 8 * n_tiles, 1, d->nphase);
+    if (t.bm == 256 && t.bn == 64) vg_launch_timed(0, (ggp_kernel<4, 64>), grid, dim3(512), 0, s, *d, pg);
+    else if (t.bm == 256) vg_launch_timed(0, ggp_kernel<4>, grid, dim3(512), 0, s, *d, pg);
+    else if (t.bn == 64 && t.detail[1] == 3) vg_launch_timed(0, (ggp_kernel<2, 64, 3>), grid, dim3(256), 0, s, *d, pg);
+    else if (t.bn == 64) vg_launch_timed(0, (ggp_kernel<2, 64>), grid, dim3(256), 0, s, *d, pg);
+    else if (t.bn == 32) vg_launch_timed(0, (ggp_kernel<2, 32>), grid, dim3(256), 0, s, *d, pg);
+    else vg_launch_timed(0, ggp_kernel<2>, grid, dim3(256), 0, s, *d, pg);
+    return VG_LAUNCH_RC();
 }
 
 }  // namespace
@@ -1007,38 +1109,31 @@ extern "C" int64_t vg_gather_gemm_ws_bytes(const vg_gg_desc* d, int dtype) {
     return plan_splitk(d, dtype, pick_tile(d, dtype == VG_BF16, dtype == VG_FP8)).ws_bytes;
 }
 
+extern "C" int vg_gather_gemm_plan(const vg_gg_desc* d, int dtype, vg_gg_plan* out) {
+    int rc = validate(d, dtype);
+    if (rc) return rc;
+    VG_CHECK_ARG(out != nullptr, VG_EINVAL);
+    GGPlan P;
+    rc = make_plan(d, dtype, &P);
+    if (rc) return rc;
+    *out = P.p;
+    return 0;
+}
+
 extern "C" int vg_gather_gemm(const vg_gg_desc* d, int dtype, void* stream) {
     int rc = validate(d, dtype);
     if (rc) return rc;
-    PatchGeo pg;
-    TileCfg t = pick_tile(d, dtype == VG_BF16, dtype == VG_FP8);
-    const SplitK sk = plan_splitk(d, dtype, t);
-    if (d->stats) {
-        const int M = d->B * d->GH * d->GW;
-        VG_CHECK_ARG(d->stats_capacity >= d->nphase * ((M + t.bm - 1) / t.bm), VG_EINVAL);
+    GGPlan P;
+    rc = make_plan(d, dtype, &P);
+    if (rc) return rc;
+    VG_CHECK_ARG(d->stats == nullptr || d->stats_capacity >= P.p.nparts, VG_EINVAL);
+    hipStream_t s = vg_stream(stream);
+    if (dtype == VG_F32) return dispatch<VG_F32>(d, s, P);
+    if (dtype == VG_FP8) return dispatch<VG_FP8>(d, s, P);
+    switch (P.p.family) {
+        case VG_GG_NARROWK: return launch_narrowk(d, s);
+        case VG_GG_PHASE4: return launch_phase4(d, P.qg, P.p.detail[0], s);
+        case VG_GG_PATCH: return launch_patch(d, s, P);
+        default: return dispatch<VG_BF16>(d, s, P);
     }
-    if (dtype == VG_F32) return dispatch<VG_F32>(d, t, vg_stream(stream), sk);
-    if (dtype == VG_FP8) return dispatch<VG_FP8>(d, t, vg_stream(stream), sk);
-    if (narrowk_ok(d, dtype)) return launch_narrowk(d, vg_stream(stream));
-    {
-        Q4Geo qg; int nr;
-        if (t.bm == 256 && t.bn <= 32 && use_dma() && sk.ksplit <= 1 && ggq_geometry(d, &qg, &nr))
-            return launch_phase4(d, qg, nr, vg_stream(stream));
-        if (t.bm == 256 && t.bn == 32) return VG_EINVAL;       // (switch flipped between planning and launch)
-    }
-    if ((t.bm == 128 || t.bm == 256) && (t.bn == GP_BN || (t.bn == 64 && patch64()) || (t.bn == 32 && d->N == 32 && patch32())) && sk.ksplit <= 1 &&
-        use_patch() && use_dma() && d->zeros != nullptr && patch_geometry(d, t.bm, &pg)) {
-        const int m_tiles = (d->B * d->GH * d->GW) / t.bm, n_tiles = (d->N + t.bn - 1) / t.bn;
-        dim3 grid(((m_tiles + 7) / 8) * 8 * n_tiles, 1, d->nphase);
-        pg.n_major = n_major(d, n_tiles, 2) ? 1 : 0;
-        if (t.bm == 256 && t.bn == 64) vg_launch_timed(0, (ggp_kernel<4, 64>), grid, dim3(512), 0, vg_stream(stream), *d, pg);
-        else if (t.bm == 256) vg_launch_timed(0, ggp_kernel<4>, grid, dim3(512), 0, vg_stream(stream), *d, pg);
-        else if (t.bn == 64 && pg.NPP <= 192 && patch_nr3()) vg_launch_timed(0, (ggp_kernel<2, 64, 3>), grid, dim3(256), 0, vg_stream(stream), *d, pg);
-        else if (t.bn == 64) vg_launch_timed(0, (ggp_kernel<2, 64>), grid, dim3(256), 0, vg_stream(stream), *d, pg);
-        else if (t.bn == 32) vg_launch_timed(0, (ggp_kernel<2, 32>), grid, dim3(256), 0, vg_stream(stream), *d, pg);
-        else vg_launch_timed(0, ggp_kernel<2>, grid, dim3(256), 0, vg_stream(stream), *d, pg);
-        return VG_LAUNCH_RC();
-    }
-    if (t.bm == 256 && t.bn >= 64) return VG_EINVAL;       // (env flipped between planning and launch)
-    return dispatch<VG_BF16>(d, t, vg_stream(stream), sk);
 }

@@ -437,6 +437,35 @@ def wgrad(wg: WGSpec, P: torch.Tensor, Q: torch.Tensor, dW: torch.Tensor, accumu
 
 
 # ---------------------------------------------------------------------------------------------
+GG_FAMILY = {0: "generic", 1: "narrowk", 2: "phase4", 3: "patch"}
+GG_REDUCE = {0: "none", 1: "flat", 2: "tile"}
+
+
+def gather_gemm_plan(g: GGSpec, dtype: int, bias: bool = False, want_stats: bool = False, act=None, mask=None,
+                     workspace: bool = True, zeros: bool = True) -> dict:
+    """What vg_gather_gemm launches for this geometry and epilogue under the current switches (vg_gather_gemm_plan: the
+    record the launcher itself launches from).  Host only, no GPU and no tensors: the descriptor's pointers are only
+    tested against NULL by the query, so placeholders stand in for them -- bias / want_stats / mask say which are set, as
+    in gather_gemm (which always passes a workspace of vg_gather_gemm_ws_bytes and the zero page).
+    -> dict(family, bm, bn, detail, dma, ksplit, stages_per_split, nstages, reduce, n_major, nparts)."""
+    some = 64                                                         # non-NULL, 16-byte aligned; never dereferenced
+    d = L.GGDesc(X=some, W=some, Y=some, bias=some if bias else 0, stats=some if want_stats else 0,
+                 zeros=some if zeros else 0, B=g.B, GH=g.GH, GW=g.GW, IH=g.IH, IW=g.IW, IC=g.IC, SY=g.SY, SX=g.SX,
+                 DY=g.DY, DX=g.DX, TH=g.TH, TW=g.TW, y0=L.i4(g.y0), x0=L.i4(g.x0), N=g.N, Kp=g.Kp, OH=g.OH, OW=g.OW,
+                 OC=g.OC, OSY=g.OSY, OSX=g.OSX, ooy=L.i4(g.ooy), oox=L.i4(g.oox), nphase=g.nphase)
+    if act is not None:
+        d.act, d.act_slope = act
+    if mask is not None:                                              # (code, slope) or gather_gemm's (tensor, code, slope)
+        d.mask_x, d.mask_act, d.mask_slope = some, mask[-2], mask[-1]
+    if workspace:
+        d.ws, d.ws_bytes = some, 1 << 62
+    p = L.GGPlan()
+    L.check(L.load().vg_gather_gemm_plan(byref(d), dtype, byref(p)), "vg_gather_gemm_plan")
+    return dict(family=GG_FAMILY[p.family], bm=p.bm, bn=p.bn, detail=(p.detail[0], p.detail[1]), dma=bool(p.dma),
+                ksplit=p.ksplit, stages_per_split=p.stages_per_split, nstages=p.nstages, reduce=GG_REDUCE[p.reduce],
+                n_major=bool(p.n_major), nparts=p.nparts)
+
+
 def gather_gemm_tile_m(g: GGSpec, X, Wp, dtype: int) -> int:
     """M edge of the tile the launcher will pick = rows covered by one BatchNorm statistics slab."""
     probe = _gg_desc(g, X, Wp, X, None, None, 0)
