@@ -48,7 +48,7 @@ extern "C" {
 #define VG_ACT_LRELU   2   /* nn.LeakyReLU(slope)    main_vae.py:25, gan_code.py:62-82 */
 #define VG_ACT_TANH    3   /* nn.Tanh()              gan_code.py:50 (vg_tnconv epilogue only) */
 
-#define VG_ABI_VERSION 19  /* 2: vg_pack_desc.tile_start, SyncBN / WGAN / data-path entry points; 3: in-kernel noise (vg_*_rng);
+#define VG_ABI_VERSION 20  /* 2: vg_pack_desc.tile_start, SyncBN / WGAN / data-path entry points; 3: in-kernel noise (vg_*_rng);
                              4: vg_bn_finalize_act_forward, vg_bn_backward_finalize_apply;
                              7: vg_bce_pair_forward_backward;
                              8: vg_head_backward; round-3 prune -- the opt-in experiments of ABI 5 / 6 that measured slower (input prologue of
@@ -63,7 +63,8 @@ extern "C" {
                              16: Discriminator-feature reconstruction loss: vg_feat_mse_forward_backward;
                              17: SSIM reconstruction loss: vg_ssim_loss_forward_backward (+ _ws_floats);
                              18: region-weighted MSE for degraded pairs: vg_region_mse_forward_backward (+ _ws_doubles);
-                             19: vg_gather_gemm_plan / vg_gg_plan: the launcher's kernel choice as a host-only query */
+                             19: vg_gather_gemm_plan / vg_gg_plan: the launcher's kernel choice as a host-only query;
+                             20: vg_bn_launch_plan / vg_bn_plan: the BatchNorm launchers' geometry as a host-only query */
 int vg_abi_version(void);
 /* The library reads its optional kernel-selection switches (VG_* environment variables, DESIGN.md "Runtime switches")
  * ONCE, when it is loaded; nothing on a launch path calls getenv.  A process that changes one of them afterwards
@@ -298,6 +299,33 @@ int vg_bn_act_backward_apply(const void* x, const void* dy, void* dx,
                              const float* mean, const float* invstd, const float* coef,
                              int64_t rows, int C, int act, float slope, int groups, int64_t gstride,
                              int64_t cstride, int dtype, void* stream);
+/* What the BatchNorm launchers launch for a shape under the current switches (host-only query; needs no GPU).  Every
+ * launcher builds this same record and launches from it, so the query cannot drift from the launch.
+ *   VG_BN_PLAN_REDUCE   vg_channel_stats (one group) / vg_bn_act_backward_reduce: a "block" is one slab row (part)
+ *   VG_BN_PLAN_FORWARD  vg_bn_act_forward(_fp8)
+ *   VG_BN_PLAN_APPLY    vg_bn_act_backward_apply
+ *   VG_BN_PLAN_FUSED    vg_bn_finalize_act_forward / vg_bn_backward_finalize_apply (needs nparts_per_group)
+ * rows = all groups' rows.  aligned16: whether every tensor of the launch (and the e4m3 twin's 8 bytes) meets the
+ * alignment that the 16-byte bf16 vectors need; the launchers test their pointers.  nparts_per_group: slab rows per
+ * group, read by VG_BN_PLAN_FUSED only.  A shape the one-launch form refuses gives fused = 0 and no geometry. */
+#define VG_BN_PLAN_REDUCE   0
+#define VG_BN_PLAN_FORWARD  1
+#define VG_BN_PLAN_APPLY    2
+#define VG_BN_PLAN_FUSED    3
+typedef struct vg_bn_plan {
+    int32_t kind;              /* VG_BN_PLAN_*                                                                          */
+    int32_t vec;               /* channels per thread: 4, or 8 (16-byte bf16 vectors)                                   */
+    int32_t threads_per_row;   /* of a full column block; a ragged last column block has C / vec - (col_blocks - 1) *
+                                  256 of them and its own 256 / that rows per pass                                      */
+    int32_t rows_per_pass;     /* rows a workgroup covers at once; 256 % threads_per_row threads idle                   */
+    int32_t rows_per_block;    /* rows a workgroup owns (the last one of a group may own fewer); reduce: rows per part  */
+    int32_t blocks_per_group;  /* gridDim.x of the streaming passes; reduce: parts (slab rows) per group                */
+    int32_t col_blocks;        /* gridDim.y: blocks of 256 threads' columns; fused: slices of 64 channels               */
+    int32_t groups;            /* gridDim.z (reduce: gridDim.x = blocks_per_group * groups)                             */
+    int32_t fused;             /* VG_BN_PLAN_FUSED: 1 when the one-launch form is taken, 0 when refused                 */
+} vg_bn_plan;
+int vg_bn_launch_plan(int kind, int64_t rows, int C, int groups, int dtype, int aligned16, int nparts_per_group,
+                      vg_bn_plan* out);
 /* Activation-only backward (first Discriminator layer has no BN, gan_code.py:61-62). */
 int vg_act_backward(const void* x, const void* dy, void* dx, int64_t n, int act, float slope,
                     int dtype, void* stream);

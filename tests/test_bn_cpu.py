@@ -1,0 +1,433 @@
+"""CPU: the numpy restatement of the BatchNorm kernels (tests/_bn_ref.py) and the integer cases of tests/test_gpu_bn.py.
+
+  * the restatement in f64 against torch autograd on Gaussian data: forward, running statistics over two groups in order, dx,
+    dgamma, dbeta for ReLU / LeakyReLU / none -- which proves that the coefficient form a * dz - b * xhat - c IS the
+    gradient -- plus eval mode and the SyncBN form (two ranks whose sums are added == one rank holding both halves);
+  * the exactness conditions of every integer case (_bn_ref's module docstring): f32 sums exact in any order, no f32
+    operation rounds, every stored value fits bf16;
+  * a blind-spot check: every perturbation a kernel could plausibly suffer (a row dropped at a block edge, a neighbouring
+    channel's or another group's coefficients, z >= 0 for z > 0, swapped coefficients or sums, a reversed group order, an
+    ignored accumulate flag) must change the reference output of every case it applies to -- a case that cannot see one is a
+    failure of the case table, found here and not on the GPU;
+  * the coverage of the launchers' branches by the table, read from the built library (vg_bn_launch_plan needs no GPU).
+"""
+import importlib
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+import _bn_ref as R
+
+PKG = "vae-gan-based-model-for-image-generation-and-denoising_amd"
+f32, f64 = np.float32, np.float64
+
+
+def _differs(a, b):
+    return not np.array_equal(np.asarray(a, dtype=f64), np.asarray(b, dtype=f64))
+
+
+# ---- the restatement is BatchNorm (+ activation) and its gradient ---------------------------------------------------------
+def _torch_act(z, act, slope):
+    return F.relu(z) if act == R.ACT_RELU else F.leaky_relu(z, slope) if act == R.ACT_LRELU else z
+
+
+@pytest.mark.parametrize("act,slope", [(R.ACT_NONE, 0.0), (R.ACT_RELU, 0.0), (R.ACT_LRELU, 0.2)], ids=["none", "relu", "lrelu"])
+def test_restatement_is_batchnorm_and_its_gradient(act, slope):
+    """Two groups through one set of parameters, as two separate F.batch_norm(train) calls in order: y, running statistics,
+    dx, dgamma, dbeta.  f64 throughout; the only difference is the order of f64 operations."""
+    rpg, groups, C, mom, eps = 37, 2, 12, 0.1, 1e-5
+    g = torch.Generator().manual_seed(11)
+    x = torch.randn(groups * rpg, C, generator=g, dtype=torch.float64) * 1.7 + 0.3
+    x[rpg:] = x[rpg:] * 0.6 - 1.1
+    dy = torch.randn(groups * rpg, C, generator=g, dtype=torch.float64)
+    gamma = torch.randn(C, generator=g, dtype=torch.float64) * 0.3 + 1
+    beta = torch.randn(C, generator=g, dtype=torch.float64) * 0.3
+    rm0, rv0 = torch.randn(C, generator=g, dtype=torch.float64), torch.rand(C, generator=g, dtype=torch.float64) + 0.5
+
+    xt, gt, bt = x.clone().requires_grad_(True), gamma.clone().requires_grad_(True), beta.clone().requires_grad_(True)
+    rm, rv = rm0.clone(), rv0.clone()
+    ys = [_torch_act(F.batch_norm(xt[k * rpg:(k + 1) * rpg], rm, rv, gt, bt, True, mom, eps), act, slope) for k in range(groups)]
+    y_ref = torch.cat(ys)
+    dx_ref, dg_ref, db_ref = torch.autograd.grad(y_ref, (xt, gt, bt), dy)
+
+    xn, dyn = x.numpy(), dy.numpy()
+    s1, s2 = R.col_stats(xn, groups, f64)
+    # momentum and eps reach the kernels as f32: the restatement uses those values, so does torch here
+    mom32, eps32 = float(f32(mom)), float(f32(eps))
+    rm, rv = rm0.clone(), rv0.clone()
+    for k in range(groups):
+        F.batch_norm(x[k * rpg:(k + 1) * rpg], rm, rv, gamma, beta, True, mom32, eps32)
+    co, rmn, rvn = R.finalize(s1, s2, rpg, gamma.numpy(), beta.numpy(), rm0.numpy(), rv0.numpy(), mom, eps, f64)
+    np.testing.assert_allclose(rmn, rm.numpy(), rtol=1e-12, atol=1e-13)
+    np.testing.assert_allclose(rvn, rv.numpy(), rtol=1e-12, atol=1e-13)
+    y = R.forward(xn, co[:, 2], co[:, 3], act, slope, R.F32, groups, f64)
+    np.testing.assert_allclose(y, y_ref.detach().numpy(), rtol=1e-9, atol=1e-11)      # eps differs by f32(1e-5) - 1e-5
+    b1, b2 = R.bwd_sums(xn, dyn, co, act, slope, groups, f64)
+    dg, db, coef = R.bwd_finalize(b1, b2, rpg, gamma.numpy(), co[:, 1], np.zeros(C), np.zeros(C), False, ft=f64)
+    dx = R.apply(xn, dyn, co, coef, act, slope, R.F32, groups, f64)
+    np.testing.assert_allclose(dx, dx_ref.numpy(), rtol=1e-8, atol=1e-10)
+    np.testing.assert_allclose(dg, dg_ref.numpy(), rtol=1e-8, atol=1e-10)
+    np.testing.assert_allclose(db, db_ref.numpy(), rtol=1e-10, atol=1e-11)
+
+
+def test_restatement_eval_mode():
+    g = torch.Generator().manual_seed(12)
+    x = torch.randn(9, 8, generator=g, dtype=torch.float64)
+    gamma, beta, rm = (torch.randn(8, generator=g, dtype=torch.float64) for _ in range(3))
+    rv = torch.rand(8, generator=g, dtype=torch.float64) + 0.5
+    eps = float(f32(1e-5))
+    sc, sh = R.eval_coeffs(gamma.numpy(), beta.numpy(), rm.numpy(), rv.numpy(), 1e-5, f64)
+    y = R.forward(x.numpy(), sc[None], sh[None], R.ACT_LRELU, 0.2, R.F32, 1, f64)
+    ref = F.leaky_relu(F.batch_norm(x, rm, rv, gamma, beta, False, 0.1, eps), 0.2)
+    np.testing.assert_allclose(y, ref.numpy(), rtol=1e-12, atol=1e-13)
+    sc1, sh1 = R.eval_coeffs(None, None, rm.numpy(), rv.numpy(), 1e-5, f64)
+    np.testing.assert_allclose(R.forward(x.numpy(), sc1[None], sh1[None], R.ACT_NONE, 0.0, R.F32, 1, f64),
+                               F.batch_norm(x, rm, rv, None, None, False, 0.1, eps).numpy(), rtol=1e-12, atol=1e-13)
+
+
+def test_restatement_syncbn_two_ranks_equal_one():
+    """Statistics: the ranks' f64 sums added, the global count.  Backward: dx coefficients from the global sums, dgamma /
+    dbeta from each rank's own (the gradient all-reduce adds them afterwards)."""
+    rng = np.random.default_rng(13)
+    rows, C = 48, 8
+    x, dy = rng.normal(size=(rows, C)), rng.normal(size=(rows, C))
+    gamma, beta = rng.normal(size=C) + 1, rng.normal(size=C)
+    one = R.finalize(*R.col_stats(x, 1, f64), rows, gamma, beta, np.zeros(C), np.ones(C), 0.1, 1e-5, f64)
+    halves = [R.col_stats(x[lo:lo + rows // 2], 1, f64) for lo in (0, rows // 2)]
+    both = R.finalize(halves[0][0] + halves[1][0], halves[0][1] + halves[1][1], rows, gamma, beta, np.zeros(C), np.ones(C),
+                      0.1, 1e-5, f64)
+    for a, b in zip(one, both):
+        np.testing.assert_allclose(b, a, rtol=1e-13, atol=1e-14)
+    co = one[0]
+    g1, g2 = R.bwd_sums(x, dy, co, R.ACT_LRELU, 0.2, 1, f64)
+    dg, db, coef = R.bwd_finalize(g1, g2, rows, gamma, co[:, 1], None, None, False, ft=f64)
+    dg_sum, db_sum = np.zeros(C), np.zeros(C)
+    for lo in (0, rows // 2):
+        l1, l2 = R.bwd_sums(x[lo:lo + rows // 2], dy[lo:lo + rows // 2], co, R.ACT_LRELU, 0.2, 1, f64)
+        ldg, ldb, lcoef = R.bwd_finalize(g1, g2, rows, gamma, co[:, 1], np.zeros(C), np.zeros(C), False, local=(l1, l2), ft=f64)
+        np.testing.assert_array_equal(lcoef, coef)
+        np.testing.assert_array_equal(ldg, l2[0]), np.testing.assert_array_equal(ldb, l1[0])
+        dg_sum, db_sum = dg_sum + ldg, db_sum + ldb
+    full = R.bwd_finalize(g1, g2, rows, gamma, co[:, 1], np.zeros(C), np.zeros(C), False, ft=f64)
+    np.testing.assert_allclose(dg_sum, full[0], rtol=1e-12, atol=1e-13)
+    np.testing.assert_allclose(db_sum, full[1], rtol=1e-12, atol=1e-13)
+    assert dg is None and db is None
+
+
+def test_bf16_round_is_torchs():
+    rng = np.random.default_rng(14)
+    a = np.concatenate([rng.normal(size=4096).astype(f32) * 37, np.array([1.00390625, 1.01171875, -3.0078125, 0.0], f32)])
+    want = torch.from_numpy(a).to(torch.bfloat16).float().numpy()
+    np.testing.assert_array_equal(R.bf16_round(a), want)
+    assert R.significant_bits(np.array([1.00390625])) == 9 and R.significant_bits(np.array([-96.0, 0.375])) == 2
+    assert R.fits_bf16(np.array([255.0, -0.498046875])) and not R.fits_bf16(np.array([257.0]))
+
+
+# ---- streaming cases: exactness and blind spots ----------------------------------------------------------------------------
+def _case_data(case, kind):
+    name, rpg, groups, C = case[:4]
+    return R.int_stream_case(R.case_seed(name), rpg, groups, C, xmax=20 if kind == "forward" else 6)
+
+
+@pytest.mark.parametrize("case", R.STREAM_CASES, ids=[c[0] for c in R.STREAM_CASES])
+def test_stream_cases_are_exact(case):
+    name, rpg, groups, C, act, slope, modes, kinds = case
+    for kind in kinds:
+        d = _case_data(case, kind)
+        x, dy, co, cf = d["x"], d["dy"], d["coeffs"], d["coef"]
+        assert R.fits_bf16(x) and R.fits_bf16(dy) and (x != 0).all() and (dy != 0).all()
+        z = co[:, 2][:, None, :] * x.reshape(groups, rpg, C) + co[:, 3][:, None, :]
+        assert (z == 0).any() and (z > 0).any() and (z < 0).any()
+        if d["z_each_channel"]:
+            assert (z == 0).any(1).all() and (z > 0).any(1).all() and (z < 0).any(1).all(), "per group and channel"
+        for k in range(4):                                           # coefficients differ between neighbours and between groups
+            assert (co[:, k, 1:] != co[:, k, :-1]).all() and (groups == 1 or (co[1:, k] != co[:-1, k]).all()), k
+        for k in range(3):
+            assert (cf[:, k, 1:] != cf[:, k, :-1]).all() and (groups == 1 or (cf[1:, k] != cf[:-1, k]).all()), k
+        if kind == "reduce":
+            xs = x.reshape(groups, rpg, C)
+            assert R.sum_is_exact(xs) and R.sum_is_exact(xs * xs)
+            dz, dzx = R.bwd_terms(x, dy, co, act, slope, groups)
+            assert R.sum_is_exact(dz) and R.sum_is_exact(dzx)
+            assert R.same_in_both(lambda ft: R.bwd_terms(x, dy, co, act, slope, groups, ft))
+            assert R.same_in_both(lambda ft: R.col_stats(x, groups, ft) + R.bwd_sums(x, dy, co, act, slope, groups, ft))
+        elif kind == "forward":
+            assert R.same_in_both(lambda ft: R.forward(x, co[:, 2], co[:, 3], act, slope, R.F32, groups, ft))
+            assert R.same_in_both(lambda ft: R.forward(x, None, None, R.ACT_LRELU, 0.25, R.F32, groups, ft))
+            y = R.forward(x, co[:, 2], co[:, 3], act, slope, R.F32, groups)
+            assert R.fits_bf16(y) and np.abs(y).max() <= 448, "bf16 stores it exactly; inside e4m3's range"
+            if rpg >= 16 and ("bf16" in modes or "bf16_wide" in modes):   # the twin DOES round: 5-bit values occur
+                assert R.significant_bits(y) > 4
+        else:
+            assert R.same_in_both(lambda ft: R.apply(x, dy, co, cf, act, slope, R.F32, groups, ft))
+            assert R.fits_bf16(R.apply(x, dy, co, cf, act, slope, R.F32, groups))
+
+
+def _part_rows(plan, rpg, g, p):
+    lo = g * rpg + p * plan["rows_per_block"]
+    return lo, min((g + 1) * rpg, lo + plan["rows_per_block"])
+
+
+def _roll_groups(t):
+    return np.roll(t, 1, axis=0)
+
+
+@pytest.mark.parametrize("case", R.STREAM_CASES, ids=[c[0] for c in R.STREAM_CASES])
+def test_stream_cases_have_no_blind_spot(case):
+    """Each perturbation must change the reference output of the case.  The elementwise passes see a dropped row through the
+    NaN fill of their destination (test_gpu_bn.py), so the row perturbations are checked on the reduce, where they are silent.
+    Row-independent perturbations are evaluated on the first rows of the three tensors that exceed a million elements."""
+    name, rpg, groups, C, act, slope, modes, kinds = case
+    ops = importlib.import_module(PKG + ".ops")
+    for kind in kinds:
+        d = _case_data(case, kind)
+        x, dy, co, cf = d["x"], d["dy"], d["coeffs"], d["coef"]
+        if x.size > 1 << 20:
+            assert groups == 1
+            x, dy = x[:300], dy[:300]
+        coeff_perturbations = {"channel c+1": lambda t: np.roll(t, 1, axis=-1), "channel c-1": lambda t: np.roll(t, -1, axis=-1)}
+        if groups > 1:
+            coeff_perturbations["other group"] = _roll_groups
+        if kind == "reduce":
+            base = R.col_stats(x, groups) + R.bwd_sums(x, dy, co, act, slope, groups)
+            plan = ops.bn_launch_plan("reduce", rpg * groups, C, R.F32, groups)
+            edges = {"last row of a row block": _part_rows(plan, rpg, 0, 0)[1] - 1, "last row of a group": rpg - 1}
+            for what, r in edges.items():                                # the row's terms leave the sums of group 0
+                keep = np.arange(rpg) != r
+                got = R.col_stats(x[:rpg][keep], 1) + R.bwd_sums(x[:rpg][keep], dy[:rpg][keep], co[:1], act, slope, 1)
+                for k in range(4):
+                    assert _differs(got[k][0], base[k][0]), (what, k)
+            twice = np.r_[0, np.arange(rpg)]
+            got = R.col_stats(x[:rpg][twice], 1) + R.bwd_sums(x[:rpg][twice], dy[:rpg][twice], co[:1], act, slope, 1)
+            for k in range(4):
+                assert _differs(got[k][0], base[k][0]), ("row 0 counted twice", k)
+            for what, f in coeff_perturbations.items():
+                got = R.bwd_sums(x, dy, f(co), act, slope, groups)
+                assert _differs(got[1], base[3]), what                   # through xhat always; through dz with an activation
+                assert act == R.ACT_NONE or _differs(got[0], base[2]), what
+            if act != R.ACT_NONE:
+                got = R.bwd_sums(x, dy, co, act, slope, groups, zero_positive=True)
+                assert _differs(got[0], base[2]) and _differs(got[1], base[3]), "z >= 0"
+                wrong = co.copy()
+                wrong[:, 3] = co[:, 0]
+                assert _differs(R.bwd_sums(x, dy, wrong, act, slope, groups)[0], base[2]), "mean for shift"
+        elif kind == "forward":
+            base = R.forward(x, co[:, 2], co[:, 3], act, slope, R.BF16, groups)
+            for what, f in coeff_perturbations.items():
+                assert _differs(R.forward(x, f(co[:, 2]), co[:, 3], act, slope, R.BF16, groups), base), what + " scale"
+                assert _differs(R.forward(x, co[:, 2], f(co[:, 3]), act, slope, R.BF16, groups), base), what + " shift"
+            assert _differs(R.forward(x, co[:, 2], co[:, 0], act, slope, R.BF16, groups), base), "mean for shift"
+        else:
+            base = R.apply(x, dy, co, cf, act, slope, R.BF16, groups)
+            for what, f in coeff_perturbations.items():
+                for k in range(4):
+                    wrong = co.copy()
+                    wrong[:, k] = f(co[:, k])
+                    if k >= 2 and act == R.ACT_NONE:
+                        continue                                         # scale and shift only select the derivative
+                    assert _differs(R.apply(x, dy, wrong, cf, act, slope, R.BF16, groups), base), (what, "coeffs", k)
+                for k in range(3):
+                    wrong = cf.copy()
+                    wrong[:, k] = f(cf[:, k])
+                    assert _differs(R.apply(x, dy, co, wrong, act, slope, R.BF16, groups), base), (what, "coef", k)
+            assert _differs(R.apply(x, dy, co, cf[:, [0, 2, 1]], act, slope, R.BF16, groups), base), "b and c swapped"
+            if act != R.ACT_NONE:
+                assert _differs(R.apply(x, dy, co, cf, act, slope, R.BF16, groups, zero_positive=True), base), "z >= 0"
+                wrong = co.copy()
+                wrong[:, 3] = co[:, 0]
+                assert _differs(R.apply(x, dy, wrong, cf, act, slope, R.BF16, groups), base), "mean for shift"
+
+
+# ---- hand-made slabs: exactness and blind spots ----------------------------------------------------------------------------
+def _fin_case(i):
+    nparts, C = R.FIN_CASES[i]
+    o = R.fin_options(i)
+    count = 4 * (9 + i)
+    fw = R.fwd_slab_case(700 + i, C, nparts, o["groups"], count, o["eps"], o["momentum"], gamma=o["affine"], beta=o["affine"],
+                         running=o["running"])
+    bw = R.bwd_slab_case(800 + i, C, nparts, o["groups"], count, gamma=o["affine"], grads=o["grads"])
+    return o, fw, bw
+
+
+def _fwd_fin(fw, ft=f32, slabs=None):
+    s1, s2 = R.slab_sums(fw["slabs"] if slabs is None else slabs)
+    return R.finalize(s1, s2, fw["count"], fw["gamma"], fw["beta"], fw["rmean"], fw["rvar"], fw["momentum"], fw["eps"], ft)
+
+
+def _bwd_fin(bw, accumulate, ft=f32, slabs=None, swap=False):
+    s1, s2 = R.slab_sums(bw["slabs"] if slabs is None else slabs)
+    if swap:
+        s1, s2 = s2, s1
+    return R.bwd_finalize(s1, s2, bw["count"], bw["gamma"], bw["invstd"], bw["dgamma"], bw["dbeta"], accumulate, ft=ft)
+
+
+def test_finalize_options_cover_every_value():
+    opts = [R.fin_options(i) for i in range(len(R.FIN_CASES))]
+    for key, values in dict(affine=(True, False), running=(True, False), accumulate=(True, False), grads=(True, False),
+                            groups=(1, 2, 3), eps=(0.0, 3.0), momentum=(0.5, 1.0)).items():
+        assert {o[key] for o in opts} == set(values), key
+    assert any(o["groups"] > 1 and o["running"] for o in opts) and any(o["groups"] > 1 and o["grads"] for o in opts)
+    n = sorted(set(R.FIN_NPARTS))                                       # FIN_PL = 128 planes, four-deep from 4 * 128 + 1 rows
+    assert n[0] == 1 and any(1 < v < 128 for v in n) and any(128 < v <= 512 for v in n) and any(v > 512 for v in n)
+    assert any(c % 8 for c in R.FIN_C) and any(c < 8 for c in R.FIN_C) and max(R.FIN_C) >= 1024
+
+
+@pytest.mark.parametrize("i", range(len(R.FIN_CASES)), ids=[f"n{n}_c{c}" for n, c in R.FIN_CASES])
+def test_finalize_cases_are_exact_and_have_no_blind_spot(i):
+    o, fw, bw = _fin_case(i)
+    nparts, C = R.FIN_CASES[i]
+    # exact: coefficients and the running mean are dyadic (f32 == f64 evaluation); the running variance is rounded once
+    co, rm, rv = _fwd_fin(fw)
+    co64, rm64, _ = _fwd_fin(fw, f64)
+    assert not _differs(co, co64) and (rm is None or not _differs(rm, rm64))
+    assert fw["momentum"] in (0.5, 1.0)
+    assert R.same_in_both(lambda ft: _bwd_fin(bw, o["accumulate"], ft))
+    for k in range(4):
+        assert (co[:, k, 1:] != co[:, k, :-1]).any() and (o["groups"] == 1 or _differs(co[0, k], co[1, k])), k
+    # blind spots of the slab sums: a part row dropped / counted twice
+    for what, sel in {"last part dropped": slice(0, nparts - 1), "part 0 twice": np.r_[0, np.arange(nparts)]}.items():
+        if nparts == 1 and what.startswith("last"):
+            continue
+        got = _fwd_fin(fw, slabs=fw["slabs"][:, sel])
+        assert _differs(got[0][:, 0], co[:, 0]) and _differs(got[0][:, 1], co[:, 1]), what
+        assert _differs(_bwd_fin(bw, o["accumulate"], slabs=bw["slabs"][:, sel])[2], _bwd_fin(bw, o["accumulate"])[2]), what
+    # a neighbouring channel's slab column
+    for shift in (1, -1):
+        got = _fwd_fin(fw, slabs=np.roll(fw["slabs"], shift, axis=-1))
+        assert all(_differs(got[0][:, k], co[:, k]) for k in range(4)), shift
+    if o["groups"] > 1:
+        got = _fwd_fin(fw, slabs=np.roll(fw["slabs"], 1, axis=0))          # another group's slab
+        assert _differs(got[0], co)
+        if o["running"]:                                                 # running statistics in reverse group order
+            rev = _fwd_fin(fw, slabs=fw["slabs"][::-1])
+            assert _differs(rev[1], rm) and _differs(rev[2], rv), "group order"
+    dg, db, cf = _bwd_fin(bw, o["accumulate"])
+    sw = _bwd_fin(bw, o["accumulate"], swap=True)
+    assert _differs(sw[2][:, 1], cf[:, 1]) and _differs(sw[2][:, 2], cf[:, 2]), "sums swapped"
+    if o["grads"]:
+        assert _differs(sw[0], dg) and _differs(sw[1], db), "sums swapped"
+        other = _bwd_fin(bw, not o["accumulate"])
+        assert _differs(other[0], dg) and _differs(other[1], db), "accumulate ignored"
+        if o["groups"] > 1:                                              # g > 0 adds even without accumulate
+            last = dict(bw, slabs=bw["slabs"][-1:], invstd=bw["invstd"][-1:])
+            alone = _bwd_fin(last, o["accumulate"])
+            assert _differs(alone[0], dg) and _differs(alone[1], db), "groups not accumulated"
+
+
+# ---- the one-launch forms and the chain -------------------------------------------------------------------------------------
+@pytest.mark.parametrize("case", R.FUSED_CASES, ids=[c[0] for c in R.FUSED_CASES])
+def test_fused_cases_are_exact(case):
+    name, rpg, groups, C, nparts, act, slope = case
+    d, fw, bw = R.fused_inputs(case)
+    co, rm, rv = _fwd_fin(fw)
+    assert not _differs(co, _fwd_fin(fw, f64)[0])
+    assert R.same_in_both(lambda ft: R.forward(d["x"], co[:, 2], co[:, 3], act, slope, R.F32, groups, ft))
+    assert R.fits_bf16(R.forward(d["x"], co[:, 2], co[:, 3], act, slope, R.F32, groups))
+    # backward: the coefficients a kernel is handed (stream table), gamma * invstd from them, b and c from the slabs
+    assert not _differs(bw["invstd"], d["coeffs"][:, 1])
+    assert R.same_in_both(lambda ft: _bwd_fin(bw, True, ft))
+    dg, db, cf = _bwd_fin(bw, True)
+    assert not _differs(cf[:, 1:], d["coef"][:, 1:])
+    assert R.same_in_both(lambda ft: R.apply(d["x"], d["dy"], d["coeffs"], cf, act, slope, R.F32, groups, ft))
+    assert R.fits_bf16(R.apply(d["x"], d["dy"], d["coeffs"], cf, act, slope, R.F32, groups))
+
+
+@pytest.mark.parametrize("case", R.CHAIN_CASES, ids=[c[0] for c in R.CHAIN_CASES])
+def test_chain_cases_are_exact(case):
+    """Every f32 operation of the chain is exact (f32 == f64 evaluation, the running variance excepted: one rounding).  dx has
+    more than 8 significant bits -- b and c carry the 1 / count of the sums -- so in bf16 it is the ONE correctly rounded value
+    of an exactly known number: still a unique reference."""
+    name, rpg, groups, C, act, slope = case
+    d = R.chain_inputs(case)
+    a, b = R.chain_ref(d, rpg, groups, C, act, slope, R.F32), R.chain_ref(d, rpg, groups, C, act, slope, R.F32, f64)
+    for k in a:
+        if k != "rvar":
+            for u, v in zip(a[k] if isinstance(a[k], tuple) else (a[k],), b[k] if isinstance(b[k], tuple) else (b[k],)):
+                assert not _differs(u, v), k
+    xs = d["x"].reshape(groups, rpg, C)
+    assert R.fits_bf16(d["x"]) and R.fits_bf16(a["y"]) and R.sum_is_exact(xs) and R.sum_is_exact(xs * xs)
+    assert all(R.sum_is_exact(t) for t in R.bwd_terms(d["x"], d["dy"], a["coeffs"], act, slope, groups))
+    z = a["coeffs"][:, 2][:, None] * xs + a["coeffs"][:, 3][:, None]
+    assert (z == 0).any() and (z > 0).any() and (z < 0).any() and d["momentum"] == 0.5 and d["eps"] == 0.0
+    assert _differs(R.chain_ref(dict(d, dy=d["dy"][::-1]), rpg, groups, C, act, slope, R.BF16)["dx"], a["dx"])
+
+
+# ---- coverage of the launchers' branches, read from the built library -------------------------------------------------------
+def _thread_rows(plan, rpg):
+    """(trips of four rows, rows of the short last trip) of every thread row slot of the first and the last row block."""
+    out = set()
+    rpb, rpp = plan["rows_per_block"], plan["rows_per_pass"]
+    for b in {0, plan["blocks_per_group"] - 1}:
+        nb = min(rpb, rpg - b * rpb)
+        for tr in range(rpp):
+            n = max(0, -(-(nb - tr) // rpp))
+            out.add((n // 4, n % 4))
+    return out
+
+
+def test_case_table_reaches_every_branch_of_the_launchers(vg_switch):
+    ops = importlib.import_module(PKG + ".ops")
+    vg_switch("VG_BN_FUSED_FWD", 1)
+    seen = {k: [] for k in ("reduce", "forward", "apply")}
+    for case, mode, kind in R.stream_params():
+        name, rpg, groups, C = case[:4]
+        dtype, wide_min = R.MODES[mode]
+        vg_switch("VG_BN_WIDE_MIN", 4194304 if wide_min is None else wide_min)
+        p = ops.bn_launch_plan(kind, rpg * groups, C, dtype, groups)
+        assert p["groups"] == groups and p["rows_per_pass"] == 256 // p["threads_per_row"]
+        assert p["blocks_per_group"] == -(-rpg // p["rows_per_block"]) and p["rows_per_block"] % p["rows_per_pass"] == 0
+        last_cols = C // p["vec"] - 256 * (p["col_blocks"] - 1)
+        assert 0 < last_cols <= 256
+        seen[kind].append(dict(p, name=name, mode=mode, rpg=rpg, last_cols=last_cols, idle=256 % p["threads_per_row"] != 0,
+                               clipped=groups > 1 and rpg % p["rows_per_block"] != 0, short=rpg % p["rows_per_block"] != 0,
+                               threads=_thread_rows(p, rpg)))
+    for kind in ("forward", "apply"):
+        s = seen[kind]
+        assert {p["vec"] for p in s} == {4, 8}, kind
+        assert {p["vec"] for p in s if p["mode"] == "bf16"} == {4} and all(p["vec"] == 4 for p in s if p["mode"] == "f32")
+        for vec in (4, 8):                                               # per kernel instantiation
+            v = [p for p in s if p["vec"] == vec]
+            assert any(p["idle"] for p in v) and any(not p["idle"] for p in v), (kind, vec)
+            assert any(p["rows_per_pass"] == 1 for p in v) and any(p["rows_per_pass"] > 1 for p in v), (kind, vec)
+            assert any(p["blocks_per_group"] == 1 for p in v) and any(p["blocks_per_group"] > 1 for p in v), (kind, vec)
+            assert any(p["col_blocks"] >= 2 for p in v), (kind, vec)
+            assert any(p["rpg"] == 1 for p in v) and any(1 < p["rpg"] < p["rows_per_pass"] for p in v), (kind, vec)
+            assert any(p["groups"] == 3 for p in v) and any(p["clipped"] for p in v), (kind, vec)
+        assert any(p["col_blocks"] >= 2 and p["last_cols"] < 256 for p in s), kind      # ragged last column block (C = 1040)
+        # beyond the workgroup cap: full trips of four rows followed by a short trip of 1, 2 and 3 rows
+        tails = {t for p in s for trips, t in p["threads"] if trips >= 1}
+        assert {1, 2, 3} <= tails, (kind, tails)
+        assert any(trips >= 1 and t for p in s if p["vec"] == 8 for trips, t in p["threads"]), kind
+    r = seen["reduce"]
+    assert all(p["vec"] == 4 for p in r)
+    assert any(p["idle"] for p in r) and any(p["rows_per_pass"] == 1 for p in r) and any(p["rows_per_pass"] > 1 for p in r)
+    assert any(p["blocks_per_group"] == 1 for p in r) and any(p["blocks_per_group"] > 1 and p["short"] for p in r)
+    assert any(p["clipped"] and p["blocks_per_group"] > 1 for p in r), "a part clipped by a group"
+    assert any(p["col_blocks"] == 2 and p["last_cols"] < 256 and 256 // p["last_cols"] != p["rows_per_pass"] for p in r)
+    assert any(-(-p["rows_per_block"] // p["rows_per_pass"]) >= 4 for p in r), "the four-deep loop of the reduce"
+    assert {p["groups"] for p in r} == {1, 2, 3}
+    # the one-launch forms: taken by every fused case, refused for each reason next to a shape that is taken
+    blocks = set()
+    for name, rpg, groups, C, nparts, act, slope in R.FUSED_CASES:
+        p = ops.bn_launch_plan("fused", rpg * groups, C, R.BF16, groups, nparts=nparts)
+        assert p["fused"] and p["vec"] == 8 and p["rows_per_pass"] == 128 and p["col_blocks"] == C // 64, name
+        assert p["blocks_per_group"] == -(-rpg // p["rows_per_block"])
+        blocks.add((p["blocks_per_group"] > 1, groups > 1 and rpg % p["rows_per_block"] != 0, rpg < 128))
+    assert {b[0] for b in blocks} == {True, False} and any(b[1] for b in blocks) and any(b[2] for b in blocks)
+    for why, (no, yes) in R.FUSED_REFUSED.items():
+        for (rpg, groups, C, nparts), want in ((no, False), (yes, True)):
+            assert ops.bn_launch_plan("fused", rpg * groups, C, R.BF16, groups, nparts=nparts)["fused"] == want, why
+    assert not ops.bn_launch_plan("fused", 144, 64, R.F32, 1, nparts=3)["fused"]
+    vg_switch("VG_BN_FUSED_FWD", 0)
+    assert not ops.bn_launch_plan("fused", 144, 64, R.BF16, 1, nparts=3)["fused"]
+    # the chain cases reach both forms
+    vg_switch("VG_BN_FUSED_FWD", 1)
+    took = {bool(ops.bn_launch_plan("fused", rpg * groups, C, R.BF16, groups, nparts=ops.bn_launch_plan(
+        "reduce", rpg * groups, C, R.BF16, groups)["blocks_per_group"])["fused"]) for _, rpg, groups, C, _, _ in R.CHAIN_CASES}
+    assert took == {True, False}
+    # an unaligned tensor keeps 8-byte vectors
+    vg_switch("VG_BN_WIDE_MIN", 0)
+    assert ops.bn_launch_plan("forward", 64, 64, R.BF16, aligned16=False)["vec"] == 4
+    assert ops.bn_launch_plan("forward", 64, 64, R.BF16)["vec"] == 8

@@ -174,6 +174,19 @@ def test_c_abi_rejects_bad_arguments_on_host():
     plan = L.GGPlan()                               # the launcher's plan as a host-only query: validated like a launch
     assert lib.vg_gather_gemm_plan(ctypes.byref(d), 0, ctypes.byref(plan)) == -1
     assert lib.vg_gather_gemm_plan(ctypes.byref(d), 7, ctypes.byref(plan)) == -3
+    # the BatchNorm launchers' plan, validated like their launches: no record, no rows, an unknown kind, rows that do not
+    # divide into the groups (-1); C % 4 (-2); a dtype the passes do not have (-3); a refused one-launch form is an answer (0)
+    bn = L.BNPlan()
+    assert lib.vg_bn_launch_plan(1, 64, 64, 1, 1, 1, 0, None) == -1
+    assert lib.vg_bn_launch_plan(1, 0, 64, 1, 1, 1, 0, ctypes.byref(bn)) == -1
+    assert lib.vg_bn_launch_plan(4, 64, 64, 1, 1, 1, 0, ctypes.byref(bn)) == -1
+    assert lib.vg_bn_launch_plan(-1, 64, 64, 1, 1, 1, 0, ctypes.byref(bn)) == -1
+    assert lib.vg_bn_launch_plan(0, 65, 64, 2, 1, 1, 0, ctypes.byref(bn)) == -1
+    assert lib.vg_bn_launch_plan(0, 64, 64, 0, 1, 1, 0, ctypes.byref(bn)) == -1
+    assert lib.vg_bn_launch_plan(2, 64, 6, 1, 1, 1, 0, ctypes.byref(bn)) == -2
+    assert lib.vg_bn_launch_plan(1, 64, 64, 1, 2, 1, 0, ctypes.byref(bn)) == -3
+    assert lib.vg_bn_launch_plan(3, 64, 96, 1, 1, 1, 4, ctypes.byref(bn)) == 0 and bn.fused == 0 and bn.kind == 3
+    assert lib.vg_bn_launch_plan(0, 64, 64, 2, 0, 1, 0, ctypes.byref(bn)) == 0 and (bn.kind, bn.vec, bn.groups) == (0, 4, 2)
     w = L.WGDesc()
     assert lib.vg_wgrad_ws_bytes(ctypes.byref(w), 0) == -1
     assert lib.vg_adam_step(None, None, None, None, 0, 1e-3, 0.9, 0.999, 1e-8, 1.0, None, None) == -1

@@ -16,7 +16,7 @@ VG_F32, VG_BF16, VG_FP8 = 0, 1, 2
 VG_FP8_WSHIFT = 6
 VG_ACT_NONE, VG_ACT_RELU, VG_ACT_LRELU, VG_ACT_TANH = 0, 1, 2, 3
 VG_MAX_PHASE = 4
-ABI_VERSION = 19
+ABI_VERSION = 20
 
 VG_ENOSUP = -3
 _ERR = {-1: "VG_EINVAL (bad shape/size/flag)", -2: "VG_EALIGN (16-byte contract violated)",
@@ -45,6 +45,13 @@ class GGPlan(Structure):
     _fields_ = [("family", c_int32), ("bm", c_int32), ("bn", c_int32), ("detail", c_int32 * 2), ("dma", c_int32),
                 ("ksplit", c_int32), ("stages_per_split", c_int32), ("nstages", c_int32), ("reduce", c_int32),
                 ("n_major", c_int32), ("nparts", c_int32)]
+
+
+class BNPlan(Structure):
+    """vg_bn_plan."""
+    _fields_ = [("kind", c_int32), ("vec", c_int32), ("threads_per_row", c_int32), ("rows_per_pass", c_int32),
+                ("rows_per_block", c_int32), ("blocks_per_group", c_int32), ("col_blocks", c_int32), ("groups", c_int32),
+                ("fused", c_int32)]
 
 
 class WGDesc(Structure):
@@ -121,6 +128,7 @@ SIGNATURES = {
     "vg_bn_finalize_act_forward_supported": (c_int, [_I, _I, _I, _L, _I]),
     "vg_bn_finalize_act_forward": (c_int, [_P, _P, _P, _I, _I, _I, _L, _P, _P, _P, _P, _F, _F, _P, _I, _F, _I, _P]),
     "vg_bn_backward_finalize_apply": (c_int, [_P, _P, _P, _P, _I, _I, _I, _L, _P, _P, _P, _P, _I, _I, _F, _I, _P]),
+    "vg_bn_launch_plan": (c_int, [_I, _L, _I, _I, _I, _I, _I, POINTER(BNPlan)]),
     "vg_bn_act_backward_apply": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _F, _I, _L, _L, _I, _P]),
     "vg_act_backward": (c_int, [_P, _P, _P, _L, _I, _F, _I, _P]),
     "vg_bias_grad": (c_int, [_P, _L, _I, _I, _P, _I, _P, _I, _I, _P]),

@@ -12,21 +12,26 @@
 
 namespace {
 
-struct RedPlan { int nparts, rows_per_part, ncolblk; };
-
-inline RedPlan plan_reduce(int64_t rows, int C) {
+// The launch geometry of every launcher below is a vg_bn_plan (include/vaegan_hip.h): vg_bn_launch_plan returns the record
+// a launcher launches from.  Column reduce: a part (rows_per_block rows of one group) per workgroup and column block.
+inline vg_bn_plan plan_reduce(int64_t rows_per_group, int C, int groups) {
     const int cols = C / 4;
     const int ncol = cols < 256 ? cols : 256;
     const int rpp = 256 / ncol;
-    const int64_t passes = (rows + rpp - 1) / rpp;
+    const int64_t passes = (rows_per_group + rpp - 1) / rpp;
     int64_t np = passes / 8;
     if (np < 1) np = 1;
     if (np > 1024) np = 1024;
     int64_t rows_per_part = ((passes + np - 1) / np) * rpp;
-    RedPlan p;
-    p.nparts = (int)((rows + rows_per_part - 1) / rows_per_part);
-    p.rows_per_part = (int)rows_per_part;
-    p.ncolblk = (cols + 255) / 256;
+    vg_bn_plan p = {};
+    p.kind = VG_BN_PLAN_REDUCE;
+    p.vec = 4;
+    p.threads_per_row = ncol;
+    p.rows_per_pass = rpp;
+    p.rows_per_block = (int)rows_per_part;
+    p.blocks_per_group = (int)((rows_per_group + rows_per_part - 1) / rows_per_part);
+    p.col_blocks = (cols + 255) / 256;
+    p.groups = groups;
     return p;
 }
 
@@ -323,15 +328,22 @@ inline bool stream_wide(int dtype, int64_t rows, int C) {
     return dtype == VG_BF16 && C % 8 == 0 && rows * C * 2 >= (int64_t)vg_sw().bn_wide_min;
 }
 
-struct StreamPlan { int rows_per_block, blocks_per_group, ncolblk; };
-
-inline StreamPlan plan_stream(int64_t rows_per_group, int cols, int groups, int max_wgs) {
+// kind: VG_BN_PLAN_FORWARD or VG_BN_PLAN_APPLY (their grid caps differ); aligned16: the tensors allow 16-byte vectors
+inline vg_bn_plan plan_stream(int kind, int dtype, int64_t rows, int C, int groups, bool aligned16) {
+    const int64_t rows_per_group = rows / groups;
+    const int max_wgs = kind == VG_BN_PLAN_FORWARD ? EW_FWD_WGS : EW_BWD_WGS;
+    vg_bn_plan p = {};
+    p.kind = kind;
+    p.vec = stream_wide(dtype, rows, C) && aligned16 ? 8 : 4;
+    const int cols = C / p.vec;
     const int ncol = cols < 256 ? cols : 256;
     const int rpp = 256 / ncol;
-    StreamPlan p;
-    p.ncolblk = (cols + 255) / 256;
+    p.threads_per_row = ncol;
+    p.rows_per_pass = rpp;
+    p.col_blocks = (cols + 255) / 256;
+    p.groups = groups;
     const int64_t passes = (rows_per_group + rpp - 1) / rpp;
-    int64_t cap = max_wgs / ((int64_t)groups * p.ncolblk);
+    int64_t cap = max_wgs / ((int64_t)groups * p.col_blocks);
     if (cap < 1) cap = 1;
     const int64_t blocks = passes < cap ? passes : cap;            // small tensors: one pass per workgroup
     const int64_t rpb = (passes + blocks - 1) / blocks * rpp;
@@ -660,6 +672,29 @@ inline bool bn_fin_fwd_ok(int nparts_per_group, int groups, int C, int64_t rows,
            nparts_per_group > 0 && nparts_per_group <= FF_MAXPARTS && rows * C * 2 <= FF_MAXBYTES;
 }
 
+// the one-launch forms (forward and backward twin share it): fused = 0 and no geometry where the shape is refused
+inline vg_bn_plan plan_fused(int nparts_per_group, int groups, int C, int64_t rows, int dtype) {
+    vg_bn_plan p = {};
+    p.kind = VG_BN_PLAN_FUSED;
+    if (!bn_fin_fwd_ok(nparts_per_group, groups, C, rows, dtype)) return p;
+    const int64_t rpg = rows / groups;
+    // ~512 workgroups in all; whole passes of 128 rows per workgroup
+    const int slices = C / FF_CH;
+    int64_t want = 512 / (slices * groups);
+    if (want < 1) want = 1;
+    int64_t rpb = (rpg + want - 1) / want;
+    rpb = (rpb + 127) / 128 * 128;
+    p.fused = 1;
+    p.vec = 8;
+    p.threads_per_row = 8;
+    p.rows_per_pass = FF_TH / 8;
+    p.rows_per_block = (int)rpb;
+    p.blocks_per_group = (int)((rpg + rpb - 1) / rpb);
+    p.col_blocks = slices;
+    p.groups = groups;
+    return p;
+}
+
 // ---- backward twin: bn_bwd_finalize_grouped + bn_act_bwd_apply in one launch (same eligibility, same structure) ----
 // Every workgroup sums the column-reduce partials (sum dz | sum dz * xhat) of its group for its 64 channels, forms the
 // three coefficients of bn_bwd_finalize_grouped_kernel and applies dx = a * dz - b * xhat - c; the workgroups of row
@@ -803,16 +838,16 @@ int launch_reduce(const void* x, const void* dy, const float* scale, const float
                   int* nparts_out, int dtype, hipStream_t s, int groups = 1, int64_t gstride = 0) {
     VG_CHECK_ARG(groups >= 1 && rows % groups == 0, VG_EINVAL);
     const int64_t rpg = rows / groups;
-    RedPlan p = plan_reduce(rpg, C);
-    if (nparts_out) *nparts_out = p.nparts;
-    VG_CHECK_ARG(partial != nullptr && capacity >= p.nparts * groups, VG_EINVAL);
-    dim3 grid(p.nparts * groups, p.ncolblk);
+    const vg_bn_plan p = plan_reduce(rpg, C, groups);
+    if (nparts_out) *nparts_out = p.blocks_per_group;
+    VG_CHECK_ARG(partial != nullptr && capacity >= p.blocks_per_group * groups, VG_EINVAL);
+    dim3 grid(p.blocks_per_group * p.groups, p.col_blocks);
     if (dtype == VG_F32)
         vg_launch_timed(4, (col_reduce_kernel<VG_F32, MODE>), grid, dim3(256), 0, s, x, dy, scale, shift, mean, invstd,
-                           rows, C, act, slope, partial, p.rows_per_part, rpg, p.nparts, gstride);
+                           rows, C, act, slope, partial, p.rows_per_block, rpg, p.blocks_per_group, gstride);
     else
         vg_launch_timed(4, (col_reduce_kernel<VG_BF16, MODE>), grid, dim3(256), 0, s, x, dy, scale, shift, mean, invstd,
-                           rows, C, act, slope, partial, p.rows_per_part, rpg, p.nparts, gstride);
+                           rows, C, act, slope, partial, p.rows_per_block, rpg, p.blocks_per_group, gstride);
     return VG_LAUNCH_RC();
 }
 
@@ -889,6 +924,19 @@ extern "C" int vg_bn_eval_coeffs(const float* gamma, const float* beta, const fl
     return VG_LAUNCH_RC();
 }
 
+extern "C" int vg_bn_launch_plan(int kind, int64_t rows, int C, int groups, int dtype, int aligned16, int nparts_per_group,
+                                 vg_bn_plan* out) {
+    VG_CHECK_ARG(out != nullptr && rows > 0 && C > 0, VG_EINVAL);
+    VG_CHECK_ARG(kind >= VG_BN_PLAN_REDUCE && kind <= VG_BN_PLAN_FUSED, VG_EINVAL);
+    VG_CHECK_ARG(dtype == VG_F32 || dtype == VG_BF16, VG_ENOSUP);
+    VG_CHECK_ARG(C % 4 == 0, VG_EALIGN);
+    VG_CHECK_ARG(groups >= 1 && rows % groups == 0, VG_EINVAL);
+    if (kind == VG_BN_PLAN_REDUCE) *out = plan_reduce(rows / groups, C, groups);
+    else if (kind == VG_BN_PLAN_FUSED) *out = plan_fused(nparts_per_group, groups, C, rows, dtype);
+    else *out = plan_stream(kind, dtype, rows, C, groups, aligned16 != 0);
+    return 0;
+}
+
 extern "C" int vg_bn_finalize_act_forward_supported(int nparts_per_group, int groups, int C, int64_t rows, int dtype) {
     return bn_fin_fwd_ok(nparts_per_group, groups, C, rows, dtype) ? 1 : 0;
 }
@@ -900,18 +948,12 @@ extern "C" int vg_bn_finalize_act_forward(const void* x, void* y, const float* s
     VG_CHECK_ARG(x && y && stats && coeffs && rows > 0 && C > 0, VG_EINVAL);
     VG_CHECK_ARG((running_mean == nullptr) == (running_var == nullptr), VG_EINVAL);
     VG_CHECK_ARG(vg_aligned16(x) && vg_aligned16(y), VG_EALIGN);
-    if (!bn_fin_fwd_ok(nparts_per_group, groups, C, rows, dtype)) return VG_ENOSUP;
+    const vg_bn_plan p = plan_fused(nparts_per_group, groups, C, rows, dtype);
+    if (!p.fused) return VG_ENOSUP;
     const int64_t rpg = rows / groups;
-    // ~512 workgroups in all; whole passes of 128 rows per workgroup
-    const int slices = C / FF_CH;
-    int64_t want = 512 / (slices * groups);
-    if (want < 1) want = 1;
-    int64_t rpb = (rpg + want - 1) / want;
-    rpb = (rpb + 127) / 128 * 128;
-    const int rb = (int)((rpg + rpb - 1) / rpb);
-    vg_launch_timed(4, bn_fin_act_fwd_kernel, dim3(rb, slices, groups), dim3(FF_TH), 0, vg_stream(stream),
+    vg_launch_timed(4, bn_fin_act_fwd_kernel, dim3(p.blocks_per_group, p.col_blocks, p.groups), dim3(FF_TH), 0, vg_stream(stream),
                        reinterpret_cast<const uint16_t*>(x), reinterpret_cast<uint16_t*>(y), stats, nparts_per_group, groups,
-                       C, (double)rpg, gamma, beta, running_mean, running_var, momentum, eps, coeffs, rpg, (int)rpb, act,
+                       C, (double)rpg, gamma, beta, running_mean, running_var, momentum, eps, coeffs, rpg, p.rows_per_block, act,
                        slope);
     return VG_LAUNCH_RC();
 }
@@ -922,18 +964,13 @@ extern "C" int vg_bn_backward_finalize_apply(const void* x, const void* dy, void
                                              float slope, int dtype, void* stream) {
     VG_CHECK_ARG(x && dy && dx && partial && coeffs && rows > 0 && C > 0, VG_EINVAL);
     VG_CHECK_ARG(vg_aligned16(x) && vg_aligned16(dy) && vg_aligned16(dx), VG_EALIGN);
-    if (!bn_fin_fwd_ok(nparts_per_group, groups, C, rows, dtype)) return VG_ENOSUP;
+    const vg_bn_plan p = plan_fused(nparts_per_group, groups, C, rows, dtype);
+    if (!p.fused) return VG_ENOSUP;
     const int64_t rpg = rows / groups;
-    const int slices = C / FF_CH;
-    int64_t want = 512 / (slices * groups);
-    if (want < 1) want = 1;
-    int64_t rpb = (rpg + want - 1) / want;
-    rpb = (rpb + 127) / 128 * 128;
-    const int rb = (int)((rpg + rpb - 1) / rpb);
-    vg_launch_timed(4, bn_bwd_fin_apply_kernel, dim3(rb, slices, groups), dim3(FF_TH), 0, vg_stream(stream),
+    vg_launch_timed(4, bn_bwd_fin_apply_kernel, dim3(p.blocks_per_group, p.col_blocks, p.groups), dim3(FF_TH), 0, vg_stream(stream),
                        reinterpret_cast<const uint16_t*>(x), reinterpret_cast<const uint16_t*>(dy),
                        reinterpret_cast<uint16_t*>(dx), partial, nparts_per_group, groups, C, (double)rpg, gamma, coeffs,
-                       dgamma, dbeta, accumulate, rpg, (int)rpb, act, slope);
+                       dgamma, dbeta, accumulate, rpg, p.rows_per_block, act, slope);
     return VG_LAUNCH_RC();
 }
 
@@ -956,10 +993,10 @@ extern "C" int vg_bn_act_forward_fp8(const void* x, void* y, void* y8, const flo
     const hipStream_t s = vg_stream(stream);
     uint8_t* twin = reinterpret_cast<uint8_t*>(y8);
     // 16-byte vectors of bf16 need 8 | C and 16-byte aligned tensors (8-byte aligned twin); otherwise 8-byte vectors
-    const bool wide = stream_wide(dtype, rows, C) && vg_aligned16(x) &&
-                      vg_aligned16(y) && (reinterpret_cast<uintptr_t>(y8) & 7u) == 0;
-    const StreamPlan p = plan_stream(rpg, C / (wide ? 8 : 4), groups, EW_FWD_WGS);
-    const dim3 grid(p.blocks_per_group, p.ncolblk, groups);
+    const vg_bn_plan p = plan_stream(VG_BN_PLAN_FORWARD, dtype, rows, C, groups,
+                                     vg_aligned16(x) && vg_aligned16(y) && (reinterpret_cast<uintptr_t>(y8) & 7u) == 0);
+    const bool wide = p.vec == 8;
+    const dim3 grid(p.blocks_per_group, p.col_blocks, p.groups);
     if (dtype == VG_F32)
         vg_launch_timed(4, (bn_act_fwd_kernel<VG_F32, 4>), grid, dim3(256), 0, s, x, y, scale, shift, rows, C, act, slope,
                            rpg, p.rows_per_block, gstride, twin);
@@ -1010,10 +1047,10 @@ extern "C" int vg_bn_act_backward_apply(const void* x, const void* dy, void* dx,
     VG_CHECK_ARG(groups >= 1 && rows % groups == 0, VG_EINVAL);
     const int64_t rpg = rows / groups;
     const hipStream_t s = vg_stream(stream);
-    const bool wide = stream_wide(dtype, rows, C) && vg_aligned16(x) &&
-                      vg_aligned16(dy) && vg_aligned16(dx);
-    const StreamPlan p = plan_stream(rpg, C / (wide ? 8 : 4), groups, EW_BWD_WGS);
-    const dim3 grid(p.blocks_per_group, p.ncolblk, groups);
+    const vg_bn_plan p = plan_stream(VG_BN_PLAN_APPLY, dtype, rows, C, groups,
+                                     vg_aligned16(x) && vg_aligned16(dy) && vg_aligned16(dx));
+    const bool wide = p.vec == 8;
+    const dim3 grid(p.blocks_per_group, p.col_blocks, p.groups);
     if (dtype == VG_F32)
         vg_launch_timed(4, (bn_act_bwd_apply_kernel<VG_F32, 4>), grid, dim3(256), 0, s, x, dy, dx, scale, shift, mean, invstd,
                            coef, rows, C, act, slope, rpg, p.rows_per_block, gstride, cstride);

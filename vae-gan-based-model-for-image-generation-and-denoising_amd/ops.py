@@ -646,6 +646,22 @@ def bn_act_backward(x, dy, coeffs, rows, C, count, gamma, act, slope, dgamma, db
     return dx
 
 
+BN_PLAN_KIND = {"reduce": 0, "forward": 1, "apply": 2, "fused": 3}
+
+
+def bn_launch_plan(kind: str, rows: int, C: int, dtype: int, groups: int = 1, aligned16: bool = True, nparts: int = 0) -> dict:
+    """What the BatchNorm launcher of this kind ("reduce", "forward", "apply", "fused") launches for a [rows][C] tensor of
+    `groups` equal row blocks under the current switches (vg_bn_launch_plan: the record the launchers themselves launch
+    from).  Host only, no GPU and no tensors.  nparts: slab rows PER GROUP, read by "fused" only.
+    -> dict(vec, threads_per_row, rows_per_pass, rows_per_block, blocks_per_group, col_blocks, groups, fused)."""
+    p = L.BNPlan()
+    L.check(L.load().vg_bn_launch_plan(BN_PLAN_KIND[kind], rows, C, groups, dtype, 1 if aligned16 else 0, nparts, byref(p)),
+            "vg_bn_launch_plan")
+    return dict(vec=p.vec, threads_per_row=p.threads_per_row, rows_per_pass=p.rows_per_pass,
+                rows_per_block=p.rows_per_block, blocks_per_group=p.blocks_per_group, col_blocks=p.col_blocks,
+                groups=p.groups, fused=bool(p.fused))
+
+
 def act_backward(x, dy, act, slope, dtype):
     dx = torch.empty_like(x)
     _bn_bytes(3, x.numel(), dtype)
