@@ -48,7 +48,7 @@ extern "C" {
 #define VG_ACT_LRELU   2   /* nn.LeakyReLU(slope)    main_vae.py:25, gan_code.py:62-82 */
 #define VG_ACT_TANH    3   /* nn.Tanh()              gan_code.py:50 (vg_tnconv epilogue only) */
 
-#define VG_ABI_VERSION 20  /* 2: vg_pack_desc.tile_start, SyncBN / WGAN / data-path entry points; 3: in-kernel noise (vg_*_rng);
+#define VG_ABI_VERSION 21  /* 2: vg_pack_desc.tile_start, SyncBN / WGAN / data-path entry points; 3: in-kernel noise (vg_*_rng);
                              4: vg_bn_finalize_act_forward, vg_bn_backward_finalize_apply;
                              7: vg_bce_pair_forward_backward;
                              8: vg_head_backward; round-3 prune -- the opt-in experiments of ABI 5 / 6 that measured slower (input prologue of
@@ -64,7 +64,10 @@ extern "C" {
                              17: SSIM reconstruction loss: vg_ssim_loss_forward_backward (+ _ws_floats);
                              18: region-weighted MSE for degraded pairs: vg_region_mse_forward_backward (+ _ws_doubles);
                              19: vg_gather_gemm_plan / vg_gg_plan: the launcher's kernel choice as a host-only query;
-                             20: vg_bn_launch_plan / vg_bn_plan: the BatchNorm launchers' geometry as a host-only query */
+                             20: vg_bn_launch_plan / vg_bn_plan: the BatchNorm launchers' geometry as a host-only query;
+                             21: vg_gg_plan.timing_family / .ws_bytes: callers size their buffers from the plan record; the four
+                                 side queries of vg_gather_gemm (slab count, timer family, tile rows, workspace bytes) and the
+                                 "supported" query of vg_bn_finalize_act_forward (vg_bn_launch_plan(VG_BN_PLAN_FUSED).fused) are gone */
 int vg_abi_version(void);
 /* The library reads its optional kernel-selection switches (VG_* environment variables, DESIGN.md "Runtime switches")
  * ONCE, when it is loaded; nothing on a launch path calls getenv.  A process that changes one of them afterwards
@@ -125,22 +128,16 @@ typedef struct vg_gg_desc {
     float   mask_slope;
 } vg_gg_desc;
 
-/* Number of stats slabs vg_gather_gemm will write for this descriptor (host-only query). */
-int vg_gather_gemm_nparts(const vg_gg_desc* d, int dtype);
-/* Kernel family a launch of this descriptor belongs to (for the roofline accounting of vg_timing_*):
- * 0 = gather-GEMM (MFMA-bound), 2 = edge layer (3-channel image side, HBM-bound: conv_narrowk.hpp). */
-int vg_gather_gemm_family(const vg_gg_desc* d, int dtype);
-/* Rows (M) covered by one statistics slab = the M edge of the tile the launcher picks (host-only query). */
-int vg_gather_gemm_tile_m(const vg_gg_desc* d, int dtype);
-/* Bytes of split-K workspace this launch can use (0: the launcher will not split K).  Skinny problems -- few
- * output tiles but a long K, e.g. the data gradient of the 1x1-input ConvTranspose2d (M=B, K=16*1024) -- are
- * split along K over gridDim.z; the f32 partial tiles are summed in fixed order by a second kernel. */
-int64_t vg_gather_gemm_ws_bytes(const vg_gg_desc* d, int dtype);
+/* Skinny problems -- few output tiles but a long K, e.g. the data gradient of the 1x1-input ConvTranspose2d (M=B,
+ * K=16*1024) -- are split along K over gridDim.z where d->ws holds vg_gg_plan.ws_bytes; the f32 partial tiles are summed
+ * in fixed order by a second kernel.  d->stats needs room for vg_gg_plan.nparts slabs (stats_capacity). */
 int vg_gather_gemm(const vg_gg_desc* d, int dtype, void* stream);
 
 /* What vg_gather_gemm launches for a descriptor under the current switches (host-only query; needs no GPU).  The launcher
  * builds this same record and launches from it, so the query cannot drift from the launch.  Pointers of the descriptor are
- * only tested against NULL / for alignment (bias, stats, ws + ws_bytes, zeros and mask_x all take part in the choice). */
+ * only tested against NULL / for alignment (bias, stats, ws + ws_bytes, zeros and mask_x all take part in the choice), so a
+ * caller asks BEFORE it allocates: with any non-NULL placeholder for `stats`, and one for `ws` with ws_bytes "enough" (e.g.
+ * 1 << 62), the record is exactly the plan of the launch that then passes nparts slabs and a workspace of ws_bytes. */
 #define VG_GG_GENERIC  0   /* gg_kernel  (conv_gemm.hip): bm x bn tile, one phase per workgroup                              */
 #define VG_GG_NARROWK  1   /* ggn_kernel (conv_narrowk.hpp): 3-channel input; detail = { NT = N / 16, KC = Kp / 32 }         */
 #define VG_GG_PHASE4   2   /* ggq_kernel (conv_phase4.hpp): four phases per workgroup; detail = { NR: patch DMA rounds, 0 }  */
@@ -160,6 +157,11 @@ typedef struct vg_gg_plan {
     int32_t reduce;            /* VG_GG_REDUCE_*: the second launch of a split                                          */
     int32_t n_major;           /* 1: workgroups are dealt XCD-major over the n tiles                                   */
     int32_t nparts;            /* statistics slabs the launch writes (0 without d->stats)                              */
+    int32_t timing_family;     /* vg_timing_* family of the launch: 0 gather-GEMM (MFMA-bound), 2 edge layer (family
+                                  VG_GG_NARROWK: 3-channel image side, HBM-bound), 3 fp8 operands                      */
+    int64_t ws_bytes;          /* split-K workspace the launch can use: what the split PLANNED for this descriptor needs,
+                                  whether or not d->ws was passed (0: K is never split).  ksplit is that split where
+                                  d->ws_bytes >= ws_bytes, 1 with a smaller (or no) workspace                          */
 } vg_gg_plan;
 int vg_gather_gemm_plan(const vg_gg_desc* d, int dtype, vg_gg_plan* out);
 
@@ -234,15 +236,14 @@ int vg_bn_finalize_grouped(const float* stats, int nparts_per_group, int groups,
  * C % 64 == 0): every workgroup of the elementwise pass re-derives the coefficients of its 64
  * channels from the slab (same double-precision sums, another order: coefficients may differ from vg_bn_finalize_grouped
  * in the last bit).  Writes coeffs [groups][4][C] and the running statistics like vg_bn_finalize_grouped.
- * vg_bn_finalize_act_forward_supported() says whether a shape qualifies (VG_BN_FUSED_FWD=0 turns the path off); the
+ * vg_bn_launch_plan(VG_BN_PLAN_FUSED).fused says whether a shape qualifies (VG_BN_FUSED_FWD=0 turns the path off); the
  * launch returns VG_ENOSUP otherwise.  rows = all groups' rows; x, y: [rows][C] bf16. */
-int vg_bn_finalize_act_forward_supported(int nparts_per_group, int groups, int C, int64_t rows, int dtype);
 int vg_bn_finalize_act_forward(const void* x, void* y, const float* stats, int nparts_per_group, int groups, int C,
                                int64_t rows, const float* gamma, const float* beta, float* running_mean,
                                float* running_var, float momentum, float eps, float* coeffs, int act, float slope,
                                int dtype, void* stream);
 /* Backward twin: vg_bn_backward_finalize_grouped + vg_bn_act_backward_apply in one launch, same eligibility
- * (vg_bn_finalize_act_forward_supported with the column-reduce partial count); VG_ENOSUP otherwise. */
+ * (the same plan with the column-reduce partial count as nparts_per_group); VG_ENOSUP otherwise. */
 int vg_bn_backward_finalize_apply(const void* x, const void* dy, void* dx, const float* partial, int nparts_per_group,
                                   int groups, int C, int64_t rows, const float* gamma, const float* coeffs,
                                   float* dgamma, float* dbeta, int accumulate, int act, float slope, int dtype,

@@ -389,3 +389,56 @@ NMAJOR_TILES8 = {c.id for c in SWITCH_CASES[:2 * len(_NM8)]}
 ALL_CASES = CASES + SWITCH_CASES
 ALL_IDS = [c.id for c in ALL_CASES]
 assert len(set(ALL_IDS)) == len(ALL_IDS), "duplicate case ids"
+
+
+# ---- the launches of the three networks ----------------------------------------------------------------------------------
+# (S, B, dtype name of nets.py) of the four benchmarked shapes; S = 256 in both operand dtypes
+NETWORK_SHAPES = ((64, 128, "bf16"), (64, 128, "fp32"), (128, 64, "bf16"), (256, 32, "bf16"), (256, 32, "fp8"))
+
+
+def build_networks(S, dtype):
+    """The Encoder, Generator and Discriminator of the benchmark on the CPU: their engines answer geometry questions host only."""
+    nets = importlib.import_module(PKG + ".nets")
+    return (("E", nets.Encoder([3, S, S], 100, dtype=dtype)), ("G", nets.Generator(nz=100, img_size=S, dtype=dtype)),
+            ("D", nets.Discriminator(img_size=S, dtype=dtype)))
+
+
+def network_launches(S, B, dtype):
+    """Every vg_gather_gemm launch a training iteration of the three networks can issue at this shape, as engine.py's forward /
+    backward issue them (fused activation of a BatchNorm-less stage, statistics of a BatchNorm stage, the mask of the stage
+    below on a data gradient; the stages on the edge-layer kernels launch no gather-GEMM) -- the Discriminator also at 2B,
+    the grouped pass.  -> [(key, GGSpec, kernel dtype, dict(bias, want_stats, act, mask))], host only."""
+    out = []
+    for name, m in build_networks(S, dtype):
+        eng = m._engine
+        for nb in ((B, 2 * B) if name == "D" else (B,)):
+            for i, st in enumerate(eng.stages):
+                if st.kind == "head":
+                    continue
+                if eng.tn(i, nb, "fprop") is None:
+                    g, pk = eng.spec(i, nb, "fprop")
+                    fuse_act = st.bn is None and st.act != 0
+                    epi = dict(bias=st.kind == "linear2" or st.has_bias, want_stats=st.bn is not None and not pk.tap_in_n,
+                               act=(st.act, st.slope) if fuse_act else None, mask=None)
+                    out.append((f"{name}.{i}.fprop.B{nb}", g, G.FP8 if eng.fp8_ok(i) else eng.dtype, epi))
+                if eng.tn(i, nb, "dgrad") is None:
+                    g, _ = eng.spec(i, nb, "dgrad")
+                    mask = None
+                    if i > 0:
+                        pst = eng.stages[i - 1]
+                        if pst.bn is None and pst.act != 0 and g.N == pst.cout and g.OC == G.padc(pst.cout, eng.dtype):
+                            mask = (pst.act, pst.slope)
+                    out.append((f"{name}.{i}.dgrad.B{nb}", g, eng.dtype, dict(bias=False, want_stats=False, act=None, mask=mask)))
+    return out
+
+
+def group_stages(S, B, dtype, groups=2):
+    """The BatchNorm stages of the Discriminator for a grouped pass of groups * B images (engine.StackEngine.can_group): ->
+    [(stage, GGSpec, kernel dtype, rows per group, single-phase plain convolution)], host only."""
+    eng = dict(build_networks(S, dtype))["D"]._engine
+    out = []
+    for i, st in enumerate(eng.stages):
+        if st.kind != "head" and st.bn is not None:
+            g, pk = eng.spec(i, B * groups, "fprop")
+            out.append((i, g, G.FP8 if eng.fp8_ok(i) else eng.dtype, B * st.hout * st.hout, g.nphase == 1 and not pk.tap_in_n))
+    return out

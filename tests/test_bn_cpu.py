@@ -12,6 +12,8 @@
   * the coverage of the launchers' branches by the table, read from the built library (vg_bn_launch_plan needs no GPU).
 """
 import importlib
+import json
+import os
 
 import numpy as np
 import pytest
@@ -431,3 +433,19 @@ def test_case_table_reaches_every_branch_of_the_launchers(vg_switch):
     vg_switch("VG_BN_WIDE_MIN", 0)
     assert ops.bn_launch_plan("forward", 64, 64, R.BF16, aligned16=False)["vec"] == 4
     assert ops.bn_launch_plan("forward", 64, 64, R.BF16)["vec"] == 8
+    # ops.bn_finalize_act_forward and the fused branch of ops.bn_act_backward decide from this plan's `fused`: over the
+    # table above it is what the library's own 'supported' query answered at the last commit that exported one
+    # (tests/golden/gg_plan_parent.json, tools/gen_golden_gg_plan.py)
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "gg_plan_parent.json")) as f:
+        recorded = json.load(f)["bn_fused"]
+    table = [(nparts, groups, C, rpg * groups, R.BF16, 1) for _, rpg, groups, C, nparts, _, _ in R.FUSED_CASES]
+    table += [(nparts, groups, C, rpg * groups, R.BF16, 1) for pair in R.FUSED_REFUSED.values() for rpg, groups, C, nparts in pair]
+    table += [(3, 1, 64, 144, R.F32, 1), (3, 1, 64, 144, R.BF16, 0)]
+    table += [(ops.bn_launch_plan("reduce", rpg * groups, C, R.BF16, groups)["blocks_per_group"], groups, C, rpg * groups, R.BF16, 1)
+              for _, rpg, groups, C, _, _ in R.CHAIN_CASES]
+    assert [(r["nparts"], r["groups"], r["C"], r["rows"], r["dtype"], r["fused_fwd"]) for r in recorded] == table
+    assert {r["supported"] for r in recorded} == {True, False}
+    for r in recorded:
+        vg_switch("VG_BN_FUSED_FWD", r["fused_fwd"])
+        got = ops.bn_launch_plan("fused", r["rows"], r["C"], r["dtype"], r["groups"], nparts=r["nparts"])["fused"]
+        assert got == r["supported"], r

@@ -4,12 +4,16 @@
     tests/_emulate.py, against torch's own convolutions in f64 on the table's integer operands -- exactly;
   * the descriptor-level statistics slabs and written mask against the vectorised ones the GPU test uses;
   * the exactness conditions (every sum below 2^24), the operand generator, the blind spots of every row;
-  * the coverage of the launcher's branches by the table, read from the built library (vg_gather_gemm_plan needs no GPU).
+  * the coverage of the launcher's branches by the table, read from the built library (vg_gather_gemm_plan needs no GPU);
+  * the plan record against the side queries it replaced (tests/golden/gg_plan_parent.json), for the table and for every
+    launch of the three networks at the benchmarked shapes, and the placeholder workspace of ops.gather_gemm.
 
 No tolerance anywhere: integer operands make every comparison an equality."""
 import dataclasses
 import functools
 import importlib
+import json
+import os
 
 import pytest
 import torch
@@ -274,3 +278,89 @@ def test_plan_query_validates_like_the_launcher_and_follows_the_workspace(set_ca
     unsplit = ops.gather_gemm_plan(g, case.dtype, bias=True, workspace=False)           # no workspace: the launcher does not split
     assert (unsplit["ksplit"], unsplit["reduce"], unsplit["stages_per_split"]) == (1, "none", 0) and unsplit["dma"]
     assert not ops.gather_gemm_plan(g, case.dtype, bias=True, zeros=False)["dma"]       # no zero page: register staging
+
+
+# ---- the record against the side queries it replaced ------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _parent():
+    """tools/gen_golden_gg_plan.py: the answers of the four side queries of vg_gather_gemm (slab count, tile rows, workspace
+    bytes, timer family) and of the plan query, recorded at the last commit that had them."""
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "gg_plan_parent.json")) as f:
+        return json.load(f)
+
+
+def _assert_reproduces(ops, rec, g, dtype, epi, where):
+    plan = ops.gather_gemm_plan(g, dtype, **epi)
+    got = (plan["nparts"], plan["bm"], plan["ws_bytes"], plan["timing_family"])
+    assert got == (rec["nparts"], rec["tile_m"], rec["ws_bytes"], rec["family"]), (where, got, rec)
+    old = dict(rec["plan"], detail=tuple(rec["plan"]["detail"]))
+    assert {k: plan[k] for k in old} == old, (where, plan, old)
+    # rows per statistics slab as engine.can_group asks for them (the old tile query on a statistics launch)
+    assert ops.gather_gemm_plan(g, dtype, want_stats=True)["bm"] == rec["tile_m_stats"], where
+
+
+@pytest.fixture
+def default_switches(vg_switch, monkeypatch):
+    for n in SWITCH_NAMES:
+        monkeypatch.delenv(n, raising=False)
+    ops = importlib.import_module(R.PKG + ".ops")
+    ops.reload_switches()
+    return ops
+
+
+def test_plan_record_reproduces_the_side_queries_on_the_case_table(set_case_switches):
+    ops = importlib.import_module(R.PKG + ".ops")
+    recorded = _parent()["cases"]
+    assert sorted(recorded) == sorted(R.ALL_IDS)
+    for c in R.ALL_CASES:
+        set_case_switches(c)
+        _assert_reproduces(ops, recorded[c.id], c.specs()[0], c.dtype,
+                           dict(bias=c.has("b"), want_stats=c.has("s"), act=c.act, mask=c.mask), c.id)
+    assert sum(r["ws_bytes"] > 0 for r in recorded.values()) >= len(R.SPLITK)
+    assert {r["family"] for r in recorded.values()} == {0, 2, 3}
+
+
+@pytest.mark.parametrize("S,B,dtype", R.NETWORK_SHAPES, ids=[f"S{s}_B{b}_{d}" for s, b, d in R.NETWORK_SHAPES])
+def test_plan_record_reproduces_the_side_queries_on_every_network_launch(S, B, dtype, default_switches):
+    """Encoder, Generator and Discriminator (the latter also at 2B), forward and data gradient, the e4m3 operands where the
+    engine takes them: what ops.gather_gemm now reads from ONE plan is what its four queries answered."""
+    ops = default_switches
+    recorded = _parent()["networks"][f"S{S}_B{B}_{dtype}"]
+    launches = R.network_launches(S, B, dtype)
+    assert sorted(recorded) == sorted(k for k, _, _, _ in launches)
+    for key, g, kdt, epi in launches:
+        _assert_reproduces(ops, recorded[key], g, kdt, epi, key)
+    assert any(r["ws_bytes"] > 0 and r["plan"]["ksplit"] > 1 for r in recorded.values())
+    assert (dtype == "fp8") == any(r["family"] == 3 for r in recorded.values())
+
+
+@pytest.mark.parametrize("S,B,dtype", R.NETWORK_SHAPES, ids=[f"S{s}_B{b}_{d}" for s, b, d in R.NETWORK_SHAPES])
+def test_can_group_answers_are_those_of_the_tile_query(S, B, dtype, default_switches):
+    """The grouped Discriminator pass (groups = 2): tile rows per BatchNorm stage and the divisibility answer, re-derived
+    from the plan, and what engine.StackEngine.can_group itself says -- host only, no tensor."""
+    ops = default_switches
+    rec = _parent()["can_group"][f"S{S}_B{B}_{dtype}"]
+    stages = R.group_stages(S, B, dtype)
+    assert [i for i, *_ in stages] == [s["stage"] for s in rec["stages"]]
+    answer = True
+    for (i, g, kdt, rows_per_group, plain), s in zip(stages, rec["stages"]):
+        bm = ops.gather_gemm_plan(g, kdt, want_stats=True)["bm"]
+        assert (bm, rows_per_group, plain) == (s["bm"], s["rows_per_group"], s["plain"]), (i, bm)
+        answer = answer and plain and rows_per_group % bm == 0
+    assert answer == rec["answer"]
+    assert dict(R.build_networks(S, dtype))["D"]._engine.can_group(B, 2) == rec["answer"]
+
+
+def test_plan_with_the_placeholder_workspace_is_the_plan_of_the_sized_launch(set_case_switches):
+    """ops.gather_gemm asks once, before it has a workspace (non-NULL placeholder of 'enough' bytes), and then passes one of
+    the plan's ws_bytes: both descriptors must give the same record, field for field; four bytes less and K is not split."""
+    ops = importlib.import_module(R.PKG + ".ops")
+    for c in R.SPLITK:
+        asked = set_case_switches(c)
+        epi = dict(bias=c.has("b"), want_stats=c.has("s"), act=c.act, mask=c.mask)
+        g, _ = c.specs()
+        assert asked["ksplit"] > 1 and asked["ws_bytes"] > 0 and asked["ws_bytes"] % 4 == 0, c.id
+        assert ops.gather_gemm_plan(g, c.dtype, workspace=asked["ws_bytes"], **epi) == asked, c.id
+        short = ops.gather_gemm_plan(g, c.dtype, workspace=asked["ws_bytes"] - 4, **epi)
+        assert short["ksplit"] == 1 and short["reduce"] == "none" and short["ws_bytes"] == asked["ws_bytes"], c.id
+        assert ops.gather_gemm_plan(g, c.dtype, workspace=False, **epi)["ws_bytes"] == asked["ws_bytes"], c.id

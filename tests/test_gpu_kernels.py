@@ -496,7 +496,7 @@ def test_fp8_mfma_one_k128_tile_deviation_from_exact_sum(ops, case):
     wp = ops.pack_weights(pk, wq.float().reshape(N, K, 1, 1).to(DEV), G.BF16)
     x = torch.zeros(Bimg * h * h, K, dtype=torch.float64)
     x8 = ops.cast_fp8(_dev(x, G.BF16, ops))
-    tm = ops.gather_gemm_tile_m(gg, x8, ops.cast_fp8(wp, 6), G.FP8)
+    tm = ops.gather_gemm_plan(gg, G.FP8, want_stats=True)["bm"]
     rows = torch.arange(0, Bimg * h * h, tm)[:xs.shape[0]]                # the first row of each statistics slab
     x[rows] = xq[:rows.numel()]
     x8 = ops.cast_fp8(_dev(x, G.BF16, ops))

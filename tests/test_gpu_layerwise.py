@@ -290,7 +290,6 @@ def selections(nets, B):
     lines, keys = [], set()
     for name, m in nets:
         eng = m._engine
-        packs = eng._ensure_packed()
         for i, st in enumerate(eng.stages):
             if st.kind == "head":
                 continue
@@ -303,8 +302,7 @@ def selections(nets, B):
                 gg, _ = eng.spec(i, B, what)
                 fp8 = what == "fprop" and eng.fp8_ok(i)
                 kdt = Gm.FP8 if fp8 else eng.dtype
-                xin = torch.empty(gg.B * gg.IH * gg.IW * gg.IC, dtype=ops.TORCH_DT[kdt], device=DEV)
-                bm = ops.gather_gemm_tile_m(gg, xin, packs[i]["fprop8" if fp8 else what], kdt)
+                bm = ops.gather_gemm_plan(gg, kdt, want_stats=True)["bm"]
                 lines.append(f"{name}.{i} {what}: gather-GEMM {'fp8' if fp8 else 'bf16'} tile rows {bm} N={gg.N} "
                              f"phases={gg.nphase}")
                 keys.add(("gg", what, st.kind, bm, gg.N <= 32))

@@ -16,7 +16,7 @@ VG_F32, VG_BF16, VG_FP8 = 0, 1, 2
 VG_FP8_WSHIFT = 6
 VG_ACT_NONE, VG_ACT_RELU, VG_ACT_LRELU, VG_ACT_TANH = 0, 1, 2, 3
 VG_MAX_PHASE = 4
-ABI_VERSION = 20
+ABI_VERSION = 21
 
 VG_ENOSUP = -3
 _ERR = {-1: "VG_EINVAL (bad shape/size/flag)", -2: "VG_EALIGN (16-byte contract violated)",
@@ -44,7 +44,7 @@ class GGPlan(Structure):
     """vg_gg_plan."""
     _fields_ = [("family", c_int32), ("bm", c_int32), ("bn", c_int32), ("detail", c_int32 * 2), ("dma", c_int32),
                 ("ksplit", c_int32), ("stages_per_split", c_int32), ("nstages", c_int32), ("reduce", c_int32),
-                ("n_major", c_int32), ("nparts", c_int32)]
+                ("n_major", c_int32), ("nparts", c_int32), ("timing_family", c_int32), ("ws_bytes", c_int64)]
 
 
 class BNPlan(Structure):
@@ -101,10 +101,6 @@ SIGNATURES = {
     "vg_build_info": (c_char_p, []),
     "vg_timing_enable": (c_int, [_I]),
     "vg_timing_collect": (c_int, [_I, POINTER(c_double), POINTER(c_int)]),
-    "vg_gather_gemm_nparts": (c_int, [POINTER(GGDesc), _I]),
-    "vg_gather_gemm_tile_m": (c_int, [POINTER(GGDesc), _I]),
-    "vg_gather_gemm_family": (c_int, [POINTER(GGDesc), _I]),
-    "vg_gather_gemm_ws_bytes": (c_int64, [POINTER(GGDesc), _I]),
     "vg_gather_gemm": (c_int, [POINTER(GGDesc), _I, _P]),
     "vg_gather_gemm_plan": (c_int, [POINTER(GGDesc), _I, POINTER(GGPlan)]),
     "vg_wgrad_ws_bytes": (c_int64, [POINTER(WGDesc), _I]),
@@ -125,7 +121,6 @@ SIGNATURES = {
     "vg_bn_act_backward_reduce": (c_int, [_P, _P, _P, _P, _P, _P, _L, _I, _I, _F, _P, _I, POINTER(c_int), _I, _L,
                                           _I, _P]),
     "vg_bn_backward_finalize": (c_int, [_P, _I, _I, _L, _P, _P, _P, _P, _I, _P, _P]),
-    "vg_bn_finalize_act_forward_supported": (c_int, [_I, _I, _I, _L, _I]),
     "vg_bn_finalize_act_forward": (c_int, [_P, _P, _P, _I, _I, _I, _L, _P, _P, _P, _P, _F, _F, _P, _I, _F, _I, _P]),
     "vg_bn_backward_finalize_apply": (c_int, [_P, _P, _P, _P, _I, _I, _I, _L, _P, _P, _P, _P, _I, _I, _F, _I, _P]),
     "vg_bn_launch_plan": (c_int, [_I, _L, _I, _I, _I, _I, _I, POINTER(BNPlan)]),

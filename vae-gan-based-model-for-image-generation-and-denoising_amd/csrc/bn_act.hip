@@ -937,10 +937,6 @@ extern "C" int vg_bn_launch_plan(int kind, int64_t rows, int C, int groups, int 
     return 0;
 }
 
-extern "C" int vg_bn_finalize_act_forward_supported(int nparts_per_group, int groups, int C, int64_t rows, int dtype) {
-    return bn_fin_fwd_ok(nparts_per_group, groups, C, rows, dtype) ? 1 : 0;
-}
-
 extern "C" int vg_bn_finalize_act_forward(const void* x, void* y, const float* stats, int nparts_per_group, int groups,
                                           int C, int64_t rows, const float* gamma, const float* beta,
                                           float* running_mean, float* running_var, float momentum, float eps,

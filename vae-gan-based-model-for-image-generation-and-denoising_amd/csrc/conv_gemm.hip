@@ -963,9 +963,12 @@ inline int make_plan(const vg_gg_desc* d, int dtype, GGPlan* P) {
     p.ksplit = 1;
     p.reduce = VG_GG_REDUCE_NONE;
     p.nparts = d->stats ? d->nphase * ((M + t.bm - 1) / t.bm) : 0;
+    p.ws_bytes = P->sk.ws_bytes;
+    p.timing_family = dtype == VG_FP8 ? 3 : 0;
     if (dtype != VG_BF16) { plan_generic(d, dtype, P); return 0; }
     if (narrowk_ok(d, dtype)) {
         p.family = VG_GG_NARROWK;
+        p.timing_family = 2;
         p.detail[0] = d->N / 16;
         p.detail[1] = d->Kp / 32;
         return 0;
@@ -1082,32 +1085,6 @@ extern "C" int vg_debug_stamps(unsigned long long* host_out, int n) {
     return (int)hipMemcpyFromSymbol(host_out, HIP_SYMBOL(vg_dbg_stamps), (size_t)n * 8);
 }
 #endif
-
-extern "C" int vg_gather_gemm_nparts(const vg_gg_desc* d, int dtype) {
-    int rc = validate(d, dtype);
-    if (rc) return rc;
-    TileCfg t = pick_tile(d, dtype == VG_BF16, dtype == VG_FP8);
-    const int M = d->B * d->GH * d->GW;
-    return d->nphase * ((M + t.bm - 1) / t.bm);
-}
-
-extern "C" int vg_gather_gemm_family(const vg_gg_desc* d, int dtype) {
-    int rc = validate(d, dtype);
-    if (rc) return rc;
-    return dtype == VG_FP8 ? 3 : (narrowk_ok(d, dtype) ? 2 : 0);
-}
-
-extern "C" int vg_gather_gemm_tile_m(const vg_gg_desc* d, int dtype) {
-    int rc = validate(d, dtype);
-    if (rc) return rc;
-    return pick_tile(d, dtype == VG_BF16, dtype == VG_FP8).bm;
-}
-
-extern "C" int64_t vg_gather_gemm_ws_bytes(const vg_gg_desc* d, int dtype) {
-    int rc = validate(d, dtype);
-    if (rc) return rc;
-    return plan_splitk(d, dtype, pick_tile(d, dtype == VG_BF16, dtype == VG_FP8)).ws_bytes;
-}
 
 extern "C" int vg_gather_gemm_plan(const vg_gg_desc* d, int dtype, vg_gg_plan* out) {
     int rc = validate(d, dtype);

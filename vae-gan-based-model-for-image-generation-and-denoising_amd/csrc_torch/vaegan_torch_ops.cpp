@@ -56,9 +56,10 @@ int64_t gather_gemm(const at::Tensor& X, const at::Tensor& W, at::Tensor& Y, con
     for (int i = 0; i < 4; ++i) d.oox[i] = nx();
     d.nphase = nx(); d.stats_capacity = nx(); d.act = nx(); d.mask_act = nx();
     d.act_slope = static_cast<float>(act_slope); d.mask_slope = static_cast<float>(mask_slope);
-    const int nparts = d.stats ? vg_gather_gemm_nparts(&d, static_cast<int>(dtype)) : 0;
+    vg_gg_plan plan;
+    rc_check(vg_gather_gemm_plan(&d, static_cast<int>(dtype), &plan), "gather_gemm_plan");
     rc_check(vg_gather_gemm(&d, static_cast<int>(dtype), cur_stream()), "gather_gemm");
-    return nparts;
+    return plan.nparts;
 }
 
 // geom: B GH GW PC NP QH QW QC NQ SY SX DY DX TH TW y0 x0 s_np s_cq s_t accumulate (21 values)

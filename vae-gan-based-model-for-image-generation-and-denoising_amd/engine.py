@@ -303,14 +303,14 @@ class StackEngine:
             self.pending_bn_ticks = 0
 
     # ---- forward ----------------------------------------------------------------------------------
-    def can_group(self, B: int, groups: int, probe_x: torch.Tensor) -> bool:
+    def can_group(self, B: int, groups: int, probe_x=None) -> bool:
         """True when `groups` independent batches of B images can run as ONE pass of groups*B images with
         per-group BatchNorm statistics: every statistics slab (one per M tile of the conv kernel) must lie inside
-        one group.  Only plain (single-phase) convolution stacks qualify (the Discriminator)."""
+        one group.  Only plain (single-phase) convolution stacks qualify (the Discriminator).  Host only: the tile
+        rows come from the launch plan (probe_x, once the device to allocate a probe tensor on, is ignored)."""
         key = ("grp", B, groups)
         if key not in self._specs:
             ok = True
-            packs = self._ensure_packed()
             for i, st in enumerate(self.stages):
                 if st.kind == "head":
                     continue
@@ -320,9 +320,7 @@ class StackEngine:
                 if gg.nphase != 1 or pk.tap_in_n:
                     ok = False
                     break
-                kdt, kop = (G.FP8, "fprop8") if self.fp8_ok(i) else (self.dtype, "fprop")
-                xin = torch.empty(gg.B * gg.IH * gg.IW * gg.IC, dtype=ops.TORCH_DT[kdt], device=probe_x.device)
-                bm = ops.gather_gemm_tile_m(gg, xin, packs[i][kop], kdt)
+                bm = ops.gather_gemm_plan(gg, G.FP8 if self.fp8_ok(i) else self.dtype, want_stats=True)["bm"]
                 if (B * st.hout * st.hout) % bm != 0:
                     ok = False
                     break

@@ -237,10 +237,7 @@ def pack_weights(pk: PackSpec, w: torch.Tensor, dtype: int, out: torch.Tensor = 
         raise RuntimeError("parameters must be float32 (fp32 master weights)")
     if out is None:
         out = torch.empty(pk.numel(), dtype=TORCH_DT[dtype], device=w.device)
-    d = L.PackDesc(src=w.data_ptr(), dst=out.data_ptr(), nphase=pk.nphase, N=pk.N, C=pk.C, IC=pk.IC, TH=pk.TH,
-                   TW=pk.TW, Kp=pk.Kp, s_n=pk.s_n, s_c=pk.s_c, KW=pk.KW, kh0=L.i4(pk.kh0), kw0=L.i4(pk.kw0),
-                   kh_step=pk.kh_step, kw_step=pk.kw_step, tap_in_n=pk.tap_in_n, KHW=pk.KHW)
-    L.check(L.load().vg_pack_weights(byref(d), dtype, L.stream_ptr()), "vg_pack_weights")
+    L.check(L.load().vg_pack_weights(byref(pack_desc(pk, w, out)), dtype, L.stream_ptr()), "vg_pack_weights")
     return out
 
 
@@ -286,17 +283,41 @@ def zero_page(device) -> torch.Tensor:
     return z
 
 
-def _gg_desc(g: GGSpec, X, Wp, Y, bias, stats, cap) -> L.GGDesc:
-    return L.GGDesc(zeros=zero_page(X.device).data_ptr(), X=X.data_ptr(), W=Wp.data_ptr(), Y=Y.data_ptr(),
-                    bias=0 if bias is None else bias.data_ptr(), stats=0 if stats is None else stats.data_ptr(),
-                    B=g.B, GH=g.GH, GW=g.GW, IH=g.IH, IW=g.IW, IC=g.IC, SY=g.SY, SX=g.SX, DY=g.DY, DX=g.DX,
-                    TH=g.TH, TW=g.TW, y0=L.i4(g.y0), x0=L.i4(g.x0), N=g.N, Kp=g.Kp, OH=g.OH, OW=g.OW, OC=g.OC,
-                    OSY=g.OSY, OSX=g.OSX, ooy=L.i4(g.ooy), oox=L.i4(g.oox), nphase=g.nphase, stats_capacity=cap)
+_SOME = 64                # a plan query only tests pointers against NULL and for 16-byte alignment: stands in for a tensor
+_WS_ENOUGH = 1 << 62      # ... and for the size of a workspace that is allocated from the plan's ws_bytes
+
+
+def _addr(t) -> int:
+    """Descriptor pointer: the tensor's; True -> the query placeholder (a buffer supplied after planning); None -> NULL."""
+    return 0 if t is None or t is False else _SOME if t is True else t.data_ptr()
+
+
+def _gg_desc(g: GGSpec, X, Wp, Y, zeros, bias=None, stats=None, act=None, mask=None, ws=None) -> L.GGDesc:
+    """The one place a vg_gg_desc is filled, for the plan query and for the launch.  Every operand: a tensor, True (see
+    _addr) or None.  act = (code, slope); mask = (code, slope) or (tensor, code, slope)."""
+    d = L.GGDesc(zeros=_addr(zeros), X=_addr(X), W=_addr(Wp), Y=_addr(Y), bias=_addr(bias), stats=_addr(stats),
+                 B=g.B, GH=g.GH, GW=g.GW, IH=g.IH, IW=g.IW, IC=g.IC, SY=g.SY, SX=g.SX, DY=g.DY, DX=g.DX,
+                 TH=g.TH, TW=g.TW, y0=L.i4(g.y0), x0=L.i4(g.x0), N=g.N, Kp=g.Kp, OH=g.OH, OW=g.OW, OC=g.OC,
+                 OSY=g.OSY, OSX=g.OSX, ooy=L.i4(g.ooy), oox=L.i4(g.oox), nphase=g.nphase,
+                 ws=_addr(ws), ws_bytes=_WS_ENOUGH if ws is True else 0)
+    if act is not None:                      # (code, slope): activation of a BatchNorm-less layer, fused in the epilogue
+        d.act, d.act_slope = act
+    if mask is not None:                     # (activated output of the layer below, code, slope): its activation backward, fused
+        d.mask_x, d.mask_act, d.mask_slope = _addr(mask[0] if len(mask) == 3 else True), mask[-2], mask[-1]
+    return d
+
+
+def _gg_plan(d: L.GGDesc, dtype: int) -> L.GGPlan:
+    p = L.GGPlan()
+    L.check(L.load().vg_gather_gemm_plan(byref(d), dtype, byref(p)), "vg_gather_gemm_plan")
+    return p
 
 
 def gather_gemm(g: GGSpec, X: torch.Tensor, Wp: torch.Tensor, dtype: int, bias: torch.Tensor = None,
                 want_stats: bool = False, out: torch.Tensor = None, alg=None, act=None, mask=None):
-    """Returns (Y [B,OH,OW,OC], stats slabs or None, nparts).  alg = (flops, bytes) of the layer for the timer."""
+    """Returns (Y [B,OH,OW,OC], stats slabs or None, nparts).  alg = (flops, bytes) of the layer for the timer.
+    Two library calls: the plan, asked with placeholders for the statistics slabs and the split-K workspace, sizes both
+    and names the timer family; the launch then runs from the same record (include/vaegan_hip.h, vg_gg_plan)."""
     _need_cuda(X, Wp, bias, out)
     if X.dtype != TORCH_DT[dtype] or Wp.dtype != TORCH_DT[dtype]:
         raise RuntimeError(f"gather_gemm: operand dtype {X.dtype}/{Wp.dtype} does not match engine dtype")
@@ -305,44 +326,28 @@ def gather_gemm(g: GGSpec, X: torch.Tensor, Wp: torch.Tensor, dtype: int, bias: 
                            f"{(g.B, g.IH, g.IW, g.IC)}")
     if Wp.numel() != g.nphase * g.N * g.Kp:
         raise RuntimeError("gather_gemm: packed weight size mismatch")
-    lib = L.load()
     Y = out if out is not None else empty_act((g.B, g.OH, g.OW, g.OC), BF16 if dtype == FP8 else dtype, X.device)
     if Y.numel() != g.B * g.OH * g.OW * g.OC:
         raise RuntimeError("gather_gemm: output size mismatch")
-    stats, nparts = None, 0
-    if want_stats:
-        probe = _gg_desc(g, X, Wp, Y, bias, None, 0)
-        probe.stats = X.data_ptr()           # the tile choice of the launch below, which emits statistics (query only)
-        nparts = lib.vg_gather_gemm_nparts(byref(probe), dtype)
-        if nparts < 0:
-            L.check(nparts, "vg_gather_gemm_nparts")
-        stats = WS.get("stats", nparts * 2 * g.N * 4, X.device)
-    d = _gg_desc(g, X, Wp, Y, bias, stats, nparts)
-    if act is not None:                      # (code, slope): activation of a BatchNorm-less layer, fused in the epilogue
-        d.act, d.act_slope = act
-    if mask is not None:                     # (activated output of the layer below, code, slope): its activation backward, fused
-        mx, mact, mslope = mask
-        if mx.numel() != Y.numel() or mx.dtype != Y.dtype:
-            raise RuntimeError("gather_gemm: mask tensor must be shaped and typed like the output")
-        d.mask_x, d.mask_act, d.mask_slope = mx.data_ptr(), mact, mslope
-    wsb = lib.vg_gather_gemm_ws_bytes(byref(d), dtype)
-    ws = None
-    if wsb > 0:
-        ws = WS.get("splitk", wsb, X.device)
-        d.ws, d.ws_bytes = ws.data_ptr(), ws.numel() * 4
+    if mask is not None and (mask[0].numel() != Y.numel() or mask[0].dtype != Y.dtype):
+        raise RuntimeError("gather_gemm: mask tensor must be shaped and typed like the output")
+    d = _gg_desc(g, X, Wp, Y, zero_page(X.device), bias, stats=want_stats, act=act, mask=mask, ws=True)
+    p = _gg_plan(d, dtype)
+    stats = WS.get("stats", p.nparts * 2 * g.N * 4, X.device) if want_stats else None
+    ws = WS.get("splitk", p.ws_bytes, X.device) if p.ws_bytes > 0 else None
+    d.stats, d.stats_capacity = _addr(stats), p.nparts
+    d.ws, d.ws_bytes = _addr(ws), ws.numel() * 4 if ws is not None else 0
     tok = None
     if TIMER is not None:
-        fam = {0: "gather_gemm", 2: "edge", 3: "gather_gemm_fp8"}[lib.vg_gather_gemm_family(byref(d), dtype)]
-        tok = TIMER.begin(fam, *(alg or (g.flops(), 0)))
+        tok = TIMER.begin({0: "gather_gemm", 2: "edge", 3: "gather_gemm_fp8"}[p.timing_family], *(alg or (g.flops(), 0)))
     if BINDING == "torchops":
-        torch_ops().gather_gemm(X, Wp, Y, bias, stats, ws if wsb > 0 else None, zero_page(X.device),
-                                mask[0] if mask is not None else None, _gg_geom(d), float(d.act_slope),
-                                float(d.mask_slope), dtype)
+        torch_ops().gather_gemm(X, Wp, Y, bias, stats, ws, zero_page(X.device), mask[0] if mask is not None else None,
+                                _gg_geom(d), float(d.act_slope), float(d.mask_slope), dtype)
     else:
-        L.check(lib.vg_gather_gemm(byref(d), dtype, L.stream_ptr()), "vg_gather_gemm")
+        L.check(L.load().vg_gather_gemm(byref(d), dtype, L.stream_ptr()), "vg_gather_gemm")
     if tok is not None:
         TIMER.end(tok)
-    return Y, stats, nparts
+    return Y, stats, p.nparts
 
 
 def edge_wgrad(ew: EWSpec, wide: torch.Tensor, narrow: torch.Tensor, dW: torch.Tensor, accumulate: bool, alg=None) -> None:
@@ -442,38 +447,22 @@ GG_REDUCE = {0: "none", 1: "flat", 2: "tile"}
 
 
 def gather_gemm_plan(g: GGSpec, dtype: int, bias: bool = False, want_stats: bool = False, act=None, mask=None,
-                     workspace: bool = True, zeros: bool = True) -> dict:
+                     workspace=True, zeros: bool = True) -> dict:
     """What vg_gather_gemm launches for this geometry and epilogue under the current switches (vg_gather_gemm_plan: the
-    record the launcher itself launches from).  Host only, no GPU and no tensors: the descriptor's pointers are only
-    tested against NULL by the query, so placeholders stand in for them -- bias / want_stats / mask say which are set, as
-    in gather_gemm (which always passes a workspace of vg_gather_gemm_ws_bytes and the zero page).
-    -> dict(family, bm, bn, detail, dma, ksplit, stages_per_split, nstages, reduce, n_major, nparts)."""
-    some = 64                                                         # non-NULL, 16-byte aligned; never dereferenced
-    d = L.GGDesc(X=some, W=some, Y=some, bias=some if bias else 0, stats=some if want_stats else 0,
-                 zeros=some if zeros else 0, B=g.B, GH=g.GH, GW=g.GW, IH=g.IH, IW=g.IW, IC=g.IC, SY=g.SY, SX=g.SX,
-                 DY=g.DY, DX=g.DX, TH=g.TH, TW=g.TW, y0=L.i4(g.y0), x0=L.i4(g.x0), N=g.N, Kp=g.Kp, OH=g.OH, OW=g.OW,
-                 OC=g.OC, OSY=g.OSY, OSX=g.OSX, ooy=L.i4(g.ooy), oox=L.i4(g.oox), nphase=g.nphase)
-    if act is not None:
-        d.act, d.act_slope = act
-    if mask is not None:                                              # (code, slope) or gather_gemm's (tensor, code, slope)
-        d.mask_x, d.mask_act, d.mask_slope = some, mask[-2], mask[-1]
-    if workspace:
-        d.ws, d.ws_bytes = some, 1 << 62
-    p = L.GGPlan()
-    L.check(L.load().vg_gather_gemm_plan(byref(d), dtype, byref(p)), "vg_gather_gemm_plan")
+    record the launcher itself launches from, and the one gather_gemm sizes its buffers from).  Host only, no GPU and no
+    tensors: the descriptor's pointers are only tested against NULL by the query, so placeholders stand in for them --
+    bias / want_stats / mask say which are set, as in gather_gemm (which always passes the zero page, and the workspace
+    the plan asks for).  workspace: True (as gather_gemm: a workspace of ws_bytes will be supplied), False (none), or the
+    bytes of the one that is passed.
+    -> dict(family, bm, bn, detail, dma, ksplit, stages_per_split, nstages, reduce, n_major, nparts, timing_family, ws_bytes);
+    bm = rows covered by one BatchNorm statistics slab."""
+    d = _gg_desc(g, True, True, True, zeros, bias, stats=want_stats, act=act, mask=mask, ws=bool(workspace))
+    if workspace is not True and workspace:
+        d.ws_bytes = int(workspace)
+    p = _gg_plan(d, dtype)
     return dict(family=GG_FAMILY[p.family], bm=p.bm, bn=p.bn, detail=(p.detail[0], p.detail[1]), dma=bool(p.dma),
                 ksplit=p.ksplit, stages_per_split=p.stages_per_split, nstages=p.nstages, reduce=GG_REDUCE[p.reduce],
-                n_major=bool(p.n_major), nparts=p.nparts)
-
-
-def gather_gemm_tile_m(g: GGSpec, X, Wp, dtype: int) -> int:
-    """M edge of the tile the launcher will pick = rows covered by one BatchNorm statistics slab."""
-    probe = _gg_desc(g, X, Wp, X, None, None, 0)
-    probe.stats = X.data_ptr()               # a launch that emits statistics (never dereferenced by the query): its tile choice
-    r = L.load().vg_gather_gemm_tile_m(byref(probe), dtype)
-    if r < 0:
-        L.check(r, "vg_gather_gemm_tile_m")
-    return r
+                n_major=bool(p.n_major), nparts=p.nparts, timing_family=p.timing_family, ws_bytes=p.ws_bytes)
 
 
 def bn_finalize(stats, nparts, C, count, gamma, beta, running_mean, running_var, momentum, eps, device, groups=1,
@@ -542,7 +531,7 @@ def bn_finalize_act_forward(x, stats, nparts, C, rows, gamma, beta, running_mean
     (bn_act.hip bn_fin_act_fwd_kernel).  Returns (coeffs [groups][4][C], y), or None when the shape does not qualify
     (the caller then runs bn_finalize + bn_act_forward)."""
     lib = L.load()
-    if x.shape[-1] != C or not lib.vg_bn_finalize_act_forward_supported(nparts // groups, groups, C, rows, dtype):
+    if x.shape[-1] != C or not bn_launch_plan("fused", rows, C, dtype, groups, nparts=nparts // groups)["fused"]:
         return None
     _need_cuda(x, stats)
     co = torch.empty(groups, 4, C, dtype=torch.float32, device=x.device)
@@ -610,8 +599,7 @@ def bn_act_backward(x, dy, coeffs, rows, C, count, gamma, act, slope, dgamma, db
                                           coeffs[0, 3].data_ptr(), coeffs[0, 0].data_ptr(), coeffs[0, 1].data_ptr(),
                                           rows, C, act, slope, partial.data_ptr(), cap, byref(n), groups, 4 * C,
                                           dtype, L.stream_ptr()), "vg_bn_act_backward_reduce")
-    if sync is None and x.shape[-1] == C and \
-            lib.vg_bn_finalize_act_forward_supported(n.value, groups, C, rows, dtype):
+    if sync is None and x.shape[-1] == C and bn_launch_plan("fused", rows, C, dtype, groups, nparts=n.value)["fused"]:
         # small layer: finalize + apply in one launch (bn_act.hip bn_bwd_fin_apply_kernel); n = partial rows PER GROUP
         dx = torch.empty_like(x)
         L.check(lib.vg_bn_backward_finalize_apply(x.data_ptr(), dy.data_ptr(), dx.data_ptr(), partial.data_ptr(),

@@ -230,7 +230,7 @@ class DCGANTrainer(_GANBase):
         real_h = ops.nchw_to_nhwc(real.contiguous(), CP, dt, out=both[:B])
         fake_h = ops.nchw_to_nhwc(fake, CP, dt, out=both[B:])
         self.opt_D.zero_grad(memset=False)                                         # :195
-        if self.group_d_passes and D._engine.can_group(B, 2, both):
+        if self.group_d_passes and D._engine.can_group(B, 2):
             p_both, c_both = D.engine_forward(both, B, groups=2)
             dp = torch.empty_like(p_both)
             ops.bce_forward_backward(p_both[:B], 1.0, 1.0, losses[0:1], False, True, out=dp[:B])   # :199-200
@@ -281,7 +281,7 @@ class WGANTrainer(_GANBase):
         CP = G.padc(D.nc, dt)
         both = ops.empty_act((2 * B, real.shape[2], real.shape[3], CP), dt, dev)
         real_h = ops.nchw_to_nhwc(real.contiguous(), CP, dt, out=both[:B])
-        grouped = self.group_d_passes and D._engine.can_group(B, 2, both)
+        grouped = self.group_d_passes and D._engine.can_group(B, 2)
         for it in range(self.critic_iters):                                        # :301
             self.opt_D.zero_grad(memset=False)                                     # :302
             fake, _ = self._gen(critic_noise[it], False)                           # :309-310 (.detach(): forward only)

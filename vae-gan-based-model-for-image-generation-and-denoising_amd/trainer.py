@@ -311,7 +311,7 @@ class VAEGANTrainer:
             if Gn._engine.trace is not None:        # test instrumentation (engine.StackEngine.trace): the unfused tail
                 Gn._engine.trace.append(dict(stage=len(Gn._engine.stages) - 1, what="tail", pre=pre.clone(),
                                              img=recon.clone(), noisy=recon_noisy.clone()))
-        grouped = self.group_d_passes and D._engine.can_group(B, 2, both)
+        grouped = self.group_d_passes and D._engine.can_group(B, 2)
         fused_head = self.fuse_head_backward and 2 * B <= ops.HEAD_BWD_MAXROWS and D._engine.stages[-1].kind == "head"
 
         # ---- Discriminator updates (:95-105) ----
