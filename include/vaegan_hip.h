@@ -48,7 +48,7 @@ extern "C" {
 #define VG_ACT_LRELU   2   /* nn.LeakyReLU(slope)    main_vae.py:25, gan_code.py:62-82 */
 #define VG_ACT_TANH    3   /* nn.Tanh()              gan_code.py:50 (vg_tnconv epilogue only) */
 
-#define VG_ABI_VERSION 21  /* 2: vg_pack_desc.tile_start, SyncBN / WGAN / data-path entry points; 3: in-kernel noise (vg_*_rng);
+#define VG_ABI_VERSION 22  /* 2: vg_pack_desc.tile_start, SyncBN / WGAN / data-path entry points; 3: in-kernel noise (vg_*_rng);
                              4: vg_bn_finalize_act_forward, vg_bn_backward_finalize_apply;
                              7: vg_bce_pair_forward_backward;
                              8: vg_head_backward; round-3 prune -- the opt-in experiments of ABI 5 / 6 that measured slower (input prologue of
@@ -67,7 +67,8 @@ extern "C" {
                              20: vg_bn_launch_plan / vg_bn_plan: the BatchNorm launchers' geometry as a host-only query;
                              21: vg_gg_plan.timing_family / .ws_bytes: callers size their buffers from the plan record; the four
                                  side queries of vg_gather_gemm (slab count, timer family, tile rows, workspace bytes) and the
-                                 "supported" query of vg_bn_finalize_act_forward (vg_bn_launch_plan(VG_BN_PLAN_FUSED).fused) are gone */
+                                 "supported" query of vg_bn_finalize_act_forward (vg_bn_launch_plan(VG_BN_PLAN_FUSED).fused) are gone;
+                             22: weight averaging: vg_ema_update */
 int vg_abi_version(void);
 /* The library reads its optional kernel-selection switches (VG_* environment variables, DESIGN.md "Runtime switches")
  * ONCE, when it is loaded; nothing on a launch path calls getenv.  A process that changes one of them afterwards
@@ -835,6 +836,29 @@ int vg_step_prologue(uint64_t* rng, float* const* states, const double* lr, cons
 int vg_adam_apply2(float* const* p, const float* const* g, float* const* m, float* const* v, const int64_t* n,
                    const double* beta1, const double* beta2, const double* eps, const float* grad_scale,
                    const float* const* state, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Weight averaging (not in the reference): an exponential moving average of the parameters of up to VG_EMA_MAX flat f32
+ * buffers (optim.Adam's flat_p) in ONE launch, meant to follow the optimizer step inside the captured iteration.
+ * Arrays of `count` entries, 1 <= count <= VG_EMA_MAX.  For buffer i (ema = ema[i], p = p[i], n = n[i] elements):
+ *     t = state[i][0]      the optimizer's step count as vg_step_prologue / vg_adam_step left it on the DEVICE, i.e. already
+ *                          incremented for this iteration (read by the kernel: a graph replay sees the current count).
+ *                          state[i] may be NULL only when warmup[i] == 0.
+ *     d = (float)(warmup[i] ? fmin(decay[i], (1.0 + t) / (10.0 + t)) : decay[i])     evaluated in double, narrowed once
+ *     w = 1.0f - d                                                                   an f32 subtraction
+ *     ema[j] = ema[j] + w * (p[j] - ema[j])       j in [0, n): three separately rounded f32 operations (subtract, multiply,
+ *                                                 add; no contraction into an fma).  Non-finite values propagate as IEEE
+ *                                                 arithmetic gives them.
+ * Any n >= 1: elements [0, n / 4 * 4) move as 16-byte vectors in a grid-stride loop, the tail past n / 4 * 4 element by
+ * element in the buffer's first workgroup.  Buffer i gets clamp(ceil(n / 4 / 256), 1, 2048) workgroups of 256 threads and
+ * the buffers' workgroups are concatenated in one grid (as in vg_adam_apply2).  12 bytes of traffic per element.
+ * Checked on the host before anything is launched, VG_EINVAL: count outside 1..VG_EMA_MAX; a NULL array or entry (apart
+ * from the NULL state[i] allowed above, so: warmup[i] != 0 with state[i] NULL); n[i] <= 0; decay[i] not finite or outside
+ * [0, 1]; [ema[i], +n[i]) overlapping [p[i], +n[i]).  Then VG_EALIGN: ema[i] or p[i] not 16-byte aligned.
+ * ---------------------------------------------------------------------------------------- */
+#define VG_EMA_MAX 4
+int vg_ema_update(float* const* ema, const float* const* p, const int64_t* n, const float* const* state,
+                  const double* decay, const int* warmup, int count, void* stream);
 
 #ifdef __cplusplus
 }

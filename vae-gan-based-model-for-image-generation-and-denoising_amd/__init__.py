@@ -11,7 +11,8 @@ its code): ``VAEGANTrainer(..., feat_layer=, alpha_feat=, alpha_pix=)`` and ``Di
 reference): ``SSIMLoss`` and ``VAEGANTrainer(..., alpha_ssim=)`` / ``VAETrainer(..., alpha_ssim=)``.  Generation (main_vae.py:415-641): ``latent`` -- ``encode_dataset``, ``LatentPrior``,
 ``evaluate_generation``, ``sample_images``.  Feature-space metrics (fid.update / fid.compute of every evaluation loop,
 README.md:22 precision / recall): ``metrics`` -- ``FeatureStats``, ``frechet_distance``, ``precision_recall``,
-``encoder_features``, ``kernel_distance`` (KID).  Data path (dataset_code.py): ``data`` -- ``ResidentImages`` (``resized``: Resize +
+``encoder_features``, ``kernel_distance`` (KID).  Weight averaging (not in the reference): ``EMA`` -- an exponential moving
+average of Encoder / Generator weights kept on the device, ``VAEGANTrainer(..., ema=)`` and the sibling trainers.  Data path (dataset_code.py): ``data`` -- ``ResidentImages`` (``resized``: Resize +
 CenterCrop on the device), ``resample_coeffs``, ``resize_geometry``.
 """
 from . import data  # noqa: F401
@@ -20,6 +21,7 @@ from . import latent  # noqa: F401
 from . import metrics  # noqa: F401
 from .data import ResidentImages, resample_coeffs, resize_geometry
 from .ddp import GradReducer
+from .ema import EMA
 from .denoise import denoise_eval, paired_test_epoch, validation_epoch
 from .graphed import graphed
 from .latent import LatentPrior, encode_dataset, evaluate_generation, sample_images
@@ -35,4 +37,5 @@ __all__ = ["ConvBlock", "Encoder", "Generator", "Discriminator", "weights_init",
            "VAEGANTrainer", "LOSS_NAMES", "configure_seed", "geometry", "denoise_eval", "validation_epoch", "paired_test_epoch", "GradReducer", "data", "VAETrainer", "DCGANTrainer", "WGANTrainer", "graphed",
            "latent", "LatentPrior", "encode_dataset", "evaluate_generation", "sample_images",
            "ResidentImages", "resample_coeffs", "resize_geometry",
+           "EMA",
            "metrics", "FeatureStats", "frechet_distance", "precision_recall", "encoder_features", "kernel_distance"]

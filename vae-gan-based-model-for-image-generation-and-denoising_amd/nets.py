@@ -170,6 +170,9 @@ class ConvBlock(_EngineNet):
 
     def __init__(self, in_channels, out_channels, kernel_size=4, stride=2, dtype="fp32"):
         super(ConvBlock, self).__init__()
+        # constructor arguments, for ema.EMA's shadow copy (a plain attribute: state_dict does not see it)
+        self._vg_ctor = dict(in_channels=in_channels, out_channels=out_channels, kernel_size=kernel_size, stride=stride,
+                             dtype=dtype)
         self.conv = Conv2d(in_channels, out_channels, kernel_size, stride)
         self.bn = BatchNorm2d(out_channels)
         self.leaky_relu = LeakyReLU(inplace=True)
@@ -213,6 +216,7 @@ class Encoder(_EngineNet):
 
     def __init__(self, img_size, latent_dim, dtype="fp32"):
         super(Encoder, self).__init__()
+        self._vg_ctor = dict(img_size=list(img_size), latent_dim=latent_dim, dtype=dtype)      # see ConvBlock
         channels = [img_size[0], 32, 64, 128, 256]
         layers = []
         for i in range(1, len(channels)):
@@ -306,6 +310,7 @@ class Generator(_EngineNet):
 
     def __init__(self, nz=128, ngf=64, nc=3, img_size=256, dtype="fp32"):
         super(Generator, self).__init__()
+        self._vg_ctor = dict(nz=nz, ngf=ngf, nc=nc, img_size=img_size, dtype=dtype)            # see ConvBlock
         n = _n_drop(img_size)
         chans = [ngf * 16, ngf * 8, ngf * 4, ngf * 2, ngf, ngf // 2, ngf // 4]
         chans = chans[:len(chans) - n]
@@ -368,6 +373,7 @@ class Discriminator(_EngineNet):
 
     def __init__(self, ndf=64, nc=3, img_size=256, dtype="fp32"):
         super(Discriminator, self).__init__()
+        self._vg_ctor = dict(ndf=ndf, nc=nc, img_size=img_size, dtype=dtype)                   # see ConvBlock
         n = _n_drop(img_size)
         chans = [ndf // 4, ndf // 2, ndf, ndf * 2, ndf * 4, ndf * 8][n:]
         mods = [Conv2d(nc, chans[0], 4, 2, 1, bias=False), LeakyReLU(0.2, inplace=True)]

@@ -1394,6 +1394,27 @@ def adam_apply2(opt_a, opt_b) -> None:
                                     eps, gs, arr(lambda o: o.state_dev.data_ptr()), L.stream_ptr()), "vg_adam_apply2")
 
 
+def ema_update(ema, p, state, decay, warmup) -> None:
+    """Weight averaging, ONE launch for up to 4 flat f32 buffers (vg_ema_update, include/vaegan_hip.h "Weight averaging"):
+    ema[i] += (1 - d_i) * (p[i] - ema[i]) with d_i = decay[i], capped at (1 + t) / (10 + t) where warmup[i] is set; t =
+    state[i][0], the optimizer's device-resident step count (state[i] may be None where warmup[i] is off).  Lists of equal
+    length; ema[i] / p[i] contiguous f32 device tensors of one size.  Capturable."""
+    import ctypes
+    k = len(ema)
+    if not (len(p) == len(state) == len(decay) == len(warmup) == k):
+        raise ValueError("ema_update: ema, p, state, decay and warmup must have one length")
+    if not 1 <= k <= L.VG_EMA_MAX:
+        raise ValueError(f"ema_update: 1..{L.VG_EMA_MAX} buffers per launch, got {k}")
+    _need_cuda(*ema, *p, *state)
+    for e, q in zip(ema, p):
+        if e.dtype != torch.float32 or q.dtype != torch.float32 or e.numel() != q.numel():
+            raise RuntimeError("ema_update: ema[i] and p[i] must be f32 tensors of one size")
+    arr = lambda ts: (ctypes.c_void_p * k)(*[None if t is None else t.data_ptr() for t in ts])       # noqa: E731
+    L.check(L.load().vg_ema_update(arr(ema), arr(p), (ctypes.c_int64 * k)(*[q.numel() for q in p]), arr(state),
+                                   (ctypes.c_double * k)(*[float(d) for d in decay]),
+                                   (ctypes.c_int * k)(*[int(bool(w)) for w in warmup]), k, L.stream_ptr()), "vg_ema_update")
+
+
 def launch_count() -> int:
     """Kernel launches libvaegan_hip.so has issued so far in this process (vg_launch_count)."""
     return int(L.load().vg_launch_count())

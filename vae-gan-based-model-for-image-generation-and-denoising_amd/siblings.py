@@ -28,6 +28,9 @@ class _Graphed:
 
     _nets: Sequence = ()
     _opts: Sequence = ()
+    # ema.EMA over the generating networks, or None: train_step then ends with ema.update(), one
+    # launch directly after the (Encoder /) Generator optimizer step; None launches exactly what it launched without it
+    ema = None
 
     def step_graphed(self, *tensors, **scalars):
         return self._graphed_call(self.train_step, tensors, scalars)
@@ -44,7 +47,7 @@ class _Graphed:
             noise = ops.default_noise(dev)
         key = (tuple(None if t is None else tuple(t.shape) for t in tensors), tuple(sorted(scalars.items())),
                tuple(n.training for n in self._nets), None if noise is None else noise.state.data_ptr()) \
-            + (() if tag is None else (tag,))
+            + (() if tag is None else (tag,)) + (() if self.ema is None else (("ema",) + self.ema.key(),))
         self._gnoise = noise
         st = getattr(self, "_gstate", None)
         if st is not None and st.key == key:
@@ -52,6 +55,8 @@ class _Graphed:
                 if s is not None:
                     s.copy_(t)
             replay(st)
+            if self.ema is not None:
+                self.ema.touch()                       # the replayed update rewrote the shadow buffers
             return st.out
         if getattr(self, "_gwarm", None) != key:
             self._gwarm, self._gstate = key, None
@@ -66,6 +71,8 @@ class _Graphed:
             self._gwarm = self._gstate = None          # nothing ran: the next call warms up again
             raise
         replay(st)
+        if self.ema is not None:
+            self.ema.touch()
         return st.out
 
 
@@ -88,8 +95,9 @@ class VAETrainer(_Graphed):
     LOSS_NAMES = ("recon_loss", "kl_loss", "total")
 
     def __init__(self, encoder, decoder, optimizer, noise_max_std: float = 0.5, kl_weight: float = 1e-5,
-                 alpha_ssim: float = 0.0, hole_weight: float = 1.0):
+                 alpha_ssim: float = 0.0, hole_weight: float = 1.0, ema=None):
         self.E, self.G, self.opt = encoder, decoder, optimizer
+        self.ema = ema
         self.sigma, self.kl_weight = noise_max_std, kl_weight                       # :66, :121
         # SSIM reconstruction loss (not in the reference): total += alpha_ssim * (1 - SSIM(recon,
         # img)), the gradient added onto the MSE's.  Off (0, the default): the iteration launches what it launched before.
@@ -162,6 +170,8 @@ class VAETrainer(_Graphed):
         dmulv = ops.reparam_kl_backward(mulv, lvc, eps_z, dz, w, L, dt)
         E._engine.backward(ctxE, dmulv.view(B, 1, 1, -1), False, sink)
         self.opt.step()                                                            # :126
+        if self.ema is not None:
+            self.ema.update()
         return losses
 
     def step_graphed(self, img, eps_img=None, eps_z=None, noisy=None, rects=None, **scalars):
@@ -179,8 +189,9 @@ class VAETrainer(_Graphed):
 # ---------------------------------------------------------------------------------------------------------------
 class _GANBase(_Graphed):
     def __init__(self, netG, netD, optimizerG, optimizerD, elide_dead_grads: bool = False,
-                 group_d_passes: bool = True):
+                 group_d_passes: bool = True, ema=None):
         self.G, self.D, self.opt_G, self.opt_D = netG, netD, optimizerG, optimizerD
+        self.ema = ema
         # The generator step's backward through D also produces D weight gradients that the next netD.zero_grad()
         # clears unread (module-level zero_grad, gan_code.py:195/:302).  False = compute them anyway, as the
         # reference does.
@@ -250,6 +261,8 @@ class DCGANTrainer(_GANBase):
         d_fake = D._engine.backward(c_adv, dp_adv, True, sink, param_grads=not self.elide_dead_grads)   # :216
         self._gen_backward(ctxG, fake, d_fake, sink)
         self.opt_G.step()                                                          # :217
+        if self.ema is not None:
+            self.ema.update()
         return losses
 
 
@@ -310,4 +323,6 @@ class WGANTrainer(_GANBase):
         d_fake = D._engine.backward(c_adv, dp_adv, True, sink, param_grads=not self.elide_dead_grads)   # :330
         self._gen_backward(ctxG, fake, d_fake, sink)
         self.opt_G.step()                                                          # :331
+        if self.ema is not None:
+            self.ema.update()
         return losses

@@ -42,7 +42,7 @@ class VAEGANTrainer:
                  alpha_adv: float = 0.1, noise_sigma: float = 0.05, real_label: float = 0.9, fake_label: float = 0.1,
                  d_iters: int = 2, elide_dead_grads: bool = False, reducer=None, group_d_passes: bool = True,
                  sync_bn: bool = False, feat_layer: Optional[int] = None, alpha_feat: float = 0.0, alpha_pix: float = 1.0,
-                 alpha_ssim: float = 0.0, hole_weight: float = 1.0):
+                 alpha_ssim: float = 0.0, hole_weight: float = 1.0, ema=None):
         self.E, self.G, self.D = encoder, decoder, discriminator
         self.opt_E, self.opt_G, self.opt_D = opt_E, opt_Dec, opt_Dis
         self.alpha_kl, self.alpha_adv, self.sigma = alpha_kl, alpha_adv, noise_sigma          # :49-50, :91-92
@@ -72,6 +72,10 @@ class VAEGANTrainer:
         self.hole_weight = float(hole_weight)
         if not (math.isfinite(self.hole_weight) and self.hole_weight >= 0.0):
             raise ValueError("hole_weight must be finite and >= 0")
+        # Weight averaging (ema.EMA over the Encoder and / or the Generator and their optimizers): the
+        # iteration ends with ema.update(), ONE more launch directly after the Encoder / Generator optimizer step, captured
+        # with the rest.  None (the default): the iteration launches exactly what it launched without it.
+        self.ema = ema
         self.group_d_passes = group_d_passes       # run a D iteration's real+fake passes as one 2B-row launch chain
         # BCE + its gradient + the sigmoid / head backward as ONE launch per Discriminator pass (ops.head_backward;
         # bit-identical to the three separate launches, which False selects)
@@ -137,7 +141,8 @@ class VAEGANTrainer:
                 self.merge_small_launches,
                 id(self.reducer), self.sync_bn, opts,
                 None if self.noise is None or inject else self.noise.state.data_ptr()) \
-            + ((True, with_rects, self.hole_weight) if paired else ())
+            + ((True, with_rects, self.hole_weight) if paired else ()) \
+            + ((("ema",) + self.ema.key(),) if self.ema is not None else ())
 
     # ---- data-parallel gradient hand-off (ddp.GradReducer) -------------------------------------------------------
     def _buckets_for(self, opt, net):
@@ -386,6 +391,8 @@ class VAEGANTrainer:
         else:
             self.opt_E.step(prepared=prep)
             self.opt_G.step(prepared=prep)
+        if self.ema is not None:
+            self.ema.update()                                 # the shadows follow the weights this iteration left
         self.losses = losses
         return losses
 
@@ -447,7 +454,7 @@ class VAEGANTrainer:
                     sin[4].copy_(noisy)
                 if rects is not None and rects.data_ptr() != sin[5].data_ptr():
                     sin[5].copy_(rects)
-            replay(g)
+            self._replay(g)
             self.last_step_weighted = self._weighted(noisy, rects)
             self.losses = g.out
             return g.out
@@ -475,10 +482,15 @@ class VAEGANTrainer:
             self._inline_failed = True
             g = self._capture(key, sin, epoch, False)
         self._graph = g
-        replay(g)
+        self._replay(g)
         self.last_step_weighted = self._weighted(noisy, rects)
         self.losses = g.out
         return g.out
+
+    def _replay(self, g) -> None:
+        replay(g)
+        if self.ema is not None:
+            self.ema.touch()                        # the replayed update rewrote the shadow buffers: their packs are stale
 
     def _capture(self, key, sin, epoch, inline):
         """Capture one iteration on the static inputs `sin` (capture.capture).  inline: the reducer's collectives are
@@ -519,13 +531,18 @@ class VAEGANTrainer:
     # :356-357).  Module state_dicts here have the reference's keys/shapes/dtypes, so those files
     # interchange both ways.  state_dict()/load_state_dict() below add what the reference lacks: all three networks
     # plus the three Adam states in one payload of plain tensors / dicts / numbers (weights_only-loadable), from
-    # which training resumes bit-identically.
+    # which training resumes bit-identically.  With an EMA attached the payload carries "ema" (ema.EMA.state_dict) as well,
+    # and only then.  A checkpoint WITHOUT "ema" loaded into a trainer that has an EMA re-initialises the shadows from the
+    # loaded live weights; a checkpoint WITH "ema" loaded into a trainer without one ignores it.
     def state_dict(self) -> Dict:
-        return {"format": 1,
-                "encoder": self.E.state_dict(), "decoder": self.G.state_dict(), "discriminator": self.D.state_dict(),
-                "opt_E": self.opt_E.state_dict(), "opt_Dec": self.opt_G.state_dict(), "opt_Dis": self.opt_D.state_dict(),
-                # generator state of the in-kernel randn_like draws: [seed, iteration counter] (None: never used)
-                "noise": None if self.noise is None else self.noise.get_state().cpu()}
+        sd = {"format": 1,
+              "encoder": self.E.state_dict(), "decoder": self.G.state_dict(), "discriminator": self.D.state_dict(),
+              "opt_E": self.opt_E.state_dict(), "opt_Dec": self.opt_G.state_dict(), "opt_Dis": self.opt_D.state_dict(),
+              # generator state of the in-kernel randn_like draws: [seed, iteration counter] (None: never used)
+              "noise": None if self.noise is None else self.noise.get_state().cpu()}
+        if self.ema is not None:
+            sd["ema"] = self.ema.state_dict()
+        return sd
 
     def load_state_dict(self, sd: Dict) -> None:
         if sd.get("format") != 1:
@@ -534,6 +551,11 @@ class VAEGANTrainer:
         self.D.load_state_dict(sd["discriminator"])
         self.opt_E.load_state_dict(sd["opt_E"]), self.opt_G.load_state_dict(sd["opt_Dec"])
         self.opt_D.load_state_dict(sd["opt_Dis"])
+        if self.ema is not None:
+            if sd.get("ema") is not None:
+                self.ema.load_state_dict(sd["ema"])
+            else:
+                self.ema.reset()
         if sd.get("noise") is not None:
             st = sd["noise"]
             dev = next(self.E.parameters()).device
