@@ -121,9 +121,49 @@ __global__ __launch_bounds__(256) void col_reduce_kernel(const void* __restrict_
 // 32 planes these ~48 launches per iteration were still 5 us each, 6 % of it), double accumulation, then a
 // fixed-order combine (xor-shuffles over the 8 planes of a wave, LDS over the 16 waves) -> bitwise reproducible.
 // Returns the sums to threads tid < 8.
-constexpr int FIN_CH = 8, FIN_PL = 128;
-__device__ __forceinline__ bool slab_sums(const float* __restrict__ slabs, int nparts, int C, double& s1, double& s2,
-                                          int& c_out) {
+//
+// Every load a thread needs is issued before the first add that waits for one: a load-add loop is one memory round trip
+// per row (s_waitcnt vmcnt(0) in front of every add), and these launches are nothing but round trips.  A thread's first
+// FIN_FIRST rows are one batch (FinRows: rows beyond nparts hold +0, and a sum that started at +0 is never -0, so adding
+// them changes no bit), the rest follows FIN_DEPTH rows at a time; the grouped kernels load the next group's first batch
+// before they finish the current group.  The adds stay in row order per thread.
+constexpr int FIN_CH = 8, FIN_PL = 128, FIN_FIRST = 4, FIN_DEPTH = 8;
+struct FinRows { float x[FIN_FIRST], y[FIN_FIRST]; };
+
+// The slab is read through a buffer descriptor over exactly its nparts rows (SlabBuf): a load is a uniform descriptor plus
+// one 32-bit per-thread byte offset, and a row beyond the slab comes back as +0 from the hardware range check -- no
+// predicate, so no branch around a load (the compiler moves the conversion to double into a predicated block, and the wait
+// with it) and no 64-bit address per load in flight.  The launchers refuse slabs of 2^31 bytes.
+struct SlabBuf {
+    __amdgpu_buffer_rsrc_t rsrc;
+    unsigned row;                                              // bytes per slab row: 2 * C floats
+    __device__ __forceinline__ SlabBuf(const float* slabs, int nparts, int C, bool live = true)
+        : rsrc(__builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(slabs), 0, live ? (int)((unsigned)nparts * 2u * (unsigned)C * 4u) : 0, 0x00020000)),
+          row((unsigned)C * 8u) {}
+    // (sum x, sum x*x) entries of row p, channel c
+    __device__ __forceinline__ void load(unsigned p, unsigned c, float& x, float& y) const {
+        const unsigned off = p * row + c * 4u;
+        x = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsrc, off, 0, 0));
+        y = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsrc, off + row / 2u, 0, 0));
+    }
+};
+
+// SlabBuf's 32-bit byte offsets: a thread asks for rows up to one batch beyond the slab, and that offset must not wrap
+inline bool slab_fits(int64_t nparts, int64_t C) { return (nparts + 2048) * 2 * C * 4 < (1ll << 32); }
+
+// a thread's first batch: rows pl + k * FIN_PL, k < FIN_FIRST -- the whole slab up to 4 * FIN_PL rows (every launch of the
+// flagship step but one).  live = false: no slab (every row +0, nothing is read).
+__device__ __forceinline__ void fin_load_first(const float* __restrict__ slabs, int nparts, int C, FinRows& r, bool live = true) {
+    const int c = blockIdx.x * FIN_CH + (threadIdx.x & (FIN_CH - 1)), pl = threadIdx.x / FIN_CH;
+    const SlabBuf sb(slabs, nparts, C, live);
+    const unsigned cc = c < C ? c : C - 1;                     // (a thread without a channel adds nothing: see slab_sums_from)
+#pragma unroll
+    for (int k = 0; k < FIN_FIRST; ++k) sb.load(pl + k * FIN_PL, cc, r.x[k], r.y[k]);
+}
+
+// r: what fin_load_first(slabs, nparts, C, .) gave
+__device__ __forceinline__ bool slab_sums_from(const float* __restrict__ slabs, int nparts, int C, const FinRows& r,
+                                               double& s1, double& s2, int& c_out) {
     constexpr int NW = FIN_CH * FIN_PL / 64;
     __shared__ double red[NW][FIN_CH][2];
     const int cl = threadIdx.x & (FIN_CH - 1);
@@ -131,21 +171,15 @@ __device__ __forceinline__ bool slab_sums(const float* __restrict__ slabs, int n
     const int c = blockIdx.x * FIN_CH + cl;
     double a = 0.0, b = 0.0;
     if (c < C) {
-        // 4 slab rows (8 loads) in flight per thread: the loop is a chain of L2/HBM latencies otherwise
-        int p = pl;
-        for (; p + 3 * FIN_PL < nparts; p += 4 * FIN_PL) {
-            float x[4], y[4];
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                x[k] = slabs[((int64_t)(p + k * FIN_PL) * 2 + 0) * C + c];
-                y[k] = slabs[((int64_t)(p + k * FIN_PL) * 2 + 1) * C + c];
-            }
+        for (int k = 0; k < FIN_FIRST; ++k) { a += (double)r.x[k]; b += (double)r.y[k]; }
+        const SlabBuf sb(slabs, nparts, C);
+        for (int base = FIN_FIRST * FIN_PL; base < nparts; base += FIN_DEPTH * FIN_PL) {
+            float x[FIN_DEPTH], y[FIN_DEPTH];
 #pragma unroll
-            for (int k = 0; k < 4; ++k) { a += (double)x[k]; b += (double)y[k]; }
-        }
-        for (; p < nparts; p += FIN_PL) {
-            a += (double)slabs[((int64_t)p * 2 + 0) * C + c];
-            b += (double)slabs[((int64_t)p * 2 + 1) * C + c];
+            for (int k = 0; k < FIN_DEPTH; ++k) sb.load(base + pl + k * FIN_PL, c, x[k], y[k]);
+#pragma unroll
+            for (int k = 0; k < FIN_DEPTH; ++k) { a += (double)x[k]; b += (double)y[k]; }
         }
     }
     // a wave holds 8 planes x 8 channels (lane = 8*plane + channel): butterfly over the plane bits
@@ -162,12 +196,40 @@ __device__ __forceinline__ bool slab_sums(const float* __restrict__ slabs, int n
     return true;
 }
 
+__device__ __forceinline__ bool slab_sums(const float* __restrict__ slabs, int nparts, int C, double& s1, double& s2,
+                                          int& c_out) {
+    FinRows r;
+    fin_load_first(slabs, nparts, C, r);
+    return slab_sums_from(slabs, nparts, C, r, s1, s2, c_out);
+}
+
+// the lead thread of channel c (the one slab_sums returns the sums to), known before the sums: it loads its per-channel
+// operands at kernel entry, together with the slab rows, not one more round trip after them
+__device__ __forceinline__ bool fin_lead(int C, int& c) {
+    c = blockIdx.x * FIN_CH + (threadIdx.x & (FIN_CH - 1));
+    return threadIdx.x < FIN_CH && c < C;
+}
+__device__ __forceinline__ float lead_load(bool lead, const float* __restrict__ p, int c, float otherwise) {
+    return (lead && p) ? p[c] : otherwise;
+}
+
+// running statistic after one batch: both products rounded, then the sum (torch's own order; spelled out because the value
+// now lives in a register across the groups, where the compiler would contract one product into the sum and move the
+// last bit of the running statistics)
+__device__ __forceinline__ float running_update(float momentum, float r, float v) {
+#pragma clang fp contract(off)
+    return (1.f - momentum) * r + momentum * v;
+}
+
 __global__ __launch_bounds__(FIN_CH * FIN_PL) void bn_finalize_kernel(
     const float* __restrict__ stats, int nparts, int C, double count, const float* __restrict__ gamma,
     const float* __restrict__ beta, float* __restrict__ rmean, float* __restrict__ rvar, float momentum, float eps,
     float* __restrict__ mean, float* __restrict__ invstd, float* __restrict__ scale, float* __restrict__ shift) {
     double s1, s2;
     int c;
+    const bool lead = fin_lead(C, c);
+    const float g = lead_load(lead, gamma, c, 1.f), b = lead_load(lead, beta, c, 0.f);
+    const float rm = lead_load(lead, rmean, c, 0.f), rv = lead_load(lead && rmean, rvar, c, 0.f);
     if (!slab_sums(stats, nparts, C, s1, s2, c)) return;
     const double mu = s1 / count;
     double var = s2 / count - mu * mu;
@@ -176,14 +238,13 @@ __global__ __launch_bounds__(FIN_CH * FIN_PL) void bn_finalize_kernel(
     const float muf = (float)mu;
     mean[c] = muf;
     invstd[c] = is;
-    const float g = gamma ? gamma[c] : 1.f, b = beta ? beta[c] : 0.f;
     const float sc = g * is;
     scale[c] = sc;
     shift[c] = b - muf * sc;
     if (rmean) {
         const double unbiased = count > 1.0 ? var * (count / (count - 1.0)) : var;
-        rmean[c] = (1.f - momentum) * rmean[c] + momentum * muf;
-        rvar[c] = (1.f - momentum) * rvar[c] + momentum * (float)unbiased;
+        rmean[c] = running_update(momentum, rm, muf);
+        rvar[c] = running_update(momentum, rv, (float)unbiased);
     }
 }
 
@@ -194,11 +255,17 @@ __global__ __launch_bounds__(FIN_CH * FIN_PL) void bn_finalize_grouped_kernel(
     const float* __restrict__ stats, int nparts, int groups, int C, double count, const float* __restrict__ gamma,
     const float* __restrict__ beta, float* __restrict__ rmean, float* __restrict__ rvar, float momentum, float eps,
     float* __restrict__ coeffs) {
+    int c;
+    const bool lead = fin_lead(C, c);
+    const float gm = lead_load(lead, gamma, c, 1.f), bt = lead_load(lead, beta, c, 0.f);
+    float rm = lead_load(lead, rmean, c, 0.f), rv = lead_load(lead && rmean, rvar, c, 0.f);
+    FinRows cur, nxt;
+    fin_load_first(stats, nparts, C, cur);
     for (int g = 0; g < groups; ++g) {
+        const float* slab = stats + (int64_t)g * nparts * 2 * C;
+        fin_load_first(slab + (int64_t)nparts * 2 * C, nparts, C, nxt, g + 1 < groups);      // in flight while g is summed
         double s1, s2;
-        int c;
-        const bool lead = slab_sums(stats + (int64_t)g * nparts * 2 * C, nparts, C, s1, s2, c);
-        if (lead) {
+        if (slab_sums_from(slab, nparts, C, cur, s1, s2, c)) {
             float* co = coeffs + (int64_t)g * 4 * C;
             const double mu = s1 / count;
             double var = s2 / count - mu * mu;
@@ -207,40 +274,55 @@ __global__ __launch_bounds__(FIN_CH * FIN_PL) void bn_finalize_grouped_kernel(
             const float muf = (float)mu;
             co[c] = muf;
             co[C + c] = is;
-            const float gm = gamma ? gamma[c] : 1.f, bt = beta ? beta[c] : 0.f;
             const float sc = gm * is;
             co[2 * C + c] = sc;
             co[3 * C + c] = bt - muf * sc;
             if (rmean) {
                 const double unbiased = count > 1.0 ? var * (count / (count - 1.0)) : var;
-                rmean[c] = (1.f - momentum) * rmean[c] + momentum * muf;
-                rvar[c] = (1.f - momentum) * rvar[c] + momentum * (float)unbiased;
+                rm = running_update(momentum, rm, muf);
+                rv = running_update(momentum, rv, (float)unbiased);
             }
         }
+        cur = nxt;
         __syncthreads();                                    // slab_sums' LDS scratch is reused by the next group
     }
+    if (lead && rmean && groups > 0) { rmean[c] = rm; rvar[c] = rv; }
 }
 
 __global__ __launch_bounds__(FIN_CH * FIN_PL) void bn_bwd_finalize_grouped_kernel(
     const float* __restrict__ partial, int nparts, int groups, int C, double count, const float* __restrict__ gamma,
     const float* __restrict__ coeffs, float* __restrict__ dgamma, float* __restrict__ dbeta, int accumulate,
     float* __restrict__ coef) {
+    int c;
+    const bool lead = fin_lead(C, c);
+    const float gm = lead_load(lead, gamma, c, 1.f);
+    float dg = lead_load(lead && accumulate, dgamma, c, 0.f), db = lead_load(lead && accumulate, dbeta, c, 0.f);
+    float is = lead_load(lead, coeffs + C, c, 0.f), is_nxt = 0.f;                           // group 0's invstd
+    FinRows cur, nxt;
+    fin_load_first(partial, nparts, C, cur);
     for (int g = 0; g < groups; ++g) {
+        const float* slab = partial + (int64_t)g * nparts * 2 * C;
+        // the next group's rows and invstd, in flight while g is summed
+        fin_load_first(slab + (int64_t)nparts * 2 * C, nparts, C, nxt, g + 1 < groups);
+        is_nxt = lead_load(lead && g + 1 < groups, coeffs + (int64_t)(g + 1) * 4 * C + C, c, 0.f);
         double s1, s2;
-        int c;
-        const bool lead = slab_sums(partial + (int64_t)g * nparts * 2 * C, nparts, C, s1, s2, c);
-        if (lead) {
+        if (slab_sums_from(slab, nparts, C, cur, s1, s2, c)) {
             const float fs1 = (float)s1, fs2 = (float)s2;
             const bool acc = accumulate || g > 0;
-            if (dgamma) dgamma[c] = acc ? dgamma[c] + fs2 : fs2;
-            if (dbeta) dbeta[c] = acc ? dbeta[c] + fs1 : fs1;
-            const float a = (gamma ? gamma[c] : 1.f) * coeffs[(int64_t)g * 4 * C + C + c];      // gamma * invstd
+            dg = acc ? dg + fs2 : fs2;
+            db = acc ? db + fs1 : fs1;
+            const float a = gm * is;                        // gamma * invstd
             float* cf = coef + (int64_t)g * 3 * C;
             cf[c] = a;
             cf[C + c] = (float)((double)a * s2 / count);
             cf[2 * C + c] = (float)((double)a * s1 / count);
         }
+        cur = nxt; is = is_nxt;
         __syncthreads();
+    }
+    if (lead && groups > 0) {
+        if (dgamma) dgamma[c] = dg;
+        if (dbeta) dbeta[c] = db;
     }
 }
 
@@ -491,11 +573,14 @@ __global__ __launch_bounds__(FIN_CH * FIN_PL) void bn_bwd_finalize_kernel(
     float* __restrict__ coef) {
     double s1, s2;
     int c;
+    const bool lead = fin_lead(C, c);
+    const float gm = lead_load(lead, gamma, c, 1.f), is = lead_load(lead, invstd, c, 0.f);
+    const float dg = lead_load(lead && accumulate, dgamma, c, 0.f), db = lead_load(lead && accumulate, dbeta, c, 0.f);
     if (!slab_sums(partial, nparts, C, s1, s2, c)) return;
     const float fs1 = (float)s1, fs2 = (float)s2;
-    if (dgamma) dgamma[c] = accumulate ? dgamma[c] + fs2 : fs2;
-    if (dbeta) dbeta[c] = accumulate ? dbeta[c] + fs1 : fs1;
-    const float a = (gamma ? gamma[c] : 1.f) * invstd[c];
+    if (dgamma) dgamma[c] = accumulate ? dg + fs2 : fs2;
+    if (dbeta) dbeta[c] = accumulate ? db + fs1 : fs1;
+    const float a = gm * is;
     coef[c] = a;
     coef[C + c] = (float)((double)a * s2 / count);
     coef[2 * C + c] = (float)((double)a * s1 / count);
@@ -576,26 +661,52 @@ __global__ __launch_bounds__(256) void bn_act_bwd_apply_kernel(const void* __res
 constexpr int FF_CH = 64, FF_PL = 16, FF_TH = FF_CH * FF_PL, FF_MAXPARTS = 200;
 constexpr int64_t FF_MAXBYTES = 9ll << 20;       // tensor size up to which re-deriving the coefficients per workgroup pays
 
-__device__ __forceinline__ void ff_slice_stats(const float* __restrict__ slabs, int nparts, int C, int c0, double count,
-                                               double (*red)[FF_CH][2], double& mu_out, double& var_out) {
+// A part lane's slab rows (pl, pl + 16, ...: at most FF_TRIPS), all loaded before the first is added: the load-add loop was
+// one memory round trip per row, up to 13 in a row before a workgroup touched its tensor.  Rows beyond nparts come back as
+// +0 (a sum that started at +0 is never -0: adding them changes no bit); the adds stay in row order.
+constexpr int FF_TRIPS = (FF_MAXPARTS + FF_PL - 1) / FF_PL;
+
+// -> a part lane's sums: T trips' loads (through a SlabBuf: rows beyond the slab are +0), then the adds
+template <int T>
+__device__ __forceinline__ void ff_lane_sums(const SlabBuf& sb, int c, double& a, double& b) {
+    const int pl = threadIdx.x / FF_CH;
+    float x[T], y[T];
+#pragma unroll
+    for (int k = 0; k < T; ++k) sb.load(pl + k * FF_PL, c, x[k], y[k]);
+    a = 0.0; b = 0.0;
+#pragma unroll
+    for (int k = 0; k < T; ++k) { a += (double)x[k]; b += (double)y[k]; }
+}
+
+// -> the slice's sums in every thread of channel ch: 16 part lanes in double, combined in lane order through LDS
+__device__ __forceinline__ void ff_slice_sums(const float* __restrict__ slabs, int nparts, int C, int c0,
+                                              double (*red)[FF_CH][2], double& s1, double& s2) {
     const int ch = threadIdx.x & (FF_CH - 1), pl = threadIdx.x / FF_CH;
-    double a = 0.0, b = 0.0;
-    for (int p = pl; p < nparts; p += FF_PL) {
-        a += (double)slabs[((int64_t)p * 2 + 0) * C + c0 + ch];
-        b += (double)slabs[((int64_t)p * 2 + 1) * C + c0 + ch];
-    }
+    const SlabBuf sb(slabs, nparts, C);
+    double a, b;
+    if (nparts <= FF_PL) ff_lane_sums<1>(sb, c0 + ch, a, b);               // no more loads than the slab has rows per lane
+    else if (nparts <= 2 * FF_PL) ff_lane_sums<2>(sb, c0 + ch, a, b);
+    else if (nparts <= 4 * FF_PL) ff_lane_sums<4>(sb, c0 + ch, a, b);
+    else if (nparts <= 8 * FF_PL) ff_lane_sums<8>(sb, c0 + ch, a, b);
+    else ff_lane_sums<FF_TRIPS>(sb, c0 + ch, a, b);
     red[pl][ch][0] = a;
     red[pl][ch][1] = b;
     __syncthreads();
-    double s1 = 0.0, s2 = 0.0;
+    s1 = 0.0; s2 = 0.0;
 #pragma unroll
     for (int k = 0; k < FF_PL; ++k) { s1 += red[k][ch][0]; s2 += red[k][ch][1]; }
+    __syncthreads();                                           // red[] is reused by the next group (publisher blocks)
+}
+
+__device__ __forceinline__ void ff_slice_stats(const float* __restrict__ slabs, int nparts, int C, int c0, double count,
+                                               double (*red)[FF_CH][2], double& mu_out, double& var_out) {
+    double s1, s2;
+    ff_slice_sums(slabs, nparts, C, c0, red, s1, s2);
     const double mu = s1 / count;
     double var = s2 / count - mu * mu;
     if (var < 0.0) var = 0.0;
     mu_out = mu;
     var_out = var;
-    __syncthreads();                                           // red[] is reused by the next group (publisher blocks)
 }
 
 __global__ __launch_bounds__(FF_TH) void bn_fin_act_fwd_kernel(
@@ -706,30 +817,21 @@ __global__ __launch_bounds__(FF_TH) void bn_bwd_fin_apply_kernel(
     int64_t rows_per_group, int rows_per_block, int act, float slope) {
     __shared__ double red[FF_PL][FF_CH][2];
     __shared__ float s_co[7][FF_CH];                            // mean | invstd | scale | shift | a | b | c
-    const int tid = threadIdx.x, ch = tid & (FF_CH - 1), pl = tid / FF_CH;
+    const int tid = threadIdx.x, ch = tid & (FF_CH - 1);
     const int c0 = blockIdx.y * FF_CH, grp = blockIdx.z;
     const bool lead = tid < FF_CH && c0 + ch < C;
     const float gm = (lead && gamma) ? gamma[c0 + ch] : 1.f;
-    auto slice_sums = [&](int g, double& s1, double& s2) {
-        const float* pp = partial + (int64_t)g * nparts * 2 * C;
-        double a = 0.0, b = 0.0;
-        for (int p = pl; p < nparts; p += FF_PL) {
-            a += (double)pp[((int64_t)p * 2 + 0) * C + c0 + ch];
-            b += (double)pp[((int64_t)p * 2 + 1) * C + c0 + ch];
-        }
-        red[pl][ch][0] = a;
-        red[pl][ch][1] = b;
-        __syncthreads();
-        s1 = 0.0; s2 = 0.0;
-#pragma unroll
-        for (int k = 0; k < FF_PL; ++k) { s1 += red[k][ch][0]; s2 += red[k][ch][1]; }
-        __syncthreads();
-    };
-    auto publish_coef = [&](int g, double s1, double s2) {      // lead threads: this group's coefficients into LDS
-        const float* co = coeffs + (int64_t)g * 4 * C + c0 + ch;
-        const float is = co[C];
+    // the forward coefficients of the group this workgroup applies (the publisher: group 0 = grp), loaded at entry with the
+    // slab rows and not one more round trip after the sums
+    float co[4] = {0.f, 0.f, 0.f, 0.f};
+    if (lead) {
+        const float* cp = coeffs + (int64_t)grp * 4 * C + c0 + ch;
+        co[0] = cp[0]; co[1] = cp[C]; co[2] = cp[2 * C]; co[3] = cp[3 * C];
+    }
+    auto publish_coef = [&](double s1, double s2) {             // lead threads: this group's coefficients into LDS
+        const float is = co[1];
         const float a = gm * is;
-        s_co[0][ch] = co[0]; s_co[1][ch] = is; s_co[2][ch] = co[2 * C]; s_co[3][ch] = co[3 * C];
+        s_co[0][ch] = co[0]; s_co[1][ch] = is; s_co[2][ch] = co[2]; s_co[3][ch] = co[3];
         s_co[4][ch] = a;
         s_co[5][ch] = (float)((double)a * s2 / count);
         s_co[6][ch] = (float)((double)a * s1 / count);
@@ -739,9 +841,9 @@ __global__ __launch_bounds__(FF_TH) void bn_bwd_fin_apply_kernel(
         float db = (lead && dbeta && accumulate) ? dbeta[c0 + ch] : 0.f;
         for (int g = 0; g < groups; ++g) {                      // dgamma / dbeta accumulate in group order
             double s1, s2;
-            slice_sums(g, s1, s2);
+            ff_slice_sums(partial + (int64_t)g * nparts * 2 * C, nparts, C, c0, red, s1, s2);
             if (lead) {
-                if (g == 0) publish_coef(0, s1, s2);            // this workgroup applies group 0's rows
+                if (g == 0) publish_coef(s1, s2);               // this workgroup applies group 0's rows
                 const bool acc = accumulate || g > 0;
                 dg = acc ? dg + (float)s2 : (float)s2;
                 db = acc ? db + (float)s1 : (float)s1;
@@ -753,8 +855,8 @@ __global__ __launch_bounds__(FF_TH) void bn_bwd_fin_apply_kernel(
         }
     } else {
         double s1, s2;
-        slice_sums(grp, s1, s2);
-        if (lead) publish_coef(grp, s1, s2);
+        ff_slice_sums(partial + (int64_t)grp * nparts * 2 * C, nparts, C, c0, red, s1, s2);
+        if (lead) publish_coef(s1, s2);
     }
     __syncthreads();
     const int u8 = (tid & 7) * 8, rl = tid >> 3;
@@ -811,9 +913,11 @@ __global__ __launch_bounds__(FIN_CH * FIN_PL) void bias_finalize_kernel(const fl
                                                                         int accumulate) {
     double s1, s2;
     int c;
+    const bool lead = fin_lead(C, c);
+    const float d0 = lead_load(lead && accumulate && c < NC, dbias, c, 0.f);
     if (!slab_sums(partial, nparts, C, s1, s2, c)) return;
     if (c >= NC) return;
-    dbias[c] = accumulate ? dbias[c] + (float)s1 : (float)s1;
+    dbias[c] = accumulate ? d0 + (float)s1 : (float)s1;
 }
 
 inline int ew_blocks(int64_t nvec) {
@@ -857,6 +961,7 @@ extern "C" int vg_bn_finalize(const float* stats, int nparts, int C, int64_t cou
                               const float* beta, float* running_mean, float* running_var, float momentum, float eps,
                               float* mean, float* invstd, float* scale, float* shift, void* stream) {
     VG_CHECK_ARG(stats && nparts > 0 && C > 0 && count > 0 && mean && invstd && scale && shift, VG_EINVAL);
+    VG_CHECK_ARG(slab_fits(nparts, C), VG_ENOSUP);
     VG_CHECK_ARG((running_mean == nullptr) == (running_var == nullptr), VG_EINVAL);
     vg_launch_timed(4, bn_finalize_kernel, dim3((C + FIN_CH - 1) / FIN_CH), dim3(FIN_CH * FIN_PL), 0, vg_stream(stream), stats, nparts, C,
                        (double)count, gamma, beta, running_mean, running_var, momentum, eps, mean, invstd, scale,
@@ -869,6 +974,7 @@ extern "C" int vg_bn_finalize_grouped(const float* stats, int nparts_per_group, 
                                       float* running_mean, float* running_var, float momentum, float eps,
                                       float* coeffs, void* stream) {
     VG_CHECK_ARG(stats && coeffs && nparts_per_group > 0 && groups > 0 && C > 0 && count_per_group > 0, VG_EINVAL);
+    VG_CHECK_ARG(slab_fits(nparts_per_group, C), VG_ENOSUP);
     VG_CHECK_ARG((running_mean == nullptr) == (running_var == nullptr), VG_EINVAL);
     vg_launch_timed(4, bn_finalize_grouped_kernel, dim3((C + FIN_CH - 1) / FIN_CH), dim3(FIN_CH * FIN_PL), 0,
                        vg_stream(stream), stats, nparts_per_group, groups, C, (double)count_per_group, gamma, beta,
@@ -882,6 +988,7 @@ extern "C" int vg_bn_backward_finalize_grouped(const float* partial, int nparts_
                                                void* stream) {
     VG_CHECK_ARG(partial && coeffs && coef && nparts_per_group > 0 && groups > 0 && C > 0 && count_per_group > 0,
                  VG_EINVAL);
+    VG_CHECK_ARG(slab_fits(nparts_per_group, C), VG_ENOSUP);
     vg_launch_timed(4, bn_bwd_finalize_grouped_kernel, dim3((C + FIN_CH - 1) / FIN_CH), dim3(FIN_CH * FIN_PL), 0,
                        vg_stream(stream), partial, nparts_per_group, groups, C, (double)count_per_group, gamma, coeffs,
                        dgamma, dbeta, accumulate, coef);
@@ -890,6 +997,7 @@ extern "C" int vg_bn_backward_finalize_grouped(const float* partial, int nparts_
 
 extern "C" int vg_slab_sums(const float* slabs, int nparts, int C, double* sums, void* stream) {
     VG_CHECK_ARG(slabs && sums && nparts > 0 && C > 0, VG_EINVAL);
+    VG_CHECK_ARG(slab_fits(nparts, C), VG_ENOSUP);
     vg_launch_timed(4, slab_sums_kernel, dim3((C + FIN_CH - 1) / FIN_CH), dim3(FIN_CH * FIN_PL), 0, vg_stream(stream),
                        slabs, nparts, C, sums);
     return VG_LAUNCH_RC();
@@ -945,7 +1053,7 @@ extern "C" int vg_bn_finalize_act_forward(const void* x, void* y, const float* s
     VG_CHECK_ARG((running_mean == nullptr) == (running_var == nullptr), VG_EINVAL);
     VG_CHECK_ARG(vg_aligned16(x) && vg_aligned16(y), VG_EALIGN);
     const vg_bn_plan p = plan_fused(nparts_per_group, groups, C, rows, dtype);
-    if (!p.fused) return VG_ENOSUP;
+    if (!p.fused || !slab_fits(nparts_per_group, C)) return VG_ENOSUP;
     const int64_t rpg = rows / groups;
     vg_launch_timed(4, bn_fin_act_fwd_kernel, dim3(p.blocks_per_group, p.col_blocks, p.groups), dim3(FF_TH), 0, vg_stream(stream),
                        reinterpret_cast<const uint16_t*>(x), reinterpret_cast<uint16_t*>(y), stats, nparts_per_group, groups,
@@ -961,7 +1069,7 @@ extern "C" int vg_bn_backward_finalize_apply(const void* x, const void* dy, void
     VG_CHECK_ARG(x && dy && dx && partial && coeffs && rows > 0 && C > 0, VG_EINVAL);
     VG_CHECK_ARG(vg_aligned16(x) && vg_aligned16(dy) && vg_aligned16(dx), VG_EALIGN);
     const vg_bn_plan p = plan_fused(nparts_per_group, groups, C, rows, dtype);
-    if (!p.fused) return VG_ENOSUP;
+    if (!p.fused || !slab_fits(nparts_per_group, C)) return VG_ENOSUP;
     const int64_t rpg = rows / groups;
     vg_launch_timed(4, bn_bwd_fin_apply_kernel, dim3(p.blocks_per_group, p.col_blocks, p.groups), dim3(FF_TH), 0, vg_stream(stream),
                        reinterpret_cast<const uint16_t*>(x), reinterpret_cast<const uint16_t*>(dy),
@@ -1028,6 +1136,7 @@ extern "C" int vg_bn_backward_finalize(const float* partial, int nparts, int C, 
                                        const float* invstd, float* dgamma, float* dbeta, int accumulate, float* coef,
                                        void* stream) {
     VG_CHECK_ARG(partial && nparts > 0 && C > 0 && count > 0 && invstd && coef, VG_EINVAL);
+    VG_CHECK_ARG(slab_fits(nparts, C), VG_ENOSUP);
     vg_launch_timed(4, bn_bwd_finalize_kernel, dim3((C + FIN_CH - 1) / FIN_CH), dim3(FIN_CH * FIN_PL), 0, vg_stream(stream), partial, nparts, C,
                        (double)count, gamma, invstd, dgamma, dbeta, accumulate, coef);
     return VG_LAUNCH_RC();
@@ -1078,6 +1187,7 @@ extern "C" int vg_bias_grad(const void* dy, int64_t rows, int C, int NC, float* 
     int rc = check_rows_c(dy, rows, C, dtype);
     if (rc) return rc;
     VG_CHECK_ARG(dbias && ws && NC > 0 && NC <= C, VG_EINVAL);
+    VG_CHECK_ARG(slab_fits(plan_reduce(rows, C, 1).blocks_per_group, C), VG_ENOSUP);
     int nparts = 0;
     rc = launch_reduce<0>(dy, nullptr, nullptr, nullptr, nullptr, nullptr, rows, C, 0, 0.f, ws, ws_capacity, &nparts,
                           dtype, vg_stream(stream));

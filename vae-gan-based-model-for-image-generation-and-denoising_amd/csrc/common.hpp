@@ -165,6 +165,7 @@ struct VgSwitches {
     int splitk_wgs;        // VG_SPLITK_WGS        1024: workgroups a split-K launch aims at (tiles x splits; at most 64 splits)
     int gg_nmajor;         // VG_GG_NMAJOR         1: XCD-major over n tiles where the weights are the larger operand (2: always)
     int edge;              // VG_EDGE              1: narrow-K direct convolution for the 3-channel image layers
+    int nk_wgs;            // VG_NK_WGS            0: most workgroups of a narrow-K direct convolution launch (0: as many as are resident at once; each walks its share of the 256-pixel tiles)
     int wg_reduce_t;       // VG_WG_REDUCE_T       1: streaming transpose-reduce of the weight-gradient slabs
     int wg_target;         // VG_WG_TARGET         512: workgroups the wgrad split-M factor aims for
     int wg_spec;           // VG_WG_SPEC           3: wave-specialised 128 x 256 wgrad kernel (0: one role per wave)

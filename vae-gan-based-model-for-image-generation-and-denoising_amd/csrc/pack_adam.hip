@@ -216,11 +216,16 @@ struct PrologueArgs {
     double lr[VG_PROLOGUE_MAX], beta1[VG_PROLOGUE_MAX], beta2[VG_PROLOGUE_MAX];
     int n;
 };
-__global__ void step_prologue_kernel(const PrologueArgs a) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    if (a.rng != nullptr) a.rng[1] += 1ull;
-    for (int i = 0; i < a.nzero; ++i) a.zero[i] = 0.f;
-    for (int i = 0; i < a.n; ++i) {
+// One lane per optimizer (VG_PROLOGUE_MAX lanes): a single thread walking them paid two pow() per optimizer one after the
+// other.  Lane 0 also advances the counter and zeroes the loss slots.
+__global__ __launch_bounds__(VG_PROLOGUE_MAX) void step_prologue_kernel(const PrologueArgs a) {
+    const int i = threadIdx.x;
+    if (blockIdx.x != 0) return;
+    if (i == 0) {
+        if (a.rng != nullptr) a.rng[1] += 1ull;
+        for (int k = 0; k < a.nzero; ++k) a.zero[k] = 0.f;
+    }
+    if (i < a.n) {
         float* state = a.state[i];
         const double t = (double)state[0] + 1.0;
         state[0] = (float)t;
@@ -433,6 +438,6 @@ extern "C" int vg_step_prologue(uint64_t* rng, float* const* states, const doubl
         VG_CHECK_ARG(states[i] != nullptr && lr[i] >= 0.0, VG_EINVAL);
         a.state[i] = states[i]; a.lr[i] = lr[i]; a.beta1[i] = beta1[i]; a.beta2[i] = beta2[i];
     }
-    hipLaunchKernelGGL(step_prologue_kernel, dim3(1), dim3(1), 0, vg_stream(stream), a);
+    hipLaunchKernelGGL(step_prologue_kernel, dim3(1), dim3(VG_PROLOGUE_MAX), 0, vg_stream(stream), a);
     return VG_LAUNCH_RC();
 }

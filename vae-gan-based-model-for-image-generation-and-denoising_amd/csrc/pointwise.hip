@@ -1010,6 +1010,7 @@ void read_switches() {
     g_sw.splitk_general = env_int("VG_SPLITK_GENERAL", 0);
     g_sw.gg_nmajor = env_int("VG_GG_NMAJOR", 1);
     g_sw.edge = env_int("VG_EDGE", 1);
+    g_sw.nk_wgs = env_int("VG_NK_WGS", 0);
     g_sw.wg_reduce_t = env_int("VG_WG_REDUCE_T", 1);
     g_sw.wg_target = env_int("VG_WG_TARGET", 512);
     g_sw.wg_spec = env_int("VG_WG_SPEC", 3);
