@@ -48,7 +48,7 @@ extern "C" {
 #define VG_ACT_LRELU   2   /* nn.LeakyReLU(slope)    main_vae.py:25, gan_code.py:62-82 */
 #define VG_ACT_TANH    3   /* nn.Tanh()              gan_code.py:50 (vg_tnconv epilogue only) */
 
-#define VG_ABI_VERSION 22  /* 2: vg_pack_desc.tile_start, SyncBN / WGAN / data-path entry points; 3: in-kernel noise (vg_*_rng);
+#define VG_ABI_VERSION 23  /* 2: vg_pack_desc.tile_start, SyncBN / WGAN / data-path entry points; 3: in-kernel noise (vg_*_rng);
                              4: vg_bn_finalize_act_forward, vg_bn_backward_finalize_apply;
                              7: vg_bce_pair_forward_backward;
                              8: vg_head_backward; round-3 prune -- the opt-in experiments of ABI 5 / 6 that measured slower (input prologue of
@@ -68,7 +68,8 @@ extern "C" {
                              21: vg_gg_plan.timing_family / .ws_bytes: callers size their buffers from the plan record; the four
                                  side queries of vg_gather_gemm (slab count, timer family, tile rows, workspace bytes) and the
                                  "supported" query of vg_bn_finalize_act_forward (vg_bn_launch_plan(VG_BN_PLAN_FUSED).fused) are gone;
-                             22: weight averaging: vg_ema_update */
+                             22: weight averaging: vg_ema_update;
+                             23: vg_wgrad_plan / vg_wg_plan, vg_edge_wgrad_plan / vg_ew_plan replace vg_wgrad_ws_bytes / vg_edge_wgrad_ws_bytes */
 int vg_abi_version(void);
 /* The library reads its optional kernel-selection switches (VG_* environment variables, DESIGN.md "Runtime switches")
  * ONCE, when it is loaded; nothing on a launch path calls getenv.  A process that changes one of them afterwards
@@ -189,8 +190,37 @@ typedef struct vg_wg_desc {
     const void* zeros;                /* >= 64 zero bytes (16-byte aligned) for the LDS-DMA path; NULL = register path */
 } vg_wg_desc;
 
-int64_t vg_wgrad_ws_bytes(const vg_wg_desc* d, int dtype);
 int vg_wgrad(const vg_wg_desc* d, int dtype, void* stream);
+
+/* What vg_wgrad launches for a descriptor under the current switches (host-only query; needs no GPU).  The launcher builds
+ * this same record and launches from it, so the query cannot drift from the launch.  The query validates the geometry like
+ * a launch; pointers of the descriptor are only tested against NULL / for alignment: `zeros` takes part in the choice of the
+ * main kernel (NULL: register-staged) and the 16-byte alignment of `dW` in the choice of the reduce kernel (the streaming
+ * one stores 16-byte vectors); P, Q and ws are not looked at.  So a caller asks BEFORE it allocates, with the zero page (or
+ * any non-NULL placeholder) and dW (or a placeholder of its alignment), and passes a workspace of ws_bytes to the launch. */
+#define VG_WG_MAIN_F32       0   /* wgrad_kernel<VG_F32>: 64 x 64 tile, 32-row stages                                       */
+#define VG_WG_MAIN_BF16_REG  1   /* wgrad_bf16_kernel: 128 x 128 tile, operands staged through registers                    */
+#define VG_WG_MAIN_BF16_DMA  2   /* wgrad_bf16_dma_kernel: 128 x 128 tile, LDS-DMA staging, one role per wave               */
+#define VG_WG_MAIN_WS        3   /* wgrad_bf16_ws_kernel<nqt, nprod>: wave-specialised, 128 x (128 * nqt) per workgroup     */
+#define VG_WG_RED_STREAM     0   /* wgrad_reduce_t_kernel: streaming transpose-reduce, one contiguous run of dW per block   */
+#define VG_WG_RED_GENERIC    1   /* wgrad_reduce_kernel<reduce_tt, reduce_vc>                                               */
+typedef struct vg_wg_plan {
+    int32_t main;              /* VG_WG_MAIN_*                                                                          */
+    int32_t nqt, nprod;        /* VG_WG_MAIN_WS: kq tiles per workgroup and producer waves (<1,8>, <2,4>, <2,8>); else 0 */
+    int32_t tile;              /* output tile edge: 64 (f32) | 128 (bf16)                                               */
+    int32_t tiles_kq, tiles_np;/* tiles over K = TH*TW*QC and over PC; the main grid is (tiles_kq / max(nqt, 1), tiles_np,
+                                  nsplit)                                                                               */
+    int32_t nsplit;            /* splits of the pixel rows M = B*GH*GW = slabs in the workspace                         */
+    int32_t rows_per_split;    /* whole stages; the last split holds M - (nsplit - 1) * rows_per_split rows             */
+    int32_t stage_rows;        /* pixel rows per main-loop stage                                                        */
+    int32_t xcd_order;         /* 1: workgroups are dealt so that one XCD owns whole splits                             */
+    int32_t reduce;            /* VG_WG_RED_*: the second launch                                                         */
+    int32_t reduce_tt;         /* generic reduce: taps per thread, 4 | 16 (0 for the streaming one, as the next two)    */
+    int32_t reduce_vc;         /*                 channels per thread, 1 | 4                                            */
+    int32_t reduce_spl;        /*                 threads that share the slabs of one element, 1 | 8 | 32               */
+    int64_t ws_bytes;          /* slab workspace the launch needs: nsplit * tiles_np * tiles_kq * tile * tile * 4       */
+} vg_wg_plan;
+int vg_wgrad_plan(const vg_wg_desc* d, int dtype, vg_wg_plan* out);
 
 /* ------------------------------------------------------------------------------------------
  * Operand packing: f32 parameter tensor (reference layout) -> K-major GEMM operand
@@ -367,7 +397,7 @@ typedef struct vg_tn_desc {
  * then dW is the [C][N][K][K] weight gradient, s_c = N*K*K, s_n = K*K) or the input of nn.ConvTranspose2d(C, N, K, S, P)
  * (gan_code.py:49 -- dW is [C][N][K][K] as well).  Nr: the 3-channel tensor on the other side, [B][NH][NW][8] bf16 with
  * channels >= N zero (the image, or the image gradient).  N <= 3, K = 3 | 4, S = 1 | 2.
- * ws: vg_edge_wgrad_ws_bytes() bytes of scratch (one [K*K*4 padded][C] f32 partial per workgroup, summed in fixed
+ * ws: vg_ew_plan.ws_bytes bytes of scratch (one [K*K*4 padded][C] f32 partial per workgroup, summed in fixed
  * order: bitwise reproducible).  zeros: >= 64 readable zero bytes. */
 typedef struct vg_ew_desc {
     const void* Wd;
@@ -378,8 +408,21 @@ typedef struct vg_ew_desc {
     const void* zeros;
     int32_t B, WH, WW, C, NH, NW, N, K, S, P, s_c, s_n, accumulate;
 } vg_ew_desc;
-int64_t vg_edge_wgrad_ws_bytes(const vg_ew_desc* d);
 int vg_edge_wgrad(const vg_ew_desc* d, void* stream);
+/* What vg_edge_wgrad launches for a descriptor (host-only query; needs no GPU): the record the launcher builds and launches
+ * from.  The query validates the geometry like a launch and looks at no pointer of the descriptor; a shape the kernel does
+ * not take gives the launch's error code.  A workgroup walks tiles of rows_per_tile rows of the wide operand (all of one
+ * image); the second launch sums the `grid` partials. */
+typedef struct vg_ew_plan {
+    int32_t ct;                /* edge_wgrad_kernel<ct>: tiles of 16 wide channels, C / 16 = 1 | 2 | 4                   */
+    int32_t jt;                /* tiles of 16 (tap, narrow channel) rows: 3 (K = 3) | 4 (K = 4)                          */
+    int32_t rows_per_tile;     /* R: rows of the wide operand per tile (<= 256 pixels, patch of the narrow one in LDS)   */
+    int32_t tiles_per_img;     /* ceil(WH / R)                                                                           */
+    int32_t ntiles;            /* B * tiles_per_img                                                                      */
+    int32_t grid;              /* workgroups: min(ntiles, 512), each walks several tiles                                 */
+    int64_t ws_bytes;          /* grid * jt * 16 * C * 4                                                                 */
+} vg_ew_plan;
+int vg_edge_wgrad_plan(const vg_ew_desc* d, vg_ew_plan* out);
 int vg_tnconv_supported(const vg_tn_desc* d);     /* 0 if vg_tnconv takes this shape, else the error code */
 int vg_tnconv(const vg_tn_desc* d, void* stream);
 

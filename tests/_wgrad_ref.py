@@ -4,9 +4,9 @@ every summation order give the same f32 bits, and the case table of tests/test_w
     dW[np*s_np + cq*s_cq + (a*TW + c)*s_t] = sum_{b,gy,gx} P[b,gy,gx,np] * Q[b, gy*SY + y0 + DY*a, gx*SX + x0 + DX*c, cq]
 
 wgrad_ref is written from that comment and takes a geometry.WGSpec: it knows nothing of torch.nn.grad, of tiles, splits or
-slabs.  plan() is the only part that looks at the launcher (csrc/wgrad.hip, vg_wgrad): it names the kernels a case reaches,
-so that the case table can be checked for coverage -- if the launcher's rules change, the coverage test fails and the table is
-revisited."""
+slabs.  Which kernels a case reaches is not restated here: label() only gives names to the launcher's own plan record
+(vg_wgrad_plan, the record vg_wgrad launches from), and every row of the case table carries the names it is there for -- if
+the launcher's rules change, the tests that compare the two fail and the table is revisited."""
 import dataclasses
 import importlib
 
@@ -77,48 +77,22 @@ def int_dw(spec, seed):
     return _VALS[torch.randint(0, 6, (spec.NP * spec.s_np,), generator=gen)]
 
 
-# ---- which kernels a case reaches (restates the launcher's documented choices) -----------------------------------------
-def plan(spec, dtype, ws_bytes, wg_spec=3, wg_dma=1, wg_reduce_t=1):
-    """nsplit recovered from vg_wgrad_ws_bytes (= nsplit * NPpad * tiles_kq * tile * 4) and the labels of the main and the
-    reduce kernel vg_wgrad launches for it under the given VG_WG_SPEC / VG_WG_DMA / VG_WG_REDUCE_T (callers pass a zero
-    page, as ops.wgrad does)."""
-    tile, srows = (64, 32) if dtype == G.F32 else (128, 64)
-    T = spec.TH * spec.TW
-    KQ = T * spec.QC
-    tiles_kq, tiles_np = -(-KQ // tile), -(-spec.PC // tile)
-    slab = tiles_np * tile * tiles_kq * tile * 4
-    assert ws_bytes > 0 and ws_bytes % slab == 0, (ws_bytes, slab)
-    nsplit = ws_bytes // slab
-    M = spec.B * spec.GH * spec.GW
-    rps = -(-(-(-M // srows)) // nsplit) * srows                     # whole stages per split
-    last = M - (nsplit - 1) * rps
-    assert 0 < last <= rps, (M, nsplit, rps)
-    if dtype == G.F32:
-        main = "f32"
-    elif not wg_dma:
-        main = "bf16_reg"
-    elif wg_spec == 3 and tiles_kq % 2 == 0:
-        main = "ws<2,8>"
-    elif wg_spec == 2 and tiles_kq % 2 == 0:
-        main = "ws<2,4>"
-    elif wg_spec != 0:
-        main = "ws<1,8>"
-    else:
-        main = "bf16_dma"
-    stream = (wg_reduce_t and T <= 16 and spec.s_t == 1 and spec.s_cq == T and spec.QC % 64 == 0 and spec.NQ == spec.QC
-              and spec.s_np % 4 == 0)
-    if dtype == G.BF16 and stream and nsplit <= 16 and spec.NP * (spec.QC >> 6) >= 256:
-        reduce, SPL = "reduce_t", 0
-    else:
-        vec = spec.NQ % 4 == 0 and spec.QC % 4 == 0
-        VC = 4 if vec else 1
-        total = spec.NP * -(-spec.NQ // VC)
-        SPL = 32 if nsplit >= 64 else (8 if nsplit >= 8 else 1)
-        EL = 256 // SPL
-        big = T >= 16 and -(-total // EL) >= 2048
-        reduce = f"generic<{16 if big else 4},{VC}> SPL={SPL}"
-    return dict(nsplit=nsplit, rows_per_split=rps, last_rows=last, partial_stage=last % srows != 0, T=T, main=main,
-                reduce=reduce)
+# ---- which kernels a case reaches: read from the launcher's own record ---------------------------------------------------
+def label(p):
+    """(main, reduce): the names this table uses for the kernels of a plan record (ops.wgrad_plan, vg_wg_plan)."""
+    main = f"ws<{p['nqt']},{p['nprod']}>" if p["main"] == "ws" else p["main"]
+    if p["reduce"] == "stream":
+        return main, "reduce_t"
+    return main, f"generic<{p['reduce_tt']},{p['reduce_vc']}> SPL={p['reduce_spl']}"
+
+
+def facts(spec, p):
+    """The plan record with the labels and what follows from its fields for this geometry: the rows of the last split,
+    whether that split ends in a partial stage, the tap count."""
+    last = spec.B * spec.GH * spec.GW - (p["nsplit"] - 1) * p["rows_per_split"]
+    assert 0 < last <= p["rows_per_split"], (last, p)
+    main, reduce = label(p)
+    return dict(p, main=main, reduce=reduce, last_rows=last, partial_stage=last % p["stage_rows"] != 0, T=spec.TH * spec.TW)
 
 
 # ---- the case table ----------------------------------------------------------------------------------------------------
@@ -134,11 +108,16 @@ class Case:
     p: int = 0
     dtypes: tuple = (G.F32, G.BF16)
     target: int = 0    # VG_WG_TARGET, 0: the default
+    label: str = ""    # "main kernel (of the bf16 launch, where the row has one), reduce kernel" under the row's own switches
 
     @property
     def id(self):
         geo = f"{self.kind}-B{self.B}-H{self.H}-{self.Cin}x{self.Cout}"
         return geo + (f"-k{self.k}s{self.s}p{self.p}" if self.kind != "linear" else "") + (f"-t{self.target}" if self.target else "")
+
+    def kernels(self, dtype):
+        main, reduce = self.label.split(", ")
+        return ("f32" if dtype == G.F32 else main), reduce
 
     def spec(self, dtype):
         if self.kind == "conv":
@@ -149,31 +128,34 @@ class Case:
 
 
 _F, _B = (G.F32,), (G.BF16,)
-NSPLIT64 = Case("conv", 16, 64, 8, 8, 4, 2, 1)                        # M=16384, nsplit 64, SPL=32; bf16 ws<1,8>
-PARTIAL_LAST = Case("conv", 16, 66, 8, 8, 4, 2, 1, _B)                # nsplit 55, SPL=8, last split 144 rows = 2 1/4 stages
-REDUCE_T6 = Case("conv", 24, 16, 64, 256, 4, 2, 1, _B)                # reduce_t, nsplit 6 (4 + 2)
-REDUCE_T9TAPS = Case("conv", 13, 16, 64, 256, 3, 1, 1, _B)            # reduce_t with T=9, nsplit 13, ws<1,8>
-TRANSPOSED = Case("convT", 12, 8, 256, 64, 4, 2, 1, _B)               # reduce_t through the transposed form, nsplit 3
-LINEAR36 = Case("linear", 70, 6, 40, 24)                              # 36 taps, 9 tap groups
+_G44 = "generic<4,4> SPL="
+NSPLIT64 = Case("conv", 16, 64, 8, 8, 4, 2, 1, label="ws<1,8>, " + _G44 + "32")                 # M=16384, nsplit 64
+XCD_DEFAULT = Case("conv", 32, 64, 8, 8, 4, 2, 1, label="ws<1,8>, " + _G44 + "32")              # M=32768, nsplit 128, 1 | 2 tiles: XCD order by default
+PARTIAL_LAST = Case("conv", 16, 66, 8, 8, 4, 2, 1, _B, label="ws<1,8>, " + _G44 + "8")          # nsplit 55, last split 144 rows = 2 1/4 stages
+REDUCE_T6 = Case("conv", 24, 16, 64, 256, 4, 2, 1, _B, label="ws<2,8>, reduce_t")               # nsplit 6 (4 + 2)
+REDUCE_T9TAPS = Case("conv", 13, 16, 64, 256, 3, 1, 1, _B, label="ws<1,8>, reduce_t")           # T=9, nsplit 13
+TRANSPOSED = Case("convT", 12, 8, 256, 64, 4, 2, 1, _B, label="ws<2,8>, reduce_t")              # the transposed form, nsplit 3
+LINEAR36 = Case("linear", 70, 6, 40, 24, label="ws<2,8>, " + _G44 + "1")                        # 36 taps, 9 tap groups
 CASES = [
     NSPLIT64,
+    XCD_DEFAULT,
     PARTIAL_LAST,
-    Case("conv", 16, 64, 3, 32, 4, 2, 0, _F),                         # 31x31 grid, nsplit 54, <4,1> SPL=8, last split 112 rows
-    Case("conv", 8, 32, 6, 10, 4, 2, 1, _F),                          # NQ % 4 != 0: <4,1>, SPL=8
-    Case("conv", 4, 31, 32, 64, 4, 2, 0, _B),                         # nsplit 3, ws<2,8>, SPL=1, partial last split
-    Case("conv", 3, 33, 8, 8, 4, 2, 1),                               # nsplit 3, odd H
-    Case("conv", 5, 9, 12, 20, 3, 1, 1),                              # 9 taps: partial tap group in <4,.>; M=405
-    Case("conv", 7, 12, 136, 72, 4, 2, 1, _B),                        # odd kq tile count (17), NP not a tile multiple
-    Case("conv", 8, 16, 64, 256, 4, 2, 1, _B),                        # reduce_t, nsplit 2
+    Case("conv", 16, 64, 3, 32, 4, 2, 0, _F, label="f32, generic<4,1> SPL=8"),                  # 31x31 grid, nsplit 54, last split 112 rows
+    Case("conv", 8, 32, 6, 10, 4, 2, 1, _F, label="f32, generic<4,1> SPL=8"),                   # NQ % 4 != 0
+    Case("conv", 4, 31, 32, 64, 4, 2, 0, _B, label="ws<2,8>, " + _G44 + "1"),                   # nsplit 3, partial last split
+    Case("conv", 3, 33, 8, 8, 4, 2, 1, label="ws<1,8>, " + _G44 + "1"),                         # nsplit 3, odd H
+    Case("conv", 5, 9, 12, 20, 3, 1, 1, label="ws<2,8>, " + _G44 + "1"),                        # 9 taps: partial tap group in <4,.>; M=405
+    Case("conv", 7, 12, 136, 72, 4, 2, 1, _B, label="ws<1,8>, " + _G44 + "1"),                  # odd kq tile count (17), NP not a tile multiple
+    Case("conv", 8, 16, 64, 256, 4, 2, 1, _B, label="ws<2,8>, reduce_t"),                       # nsplit 2
     REDUCE_T6,
-    Case("conv", 40, 16, 64, 256, 4, 2, 1, _B),                       # reduce_t, nsplit 10
+    Case("conv", 40, 16, 64, 256, 4, 2, 1, _B, label="ws<2,8>, reduce_t"),                      # nsplit 10
     REDUCE_T9TAPS,
     TRANSPOSED,
-    Case("linear", 300, 2, 256, 200, dtypes=_B),                      # reduce_t T=4, M=300 (partial stage)
-    Case("linear", 300, 1, 256, 300, dtypes=_B),                      # reduce_t T=1
+    Case("linear", 300, 2, 256, 200, dtypes=_B, label="ws<2,8>, reduce_t"),                     # T=4, M=300 (partial stage)
+    Case("linear", 300, 1, 256, 300, dtypes=_B, label="ws<2,8>, reduce_t"),                     # T=1
     LINEAR36,
-    Case("conv", 2, 64, 512, 512, 4, 2, 1, _F, 8192),                 # <16,4>, SPL=8
-    Case("conv", 16, 64, 130, 128, 4, 2, 1, _F, 8192),                # <16,1>, SPL=32
+    Case("conv", 2, 64, 512, 512, 4, 2, 1, _F, 8192, label="f32, generic<16,4> SPL=8"),
+    Case("conv", 16, 64, 130, 128, 4, 2, 1, _F, 8192, label="f32, generic<16,1> SPL=32"),
 ]
 CASE_PARAMS = [(c, dt) for c in CASES for dt in c.dtypes]
 
@@ -186,3 +168,47 @@ SWITCH_PARAMS = [(c, dt, name, val) for c in SWITCH_CASES for dt in c.dtypes for
                  if dt == G.BF16 or name in _F32_SWITCHES]
 CASE_IDS = [f"{c.id}-{DT_NAME[dt]}" for c, dt in CASE_PARAMS]
 SWITCH_IDS = [f"{c.id}-{DT_NAME[dt]}-{name}={val}" for c, dt, name, val in SWITCH_PARAMS]
+
+
+# ---- the edge layers (vg_edge_wgrad) ---------------------------------------------------------------------------------------
+EDGE_SHAPES = [("conv", 64, 4, 2, 1, 64, 3),     # Discriminator's first layer, S=64 (gan_code.py:61)
+               ("convT", 64, 3, 1, 1, 64, 2),   # Generator's last layer, S=64 (gan_code.py:49)
+               ("conv", 32, 4, 2, 0, 64, 2),    # Encoder's first layer: 31x31 outputs, p=0
+               ("conv", 32, 4, 2, 1, 128, 1),   # S=128 members
+               ("convT", 32, 3, 1, 1, 128, 1),
+               ("conv", 64, 4, 2, 1, 16, 5),    # many images per workgroup walk, tiny maps
+               ("conv", 16, 4, 2, 1, 256, 1),   # S=256 members: 16 channels on the wide side
+               ("convT", 16, 3, 1, 1, 256, 1),  # (gan_code.py:49 and :61 as written)
+               ("conv", 16, 4, 2, 1, 32, 3)]
+
+
+def edge_id(kind, C, k, s, p, H, B):
+    return f"{kind}-C{C}-k{k}s{s}p{p}-H{H}-B{B}"
+
+
+def edge_spec(kind, C, k, s, p, H, B):
+    """EWSpec of a row of EDGE_SHAPES: the 3-channel side is the input of a Conv2d, the output of a ConvTranspose2d."""
+    if kind == "conv":
+        return G.conv_wgrad_edge(B, H, H, 3, C, k, s, p, G.BF16)
+    return G.convT_wgrad_edge(B, H, H, C, 3, k, s, p, G.BF16)
+
+
+# ---- the weight gradients of the three networks ----------------------------------------------------------------------------
+def network_wgrads(S, B, dtype):
+    """Every weight gradient a training iteration of the three networks launches at this shape, as engine.py's backward
+    issues them (beside _gg_ref.network_launches; the Discriminator also at 2B, the grouped pass) -> [(key, EWSpec, None)
+    for the edge layers | (key, WGSpec, kernel dtype)], host only."""
+    import _gg_ref
+    out = []
+    for name, m in _gg_ref.build_networks(S, dtype):
+        eng = m._engine
+        for nb in ((B, 2 * B) if name == "D" else (B,)):
+            for i, st in enumerate(eng.stages):
+                if st.kind == "head":
+                    continue
+                ew = eng.edge_wg(i, nb)
+                if ew is not None:
+                    out.append((f"{name}.{i}.edge_wgrad.B{nb}", ew, None))
+                else:
+                    out.append((f"{name}.{i}.wgrad.B{nb}", eng.spec(i, nb, "wgrad"), eng.dtype))
+    return out

@@ -10,6 +10,7 @@ import torch.nn.functional as F
 
 from _emulate import from_nhwc, to_nhwc
 from _pack_ref import pack_specs
+from _wgrad_ref import EDGE_SHAPES
 
 pytestmark = pytest.mark.gpu
 
@@ -369,15 +370,7 @@ def test_edge_layer_kernel_rejects_what_it_does_not_take(ops):
         ops.tnconv(tn, x, torch.zeros(5, dtype=torch.bfloat16, device=DEV))
 
 
-@pytest.mark.parametrize("kind,C,k,s,p,H,B", [("conv", 64, 4, 2, 1, 64, 3),     # Discriminator's first layer, S=64 (gan_code.py:61)
-                                              ("convT", 64, 3, 1, 1, 64, 2),   # Generator's last layer, S=64 (gan_code.py:49)
-                                              ("conv", 32, 4, 2, 0, 64, 2),    # Encoder's first layer: 31x31 outputs, p=0
-                                              ("conv", 32, 4, 2, 1, 128, 1),   # S=128 members
-                                              ("convT", 32, 3, 1, 1, 128, 1),
-                                              ("conv", 64, 4, 2, 1, 16, 5),    # many images per workgroup walk, tiny maps
-                                              ("conv", 16, 4, 2, 1, 256, 1),   # S=256 members: 16 channels on the wide side
-                                              ("convT", 16, 3, 1, 1, 256, 1),  # (gan_code.py:49 and :61 as written)
-                                              ("conv", 16, 4, 2, 1, 32, 3)])
+@pytest.mark.parametrize("kind,C,k,s,p,H,B", EDGE_SHAPES)
 def test_edge_layer_weight_gradient_vs_torch(ops, kind, C, k, s, p, H, B):
     """vg_edge_wgrad (transposed LDS reads of both operands, narrow operand read straight from the image patch) against
     torch's convolution weight gradient in fp64 on the bf16-rounded operands; plain and accumulating."""
@@ -400,11 +393,16 @@ def test_edge_layer_weight_gradient_vs_torch(ops, kind, C, k, s, p, H, B):
         ew = G.convT_wgrad_edge(B, H, H, C, 3, k, s, p, G.BF16)
         wide, narrow = _dev(to_nhwc(x, C), G.BF16, ops), _dev(to_nhwc(dy, 8), G.BF16, ops)
     assert ew is not None
+    assert ops.edge_wgrad_plan(ew)["ct"] == C // 16                   # edge_wgrad_kernel<1 | 2 | 4>
     ref = w.grad
     dW = torch.full((C, 3, k, k), float("nan"), device=DEV)
+    n0 = ops.launch_count()
     ops.edge_wgrad(ew, wide, narrow, dW, False)
+    assert ops.launch_count() - n0 == 2
     close(dW.double().cpu(), ref, G.F32, f32=(1e-4, 2e-5))            # exact bf16 products, f32 accumulation
+    n0 = ops.launch_count()
     ops.edge_wgrad(ew, wide, narrow, dW, True)                        # accumulate: twice the gradient
+    assert ops.launch_count() - n0 == 2
     close(dW.double().cpu(), 2 * ref, G.F32, f32=(1e-4, 4e-5))
     first = dW.clone()
     ops.edge_wgrad(ew, wide, narrow, dW, False)

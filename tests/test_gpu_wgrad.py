@@ -3,10 +3,13 @@
 Every real channel holds +-1, +-2 or +-3: the products are integers of magnitude <= 9 and every partial sum stays below 2^24,
 so f32 adds them exactly in ANY order.  Whatever main kernel, split count, slab order or reduce kernel a case takes, it has
 to produce the reference's bits; a mismatch is a wrong, missing or doubled term, never rounding, and the difference names
-it (one product = one pixel row).  The case table (with the branch every row reaches) is in _wgrad_ref.py; its coverage
-of the launcher is asserted against the built library in tests/test_wgrad_cpu.py."""
+it (one product = one pixel row).  The case table (with the branch every row reaches) is in _wgrad_ref.py; before each
+launch the launcher's own plan record has to name the kernels the row is there for, and each call has to issue exactly the
+two launches of that plan.  The table's coverage of the launcher is asserted in tests/test_wgrad_cpu.py."""
 import functools
 import importlib
+import json
+import os
 
 import pytest
 import torch
@@ -45,15 +48,20 @@ def _first_mismatch(wg, got, ref):
            f"reference {float(ref[i])}, difference {float(got[i]) - float(ref[i])}"
 
 
-def _check(ops, case, dtype):
+def _check(ops, case, dtype, kernels):
     wg, P, Q, d0, ref = _problem(case, dtype)
+    assert R.label(ops.wgrad_plan(wg, dtype)) == kernels
     Pd, Qd = P.to(DEV), Q.to(DEV)
     dW = torch.full((ref.numel(),), float("nan"), device=DEV)
+    n0 = ops.launch_count()
     ops.wgrad(wg, Pd, Qd, dW, False, dtype)
+    assert ops.launch_count() - n0 == 2
     got = dW.cpu()
     assert torch.equal(got, ref), _first_mismatch(wg, got, ref)
     dW = d0.to(DEV)
+    n0 = ops.launch_count()
     ops.wgrad(wg, Pd, Qd, dW, True, dtype)
+    assert ops.launch_count() - n0 == 2
     got = dW.cpu()
     assert torch.equal(got, d0 + ref), "accumulate: " + _first_mismatch(wg, got, d0 + ref)
 
@@ -62,7 +70,14 @@ def _check(ops, case, dtype):
 def test_weight_gradient_of_integer_operands_is_exact(ops, vg_switch, case, dtype):
     if case.target:
         vg_switch("VG_WG_TARGET", case.target)
-    _check(ops, case, dtype)
+    _check(ops, case, dtype, case.kernels(dtype))
+
+
+@functools.lru_cache(maxsize=None)
+def _switched_kernels():
+    """id of a SWITCH_PARAMS row -> (main, reduce) it reached at the parent commit (tools/gen_golden_wg_plan.py)."""
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "wg_plan_parent.json")) as f:
+        return {k: (v["main"], v["reduce"]) for k, v in json.load(f)["switches"].items()}
 
 
 @pytest.mark.parametrize("case,dtype,switch,value", R.SWITCH_PARAMS, ids=R.SWITCH_IDS)
@@ -71,4 +86,4 @@ def test_every_build_of_the_weight_gradient_gives_the_same_bits(ops, vg_switch, 
     (VG_WG_REDUCE_T), other split counts (VG_WG_TARGET) and the forced XCD order: each equals the reference exactly, hence
     every other variant."""
     vg_switch(switch, value)
-    _check(ops, case, dtype)
+    _check(ops, case, dtype, _switched_kernels()[f"{case.id}-{R.DT_NAME[dtype]}-{switch}={value}"])

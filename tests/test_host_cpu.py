@@ -187,8 +187,16 @@ def test_c_abi_rejects_bad_arguments_on_host():
     assert lib.vg_bn_launch_plan(1, 64, 64, 1, 2, 1, 0, ctypes.byref(bn)) == -3
     assert lib.vg_bn_launch_plan(3, 64, 96, 1, 1, 1, 4, ctypes.byref(bn)) == 0 and bn.fused == 0 and bn.kind == 3
     assert lib.vg_bn_launch_plan(0, 64, 64, 2, 0, 1, 0, ctypes.byref(bn)) == 0 and (bn.kind, bn.vec, bn.groups) == (0, 4, 2)
-    w = L.WGDesc()
-    assert lib.vg_wgrad_ws_bytes(ctypes.byref(w), 0) == -1
+    # the weight-gradient launchers' plans, validated like their launches
+    w, wp = L.WGDesc(), L.WGPlan()
+    assert lib.vg_wgrad_plan(ctypes.byref(w), 0, ctypes.byref(wp)) == -1
+    assert lib.vg_wgrad_plan(ctypes.byref(w), 7, ctypes.byref(wp)) == -3
+    assert lib.vg_wgrad_plan(ctypes.byref(w), 0, None) == -1
+    e, ep = L.EWDesc(), L.EWPlan()
+    assert lib.vg_edge_wgrad_plan(ctypes.byref(e), ctypes.byref(ep)) == -1
+    assert lib.vg_edge_wgrad_plan(ctypes.byref(e), None) == -1
+    e = L.EWDesc(B=1, WH=8, WW=8, C=48, NH=16, NW=16, N=3, K=4, S=2, P=1)
+    assert lib.vg_edge_wgrad_plan(ctypes.byref(e), ctypes.byref(ep)) == -3
     assert lib.vg_adam_step(None, None, None, None, 0, 1e-3, 0.9, 0.999, 1e-8, 1.0, None, None) == -1
     # the iteration prologue: nothing to do at all, too many optimizers, a NULL state
     assert lib.vg_step_prologue(None, None, None, None, None, 0, None, 0, None) == -1

@@ -1,9 +1,11 @@
 """CPU: the weight-gradient restatement of tests/_wgrad_ref.py against torch in f64 (which also validates the WGSpec
 builders of geometry.py), the blind-spot check of the integer case table, and the coverage of the launcher's branches by
-that table, asked of the built library (vg_wgrad_ws_bytes needs no GPU)."""
+that table, read from the launcher's own plan record (vg_wgrad_plan / vg_edge_wgrad_plan need no GPU) and held against what
+the parent commit planned (tests/golden/wg_plan_parent.json, tools/gen_golden_wg_plan.py)."""
 import dataclasses
 import importlib
-from ctypes import byref
+import json
+import os
 
 import pytest
 import torch
@@ -13,7 +15,8 @@ import _wgrad_ref as R
 from _emulate import to_nhwc
 
 G = R.G
-L = importlib.import_module(R.PKG + "._lib")
+with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "wg_plan_parent.json")) as _f:
+    PARENT = json.load(_f)
 
 REF_CASES = [  # B, H, Cin, Cout, k, s, p
     (2, 8, 8, 16, 4, 2, 1),          # k4 s2 p1
@@ -104,41 +107,43 @@ def test_every_case_reads_the_element_that_is_negated(case, dtype):
     assert R.wgrad_ref(one, P[b:b + 1], dQ).abs().max() > 0, ("Q", b, iy, ix, ch)
 
 
-def _ws_bytes(wg, dtype):
-    d = L.WGDesc(B=wg.B, GH=wg.GH, GW=wg.GW, PC=wg.PC, NP=wg.NP, QH=wg.QH, QW=wg.QW, QC=wg.QC, NQ=wg.NQ, SY=wg.SY, SX=wg.SX,
-                 DY=wg.DY, DX=wg.DX, TH=wg.TH, TW=wg.TW, y0=wg.y0, x0=wg.x0, s_np=wg.s_np, s_cq=wg.s_cq, s_t=wg.s_t)
-    n = L.load().vg_wgrad_ws_bytes(byref(d), dtype)
-    assert n > 0, n
-    return n
+def _same_as_parent(p, want, what):
+    """p: R.facts of the launcher's record; want: the fixture row of the same geometry and switches."""
+    for key in ("ws_bytes", "nsplit", "rows_per_split", "last_rows", "partial_stage", "main", "reduce"):
+        assert p[key] == want[key], f"{what}: {key} is {p[key]}, the parent commit planned {want[key]}"
 
 
 def test_case_table_reaches_every_branch_of_the_launcher(vg_switch, monkeypatch, capsys):
-    """The labels plan() derives from the library's own split count, over the case table and the switch settings of
-    tests/test_gpu_wgrad.py, name every main kernel and every reduce-kernel form vg_wgrad can launch."""
+    """The launcher's own record (ops.wgrad_plan), over the case table and the switch settings of tests/test_gpu_wgrad.py:
+    every row reaches the kernels it is labelled with and plans what the parent commit planned, and the labels name every
+    main kernel and every reduce-kernel form vg_wgrad can launch."""
     ops = importlib.import_module(R.PKG + ".ops")
     names = sorted({n for n, _ in R.SWITCHES})
     rows = []
 
-    def record(case, dtype, **sw):
+    def record(name, want, case, dtype, **sw):
         for n in names:
             monkeypatch.delenv(n, raising=False)
         ops.reload_switches()
         for n, v in sw.items():
             vg_switch(n, v)
         wg = case.spec(dtype)
-        p = R.plan(wg, dtype, _ws_bytes(wg, dtype), wg_spec=sw.get("VG_WG_SPEC", 3), wg_dma=sw.get("VG_WG_DMA", 1),
-                   wg_reduce_t=sw.get("VG_WG_REDUCE_T", 1))
-        rows.append((f"{case.id}-{R.DT_NAME[dtype]}", sw, dtype, p))
+        p = R.facts(wg, ops.wgrad_plan(wg, dtype))
+        _same_as_parent(p, want, name)
+        rows.append((name, sw, dtype, p))
 
-    for case, dtype in R.CASE_PARAMS:
-        record(case, dtype, **({"VG_WG_TARGET": case.target} if case.target else {}))
+    for (case, dtype), name in zip(R.CASE_PARAMS, R.CASE_IDS):
+        record(name, PARENT["cases"][name], case, dtype, **({"VG_WG_TARGET": case.target} if case.target else {}))
+        assert (rows[-1][3]["main"], rows[-1][3]["reduce"]) == case.kernels(dtype), name
+        assert rows[-1][3]["xcd_order"] == (case is R.XCD_DEFAULT), name
     n_table = len(rows)
-    for case, dtype, name, val in R.SWITCH_PARAMS:
-        record(case, dtype, **{name: val})
+    for (case, dtype, sw_name, val), sid in zip(R.SWITCH_PARAMS, R.SWITCH_IDS):
+        record(f"{case.id}-{R.DT_NAME[dtype]}", PARENT["switches"][sid], case, dtype, **{sw_name: val})
+        assert rows[-1][3]["xcd_order"] == (sw_name == "VG_WG_XCD"), sid             # =2: always; no other row qualifies
     with capsys.disabled():
         for name, sw, _, p in rows:
             print(f"\n  {name:42s} {str(sw or ''):26s} nsplit {p['nsplit']:3d} rows/split {p['rows_per_split']:5d} "
-                  f"last {p['last_rows']:5d}  {p['main']:8s} {p['reduce']}", end="")
+                  f"last {p['last_rows']:5d}  {p['main']:8s} {p['reduce']}{' xcd' if p['xcd_order'] else ''}", end="")
         print()
 
     table = [p for _, _, _, p in rows[:n_table]]
@@ -163,3 +168,38 @@ def test_case_table_reaches_every_branch_of_the_launcher(vg_switch, monkeypatch,
                for name, sw, _, p in switched)
     # (every case of the subset is already limited by its stage count at the default target: 4096 repeats the default split)
     assert any(sw == {"VG_WG_TARGET": 64} and p["nsplit"] != base[name]["nsplit"] for name, sw, _, p in switched)
+
+
+def test_networks_plan_what_the_parent_commit_planned(monkeypatch):
+    """Under the default switches, every weight gradient of the three networks at the benchmarked shapes: the records of
+    vg_wgrad_plan / vg_edge_wgrad_plan against the workspace sizes and kernels of the parent commit."""
+    import _gg_ref
+    ops = importlib.import_module(R.PKG + ".ops")
+    for n in {n for n, _ in R.SWITCHES}:
+        monkeypatch.delenv(n, raising=False)
+    ops.reload_switches()
+    for S, nb, dtype in _gg_ref.NETWORK_SHAPES:
+        want = PARENT["networks"][f"S{S}_B{nb}_{dtype}"]
+        launches = R.network_wgrads(S, nb, dtype)
+        assert sorted(key for key, _, _ in launches) == sorted(want)
+        for key, sp, kdt in launches:
+            if kdt is None:
+                assert ops.edge_wgrad_plan(sp)["ws_bytes"] == want[key]["ws_bytes"], key
+            else:
+                _same_as_parent(R.facts(sp, ops.wgrad_plan(sp, kdt)), want[key], f"S{S} B{nb} {dtype} {key}")
+
+
+def test_edge_shapes_reach_every_instantiation_of_the_edge_kernel():
+    """The shape list of the edge-layer GPU test (tests/test_gpu_kernels.py), asked of vg_edge_wgrad_plan: it reaches
+    edge_wgrad_kernel<1 | 2 | 4> with 3 and 4 tap-row tiles, and sizes the workspace as the parent commit did."""
+    ops = importlib.import_module(R.PKG + ".ops")
+    plans = {}
+    for row in R.EDGE_SHAPES:
+        ew = R.edge_spec(*row)
+        assert ew is not None, row
+        p = plans[R.edge_id(*row)] = ops.edge_wgrad_plan(ew)
+        assert p["ws_bytes"] == PARENT["edge"][R.edge_id(*row)]["ws_bytes"], row
+        assert p["ct"] == ew.C // 16 and p["jt"] == (4 if ew.K == 4 else 3), (row, p)
+        assert p["tiles_per_img"] == -(-ew.WH // p["rows_per_tile"]) and p["ntiles"] == ew.B * p["tiles_per_img"], (row, p)
+        assert p["grid"] == min(p["ntiles"], 512) and p["ws_bytes"] == p["grid"] * p["jt"] * 16 * ew.C * 4, (row, p)
+    assert {p["ct"] for p in plans.values()} == {1, 2, 4} and {p["jt"] for p in plans.values()} == {3, 4}

@@ -17,7 +17,7 @@ VG_FP8_WSHIFT = 6
 VG_ACT_NONE, VG_ACT_RELU, VG_ACT_LRELU, VG_ACT_TANH = 0, 1, 2, 3
 VG_MAX_PHASE = 4
 VG_EMA_MAX = 4
-ABI_VERSION = 22
+ABI_VERSION = 23
 
 VG_ENOSUP = -3
 _ERR = {-1: "VG_EINVAL (bad shape/size/flag)", -2: "VG_EALIGN (16-byte contract violated)",
@@ -65,6 +65,13 @@ class WGDesc(Structure):
                 ("s_np", c_int32), ("s_cq", c_int32), ("s_t", c_int32), ("accumulate", c_int32), ("zeros", c_void_p)]
 
 
+class WGPlan(Structure):
+    """vg_wg_plan."""
+    _fields_ = [(n, c_int32) for n in ("main", "nqt", "nprod", "tile", "tiles_kq", "tiles_np", "nsplit", "rows_per_split",
+                                       "stage_rows", "xcd_order", "reduce", "reduce_tt", "reduce_vc", "reduce_spl")] + \
+               [("ws_bytes", c_int64)]
+
+
 class TNDesc(Structure):
     """vg_tn_desc."""
     _fields_ = [("X", c_void_p), ("Wp", c_void_p), ("Y", c_void_p), ("Y_nchw", c_void_p), ("eps", c_void_p),
@@ -81,6 +88,11 @@ class EWDesc(Structure):
                 ("B", c_int32), ("WH", c_int32), ("WW", c_int32), ("C", c_int32), ("NH", c_int32), ("NW", c_int32),
                 ("N", c_int32), ("K", c_int32), ("S", c_int32), ("P", c_int32), ("s_c", c_int32), ("s_n", c_int32),
                 ("accumulate", c_int32)]
+
+
+class EWPlan(Structure):
+    """vg_ew_plan."""
+    _fields_ = [(n, c_int32) for n in ("ct", "jt", "rows_per_tile", "tiles_per_img", "ntiles", "grid")] + [("ws_bytes", c_int64)]
 
 
 class PackDesc(Structure):
@@ -104,8 +116,8 @@ SIGNATURES = {
     "vg_timing_collect": (c_int, [_I, POINTER(c_double), POINTER(c_int)]),
     "vg_gather_gemm": (c_int, [POINTER(GGDesc), _I, _P]),
     "vg_gather_gemm_plan": (c_int, [POINTER(GGDesc), _I, POINTER(GGPlan)]),
-    "vg_wgrad_ws_bytes": (c_int64, [POINTER(WGDesc), _I]),
     "vg_wgrad": (c_int, [POINTER(WGDesc), _I, _P]),
+    "vg_wgrad_plan": (c_int, [POINTER(WGDesc), _I, POINTER(WGPlan)]),
     "vg_pack_weights": (c_int, [POINTER(PackDesc), _I, _P]),
     "vg_pack_tile_count": (c_int, [POINTER(PackDesc)]),
     "vg_pack_weights_multi": (c_int, [_P, _I, _L, _I, _P]),
@@ -192,8 +204,8 @@ SIGNATURES = {
     "vg_reparam_kl_backward_rng": (c_int, [_P, _P, _P, _I, _P, _F, _P, _I, _I, _I, _I, _I, _P]),
     "vg_memset_zero": (c_int, [_P, _L, _P]),
     "vg_cast_fp8": (c_int, [_P, _P, _L, _I, _P]),
-    "vg_edge_wgrad_ws_bytes": (c_int64, [POINTER(EWDesc)]),
     "vg_edge_wgrad": (c_int, [POINTER(EWDesc), _P]),
+    "vg_edge_wgrad_plan": (c_int, [POINTER(EWDesc), POINTER(EWPlan)]),
     "vg_tnconv_supported": (c_int, [POINTER(TNDesc)]),
     "vg_tnconv": (c_int, [POINTER(TNDesc), _P]),
 }

@@ -444,27 +444,25 @@ __global__ __launch_bounds__(64 * EW_G) void edge_wgrad_reduce_kernel(const vg_e
     *dst = d.accumulate ? *dst + t : t;
 }
 
-struct EwPlan { int R, tiles_per_img, ntiles, JT, CT, grid; int64_t ws_bytes; };
-
-inline int ew_plan(const vg_ew_desc* d, EwPlan* p) {
+inline int ew_plan(const vg_ew_desc* d, vg_ew_plan* p) {
     VG_CHECK_ARG(d != nullptr, VG_EINVAL);
     VG_CHECK_ARG(d->B > 0 && d->WH > 0 && d->WW > 0 && d->NH > 0 && d->NW > 0 && d->P >= 0, VG_EINVAL);
     VG_CHECK_ARG(d->C == 16 || d->C == 32 || d->C == 64, VG_ENOSUP);
     VG_CHECK_ARG(d->N >= 1 && d->N <= 3, VG_ENOSUP);              // channel 3 of the narrow operand must be the zero pad
     VG_CHECK_ARG((d->K == 3 || d->K == 4) && (d->S == 1 || d->S == 2), VG_ENOSUP);
     VG_CHECK_ARG(d->WW <= EW_TP, VG_ENOSUP);
-    p->JT = (d->K * d->K * 4 + 15) / 16;                           // 3 (k3) | 4 (k4)
-    p->CT = d->C / 16;
+    p->jt = (d->K * d->K * 4 + 15) / 16;                           // 3 (k3) | 4 (k4)
+    p->ct = d->C / 16;
     int R = EW_TP / d->WW;
-    const int64_t pmax = ew_patch_max(p->CT);
+    const int64_t pmax = ew_patch_max(p->ct);
     while (R > 1 && (int64_t)(((R - 1) * d->S + d->K) * ((d->WW - 1) * d->S + d->K) + 1) * 16 > pmax) --R;
     VG_CHECK_ARG((int64_t)(((R - 1) * d->S + d->K) * ((d->WW - 1) * d->S + d->K) + 1) * 16 <= pmax, VG_ENOSUP);
     if (R > d->WH) R = d->WH;
-    p->R = R;
+    p->rows_per_tile = R;
     p->tiles_per_img = (d->WH + R - 1) / R;
     p->ntiles = d->B * p->tiles_per_img;
     p->grid = p->ntiles < 512 ? p->ntiles : 512;                   // 2 workgroups per CU, each walks several tiles
-    p->ws_bytes = (int64_t)p->grid * p->JT * 16 * d->C * 4;          // one [J][C] partial per workgroup
+    p->ws_bytes = (int64_t)p->grid * p->jt * 16 * d->C * 4;        // one [J][C] partial per workgroup
     return 0;
 }
 
@@ -490,26 +488,24 @@ extern "C" int vg_tnconv(const vg_tn_desc* d, void* stream) {
     return VG_LAUNCH_RC();
 }
 
-extern "C" int64_t vg_edge_wgrad_ws_bytes(const vg_ew_desc* d) {
-    EwPlan p;
-    int rc = ew_plan(d, &p);
-    return rc ? (int64_t)rc : p.ws_bytes;
+extern "C" int vg_edge_wgrad_plan(const vg_ew_desc* d, vg_ew_plan* out) {
+    VG_CHECK_ARG(out != nullptr, VG_EINVAL);
+    return ew_plan(d, out);
 }
 
 extern "C" int vg_edge_wgrad(const vg_ew_desc* d, void* stream) {
-    EwPlan p;
+    vg_ew_plan p;
     int rc = ew_plan(d, &p);
     if (rc) return rc;
     VG_CHECK_ARG(d->Wd && d->Nr && d->dW && d->ws && d->zeros, VG_EINVAL);
     VG_CHECK_ARG(vg_aligned16(d->Wd) && vg_aligned16(d->Nr) && vg_aligned16(d->ws), VG_EALIGN);
     VG_CHECK_ARG(d->ws_bytes >= p.ws_bytes, VG_EINVAL);
     hipStream_t s = vg_stream(stream);
-    if (p.CT == 4) vg_launch_timed(1, edge_wgrad_kernel<4>, dim3(p.grid), dim3(256), 0, s, *d, p.R, p.tiles_per_img, p.ntiles, p.JT);
-    else if (p.CT == 1) vg_launch_timed(1, edge_wgrad_kernel<1>, dim3(p.grid), dim3(256), 0, s, *d, p.R, p.tiles_per_img, p.ntiles, p.JT);
-    else vg_launch_timed(1, edge_wgrad_kernel<2>, dim3(p.grid), dim3(256), 0, s, *d, p.R, p.tiles_per_img, p.ntiles, p.JT);
+    auto kernel = p.ct == 4 ? edge_wgrad_kernel<4> : p.ct == 1 ? edge_wgrad_kernel<1> : edge_wgrad_kernel<2>;
+    vg_launch_timed(1, kernel, dim3(p.grid), dim3(256), 0, s, *d, p.rows_per_tile, p.tiles_per_img, p.ntiles, p.jt);
     rc = VG_LAUNCH_RC();
     if (rc) return rc;
-    const int JC = p.JT * 16 * d->C;                                // multiple of 256 (C >= 32, J >= 48)
-    hipLaunchKernelGGL(edge_wgrad_reduce_kernel, dim3(JC / 64), dim3(64 * EW_G), 0, s, *d, d->ws, p.grid, p.JT * 16, d->C);
+    const int JC = p.jt * 16 * d->C;                                // multiple of 256 (C >= 32, J >= 48)
+    hipLaunchKernelGGL(edge_wgrad_reduce_kernel, dim3(JC / 64), dim3(64 * EW_G), 0, s, *d, d->ws, p.grid, p.jt * 16, d->C);
     return VG_LAUNCH_RC();
 }

@@ -831,20 +831,8 @@ inline bool Ttaps_ok(const vg_wg_desc* d) {
            ((64 * T) % 4) == 0 && vg_aligned16(d->dW);
 }
 
-struct Plan { int tiles_kq, tiles_np, nsplit, rows_per_split, KQ, NPpad, tile; int64_t ws_bytes; };
-
-inline int wg_target() { return vg_sw().wg_target; }
-
-// 0: one role per wave (wgrad_bf16_dma_kernel); 1: 128 x 128 tile, 4 consumer + 8 producer waves; 2: 128 x 256 tile,
-// 8 consumers + 4 producers; 3 (default): 128 x 256 tile, 8 consumers + 8 producers.
-inline int wg_spec() { return vg_sw().wg_spec; }
-
-inline bool wg_use_dma(const vg_wg_desc* d) {
-    // default on with 64-row stages (+5..10 % on the generator layers); VG_WG_DMA=0 -> register-staged kernel
-    return vg_sw().wg_dma != 0 && d->zeros != nullptr;
-}
-
-inline int make_plan(const vg_wg_desc* d, int dtype, Plan* p) {
+// Every decision of the launch, as the public record (include/vaegan_hip.h, vg_wg_plan).
+inline int make_plan(const vg_wg_desc* d, int dtype, vg_wg_plan* r) {
     VG_CHECK_ARG(d != nullptr, VG_EINVAL);
     VG_CHECK_ARG(dtype == VG_F32 || dtype == VG_BF16, VG_ENOSUP);
     const int esz = dtype == VG_F32 ? 4 : 2;
@@ -854,88 +842,94 @@ inline int make_plan(const vg_wg_desc* d, int dtype, Plan* p) {
     VG_CHECK_ARG(d->TH > 0 && d->TW > 0, VG_EINVAL);
     const int64_t M = (int64_t)d->B * d->GH * d->GW;
     VG_CHECK_ARG(M < (1ll << 31), VG_EINVAL);
-    p->KQ = d->TH * d->TW * d->QC;
-    const int tile = dtype == VG_F32 ? WG_BNP : WB_T;          // output tile edge
-    const int srows = dtype == VG_F32 ? WG_BMK : (wg_use_dma(d) ? WD_SM : WB_SM);     // pixel rows per stage
-    p->tile = tile;
-    p->tiles_kq = (p->KQ + tile - 1) / tile;
-    p->tiles_np = (d->PC + tile - 1) / tile;
-    p->NPpad = p->tiles_np * tile;
-    const int tiles = p->tiles_kq * p->tiles_np;
-    int64_t stages = (M + srows - 1) / srows;
-    int nsplit = (int)((wg_target() + tiles - 1) / tiles);    // ~2 workgroups per CU
-    // at least 8 (f32) / 4 (bf16) stages of work per workgroup, at most 1024 splits
+    const VgSwitches& sw = vg_sw();
+    *r = vg_wg_plan{};
+    // main kernel.  LDS-DMA staging: default on with 64-row stages (+5..10 % on the generator layers); VG_WG_DMA=0 or no
+    // zero page -> register-staged kernel.  VG_WG_SPEC 0: one role per wave (wgrad_bf16_dma_kernel); 1: 128 x 128 tile,
+    // 4 consumer + 8 producer waves; 2: 128 x 256 tile, 8 consumers + 4 producers; 3 (default): 128 x 256 tile, 8 + 8.
+    const bool dma = sw.wg_dma != 0 && d->zeros != nullptr;
+    r->tile = dtype == VG_F32 ? WG_BNP : WB_T;
+    r->stage_rows = dtype == VG_F32 ? WG_BMK : (dma ? WD_SM : WB_SM);
+    r->tiles_kq = (d->TH * d->TW * d->QC + r->tile - 1) / r->tile;
+    r->tiles_np = (d->PC + r->tile - 1) / r->tile;
+    const bool wide = r->tiles_kq % 2 == 0 && (sw.wg_spec == 2 || sw.wg_spec == 3);      // two kq tiles per workgroup
+    r->main = dtype == VG_F32 ? VG_WG_MAIN_F32 : !dma ? VG_WG_MAIN_BF16_REG : sw.wg_spec == 0 ? VG_WG_MAIN_BF16_DMA : VG_WG_MAIN_WS;
+    if (r->main == VG_WG_MAIN_WS) {
+        r->nqt = wide ? 2 : 1;
+        r->nprod = wide && sw.wg_spec == 2 ? 4 : 8;
+    }
+    // split-M factor: ~2 workgroups per CU, at least 8 (f32) / 4 (bf16) stages of work per workgroup, at most 1024 splits
+    const int tiles = r->tiles_kq * r->tiles_np;
+    const int64_t stages = (M + r->stage_rows - 1) / r->stage_rows;
+    int nsplit = (int)((sw.wg_target + tiles - 1) / tiles);
     const int min_stages = dtype == VG_F32 ? 8 : 4;
     if (nsplit > stages / min_stages) nsplit = (int)(stages / min_stages);
     if (nsplit < 1) nsplit = 1;
     if (nsplit > 1024) nsplit = 1024;
-    int64_t rps = ((stages + nsplit - 1) / nsplit) * srows;
-    nsplit = (int)((M + rps - 1) / rps);
-    p->nsplit = nsplit;
-    p->rows_per_split = (int)rps;
-    p->ws_bytes = (int64_t)nsplit * p->NPpad * (int64_t)(p->tiles_kq * tile) * 4;
+    const int64_t rps = ((stages + nsplit - 1) / nsplit) * r->stage_rows;
+    r->nsplit = (int)((M + rps - 1) / rps);
+    r->rows_per_split = (int)rps;
+    r->ws_bytes = (int64_t)r->nsplit * (r->tiles_np * r->tile) * (int64_t)(r->tiles_kq * r->tile) * 4;
+    // XCD-aware order (wg_tile) where it pays: few tiles per split, many splits, long operands (measured S=64 B=128:
+    // G4 81 -> 55 us, D1 2B 44 -> 31, D1 26 -> 21, G3 55 -> 54; layers with >= 128 tiles per split lose 2-3 us)
+    r->xcd_order = sw.wg_xcd == 2 || (sw.wg_xcd == 1 && tiles <= 32 && r->nsplit >= 16 && M >= 32768);
+    // reduce kernel.  Weight-heavy layers with few splits: streaming transpose-reduce (one contiguous run of dW per block)
+    if (dtype == VG_BF16 && Ttaps_ok(d) && r->nsplit <= 16 && (int64_t)d->NP * (d->QC >> 6) >= 256) {
+        r->reduce = VG_WG_RED_STREAM;
+        return 0;
+    }
+    r->reduce = VG_WG_RED_GENERIC;
+    r->reduce_vc = (d->NQ % 4 == 0) && (d->QC % 4 == 0) ? 4 : 1;
+    r->reduce_spl = r->nsplit >= 64 ? 32 : (r->nsplit >= 8 ? 8 : 1);
+    // 16 taps per thread only when there is plenty of parallelism anyway; otherwise 4 (tap groups -> blockIdx.y)
+    const int64_t blocks = ((int64_t)d->NP * ((d->NQ + r->reduce_vc - 1) / r->reduce_vc) * r->reduce_spl + 255) / 256;
+    r->reduce_tt = d->TH * d->TW >= 16 && blocks >= 2048 ? 16 : 4;
     return 0;
+}
+
+// The two launches only translate the record into a template instantiation and a grid.
+inline int launch_main(const vg_wg_desc* d, const vg_wg_plan& r, hipStream_t s) {
+    void (*kernel)(vg_wg_desc, int, int, int, int) =
+        r.main == VG_WG_MAIN_F32 ? wgrad_kernel<VG_F32> : r.main == VG_WG_MAIN_BF16_REG ? wgrad_bf16_kernel :
+        r.main == VG_WG_MAIN_BF16_DMA ? wgrad_bf16_dma_kernel : r.nqt == 1 ? wgrad_bf16_ws_kernel<1, 8> :
+        r.nprod == 4 ? wgrad_bf16_ws_kernel<2, 4> : wgrad_bf16_ws_kernel<2, 8>;
+    const bool ws = r.main == VG_WG_MAIN_WS;
+    vg_launch_timed(1, kernel, dim3(r.tiles_kq / (ws ? r.nqt : 1), r.tiles_np, r.nsplit), dim3(ws ? 64 * (4 * r.nqt + r.nprod) : 256),
+                    0, s, *d, r.rows_per_split, d->TH * d->TW * d->QC, r.tiles_np * r.tile, r.xcd_order);
+    return VG_LAUNCH_RC();
+}
+
+inline int launch_reduce(const vg_wg_desc* d, const vg_wg_plan& r, hipStream_t s) {
+    const int NPpad = r.tiles_np * r.tile, ldk = r.tiles_kq * r.tile;
+    if (r.reduce == VG_WG_RED_STREAM) {
+        hipLaunchKernelGGL(wgrad_reduce_t_kernel, dim3((unsigned)(d->NP * (d->QC >> 6))), dim3(256), 0, s, *d, r.nsplit, NPpad, ldk);
+        return VG_LAUNCH_RC();
+    }
+    const int EL = 256 / r.reduce_spl, T = d->TH * d->TW;
+    const int64_t total = (int64_t)d->NP * ((d->NQ + r.reduce_vc - 1) / r.reduce_vc);
+    const dim3 grid((unsigned)((total + EL - 1) / EL), (unsigned)((T + r.reduce_tt - 1) / r.reduce_tt));
+    const size_t shm = (size_t)256 * r.reduce_vc * r.reduce_tt * sizeof(float);                // <= 64 KB
+    auto kernel = r.reduce_tt == 16 ? (r.reduce_vc == 4 ? wgrad_reduce_kernel<16, 4> : wgrad_reduce_kernel<16, 1>)
+                                    : (r.reduce_vc == 4 ? wgrad_reduce_kernel<4, 4> : wgrad_reduce_kernel<4, 1>);
+    hipLaunchKernelGGL(kernel, grid, dim3(256), shm, s, *d, r.nsplit, NPpad, ldk, r.reduce_spl);
+    return VG_LAUNCH_RC();
 }
 
 }  // namespace
 
-extern "C" int64_t vg_wgrad_ws_bytes(const vg_wg_desc* d, int dtype) {
-    Plan p;
-    int rc = make_plan(d, dtype, &p);
-    return rc ? (int64_t)rc : p.ws_bytes;
+extern "C" int vg_wgrad_plan(const vg_wg_desc* d, int dtype, vg_wg_plan* out) {
+    VG_CHECK_ARG(out != nullptr, VG_EINVAL);
+    return make_plan(d, dtype, out);
 }
 
 extern "C" int vg_wgrad(const vg_wg_desc* d, int dtype, void* stream) {
-    Plan p;
+    vg_wg_plan p;
     int rc = make_plan(d, dtype, &p);
     if (rc) return rc;
     VG_CHECK_ARG(d->P && d->Q && d->dW && d->ws, VG_EINVAL);
     VG_CHECK_ARG(vg_aligned16(d->P) && vg_aligned16(d->Q) && vg_aligned16(d->ws), VG_EALIGN);
     VG_CHECK_ARG(d->ws_bytes >= p.ws_bytes, VG_EINVAL);
     hipStream_t s = vg_stream(stream);
-    dim3 grid(p.tiles_kq, p.tiles_np, p.nsplit);
-    // XCD-aware order (wg_tile) where it pays: few tiles per split, many splits, long operands (measured S=64 B=128:
-    // G4 81 -> 55 us, D1 2B 44 -> 31, D1 26 -> 21, G3 55 -> 54; layers with >= 128 tiles per split lose 2-3 us)
-    const int xcd_env = vg_sw().wg_xcd;
-    const int64_t Mrows = (int64_t)d->B * d->GH * d->GW;
-    const int xcd_order = xcd_env == 2 || (xcd_env == 1 && p.tiles_kq * p.tiles_np <= 32 && p.nsplit >= 16 && Mrows >= 32768);
-    if (dtype == VG_F32)
-        vg_launch_timed(1, wgrad_kernel<VG_F32>, grid, dim3(256), 0, s, *d, p.rows_per_split, p.KQ, p.NPpad, xcd_order);
-    else if (wg_use_dma(d) && wg_spec() == 3 && p.tiles_kq % 2 == 0)
-        vg_launch_timed(1, (wgrad_bf16_ws_kernel<2, 8>), dim3(p.tiles_kq / 2, p.tiles_np, p.nsplit), dim3(1024), 0, s, *d,
-                        p.rows_per_split, p.KQ, p.NPpad, xcd_order);
-    else if (wg_use_dma(d) && wg_spec() == 2 && p.tiles_kq % 2 == 0)
-        vg_launch_timed(1, (wgrad_bf16_ws_kernel<2, 4>), dim3(p.tiles_kq / 2, p.tiles_np, p.nsplit), dim3(768), 0, s, *d,
-                        p.rows_per_split, p.KQ, p.NPpad, xcd_order);
-    else if (wg_use_dma(d) && wg_spec() != 0)
-        vg_launch_timed(1, (wgrad_bf16_ws_kernel<1, 8>), grid, dim3(768), 0, s, *d, p.rows_per_split, p.KQ, p.NPpad, xcd_order);
-    else if (wg_use_dma(d))
-        vg_launch_timed(1, wgrad_bf16_dma_kernel, grid, dim3(256), 0, s, *d, p.rows_per_split, p.KQ, p.NPpad, xcd_order);
-    else
-        vg_launch_timed(1, wgrad_bf16_kernel, grid, dim3(256), 0, s, *d, p.rows_per_split, p.KQ, p.NPpad, xcd_order);
-    rc = VG_LAUNCH_RC();
-    if (rc) return rc;
-    // weight-heavy layers with few splits: streaming transpose-reduce (one contiguous run of dW per block)
-    if (dtype == VG_BF16 && Ttaps_ok(d) && p.nsplit <= 16 && (int64_t)d->NP * (d->QC >> 6) >= 256) {
-        hipLaunchKernelGGL(wgrad_reduce_t_kernel, dim3((unsigned)(d->NP * (d->QC >> 6))), dim3(256), 0, s, *d, p.nsplit,
-                           p.NPpad, p.tiles_kq * p.tile);
-        return VG_LAUNCH_RC();
-    }
-    const bool vec = (d->NQ % 4 == 0) && (d->QC % 4 == 0);
-    const int VC = vec ? 4 : 1;
-    const int64_t total = (int64_t)d->NP * ((d->NQ + VC - 1) / VC);
-    const int SPL = p.nsplit >= 64 ? 32 : (p.nsplit >= 8 ? 8 : 1);
-    const int EL = 256 / SPL;
-    const int ldk = p.tiles_kq * p.tile;
-    const int Ttaps = d->TH * d->TW;
-    // 16 taps per thread only when there is plenty of parallelism anyway; otherwise 4 (tap groups -> blockIdx.y)
-    const bool big = Ttaps >= 16 && (total + EL - 1) / EL >= 2048;
-    const int TTv = big ? 16 : 4;
-    const dim3 rgrid((unsigned)((total + EL - 1) / EL), (unsigned)((Ttaps + TTv - 1) / TTv));
-    const size_t shm = (size_t)256 * VC * TTv * sizeof(float);                    // <= 64 KB
-    if (vec && big) hipLaunchKernelGGL((wgrad_reduce_kernel<16, 4>), rgrid, dim3(256), shm, s, *d, p.nsplit, p.NPpad, ldk, SPL);
-    else if (vec) hipLaunchKernelGGL((wgrad_reduce_kernel<4, 4>), rgrid, dim3(256), shm, s, *d, p.nsplit, p.NPpad, ldk, SPL);
-    else if (big) hipLaunchKernelGGL((wgrad_reduce_kernel<16, 1>), rgrid, dim3(256), shm, s, *d, p.nsplit, p.NPpad, ldk, SPL);
-    else hipLaunchKernelGGL((wgrad_reduce_kernel<4, 1>), rgrid, dim3(256), shm, s, *d, p.nsplit, p.NPpad, ldk, SPL);
-    return VG_LAUNCH_RC();
+    rc = launch_main(d, p, s);
+    return rc ? rc : launch_reduce(d, p, s);
 }

@@ -63,34 +63,35 @@ int64_t gather_gemm(const at::Tensor& X, const at::Tensor& W, at::Tensor& Y, con
 }
 
 // geom: B GH GW PC NP QH QW QC NQ SY SX DY DX TH TW y0 x0 s_np s_cq s_t accumulate (21 values)
+static vg_wg_desc wg_desc(at::IntArrayRef geom, const char* what) {
+    TORCH_CHECK(geom.size() == 21, "vaegan::", what, ": geom must hold 21 integers, got ", geom.size());
+    vg_wg_desc d;
+    std::memset(&d, 0, sizeof(d));
+    int k = 0;
+    auto nx = [&]() { return static_cast<int32_t>(geom[k++]); };
+    d.B = nx(); d.GH = nx(); d.GW = nx(); d.PC = nx(); d.NP = nx(); d.QH = nx(); d.QW = nx(); d.QC = nx(); d.NQ = nx();
+    d.SY = nx(); d.SX = nx(); d.DY = nx(); d.DX = nx(); d.TH = nx(); d.TW = nx(); d.y0 = nx(); d.x0 = nx();
+    d.s_np = nx(); d.s_cq = nx(); d.s_t = nx(); d.accumulate = nx();
+    return d;
+}
+
 void wgrad(const at::Tensor& P, const at::Tensor& Q, at::Tensor& dW, at::Tensor& ws, const at::Tensor& zeros,
            at::IntArrayRef geom, int64_t dtype) {
     check_dev(P, "wgrad"); check_dev(Q, "wgrad"); check_dev(dW, "wgrad"); check_dev(ws, "wgrad"); check_dev(zeros, "wgrad");
-    TORCH_CHECK(geom.size() == 21, "vaegan::wgrad: geom must hold 21 integers, got ", geom.size());
     TORCH_CHECK(dW.scalar_type() == at::kFloat && ws.scalar_type() == at::kFloat, "vaegan::wgrad: dW and ws are float32");
-    vg_wg_desc d;
-    std::memset(&d, 0, sizeof(d));
+    vg_wg_desc d = wg_desc(geom, "wgrad");
     d.P = P.data_ptr(); d.Q = Q.data_ptr(); d.dW = static_cast<float*>(dW.data_ptr());
     d.ws = static_cast<float*>(ws.data_ptr()); d.ws_bytes = ws.numel() * 4; d.zeros = zeros.data_ptr();
-    int k = 0;
-    auto nx = [&]() { return static_cast<int32_t>(geom[k++]); };
-    d.B = nx(); d.GH = nx(); d.GW = nx(); d.PC = nx(); d.NP = nx(); d.QH = nx(); d.QW = nx(); d.QC = nx(); d.NQ = nx();
-    d.SY = nx(); d.SX = nx(); d.DY = nx(); d.DX = nx(); d.TH = nx(); d.TW = nx(); d.y0 = nx(); d.x0 = nx();
-    d.s_np = nx(); d.s_cq = nx(); d.s_t = nx(); d.accumulate = nx();
     rc_check(vg_wgrad(&d, static_cast<int>(dtype), cur_stream()), "wgrad");
 }
 
+// vg_wgrad_plan(...).ws_bytes, or the library's (negative) error code
 int64_t wgrad_ws_bytes(at::IntArrayRef geom, int64_t dtype) {
-    TORCH_CHECK(geom.size() == 21, "vaegan::wgrad_ws_bytes: geom must hold 21 integers");
-    vg_wg_desc d;
-    std::memset(&d, 0, sizeof(d));
-    int k = 0;
-    auto nx = [&]() { return static_cast<int32_t>(geom[k++]); };
-    d.B = nx(); d.GH = nx(); d.GW = nx(); d.PC = nx(); d.NP = nx(); d.QH = nx(); d.QW = nx(); d.QC = nx(); d.NQ = nx();
-    d.SY = nx(); d.SX = nx(); d.DY = nx(); d.DX = nx(); d.TH = nx(); d.TW = nx(); d.y0 = nx(); d.x0 = nx();
-    d.s_np = nx(); d.s_cq = nx(); d.s_t = nx(); d.accumulate = nx();
+    vg_wg_desc d = wg_desc(geom, "wgrad_ws_bytes");
     d.zeros = reinterpret_cast<const void*>(16);        // only its presence selects the LDS-DMA plan; never dereferenced here
-    return vg_wgrad_ws_bytes(&d, static_cast<int>(dtype));
+    vg_wg_plan plan;
+    const int rc = vg_wgrad_plan(&d, static_cast<int>(dtype), &plan);
+    return rc ? rc : plan.ws_bytes;
 }
 
 void adam_step(at::Tensor& p, const at::Tensor& g, at::Tensor& m, at::Tensor& v, double lr, double beta1, double beta2,

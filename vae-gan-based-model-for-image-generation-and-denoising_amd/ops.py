@@ -70,13 +70,9 @@ class KernelTimer:
         self.acc = {k: dict(flops=0, bytes=0) for k in self.FAMILIES}
         L.load().vg_timing_enable(1)
 
-    def begin(self, family, flops, nbytes):
+    def add(self, family, flops, nbytes):
         self.acc[family]["flops"] += flops
         self.acc[family]["bytes"] += nbytes
-        return None
-
-    def end(self, tok):
-        pass
 
     def summary(self):
         """family -> dict(launches, ms, flops, bytes); synchronises the recorded events and stops timing."""
@@ -99,7 +95,7 @@ def _bn_bytes(passes: int, numel: int, dtype: int) -> None:
     (forward: read the raw output, write the activated one = 2; backward: reduce reads x and dy, apply reads x and dy and
     writes dx = 5; the small statistics / coefficient vectors are not counted)."""
     if TIMER is not None:
-        TIMER.begin("bn", 0, passes * numel * (4 if dtype == F32 else 2))
+        TIMER.add("bn", 0, passes * numel * (4 if dtype == F32 else 2))
 
 # ---- binding ---------------------------------------------------------------------------------------------------------
 # The kernels live behind the C ABI (include/vaegan_hip.h).  Two faces reach it from Python:
@@ -313,6 +309,33 @@ def _gg_plan(d: L.GGDesc, dtype: int) -> L.GGPlan:
     return p
 
 
+def _wg_desc(wg: WGSpec, P, Q, dW, zeros, accumulate=False) -> L.WGDesc:
+    """The one place a vg_wg_desc is filled, for the plan query and for the launch (operands as in _gg_desc); the launch
+    adds the workspace the plan asks for."""
+    return L.WGDesc(P=_addr(P), Q=_addr(Q), dW=_addr(dW), zeros=_addr(zeros), B=wg.B, GH=wg.GH, GW=wg.GW, PC=wg.PC, NP=wg.NP,
+                    QH=wg.QH, QW=wg.QW, QC=wg.QC, NQ=wg.NQ, SY=wg.SY, SX=wg.SX, DY=wg.DY, DX=wg.DX, TH=wg.TH, TW=wg.TW,
+                    y0=wg.y0, x0=wg.x0, s_np=wg.s_np, s_cq=wg.s_cq, s_t=wg.s_t, accumulate=1 if accumulate else 0)
+
+
+def _wg_plan(d: L.WGDesc, dtype: int) -> L.WGPlan:
+    p = L.WGPlan()
+    L.check(L.load().vg_wgrad_plan(byref(d), dtype, byref(p)), "vg_wgrad_plan")
+    return p
+
+
+def _ew_desc(ew: EWSpec, wide, narrow, dW, zeros, accumulate=False) -> L.EWDesc:
+    """The same for vg_ew_desc."""
+    return L.EWDesc(Wd=_addr(wide), Nr=_addr(narrow), dW=_addr(dW), zeros=_addr(zeros), B=ew.B, WH=ew.WH, WW=ew.WW, C=ew.C,
+                    NH=ew.NH, NW=ew.NW, N=ew.N, K=ew.K, S=ew.S, P=ew.P, s_c=ew.s_c, s_n=ew.s_n,
+                    accumulate=1 if accumulate else 0)
+
+
+def _ew_plan(d: L.EWDesc) -> L.EWPlan:
+    p = L.EWPlan()
+    L.check(L.load().vg_edge_wgrad_plan(byref(d), byref(p)), "vg_edge_wgrad_plan")
+    return p
+
+
 def gather_gemm(g: GGSpec, X: torch.Tensor, Wp: torch.Tensor, dtype: int, bias: torch.Tensor = None,
                 want_stats: bool = False, out: torch.Tensor = None, alg=None, act=None, mask=None):
     """Returns (Y [B,OH,OW,OC], stats slabs or None, nparts).  alg = (flops, bytes) of the layer for the timer.
@@ -337,16 +360,13 @@ def gather_gemm(g: GGSpec, X: torch.Tensor, Wp: torch.Tensor, dtype: int, bias: 
     ws = WS.get("splitk", p.ws_bytes, X.device) if p.ws_bytes > 0 else None
     d.stats, d.stats_capacity = _addr(stats), p.nparts
     d.ws, d.ws_bytes = _addr(ws), ws.numel() * 4 if ws is not None else 0
-    tok = None
     if TIMER is not None:
-        tok = TIMER.begin({0: "gather_gemm", 2: "edge", 3: "gather_gemm_fp8"}[p.timing_family], *(alg or (g.flops(), 0)))
+        TIMER.add({0: "gather_gemm", 2: "edge", 3: "gather_gemm_fp8"}[p.timing_family], *(alg or (g.flops(), 0)))
     if BINDING == "torchops":
         torch_ops().gather_gemm(X, Wp, Y, bias, stats, ws, zero_page(X.device), mask[0] if mask is not None else None,
                                 _gg_geom(d), float(d.act_slope), float(d.mask_slope), dtype)
     else:
         L.check(L.load().vg_gather_gemm(byref(d), dtype, L.stream_ptr()), "vg_gather_gemm")
-    if tok is not None:
-        TIMER.end(tok)
     return Y, stats, p.nparts
 
 
@@ -357,19 +377,12 @@ def edge_wgrad(ew: EWSpec, wide: torch.Tensor, narrow: torch.Tensor, dW: torch.T
         raise RuntimeError("edge_wgrad: bf16 operands, float32 gradient")
     if wide.numel() != ew.B * ew.WH * ew.WW * ew.C or narrow.numel() != ew.B * ew.NH * ew.NW * 8:
         raise RuntimeError("edge_wgrad: operand size mismatch")
-    lib = L.load()
-    d = L.EWDesc(Wd=wide.data_ptr(), Nr=narrow.data_ptr(), dW=dW.data_ptr(), ws=0, ws_bytes=0,
-                 zeros=zero_page(wide.device).data_ptr(), B=ew.B, WH=ew.WH, WW=ew.WW, C=ew.C, NH=ew.NH, NW=ew.NW, N=ew.N,
-                 K=ew.K, S=ew.S, P=ew.P, s_c=ew.s_c, s_n=ew.s_n, accumulate=1 if accumulate else 0)
-    nbytes = lib.vg_edge_wgrad_ws_bytes(byref(d))
-    if nbytes < 0:
-        L.check(int(nbytes), "vg_edge_wgrad_ws_bytes")
-    ws = WS.get("wgrad", nbytes, wide.device)
+    d = _ew_desc(ew, wide, narrow, dW, zero_page(wide.device), accumulate)
+    ws = WS.get("wgrad", _ew_plan(d).ws_bytes, wide.device)
     d.ws, d.ws_bytes = ws.data_ptr(), ws.numel() * 4
-    tok = TIMER.begin("wgrad", *(alg or (ew.flops(), 0))) if TIMER is not None else None
-    L.check(lib.vg_edge_wgrad(byref(d), L.stream_ptr()), "vg_edge_wgrad")
-    if tok is not None:
-        TIMER.end(tok)
+    if TIMER is not None:
+        TIMER.add("wgrad", *(alg or (ew.flops(), 0)))
+    L.check(L.load().vg_edge_wgrad(byref(d), L.stream_ptr()), "vg_edge_wgrad")
 
 
 def cast_fp8(x: torch.Tensor, shift: int = 0, out: torch.Tensor = None) -> torch.Tensor:
@@ -406,10 +419,9 @@ def tnconv(tn: TNSpec, X: torch.Tensor, Wp: torch.Tensor, want_nhwc: bool = True
                  rng=noise.state.data_ptr() if rng else 0, draw=noise.draw if rng else 0, sigma=sigma,
                  B=tn.B, IH=tn.IH, IW=tn.IW, C=tn.C, N=tn.N, K=tn.K, S=tn.S, P=tn.P, OH=tn.OH, OW=tn.OW, OC=tn.OC,
                  Wpitch=tn.Wpitch, act=act)
-    tok = TIMER.begin("edge", *(alg or (tn.flops(), 0))) if TIMER is not None else None
+    if TIMER is not None:
+        TIMER.add("edge", *(alg or (tn.flops(), 0)))
     L.check(L.load().vg_tnconv(byref(d), L.stream_ptr()), "vg_tnconv")
-    if tok is not None:
-        TIMER.end(tok)
     return Y, Yc
 
 
@@ -420,25 +432,16 @@ def wgrad(wg: WGSpec, P: torch.Tensor, Q: torch.Tensor, dW: torch.Tensor, accumu
         raise RuntimeError("weight gradients are float32")
     if P.numel() != wg.B * wg.GH * wg.GW * wg.PC or Q.numel() != wg.B * wg.QH * wg.QW * wg.QC:
         raise RuntimeError("wgrad: operand size mismatch")
-    lib = L.load()
-    d = L.WGDesc(P=P.data_ptr(), Q=Q.data_ptr(), dW=dW.data_ptr(), ws=0, ws_bytes=0, B=wg.B, GH=wg.GH, GW=wg.GW,
-                 PC=wg.PC, NP=wg.NP, QH=wg.QH, QW=wg.QW, QC=wg.QC, NQ=wg.NQ, SY=wg.SY, SX=wg.SX, DY=wg.DY,
-                 DX=wg.DX, TH=wg.TH, TW=wg.TW, y0=wg.y0, x0=wg.x0, s_np=wg.s_np, s_cq=wg.s_cq, s_t=wg.s_t,
-                 accumulate=1 if accumulate else 0, zeros=zero_page(P.device).data_ptr())
-    nbytes = lib.vg_wgrad_ws_bytes(byref(d), dtype)
-    if nbytes < 0:
-        L.check(int(nbytes), "vg_wgrad_ws_bytes")
+    d = _wg_desc(wg, P, Q, dW, zero_page(P.device), accumulate)
     # the slab workspace is shared by all launches of one stream; work forked onto another stream gets its own
-    ws = WS.get("wgrad", nbytes, P.device)
-    d.ws = ws.data_ptr()
-    d.ws_bytes = ws.numel() * 4
-    tok = TIMER.begin("wgrad", *(alg or (0, 0))) if TIMER is not None else None
+    ws = WS.get("wgrad", _wg_plan(d, dtype).ws_bytes, P.device)
+    d.ws, d.ws_bytes = ws.data_ptr(), ws.numel() * 4
+    if TIMER is not None:
+        TIMER.add("wgrad", *(alg or (0, 0)))
     if BINDING == "torchops":
         torch_ops().wgrad(P, Q, dW, ws, zero_page(P.device), _wg_geom(d), dtype)
     else:
-        L.check(lib.vg_wgrad(byref(d), dtype, L.stream_ptr()), "vg_wgrad")
-    if tok is not None:
-        TIMER.end(tok)
+        L.check(L.load().vg_wgrad(byref(d), dtype, L.stream_ptr()), "vg_wgrad")
 
 
 # ---------------------------------------------------------------------------------------------
@@ -463,6 +466,29 @@ def gather_gemm_plan(g: GGSpec, dtype: int, bias: bool = False, want_stats: bool
     return dict(family=GG_FAMILY[p.family], bm=p.bm, bn=p.bn, detail=(p.detail[0], p.detail[1]), dma=bool(p.dma),
                 ksplit=p.ksplit, stages_per_split=p.stages_per_split, nstages=p.nstages, reduce=GG_REDUCE[p.reduce],
                 n_major=bool(p.n_major), nparts=p.nparts, timing_family=p.timing_family, ws_bytes=p.ws_bytes)
+
+
+WG_MAIN = {0: "f32", 1: "bf16_reg", 2: "bf16_dma", 3: "ws"}
+WG_REDUCE = {0: "stream", 1: "generic"}
+
+
+def wgrad_plan(wg: WGSpec, dtype: int, zeros: bool = True, aligned16: bool = True) -> dict:
+    """What vg_wgrad launches for this geometry under the current switches (vg_wgrad_plan: the record the launcher itself
+    launches from, and the one wgrad sizes its workspace from).  Host only, no GPU and no tensors.  zeros: whether the
+    zero page is passed (wgrad always does); aligned16: whether dW is 16-byte aligned.
+    -> dict of the fields of vg_wg_plan, main and reduce by name (WG_MAIN, WG_REDUCE)."""
+    d = _wg_desc(wg, True, True, True, zeros)
+    if not aligned16:
+        d.dW = _SOME + 4
+    p = _wg_plan(d, dtype)
+    return dict({name: getattr(p, name) for name, _ in L.WGPlan._fields_}, main=WG_MAIN[p.main], reduce=WG_REDUCE[p.reduce],
+                xcd_order=bool(p.xcd_order))
+
+
+def edge_wgrad_plan(ew: EWSpec) -> dict:
+    """What vg_edge_wgrad launches for this geometry (vg_edge_wgrad_plan).  Host only -> dict of the fields of vg_ew_plan."""
+    p = _ew_plan(_ew_desc(ew, True, True, True, True))
+    return {name: getattr(p, name) for name, _ in L.EWPlan._fields_}
 
 
 def bn_finalize(stats, nparts, C, count, gamma, beta, running_mean, running_var, momentum, eps, device, groups=1,
