@@ -48,7 +48,7 @@ extern "C" {
 #define VG_ACT_LRELU   2   /* nn.LeakyReLU(slope)    main_vae.py:25, gan_code.py:62-82 */
 #define VG_ACT_TANH    3   /* nn.Tanh()              gan_code.py:50 (vg_tnconv epilogue only) */
 
-#define VG_ABI_VERSION 23  /* 2: vg_pack_desc.tile_start, SyncBN / WGAN / data-path entry points; 3: in-kernel noise (vg_*_rng);
+#define VG_ABI_VERSION 24  /* 2: vg_pack_desc.tile_start, SyncBN / WGAN / data-path entry points; 3: in-kernel noise (vg_*_rng);
                              4: vg_bn_finalize_act_forward, vg_bn_backward_finalize_apply;
                              7: vg_bce_pair_forward_backward;
                              8: vg_head_backward; round-3 prune -- the opt-in experiments of ABI 5 / 6 that measured slower (input prologue of
@@ -69,7 +69,8 @@ extern "C" {
                                  side queries of vg_gather_gemm (slab count, timer family, tile rows, workspace bytes) and the
                                  "supported" query of vg_bn_finalize_act_forward (vg_bn_launch_plan(VG_BN_PLAN_FUSED).fused) are gone;
                              22: weight averaging: vg_ema_update;
-                             23: vg_wgrad_plan / vg_wg_plan, vg_edge_wgrad_plan / vg_ew_plan replace vg_wgrad_ws_bytes / vg_edge_wgrad_ws_bytes */
+                             23: vg_wgrad_plan / vg_wg_plan, vg_edge_wgrad_plan / vg_ew_plan replace vg_wgrad_ws_bytes / vg_edge_wgrad_ws_bytes;
+                             24: gradient-norm clipping: vg_grad_norm_clip, vg_adam_apply_clip */
 int vg_abi_version(void);
 /* The library reads its optional kernel-selection switches (VG_* environment variables, DESIGN.md "Runtime switches")
  * ONCE, when it is loaded; nothing on a launch path calls getenv.  A process that changes one of them afterwards
@@ -902,6 +903,55 @@ int vg_adam_apply2(float* const* p, const float* const* g, float* const* m, floa
 #define VG_EMA_MAX 4
 int vg_ema_update(float* const* ema, const float* const* p, const int64_t* n, const float* const* state,
                   const double* decay, const int* warmup, int count, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Gradient-norm clipping (not in the reference): torch.nn.utils.clip_grad_norm_(params, max_norm, norm_type=2,
+ * error_if_nonfinite=False) of torch 2.10 over flat f32 gradient buffers (optim.Adam's flat_g), with the coefficient left
+ * ON THE DEVICE and applied where Adam reads the gradient.  The gradient buffers are never rewritten.
+ *
+ * vg_grad_norm_clip: arrays of `count` entries, 1 <= count <= VG_GNORM_MAX; every buffer is clipped to ITS OWN norm.  For
+ * buffer i (g = g[i], n = n[i] elements, grad_scale = grad_scale[i], max_norm = max_norm[i]):
+ *     S     = sum_j (double)g[j] * (double)g[j]        every product exact in f64; summed in f64 in a FIXED order that depends
+ *                                                      on n alone (not on the other buffers of the call or on i)
+ *     norm  = fabs((double)grad_scale) * sqrt(S)       f64: the norm of the gradient Adam is actually handed
+ *                                                      (grad_scale = 1/world_size after an all-reduce SUM)
+ *     c     = max_norm / (norm + 1e-6)                 f64
+ *     coef  = (float)(c < 1.0 ? c : (c != c ? c : 1.0))     torch.clamp(max=1): NaN propagates; narrowed once
+ *     out[i][0] = (float)norm,  out[i][1] = coef
+ * So: a NaN element gives norm = coef = NaN; an infinite one norm = inf and coef = 0 (NaN with max_norm = inf); an all-zero
+ * gradient norm 0 and coef 1; max_norm = +inf coef 1 for every finite norm (a norm monitor); max_norm = 0 coef 0.
+ * Two launches on `stream`:
+ *   A  partial sums.  Buffer i gets nb_i = clamp(ceil(n / 4 / 1024), 1, VG_GNORM_PARTS) workgroups of 256 threads, the
+ *      buffers' workgroups concatenated in one grid (as in vg_ema_update).  A workgroup walks sweeps of 1024 16-byte vectors
+ *      (sweep s belongs to workgroup s mod nb_i); per sweep a thread issues FOUR independent 16-byte loads (vectors t, t + 256,
+ *      t + 512, t + 768 of the sweep) before it consumes any, each into an f64 accumulator of its own.  The tail past
+ *      n / 4 * 4 is added element by element in the buffer's first workgroup.  The 256 thread sums are added by an xor
+ *      butterfly inside each wave and the four wave sums in wave order through LDS; the workgroup writes ONE f64 to
+ *      ws[i * VG_GNORM_PARTS + b].  4 bytes of traffic per element, no write pass.
+ *   B  finalize.  `count` workgroups of 256 threads; workgroup i adds buffer i's nb_i partials in the same fixed order,
+ *      evaluates the formulas above and writes out[i].
+ * No atomics, no fences, no hand-off between workgroups inside a launch: the kernel boundary is the hand-off.  The same
+ * inputs give the same bits on every launch, eager or replayed.
+ * Checked on the host before anything is launched, VG_EINVAL: count outside 1..VG_GNORM_MAX; a NULL array, entry, out[i] or
+ * ws; n[i] <= 0; max_norm[i] NaN or < 0 (+inf is allowed); grad_scale[i] not finite.  Then VG_EALIGN: g[i] not 16-byte
+ * aligned.  ws: at least VG_GNORM_MAX * VG_GNORM_PARTS doubles, contents irrelevant before and after the call.
+ *
+ * vg_adam_apply_clip: vg_adam_apply (count = 1) / vg_adam_apply2 (count = 2, the two grids concatenated) with the gradient
+ * scale  s = grad_scale[i] * coef[i][0]  -- ONE rounded f32 product (no contraction), read from the device, uniform per
+ * buffer -- wherever those kernels use grad_scale: gr = g * s (rounded), everything after that unchanged.  coef[i] == NULL:
+ * s = grad_scale[i].  So coef == 1.0f gives the unclipped launch's bits, and with grad_scale == 1 gr is the very f32 product
+ * torch's g.mul_(coef) produces.  Grid per buffer, per-element arithmetic and host checks are vg_adam_apply2's; in addition
+ * VG_EINVAL for count outside 1..2 or a NULL coef array.
+ * ---------------------------------------------------------------------------------------- */
+#define VG_GNORM_MAX   4        /* buffers per call */
+#define VG_GNORM_PARTS 512      /* workgroups, = f64 partial sums, per buffer at most */
+int vg_grad_norm_clip(const float* const* g, const int64_t* n, const float* grad_scale, const double* max_norm,
+                      int count, float* const* out /* out[i]: 2 device floats {norm, coef} */,
+                      double* ws /* device, >= VG_GNORM_MAX * VG_GNORM_PARTS doubles */, void* stream);
+int vg_adam_apply_clip(float* const* p, const float* const* g, float* const* m, float* const* v, const int64_t* n,
+                       const double* beta1, const double* beta2, const double* eps, const float* grad_scale,
+                       const float* const* state /* prepared */, const float* const* coef /* device; entry may be NULL */,
+                       int count /* 1 or 2 */, void* stream);
 
 #ifdef __cplusplus
 }

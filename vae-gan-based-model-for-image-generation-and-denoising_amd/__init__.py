@@ -12,7 +12,10 @@ reference): ``SSIMLoss`` and ``VAEGANTrainer(..., alpha_ssim=)`` / ``VAETrainer(
 ``evaluate_generation``, ``sample_images``.  Feature-space metrics (fid.update / fid.compute of every evaluation loop,
 README.md:22 precision / recall): ``metrics`` -- ``FeatureStats``, ``frechet_distance``, ``precision_recall``,
 ``encoder_features``, ``kernel_distance`` (KID).  Weight averaging (not in the reference): ``EMA`` -- an exponential moving
-average of Encoder / Generator weights kept on the device, ``VAEGANTrainer(..., ema=)`` and the sibling trainers.  Data path (dataset_code.py): ``data`` -- ``ResidentImages`` (``resized``: Resize +
+average of Encoder / Generator weights kept on the device, ``VAEGANTrainer(..., ema=)`` and the sibling trainers.
+Gradient-norm clipping (not in the reference): ``clip_grad_norm_`` / ``Adam.clip_grad_norm_`` -- torch's
+``clip_grad_norm_`` with the coefficient kept on the device and applied inside the Adam step, ``max_grad_norm=`` on the four
+trainers.  Data path (dataset_code.py): ``data`` -- ``ResidentImages`` (``resized``: Resize +
 CenterCrop on the device), ``resample_coeffs``, ``resize_geometry``.
 """
 from . import data  # noqa: F401
@@ -28,7 +31,7 @@ from .latent import LatentPrior, encode_dataset, evaluate_generation, sample_ima
 from .metrics import FeatureStats, encoder_features, frechet_distance, kernel_distance, precision_recall
 from .losses import BCELoss, MSELoss, SSIMLoss
 from .nets import ConvBlock, Discriminator, Encoder, Generator, weights_init
-from .optim import Adam
+from .optim import Adam, clip_grad_norm_
 from .siblings import DCGANTrainer, VAETrainer, WGANTrainer
 from .trainer import LOSS_NAMES, VAEGANTrainer
 from .utils import configure_seed
@@ -37,5 +40,5 @@ __all__ = ["ConvBlock", "Encoder", "Generator", "Discriminator", "weights_init",
            "VAEGANTrainer", "LOSS_NAMES", "configure_seed", "geometry", "denoise_eval", "validation_epoch", "paired_test_epoch", "GradReducer", "data", "VAETrainer", "DCGANTrainer", "WGANTrainer", "graphed",
            "latent", "LatentPrior", "encode_dataset", "evaluate_generation", "sample_images",
            "ResidentImages", "resample_coeffs", "resize_geometry",
-           "EMA",
+           "EMA", "clip_grad_norm_",
            "metrics", "FeatureStats", "frechet_distance", "precision_recall", "encoder_features", "kernel_distance"]

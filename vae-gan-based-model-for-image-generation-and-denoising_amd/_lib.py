@@ -17,7 +17,9 @@ VG_FP8_WSHIFT = 6
 VG_ACT_NONE, VG_ACT_RELU, VG_ACT_LRELU, VG_ACT_TANH = 0, 1, 2, 3
 VG_MAX_PHASE = 4
 VG_EMA_MAX = 4
-ABI_VERSION = 23
+VG_GNORM_MAX = 4
+VG_GNORM_PARTS = 512
+ABI_VERSION = 24
 
 VG_ENOSUP = -3
 _ERR = {-1: "VG_EINVAL (bad shape/size/flag)", -2: "VG_EALIGN (16-byte contract violated)",
@@ -175,6 +177,8 @@ SIGNATURES = {
     "vg_step_prologue": (c_int, [_P, _P, _P, _P, _P, _I, _P, _I, _P]),
     "vg_adam_apply2": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "vg_ema_update": (c_int, [_P, _P, _P, _P, _P, _P, _I, _P]),
+    "vg_grad_norm_clip": (c_int, [_P, _P, _P, _P, _I, _P, _P, _P]),
+    "vg_adam_apply_clip": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
     "vg_nchw_to_nhwc_pair": (c_int, [_P, _P, _P, _I, _F, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "vg_mse_partial": (c_int, [_P, _P, _L, _F, _P, _P, _I, POINTER(c_int), _P]),
     "vg_kl_forward_mse_final": (c_int, [_P, _P, _I, _I, _I, _F, _P, _P, _I, _L, _P, _I, _P]),

@@ -250,43 +250,53 @@ __device__ __forceinline__ float adam_lerp(float m, float g, float w) {
     return w < 0.5f ? m + w * d : g - d * (1.0f - w);
 }
 
-__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                   float* __restrict__ m, float* __restrict__ v, int64_t n4,
-                                                   int64_t n, float w1, float beta2, float w2, float eps,
-                                                   float gscale, const float* __restrict__ state) {
-    const float step_size = state[1];
-    const float bc2_sqrt = state[2];
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+// One Adam update (torch 2.10 _single_tensor_adam) of one element: the per-element code of every Adam kernel below.
+struct AdamConsts {
+    float w1, beta2, w2, eps, gscale, step_size, bc2_sqrt;
+};
+__device__ __forceinline__ void adam_update(float& p, float g, float& m, float& v, const AdamConsts& c) {
+    const float gr = adam_grad(g, c.gscale);
+    m = adam_lerp(m, gr, c.w1);                                // exp_avg.lerp_(grad, 1-beta1)
+    v = v * c.beta2 + c.w2 * (gr * gr);                        // mul_(beta2).addcmul_(g, g, 1-beta2)
+    const float denom = sqrtf(v) / c.bc2_sqrt + c.eps;
+    p = p - c.step_size * (m / denom);                         // addcdiv_(exp_avg, denom, -step_size)
+}
+
+// Workgroup `bid` of the `nb` that walk one flat buffer: 16-byte vectors in a grid-stride loop, the tail past n / 4 * 4
+// element by element in workgroup 0.
+__device__ __forceinline__ void adam_span(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                          float* __restrict__ v, int64_t n, int bid, int nb, const AdamConsts& c) {
+    const int64_t n4 = n / 4;
+    for (int64_t i = (int64_t)bid * blockDim.x + threadIdx.x; i < n4; i += (int64_t)nb * blockDim.x) {
         float4 pp = reinterpret_cast<float4*>(p)[i];
         float4 gg = reinterpret_cast<const float4*>(g)[i];
         float4 mm = reinterpret_cast<float4*>(m)[i];
         float4 vv = reinterpret_cast<float4*>(v)[i];
         float* P = &pp.x; float* G = &gg.x; float* Mv = &mm.x; float* V = &vv.x;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const float gr = adam_grad(G[k], gscale);
-            Mv[k] = adam_lerp(Mv[k], gr, w1);                  // exp_avg.lerp_(grad, 1-beta1)
-            V[k] = V[k] * beta2 + w2 * (gr * gr);              // mul_(beta2).addcmul_(g, g, 1-beta2)
-            const float denom = sqrtf(V[k]) / bc2_sqrt + eps;
-            P[k] = P[k] - step_size * (Mv[k] / denom);         // addcdiv_(exp_avg, denom, -step_size)
-        }
+        for (int k = 0; k < 4; ++k) adam_update(P[k], G[k], Mv[k], V[k], c);
         reinterpret_cast<float4*>(p)[i] = pp;
         reinterpret_cast<float4*>(m)[i] = mm;
         reinterpret_cast<float4*>(v)[i] = vv;
     }
     // tail (n not a multiple of 4)
-    if (blockIdx.x == 0) {
+    if (bid == 0) {
         for (int64_t i = n4 * 4 + threadIdx.x; i < n; i += blockDim.x) {
-            const float gr = adam_grad(g[i], gscale);
-            float mi = m[i], vi = v[i];
-            mi = adam_lerp(mi, gr, w1);
-            vi = vi * beta2 + w2 * (gr * gr);
-            const float denom = sqrtf(vi) / bc2_sqrt + eps;
-            p[i] = p[i] - step_size * (mi / denom);
+            float pi = p[i], mi = m[i], vi = v[i];
+            adam_update(pi, g[i], mi, vi, c);
+            p[i] = pi;
             m[i] = mi;
             v[i] = vi;
         }
     }
+}
+
+__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                   float* __restrict__ m, float* __restrict__ v, int64_t n4,
+                                                   int64_t n, float w1, float beta2, float w2, float eps,
+                                                   float gscale, const float* __restrict__ state) {
+    const AdamConsts c{w1, beta2, w2, eps, gscale, state[1], state[2]};
+    adam_span(p, g, m, v, n, (int)blockIdx.x, (int)gridDim.x, c);
 }
 
 // Two optimizers in ONE launch (the Encoder's and the Generator's step at the end of the iteration, vaegan_code.py:134-135):
@@ -301,42 +311,27 @@ __global__ __launch_bounds__(256) void adam2_kernel(const Adam2Args a) {
     const int which = blockIdx.x < a.nb0 ? 0 : 1;
     const int bid = which == 0 ? blockIdx.x : blockIdx.x - a.nb0;
     const int nb = which == 0 ? a.nb0 : (int)gridDim.x - a.nb0;
-    float* __restrict__ p = a.p[which]; const float* __restrict__ g = a.g[which];
-    float* __restrict__ m = a.m[which]; float* __restrict__ v = a.v[which];
-    const float w1 = a.w1[which], beta2 = a.beta2[which], w2 = a.w2[which], eps = a.eps[which], gscale = a.gscale[which];
-    const float step_size = a.state[which][1];
-    const float bc2_sqrt = a.state[which][2];
-    const int64_t n = a.n[which], n4 = n / 4;
-    for (int64_t i = (int64_t)bid * blockDim.x + threadIdx.x; i < n4; i += (int64_t)nb * blockDim.x) {
-        float4 pp = reinterpret_cast<float4*>(p)[i];
-        float4 gg = reinterpret_cast<const float4*>(g)[i];
-        float4 mm = reinterpret_cast<float4*>(m)[i];
-        float4 vv = reinterpret_cast<float4*>(v)[i];
-        float* P = &pp.x; float* G = &gg.x; float* Mv = &mm.x; float* V = &vv.x;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const float gr = adam_grad(G[k], gscale);
-            Mv[k] = adam_lerp(Mv[k], gr, w1);
-            V[k] = V[k] * beta2 + w2 * (gr * gr);
-            const float denom = sqrtf(V[k]) / bc2_sqrt + eps;
-            P[k] = P[k] - step_size * (Mv[k] / denom);
-        }
-        reinterpret_cast<float4*>(p)[i] = pp;
-        reinterpret_cast<float4*>(m)[i] = mm;
-        reinterpret_cast<float4*>(v)[i] = vv;
-    }
-    if (bid == 0) {
-        for (int64_t i = n4 * 4 + threadIdx.x; i < n; i += blockDim.x) {
-            const float gr = adam_grad(g[i], gscale);
-            float mi = m[i], vi = v[i];
-            mi = adam_lerp(mi, gr, w1);
-            vi = vi * beta2 + w2 * (gr * gr);
-            const float denom = sqrtf(vi) / bc2_sqrt + eps;
-            p[i] = p[i] - step_size * (mi / denom);
-            m[i] = mi;
-            v[i] = vi;
-        }
-    }
+    const AdamConsts c{a.w1[which], a.beta2[which], a.w2[which], a.eps[which], a.gscale[which], a.state[which][1],
+                       a.state[which][2]};
+    adam_span(a.p[which], a.g[which], a.m[which], a.v[which], a.n[which], bid, nb, c);
+}
+
+// The clipped step (include/vaegan_hip.h "Gradient-norm clipping"): adam2_kernel over one or two buffers (nb0 = the whole
+// grid for one) whose gradient scale is grad_scale * coef, coef read from the DEVICE where vg_grad_norm_clip left it -- one
+// rounded f32 product, uniform per buffer.  coef == NULL: grad_scale as it is.
+struct AdamClipArgs {
+    Adam2Args a;
+    const float* coef[2];
+};
+__global__ __launch_bounds__(256) void adam_clip_kernel(const AdamClipArgs ca) {
+    const Adam2Args& a = ca.a;
+    const int which = blockIdx.x < a.nb0 ? 0 : 1;
+    const int bid = which == 0 ? blockIdx.x : blockIdx.x - a.nb0;
+    const int nb = which == 0 ? a.nb0 : (int)gridDim.x - a.nb0;
+    const float* coef = ca.coef[which];
+    const float s = coef != nullptr ? adam_grad(a.gscale[which], coef[0]) : a.gscale[which];
+    const AdamConsts c{a.w1[which], a.beta2[which], a.w2[which], a.eps[which], s, a.state[which][1], a.state[which][2]};
+    adam_span(a.p[which], a.g[which], a.m[which], a.v[which], a.n[which], bid, nb, c);
 }
 
 }  // namespace
@@ -405,23 +400,48 @@ extern "C" int vg_adam_apply(float* p, const float* g, float* m, float* v, int64
     return adam_launch(p, g, m, v, n, beta1, beta2, eps, grad_scale, const_cast<float*>(state), vg_stream(stream));
 }
 
-extern "C" int vg_adam_apply2(float* const* p, const float* const* g, float* const* m, float* const* v, const int64_t* n,
-                              const double* beta1, const double* beta2, const double* eps, const float* grad_scale,
-                              const float* const* state, void* stream) {
+// Host checks and grid of vg_adam_apply2 / vg_adam_apply_clip: buffer i gets adam_launch's grid (same elements per thread,
+// same results).  Returns the workgroups of buffer i in nb[i].
+static int adam_fill(Adam2Args& a, int* nb, int count, float* const* p, const float* const* g, float* const* m,
+                     float* const* v, const int64_t* n, const double* beta1, const double* beta2, const double* eps,
+                     const float* grad_scale, const float* const* state) {
     VG_CHECK_ARG(p && g && m && v && n && beta1 && beta2 && eps && grad_scale && state, VG_EINVAL);
-    Adam2Args a{};
-    int nb[2];
-    for (int i = 0; i < 2; ++i) {
+    for (int i = 0; i < count; ++i) {
         VG_CHECK_ARG(p[i] && g[i] && m[i] && v[i] && state[i] && n[i] > 0, VG_EINVAL);
         VG_CHECK_ARG(vg_aligned16(p[i]) && vg_aligned16(g[i]) && vg_aligned16(m[i]) && vg_aligned16(v[i]), VG_EALIGN);
         a.p[i] = p[i]; a.g[i] = g[i]; a.m[i] = m[i]; a.v[i] = v[i]; a.state[i] = state[i]; a.n[i] = n[i];
         a.w1[i] = (float)(1.0 - beta1[i]); a.beta2[i] = (float)beta2[i]; a.w2[i] = (float)(1.0 - beta2[i]);
         a.eps[i] = (float)eps[i]; a.gscale[i] = grad_scale[i];
         int64_t b = (n[i] / 4 + 255) / 256;
-        nb[i] = (int)(b < 1 ? 1 : (b > 2048 ? 2048 : b));       // adam_launch's grid: same elements per thread, same results
+        nb[i] = (int)(b < 1 ? 1 : (b > 2048 ? 2048 : b));
     }
+    return 0;
+}
+
+extern "C" int vg_adam_apply2(float* const* p, const float* const* g, float* const* m, float* const* v, const int64_t* n,
+                              const double* beta1, const double* beta2, const double* eps, const float* grad_scale,
+                              const float* const* state, void* stream) {
+    Adam2Args a{};
+    int nb[2];
+    const int rc = adam_fill(a, nb, 2, p, g, m, v, n, beta1, beta2, eps, grad_scale, state);
+    if (rc) return rc;
     a.nb0 = nb[0];
     hipLaunchKernelGGL(adam2_kernel, dim3(nb[0] + nb[1]), dim3(256), 0, vg_stream(stream), a);
+    return VG_LAUNCH_RC();
+}
+
+extern "C" int vg_adam_apply_clip(float* const* p, const float* const* g, float* const* m, float* const* v, const int64_t* n,
+                                  const double* beta1, const double* beta2, const double* eps, const float* grad_scale,
+                                  const float* const* state, const float* const* coef, int count, void* stream) {
+    VG_CHECK_ARG(count == 1 || count == 2, VG_EINVAL);
+    VG_CHECK_ARG(coef != nullptr, VG_EINVAL);
+    AdamClipArgs ca{};
+    int nb[2] = {0, 0};
+    const int rc = adam_fill(ca.a, nb, count, p, g, m, v, n, beta1, beta2, eps, grad_scale, state);
+    if (rc) return rc;
+    for (int i = 0; i < count; ++i) ca.coef[i] = coef[i];
+    ca.a.nb0 = nb[0];
+    hipLaunchKernelGGL(adam_clip_kernel, dim3(nb[0] + nb[1]), dim3(256), 0, vg_stream(stream), ca);
     return VG_LAUNCH_RC();
 }
 

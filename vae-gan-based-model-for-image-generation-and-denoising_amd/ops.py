@@ -1441,6 +1441,59 @@ def ema_update(ema, p, state, decay, warmup) -> None:
                                    (ctypes.c_int * k)(*[int(bool(w)) for w in warmup]), k, L.stream_ptr()), "vg_ema_update")
 
 
+def grad_norm_clip(grads, grad_scales, max_norms, out, ws) -> None:
+    """Gradient-norm clipping, the reduction (vg_grad_norm_clip, include/vaegan_hip.h "Gradient-norm clipping"): for up to 4
+    flat f32 gradient buffers, out[i] = [norm_i, coef_i] with norm_i = |grad_scales[i]| * ||grads[i]||_2 (f64 sum in a fixed
+    order) and coef_i = min(1, max_norms[i] / (norm_i + 1e-6)) as torch.nn.utils.clip_grad_norm_ forms it -- each buffer
+    against its OWN norm.  TWO launches; nothing is synchronised and grads are not rewritten (adam_apply_clip applies the
+    coefficient).  Lists of equal length; out[i]: f32 device tensor of >= 2 elements; ws: f64 device tensor of at least
+    VG_GNORM_MAX * VG_GNORM_PARTS elements.  Capturable."""
+    import ctypes
+    k = len(grads)
+    if not (len(grad_scales) == len(max_norms) == len(out) == k):
+        raise ValueError("grad_norm_clip: grads, grad_scales, max_norms and out must have one length")
+    if not 1 <= k <= L.VG_GNORM_MAX:
+        raise ValueError(f"grad_norm_clip: 1..{L.VG_GNORM_MAX} buffers per call, got {k}")
+    _need_cuda(*grads, *out, ws)
+    for g, o in zip(grads, out):
+        if g.dtype != torch.float32 or not g.is_contiguous():
+            raise RuntimeError("grad_norm_clip: grads[i] must be contiguous f32 tensors")
+        if o.dtype != torch.float32 or o.numel() < 2 or not o.is_contiguous() or o.device != g.device:
+            raise RuntimeError("grad_norm_clip: out[i] must be a contiguous f32 tensor of >= 2 elements on grads[i]'s device")
+    if ws.dtype != torch.float64 or ws.numel() < L.VG_GNORM_MAX * L.VG_GNORM_PARTS or ws.device != grads[0].device:
+        raise RuntimeError(f"grad_norm_clip: ws must hold {L.VG_GNORM_MAX * L.VG_GNORM_PARTS} f64 on the gradients' device")
+    arr = lambda ts: (ctypes.c_void_p * k)(*[t.data_ptr() for t in ts])       # noqa: E731
+    L.check(L.load().vg_grad_norm_clip(arr(grads), (ctypes.c_int64 * k)(*[g.numel() for g in grads]),
+                                       (ctypes.c_float * k)(*[float(s) for s in grad_scales]),
+                                       (ctypes.c_double * k)(*[float(m) for m in max_norms]), k, arr(out), ws.data_ptr(),
+                                       L.stream_ptr()), "vg_grad_norm_clip")
+
+
+def adam_apply_clip(opts, coefs) -> None:
+    """The prepared update of ONE or TWO optim.Adam instances in one launch with the gradient scale grad_scale * coefs[i][0],
+    the coefficient read from the device (vg_adam_apply_clip); coefs[i] None: grad_scale as it is, i.e. adam_apply2's /
+    adam_step(prepared=True)'s bits for that optimizer."""
+    import ctypes
+    k = len(opts)
+    if len(coefs) != k:
+        raise ValueError("adam_apply_clip: opts and coefs must have one length")
+    if k not in (1, 2):
+        raise ValueError(f"adam_apply_clip: 1 or 2 optimizers per launch, got {k}")
+    for o, c in zip(opts, coefs):
+        if c is not None:
+            _need_cuda(c)
+            if c.dtype != torch.float32 or c.numel() < 1 or c.device != o.flat_p.device:
+                raise RuntimeError("adam_apply_clip: coefs[i] must be an f32 tensor on the optimizer's device (or None)")
+    arr = lambda f: (ctypes.c_void_p * k)(*[f(o) for o in opts])       # noqa: E731
+    L.check(L.load().vg_adam_apply_clip(
+        arr(lambda o: o.flat_p.data_ptr()), arr(lambda o: o.flat_g.data_ptr()), arr(lambda o: o.exp_avg.data_ptr()),
+        arr(lambda o: o.exp_avg_sq.data_ptr()), (ctypes.c_int64 * k)(*[o.flat_p.numel() for o in opts]),
+        (ctypes.c_double * k)(*[o.betas[0] for o in opts]), (ctypes.c_double * k)(*[o.betas[1] for o in opts]),
+        (ctypes.c_double * k)(*[o.eps for o in opts]), (ctypes.c_float * k)(*[o.grad_scale for o in opts]),
+        arr(lambda o: o.state_dev.data_ptr()), (ctypes.c_void_p * k)(*[None if c is None else c.data_ptr() for c in coefs]),
+        k, L.stream_ptr()), "vg_adam_apply_clip")
+
+
 def launch_count() -> int:
     """Kernel launches libvaegan_hip.so has issued so far in this process (vg_launch_count)."""
     return int(L.load().vg_launch_count())

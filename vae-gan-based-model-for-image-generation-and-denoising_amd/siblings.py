@@ -19,9 +19,10 @@ from . import geometry as G
 from . import ops
 from .capture import HostMirrors, capture, replay
 from .engine import GradSink, bump_weights_epoch
+from .gradclip import ClipOption
 
 
-class _Graphed:
+class _Graphed(ClipOption):
     """Whole-iteration hipGraph replay for a trainer whose ``train_step(*tensors, **scalars)`` takes device tensors
     (static shapes) and plain scalars.  First call with a new signature runs eagerly (it also sizes the
     workspaces), the second captures and replays, later calls replay; every call is exactly one iteration."""
@@ -31,6 +32,10 @@ class _Graphed:
     # ema.EMA over the generating networks, or None: train_step then ends with ema.update(), one
     # launch directly after the (Encoder /) Generator optimizer step; None launches exactly what it launched without it
     ema = None
+    # max_grad_norm (gradclip.ClipOption): every optimizer's gradient is clipped to its own global L2
+    # norm directly before its step(), two launches per step, the coefficient applied inside the Adam launch; a number, a
+    # dict over the trainer's network names, inf (monitor only) or None (the default: nothing launched, nothing allocated).
+    # grad_norms: [networks, 2] device tensor, [norm, coefficient] of each network's last update.
 
     def step_graphed(self, *tensors, **scalars):
         return self._graphed_call(self.train_step, tensors, scalars)
@@ -47,7 +52,8 @@ class _Graphed:
             noise = ops.default_noise(dev)
         key = (tuple(None if t is None else tuple(t.shape) for t in tensors), tuple(sorted(scalars.items())),
                tuple(n.training for n in self._nets), None if noise is None else noise.state.data_ptr()) \
-            + (() if tag is None else (tag,)) + (() if self.ema is None else (("ema",) + self.ema.key(),))
+            + (() if tag is None else (tag,)) + (() if self.ema is None else (("ema",) + self.ema.key(),)) \
+            + self._clip_key()
         self._gnoise = noise
         st = getattr(self, "_gstate", None)
         if st is not None and st.key == key:
@@ -95,9 +101,12 @@ class VAETrainer(_Graphed):
     LOSS_NAMES = ("recon_loss", "kl_loss", "total")
 
     def __init__(self, encoder, decoder, optimizer, noise_max_std: float = 0.5, kl_weight: float = 1e-5,
-                 alpha_ssim: float = 0.0, hole_weight: float = 1.0, ema=None):
+                 alpha_ssim: float = 0.0, hole_weight: float = 1.0, ema=None, max_grad_norm=None):
+        """max_grad_norm: the one optimizer holds both networks, so its one norm is the network "EG" (a number, or
+        {"EG": number}); reported in grad_norms[0]."""
         self.E, self.G, self.opt = encoder, decoder, optimizer
         self.ema = ema
+        self.max_grad_norm = max_grad_norm
         self.sigma, self.kl_weight = noise_max_std, kl_weight                       # :66, :121
         # SSIM reconstruction loss (not in the reference; DESIGN.md section 4.4f): total += alpha_ssim * (1 - SSIM(recon,
         # img)), the gradient added onto the MSE's.  Off (0, the default): the iteration launches what it launched before.
@@ -109,6 +118,9 @@ class VAETrainer(_Graphed):
             raise ValueError("hole_weight must be finite and >= 0")
         self.dt = _same_dtype(encoder, decoder)
         self._nets, self._opts = (encoder, decoder), (optimizer,)
+
+    def _clip_opts(self):
+        return {"EG": self.opt}
 
     def train(self):
         self.E.train(), self.G.train()                                             # :98-99
@@ -169,6 +181,8 @@ class VAETrainer(_Graphed):
         dz = Gn._engine.backward(ctxG, d_pre, True, sink)
         dmulv = ops.reparam_kl_backward(mulv, lvc, eps_z, dz, w, L, dt)
         E._engine.backward(ctxE, dmulv.view(B, 1, 1, -1), False, sink)
+        if self._clip is not None:
+            self._clip.clip("EG")
         self.opt.step()                                                            # :126
         if self.ema is not None:
             self.ema.update()
@@ -189,9 +203,11 @@ class VAETrainer(_Graphed):
 # ---------------------------------------------------------------------------------------------------------------
 class _GANBase(_Graphed):
     def __init__(self, netG, netD, optimizerG, optimizerD, elide_dead_grads: bool = False,
-                 group_d_passes: bool = True, ema=None):
+                 group_d_passes: bool = True, ema=None, max_grad_norm=None):
+        """max_grad_norm: networks "G" and "D"; grad_norms rows in that order (D's row: its last update's)."""
         self.G, self.D, self.opt_G, self.opt_D = netG, netD, optimizerG, optimizerD
         self.ema = ema
+        self.max_grad_norm = max_grad_norm
         # The generator step's backward through D also produces D weight gradients that the next netD.zero_grad()
         # clears unread (module-level zero_grad, gan_code.py:195/:302).  False = compute them anyway, as the
         # reference does.
@@ -199,6 +215,9 @@ class _GANBase(_Graphed):
         self.group_d_passes = group_d_passes
         self.dt = _same_dtype(netG, netD)
         self._nets, self._opts = (netG, netD), (optimizerG, optimizerD)
+
+    def _clip_opts(self):
+        return {"G": self.opt_G, "D": self.opt_D}
 
     def train(self):
         self.G.train(), self.D.train()
@@ -254,12 +273,16 @@ class DCGANTrainer(_GANBase):
             dp_fake = ops.bce_forward_backward(p_fake, 0.0, 1.0, losses[1:2], False, True)
             D._engine.backward(c_real, dp_real, False, sink)
             D._engine.backward(c_fake, dp_fake, False, sink)
+        if self._clip is not None:
+            self._clip.clip("D")
         self.opt_D.step()                                                          # :209
         self.opt_G.zero_grad(memset=False)                                         # :212
         p_adv, c_adv = D.engine_forward(fake_h, B)                                 # :214
         dp_adv = ops.bce_forward_backward(p_adv, 1.0, 1.0, losses[2:3], False, True)   # :215
         d_fake = D._engine.backward(c_adv, dp_adv, True, sink, param_grads=not self.elide_dead_grads)   # :216
         self._gen_backward(ctxG, fake, d_fake, sink)
+        if self._clip is not None:
+            self._clip.clip("G")
         self.opt_G.step()                                                          # :217
         if self.ema is not None:
             self.ema.update()
@@ -312,6 +335,8 @@ class WGANTrainer(_GANBase):
                 dp_fake = ops.mean_forward_backward(p_fake, 1.0, 1.0, losses[0:1], True, True)
                 D._engine.backward(c_real, dp_real, False, sink)
                 D._engine.backward(c_fake, dp_fake, False, sink)
+            if self._clip is not None:
+                self._clip.clip("D")
             self.opt_D.step()                                                      # :317
             ops.clamp_(self.opt_D.flat_p, -self.clip_value, self.clip_value)       # :320-321
             bump_weights_epoch(self.opt_D.params)
@@ -322,6 +347,8 @@ class WGANTrainer(_GANBase):
         dp_adv = ops.mean_forward_backward(p_adv, -1.0, 1.0, losses[1:2], False, True)   # :328
         d_fake = D._engine.backward(c_adv, dp_adv, True, sink, param_grads=not self.elide_dead_grads)   # :330
         self._gen_backward(ctxG, fake, d_fake, sink)
+        if self._clip is not None:
+            self._clip.clip("G")
         self.opt_G.step()                                                          # :331
         if self.ema is not None:
             self.ema.update()

@@ -9,6 +9,7 @@ parity runs or are drawn on the device.
 """
 import math
 import os
+import time
 from typing import Dict, Optional
 
 import torch
@@ -17,8 +18,11 @@ from . import geometry as G
 from . import ops
 from .capture import CaptureRefused, HostMirrors, capture, replay
 from .engine import GradSink
+from .gradclip import ClipOption
 
 LOSS_NAMES = ("recon_loss", "kl_loss", "g_loss_adv", "d_loss_1", "d_loss_2")
+# more than two periods of c10d's NCCL watchdog (ProcessGroupNCCL::kWatchdogThreadSleepMillis = 100): see _capture
+WATCHDOG_PASS_SECONDS = 0.25
 
 
 class _SyncBNHandoff:
@@ -37,12 +41,12 @@ class _SyncBNHandoff:
         self.trainer._cut(lambda: self.trainer.reducer.all_reduce_sum(t))
 
 
-class VAEGANTrainer:
+class VAEGANTrainer(ClipOption):
     def __init__(self, encoder, decoder, discriminator, opt_E, opt_Dec, opt_Dis, alpha_kl: float = 0.1,
                  alpha_adv: float = 0.1, noise_sigma: float = 0.05, real_label: float = 0.9, fake_label: float = 0.1,
                  d_iters: int = 2, elide_dead_grads: bool = False, reducer=None, group_d_passes: bool = True,
                  sync_bn: bool = False, feat_layer: Optional[int] = None, alpha_feat: float = 0.0, alpha_pix: float = 1.0,
-                 alpha_ssim: float = 0.0, hole_weight: float = 1.0, ema=None):
+                 alpha_ssim: float = 0.0, hole_weight: float = 1.0, ema=None, max_grad_norm=None):
         self.E, self.G, self.D = encoder, decoder, discriminator
         self.opt_E, self.opt_G, self.opt_D = opt_E, opt_Dec, opt_Dis
         self.alpha_kl, self.alpha_adv, self.sigma = alpha_kl, alpha_adv, noise_sigma          # :49-50, :91-92
@@ -76,6 +80,15 @@ class VAEGANTrainer:
         # iteration ends with ema.update(), ONE more launch directly after the Encoder / Generator optimizer step, captured
         # with the rest.  None (the default): the iteration launches exactly what it launched without it.
         self.ema = ema
+        # Gradient-norm clipping: each network's gradient is clipped to its OWN global L2 norm
+        # (torch.nn.utils.clip_grad_norm_ per optimizer; a joint Encoder + Generator norm is not offered).  A number clips
+        # all three networks at that value, a dict with keys among "E", "G", "D" only the named ones, float("inf") only
+        # reports the norms.  The reduction runs directly before each optimizer step (after the gradient all-reduce under
+        # data parallelism) and leaves the coefficient on the device, where the Adam launch reads it: 2 launches per clip
+        # point, 2 d_iters + 2 per iteration, captured with the rest.  grad_norms ([3, 2] device tensor, rows E, G, D =
+        # [norm, coefficient]; D's is the last Discriminator update's) and loss_dict() report them.  None (the default): the
+        # iteration launches exactly what it launched without it and nothing is allocated.
+        self.max_grad_norm = max_grad_norm
         self.group_d_passes = group_d_passes       # run a D iteration's real+fake passes as one 2B-row launch chain
         # BCE + its gradient + the sigmoid / head backward as ONE launch per Discriminator pass (ops.head_backward;
         # bit-identical to the three separate launches, which False selects)
@@ -110,6 +123,9 @@ class VAEGANTrainer:
         self._inline_failed = False     # capturing the collectives inside the graph failed once: use the segmented form
         self.last_step_weighted = False # the last iteration used the region-weighted term (loss_dict reports hole_mse)
 
+    def _clip_opts(self):
+        return {"E": self.opt_E, "G": self.opt_G, "D": self.opt_D}
+
     def train(self):
         self.E.train(), self.G.train(), self.D.train()                                         # :56-58
 
@@ -142,7 +158,7 @@ class VAEGANTrainer:
                 id(self.reducer), self.sync_bn, opts,
                 None if self.noise is None or inject else self.noise.state.data_ptr()) \
             + ((True, with_rects, self.hole_weight) if paired else ()) \
-            + ((("ema",) + self.ema.key(),) if self.ema is not None else ())
+            + ((("ema",) + self.ema.key(),) if self.ema is not None else ()) + self._clip_key()
 
     # ---- data-parallel gradient hand-off (ddp.GradReducer) -------------------------------------------------------
     def _buckets_for(self, opt, net):
@@ -341,6 +357,8 @@ class VAEGANTrainer:
                 D._engine.backward(c_real, dp_real, False, sink)
                 D._engine.backward(c_fake, dp_fake, False, sink, on_grads=self._grad_hook(self.opt_D, D))   # the accumulating pass
             self._finish_reduce(self.opt_D, D)            # D's buckets overlap the rest of its own backward
+            if self._clip is not None:
+                self._clip.clip("D")                      # norm of the reduced gradient; the step below applies the coefficient
             self.opt_D.step(prepared=prep and it == 0)
 
         # ---- Generator + VAE loss (:110-117) ----
@@ -386,6 +404,8 @@ class VAEGANTrainer:
         dmulv = ops.reparam_kl_backward(mulv, lvc, eps_z, dz, kl_w / B, L, dt)
         E._engine.backward(ctxE, dmulv.view(B, 1, 1, -1), False, sink, on_grads=self._grad_hook(self.opt_E, E))
         self._finish_reduce(self.opt_E, E, also_wait=(self.opt_G,))
+        if self._clip is not None:
+            self._clip.clip("E", "G")                         # one call for both, each against its own norm
         if prep and self.merge_small_launches:
             self.opt_E.step_pair(self.opt_G)                  # :134-135 in one launch (both prepared by the prologue)
         else:
@@ -506,6 +526,16 @@ class VAEGANTrainer:
                 self.reducer.drain()
             if self.reducer is not None and getattr(self.reducer, "outstanding", lambda: 0)() != 0:
                 raise CaptureRefused("hipGraph capture refused: the gradient reducer still has collectives in flight")
+            if inline:
+                # Collectives recorded INSIDE the graph put RCCL's stream into the capture.  c10d's watchdog keeps every
+                # eagerly launched collective (the warm-up iteration's) in its list until its next pass (one every 100 ms)
+                # finds it complete, and asks with hipEventQuery; a pass that falls into the capture asks about end events
+                # that sit on RCCL's stream, which HIP answers with hipErrorCapturedEvent -- the watchdog then takes the
+                # process down.  So: let the device finish what was launched, then give the watchdog time for a pass over
+                # work that is all complete, after which its list is empty until the capture has ended (torch enqueues
+                # nothing while the current stream is capturing).  Once per capture.
+                torch.cuda.synchronize()
+                time.sleep(WATCHDOG_PASS_SECONDS)
 
         def set_cut_hook(cut):                     # inline: _cut runs the collective at once, i.e. records it
             self._cut_hook = None if inline else cut
@@ -593,6 +623,8 @@ class VAEGANTrainer:
         if self.last_step_weighted:
             out["hole_mse"] = v[7]               # mean squared error inside the occlusion rectangles: only after a step that
                                                  # used the weighted term (slot 7 reads 0 after any other)
+        if self._clip is not None:
+            out.update(self._clip.report())      # grad_norm_E/G/D, clip_coef_E/G/D of the networks that are configured
         if epoch is not None:
             out["total"] = self.alpha_pix * out["recon_loss"] + self.alpha_kl * min(1.0, epoch / 50) * out["kl_loss"] \
                 + self.alpha_adv * out["g_loss_adv"] + self.alpha_feat * v[5] + self.alpha_ssim * v[6]
