@@ -48,7 +48,7 @@ extern "C" {
 #define VG_ACT_LRELU   2   /* nn.LeakyReLU(slope)    main_vae.py:25, gan_code.py:62-82 */
 #define VG_ACT_TANH    3   /* nn.Tanh()              gan_code.py:50 (vg_tnconv epilogue only) */
 
-#define VG_ABI_VERSION 24  /* 2: vg_pack_desc.tile_start, SyncBN / WGAN / data-path entry points; 3: in-kernel noise (vg_*_rng);
+#define VG_ABI_VERSION 25  /* 2: vg_pack_desc.tile_start, SyncBN / WGAN / data-path entry points; 3: in-kernel noise (vg_*_rng);
                              4: vg_bn_finalize_act_forward, vg_bn_backward_finalize_apply;
                              7: vg_bce_pair_forward_backward;
                              8: vg_head_backward; round-3 prune -- the opt-in experiments of ABI 5 / 6 that measured slower (input prologue of
@@ -70,7 +70,8 @@ extern "C" {
                                  "supported" query of vg_bn_finalize_act_forward (vg_bn_launch_plan(VG_BN_PLAN_FUSED).fused) are gone;
                              22: weight averaging: vg_ema_update;
                              23: vg_wgrad_plan / vg_wg_plan, vg_edge_wgrad_plan / vg_ew_plan replace vg_wgrad_ws_bytes / vg_edge_wgrad_ws_bytes;
-                             24: gradient-norm clipping: vg_grad_norm_clip, vg_adam_apply_clip */
+                             24: gradient-norm clipping: vg_grad_norm_clip, vg_adam_apply_clip;
+                             25: differentiable augmentation: vg_diffaug_params, vg_diffaug_forward, vg_diffaug_backward (+ _ws_floats) */
 int vg_abi_version(void);
 /* The library reads its optional kernel-selection switches (VG_* environment variables, DESIGN.md "Runtime switches")
  * ONCE, when it is loaded; nothing on a launch path calls getenv.  A process that changes one of them afterwards
@@ -952,6 +953,72 @@ int vg_adam_apply_clip(float* const* p, const float* const* g, float* const* m, 
                        const double* beta1, const double* beta2, const double* eps, const float* grad_scale,
                        const float* const* state /* prepared */, const float* const* coef /* device; entry may be NULL */,
                        int count /* 1 or 2 */, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Differentiable augmentation (not in the reference; Zhao et al., NeurIPS 2020, "DiffAugment"; ABI 25; csrc/diffaug.hip): a
+ * random colour change, translation and cutout per image, applied to everything the Discriminator sees -- exactly where the
+ * reference perturbs D's inputs with instance noise (vaegan_code.py:91-92) -- and the exact adjoint that carries the
+ * Generator's gradient back through it.
+ *
+ * x, y (forward) and g, dx (backward): images in the engine layout [N][H][W][CP], dtype VG_F32 or VG_BF16, C real channels,
+ * CP - C pad channels (read as anything, written as zero); one pixel is a whole number of 16-byte units (CP % 4 == 0 for f32,
+ * CP % 8 == 0 for bf16).  params: f32 [PB][8] = {beta, s, k, ty, tx, cy, cx, unused}; N % PB == 0 and image n uses row n % PB
+ * (N = 2 B, PB = B: a real image and its reconstruction share one draw).  cut_h, cut_w: the cutout's size, per launch.
+ *
+ * Forward.  m(p) = (sum_c x_c(p)) / C, M = (sum_{c,p} x_c(p)) / (C H W) over the whole SOURCE image,
+ *     col_c(p) = k s x_c(p) + (k - k s) m(p) + (1 - k) M + beta
+ * (brightness x + beta, then saturation about the channel mean by s, then contrast about the image mean by k), and
+ *     y_c(h, w) = col_c(h + ty, w + tx)   where (h + ty, w + tx) lies in the image and (h, w) is not in the cutout, else 0.
+ * The cutout is cy <= h < cy + cut_h and cx <= w < cx + cut_w, clipped by the image; cut_h == 0 or cut_w == 0: no cutout.
+ * Backward, the adjoint.  g'_c(p) = g_c(p - t) where p - t lies in the image and is not in the cutout, else 0;
+ *     Gsum = sum_{c,p} g'_c(p);   dx_c(p) = k s g'_c(p) + (k - k s) (sum_c' g'_c'(p)) / C + (1 - k) Gsum / (C H W).
+ * So <T x, g> = <x, T' g> with T the linear part (beta = 0).
+ *
+ * Arithmetic: f32, every product, sum and quotient rounded on its own (no contraction into an fma), ONE rounding to dtype on
+ * the store.  With v = x (forward) or g' (backward; zero where masked), both directions evaluate, in this order:
+ *     ks = k * s;  b = k - ks;  c = 1 - k                                    per image
+ *     S  = the whole-image sum, see below;  mean = S / (float)(C H W);  e = c * mean  (forward: e = c * mean + beta)
+ *     sc = ((0 + v_0) + v_1) + ... + v_{C-1};  m = sc / (float)C                per pixel, channels ascending
+ *     out_c = ((ks * v_c) + (b * m)) + e
+ * and the forward then writes 0 where the destination has no source or lies in the cutout (the backward writes out_c
+ * everywhere: a pixel whose g' is zero still receives e).  An identity row {0, 1, 1, 0, 0, ., ., .} with no cutout therefore
+ * reproduces its input bit for bit, except that -0 is stored as +0.
+ * The whole-image sum S (of x, or of g') does not depend on the grid and uses no atomics: the pixels p = h W + w of an image
+ * are cut into parts of 1024; in part q thread t (of 256) owns pixels 1024 q + t + 256 j, j < 4, and forms
+ * (sc_0 + sc_1) + (sc_2 + sc_3) (sc_j = 0 past the image's end); each 64-thread wave adds its values by the xor butterfly
+ * v += v[lane ^ o], o = 32, 16, 8, 4, 2, 1; the part's sum is ((w_0 + w_1) + w_2) + w_3 over the four waves and goes to
+ * ws[n * parts + q]; S = (((0 + ws[n][0]) + ws[n][1]) + ...) in ascending part order.  In the backward the sum runs over dx's
+ * pixels p of g'.  ws == NULL: the reduce launch is skipped and S = 0 (for callers whose k is 1 in every row: c = 0).
+ *
+ * Parameter safety.  ty, tx, cy, cx are integers carried in f32; the kernels truncate them toward zero.  NaN or |value| >= 2^30
+ * in ty or tx counts as 0, in cy or cx as "no cutout" for that image.  Every source index is bound-checked in integer
+ * arithmetic before an address is formed from it: no content of params can cause an out-of-range access (the promise
+ * vg_region_mse_forward_backward makes for rects).  beta, s, k are used as they are (a NaN gives NaN pixels).
+ *
+ * vg_diffaug_params: out f32 [B][8] drawn from rng = {seed, iteration} (device memory) like every in-kernel draw, draw id
+ * VG_DRAW_AUGMENT; with w_i = word(VG_DRAW_AUGMENT, 8 b + i) for image b (u01, rint, word: "Degraded pairs" above), all f32:
+ *     beta = u01(w_0) - 0.5;  s = 2 * u01(w_1);  k = u01(w_2) + 0.5  (one rounding)
+ *     ty = rint(w_3, -sh_h, sh_h + 1), tx = rint(w_4, -sh_w, sh_w + 1),  sh = floor(size / 8 + 0.5) = (size + 4) / 8
+ *     cy = rint(w_5, 0, H + 1 - cut_h % 2) - cut_h / 2,  cx likewise from w_6 and W,  cut = floor(size / 2 + 0.5) = (size + 1) / 2
+ * policy bits: 1 brightness, 2 saturation, 4 contrast, 8 translation, 16 cutout; a cleared bit writes the identity value (0,
+ * 1, 1, 0 and 0, cy = cx = 0); the caller passes cut_h = cut_w = 0 to the apply launches when bit 16 is clear, else the cut
+ * sizes above.  H, W < 2^24.  One launch.
+ *
+ * vg_diffaug_forward / vg_diffaug_backward: at most two launches each (per-part sums into ws, then the apply pass), one
+ * workgroup of 256 threads per part, per thread four independent 16-byte loads in flight; no LDS beyond the block sum.
+ * HBM traffic with the reduce: 3 passes over the tensor (read, read, write), 2 without.  ws: at least
+ * vg_diffaug_ws_floats(N, H, W) = N * ceil(H W / 1024) floats, ws_capacity its capacity in floats.
+ * Checked on the host before anything is launched.  VG_EINVAL: in, out or params NULL, in == out, a size < 1, N % PB != 0,
+ * C > CP, cut_h or cut_w outside [0, H] / [0, W], H W >= 2^30, ws given but too small.  VG_ENOSUP: VG_FP8 (any dtype but f32 /
+ * bf16).  VG_EALIGN: a pixel that is not whole 16-byte units, or in, out, params or ws not 16-byte aligned.
+ * ---------------------------------------------------------------------------------------- */
+#define VG_DRAW_AUGMENT 48
+int64_t vg_diffaug_ws_floats(int N, int H, int W);              /* VG_EINVAL (negative) for sizes outside the contract */
+int vg_diffaug_params(const uint64_t* rng, int B, int policy, int H, int W, float* out, void* stream);
+int vg_diffaug_forward(const void* in, void* out, const float* params, int N, int PB, int H, int W, int C, int CP, int cut_h,
+                       int cut_w, float* ws, int64_t ws_capacity, int dtype, void* stream);
+int vg_diffaug_backward(const void* in, void* out, const float* params, int N, int PB, int H, int W, int C, int CP, int cut_h,
+                        int cut_w, float* ws, int64_t ws_capacity, int dtype, void* stream);
 
 #ifdef __cplusplus
 }

@@ -15,7 +15,8 @@ README.md:22 precision / recall): ``metrics`` -- ``FeatureStats``, ``frechet_dis
 average of Encoder / Generator weights kept on the device, ``VAEGANTrainer(..., ema=)`` and the sibling trainers.
 Gradient-norm clipping (not in the reference): ``clip_grad_norm_`` / ``Adam.clip_grad_norm_`` -- torch's
 ``clip_grad_norm_`` with the coefficient kept on the device and applied inside the Adam step, ``max_grad_norm=`` on the four
-trainers.  Data path (dataset_code.py): ``data`` -- ``ResidentImages`` (``resized``: Resize +
+trainers.  Differentiable augmentation of the Discriminator's inputs (not in the reference): ``DiffAugment`` and
+``augment=`` on the three adversarial trainers.  Data path (dataset_code.py): ``data`` -- ``ResidentImages`` (``resized``: Resize +
 CenterCrop on the device), ``resample_coeffs``, ``resize_geometry``.
 """
 from . import data  # noqa: F401
@@ -23,6 +24,7 @@ from . import geometry  # noqa: F401
 from . import latent  # noqa: F401
 from . import metrics  # noqa: F401
 from .data import ResidentImages, resample_coeffs, resize_geometry
+from .augment import DiffAugment
 from .ddp import GradReducer
 from .ema import EMA
 from .denoise import denoise_eval, paired_test_epoch, validation_epoch
@@ -40,5 +42,5 @@ __all__ = ["ConvBlock", "Encoder", "Generator", "Discriminator", "weights_init",
            "VAEGANTrainer", "LOSS_NAMES", "configure_seed", "geometry", "denoise_eval", "validation_epoch", "paired_test_epoch", "GradReducer", "data", "VAETrainer", "DCGANTrainer", "WGANTrainer", "graphed",
            "latent", "LatentPrior", "encode_dataset", "evaluate_generation", "sample_images",
            "ResidentImages", "resample_coeffs", "resize_geometry",
-           "EMA", "clip_grad_norm_",
+           "EMA", "clip_grad_norm_", "DiffAugment",
            "metrics", "FeatureStats", "frechet_distance", "precision_recall", "encoder_features", "kernel_distance"]

@@ -19,7 +19,7 @@ VG_MAX_PHASE = 4
 VG_EMA_MAX = 4
 VG_GNORM_MAX = 4
 VG_GNORM_PARTS = 512
-ABI_VERSION = 24
+ABI_VERSION = 25
 
 VG_ENOSUP = -3
 _ERR = {-1: "VG_EINVAL (bad shape/size/flag)", -2: "VG_EALIGN (16-byte contract violated)",
@@ -179,6 +179,10 @@ SIGNATURES = {
     "vg_ema_update": (c_int, [_P, _P, _P, _P, _P, _P, _I, _P]),
     "vg_grad_norm_clip": (c_int, [_P, _P, _P, _P, _I, _P, _P, _P]),
     "vg_adam_apply_clip": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
+    "vg_diffaug_ws_floats": (c_int64, [_I, _I, _I]),
+    "vg_diffaug_params": (c_int, [_P, _I, _I, _I, _I, _P, _P]),
+    "vg_diffaug_forward": (c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _L, _I, _P]),
+    "vg_diffaug_backward": (c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _L, _I, _P]),
     "vg_nchw_to_nhwc_pair": (c_int, [_P, _P, _P, _I, _F, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "vg_mse_partial": (c_int, [_P, _P, _L, _F, _P, _P, _I, POINTER(c_int), _P]),
     "vg_kl_forward_mse_final": (c_int, [_P, _P, _I, _I, _I, _F, _P, _P, _I, _L, _P, _I, _P]),

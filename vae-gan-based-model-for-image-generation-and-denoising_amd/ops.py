@@ -1384,6 +1384,68 @@ def region_mse_forward_backward(a, b, rects, w_hole, gscale, loss=None, hole_mse
     return da
 
 
+# draw id of the augmentation table (include/vaegan_hip.h "Differentiable augmentation"): outside 0..2, 16..18 and 32..34
+DRAW_AUGMENT = 48
+AUG_BRIGHTNESS, AUG_SATURATION, AUG_CONTRAST, AUG_TRANSLATION, AUG_CUTOUT = 1, 2, 4, 8, 16
+
+
+def diffaug_cut(policy: int, H: int, W: int):
+    """(cut_h, cut_w) the apply launches take for a table drawn with `policy`: floor(size / 2 + 0.5), or (0, 0) when the
+    cutout bit is clear."""
+    return ((H + 1) // 2, (W + 1) // 2) if policy & AUG_CUTOUT else (0, 0)
+
+
+def diffaug_params(state: torch.Tensor, B: int, policy: int, H: int, W: int, out=None) -> torch.Tensor:
+    """-> f32 [B, 8] on the device = {beta, s, k, ty, tx, cy, cx, 0} per image (vg_diffaug_params), drawn from state
+    (int64[2] = {seed, counter}, NoiseStream.state) with draw id DRAW_AUGMENT; policy: a sum of the AUG_* bits."""
+    _need_cuda(state, out)
+    if state.dtype != torch.int64 or state.numel() != 2:
+        raise RuntimeError("diffaug_params: state must be the int64[2] {seed, counter} of a NoiseStream")
+    if not 0 <= int(policy) < 32:
+        raise RuntimeError("diffaug_params: policy is a sum of the AUG_* bits (0..31)")
+    y = out if out is not None else torch.empty(B, 8, dtype=torch.float32, device=state.device)
+    if y.dtype != torch.float32 or tuple(y.shape) != (B, 8):
+        raise RuntimeError("diffaug_params: out must be f32 [B, 8]")
+    L.check(L.load().vg_diffaug_params(state.data_ptr(), B, int(policy), H, W, y.data_ptr(), L.stream_ptr()),
+            "vg_diffaug_params")
+    return y
+
+
+def _diffaug(name, fn_name, x, params, C, cut, dtype, out, need_sum):
+    _need_cuda(x, params, out)
+    if x.dtype != TORCH_DT[dtype] or x.dim() != 4:
+        raise RuntimeError(f"{name}: the image must be an engine-layout [N,H,W,CP] tensor of {TORCH_DT[dtype]}")
+    if params.dtype != torch.float32 or params.dim() != 2 or params.shape[1] != 8 or params.shape[0] < 1:
+        raise RuntimeError(f"{name}: params must be f32 [PB, 8] (ops.diffaug_params)")
+    N, H, W, CP = x.shape
+    PB = params.shape[0]
+    if N % PB != 0:
+        raise RuntimeError(f"{name}: the number of images must be a multiple of the parameter rows")
+    y = out if out is not None else torch.empty_like(x)
+    if y.shape != x.shape or y.dtype != x.dtype:
+        raise RuntimeError(f"{name}: out must match the input")
+    lib = L.load()
+    ws, nws = None, 0
+    if need_sum:
+        nws = _ws_query(lib.vg_diffaug_ws_floats(N, H, W), "vg_diffaug_ws_floats (needs N, H, W >= 1)")
+        ws = WS.get("diffaug", nws * 4, x.device)
+    L.check(getattr(lib, fn_name)(x.data_ptr(), y.data_ptr(), params.data_ptr(), N, PB, H, W, C, CP, int(cut[0]), int(cut[1]),
+                                  L.ptr(ws), nws, dtype, L.stream_ptr()), fn_name)
+    return y
+
+
+def diffaug_forward(x, params, C, cut, dtype, out=None, need_sum=True):
+    """y = T(x) (vg_diffaug_forward): colour, translation and cutout per image of x [N,H,W,CP] (engine layout, C real channels)
+    by the rows of params [PB, 8], image n using row n % PB; cut = (cut_h, cut_w) (ops.diffaug_cut).  need_sum=False skips the
+    whole-image mean's reduce launch (only for tables whose k is 1 everywhere)."""
+    return _diffaug("diffaug_forward", "vg_diffaug_forward", x, params, C, cut, dtype, out, need_sum)
+
+
+def diffaug_backward(g, params, C, cut, dtype, out=None, need_sum=True):
+    """dx = T'(g) (vg_diffaug_backward): the exact adjoint of diffaug_forward's linear part, same arguments."""
+    return _diffaug("diffaug_backward", "vg_diffaug_backward", g, params, C, cut, dtype, out, need_sum)
+
+
 def axpy(a, b, alpha, out=None):
     out = out if out is not None else torch.empty_like(a)
     L.check(L.load().vg_axpy(a.data_ptr(), b.data_ptr(), alpha, out.data_ptr(), a.numel(), L.stream_ptr()), "vg_axpy")

@@ -15,6 +15,7 @@ from typing import List, Optional, Sequence
 
 import torch
 
+from . import augment as A
 from . import geometry as G
 from . import ops
 from .capture import HostMirrors, capture, replay
@@ -40,6 +41,10 @@ class _Graphed(ClipOption):
     def step_graphed(self, *tensors, **scalars):
         return self._graphed_call(self.train_step, tensors, scalars)
 
+    def _extra_key(self):
+        """Whatever else a subclass's captured iteration freezes."""
+        return ()
+
     def _graphed_call(self, step, tensors, scalars, tag=None):
         """step(*tensors, **scalars) eagerly, then captured, then replayed; tag: whatever else the capture freezes."""
         # Draws that are not injected come from the per-device default NoiseStream, whose STATE BUFFER the captured
@@ -53,7 +58,7 @@ class _Graphed(ClipOption):
         key = (tuple(None if t is None else tuple(t.shape) for t in tensors), tuple(sorted(scalars.items())),
                tuple(n.training for n in self._nets), None if noise is None else noise.state.data_ptr()) \
             + (() if tag is None else (tag,)) + (() if self.ema is None else (("ema",) + self.ema.key(),)) \
-            + self._clip_key()
+            + self._clip_key() + self._extra_key()
         self._gnoise = noise
         st = getattr(self, "_gstate", None)
         if st is not None and st.key == key:
@@ -203,8 +208,13 @@ class VAETrainer(_Graphed):
 # ---------------------------------------------------------------------------------------------------------------
 class _GANBase(_Graphed):
     def __init__(self, netG, netD, optimizerG, optimizerD, elide_dead_grads: bool = False,
-                 group_d_passes: bool = True, ema=None, max_grad_norm=None):
-        """max_grad_norm: networks "G" and "D"; grad_norms rows in that order (D's row: its last update's)."""
+                 group_d_passes: bool = True, ema=None, max_grad_norm=None, augment=None):
+        """max_grad_norm: networks "G" and "D"; grad_norms rows in that order (D's row: its last update's).
+        augment (augment.DiffAugment or a policy string): every Discriminator pass reads the augmented
+        copy of its [2B] input, real image b and fake image b sharing row b of ONE table per train_step (aug_params, [B, 8]);
+        the generator pass's input gradient goes back through the adjoint.  The table is drawn from a NoiseStream of the
+        trainer's own (seeded from torch's device seed like the VAE-GAN's, advanced once per train_step; augment_state() /
+        load_augment_state() save and restore it).  None: nothing launched, nothing allocated."""
         self.G, self.D, self.opt_G, self.opt_D = netG, netD, optimizerG, optimizerD
         self.ema = ema
         self.max_grad_norm = max_grad_norm
@@ -215,6 +225,43 @@ class _GANBase(_Graphed):
         self.group_d_passes = group_d_passes
         self.dt = _same_dtype(netG, netD)
         self._nets, self._opts = (netG, netD), (optimizerG, optimizerD)
+        self.augment = A.DiffAugment.of(augment)
+        self.aug_params, self.aug_noise = None, None
+        if self.augment is not None:
+            A.check_dtype(self.dt)
+
+    def _extra_key(self):
+        if self.augment is None:
+            return ()
+        if self.aug_noise is None:                 # on the host, before any capture: the key names the state buffer
+            self.aug_noise = ops.NoiseStream(next(self.D.parameters()).device, torch.cuda.initial_seed())
+        return self.augment.key() + (self.aug_noise.state.data_ptr(),)
+
+    def _aug_begin(self, B, H, W, dev):
+        """Top of an augmented train_step: advance the trainer's stream, draw the step's one table."""
+        if self.aug_noise is None or self.aug_params is None or self.aug_params.shape[0] != B:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("the augmentation state would be allocated during graph capture; run a warm-up step first")
+            if self.aug_noise is None:
+                self.aug_noise = ops.NoiseStream(dev, torch.cuda.initial_seed())
+            self.aug_params = torch.empty(B, 8, dtype=torch.float32, device=dev)
+            self._gstate = None                    # a captured iteration points at the old buffers
+        self.aug_noise.advance()
+        self.augment.draw(self.aug_noise.state, B, H, W, out=self.aug_params)
+
+    def augment_state(self):
+        """The augmentation stream's {seed, iteration} (host int64[2]) for a checkpoint, or None."""
+        return None if self.aug_noise is None else self.aug_noise.get_state().cpu()
+
+    def load_augment_state(self, st) -> None:
+        if st is None or self.augment is None:
+            return
+        dev = next(self.D.parameters()).device
+        if self.aug_noise is None:
+            self.aug_noise = ops.NoiseStream(dev, int(st[0]))
+            self._gstate = None
+        self.aug_noise.seed = int(st[0])
+        self.aug_noise.set_state(st)
 
     def _clip_opts(self):
         return {"G": self.opt_G, "D": self.opt_D}
@@ -259,6 +306,11 @@ class DCGANTrainer(_GANBase):
         both = ops.empty_act((2 * B, real.shape[2], real.shape[3], CP), dt, dev)
         real_h = ops.nchw_to_nhwc(real.contiguous(), CP, dt, out=both[:B])
         fake_h = ops.nchw_to_nhwc(fake, CP, dt, out=both[B:])
+        aug = self.augment
+        if aug is not None:
+            self._aug_begin(B, both.shape[1], both.shape[2], dev)
+            both = aug.forward(both, self.aug_params, D.nc, dt)
+            real_h, fake_h = both[:B], both[B:]
         self.opt_D.zero_grad(memset=False)                                         # :195
         if self.group_d_passes and D._engine.can_group(B, 2):
             p_both, c_both = D.engine_forward(both, B, groups=2)
@@ -280,6 +332,8 @@ class DCGANTrainer(_GANBase):
         p_adv, c_adv = D.engine_forward(fake_h, B)                                 # :214
         dp_adv = ops.bce_forward_backward(p_adv, 1.0, 1.0, losses[2:3], False, True)   # :215
         d_fake = D._engine.backward(c_adv, dp_adv, True, sink, param_grads=not self.elide_dead_grads)   # :216
+        if aug is not None:
+            d_fake = aug.backward(d_fake, self.aug_params, D.nc, dt)
         self._gen_backward(ctxG, fake, d_fake, sink)
         if self._clip is not None:
             self._clip.clip("G")
@@ -318,12 +372,19 @@ class WGANTrainer(_GANBase):
         both = ops.empty_act((2 * B, real.shape[2], real.shape[3], CP), dt, dev)
         real_h = ops.nchw_to_nhwc(real.contiguous(), CP, dt, out=both[:B])
         grouped = self.group_d_passes and D._engine.can_group(B, 2)
+        aug, seen = self.augment, both
+        if aug is not None:
+            self._aug_begin(B, both.shape[1], both.shape[2], dev)
+            seen = torch.empty_like(both)                                          # what the critic reads
         for it in range(self.critic_iters):                                        # :301
             self.opt_D.zero_grad(memset=False)                                     # :302
             fake, _ = self._gen(critic_noise[it], False)                           # :309-310 (.detach(): forward only)
             fake_h = ops.nchw_to_nhwc(fake, CP, dt, out=both[B:])
+            if aug is not None:
+                aug.forward(both, self.aug_params, D.nc, dt, out=seen)             # the refilled batch, the step's one table
+                real_h, fake_h = seen[:B], seen[B:]
             if grouped:
-                p_both, c_both = D.engine_forward(both, B, groups=2)
+                p_both, c_both = D.engine_forward(seen, B, groups=2)
                 dp = torch.empty_like(p_both)
                 ops.mean_forward_backward(p_both[:B], -1.0, 1.0, losses[0:1], False, True, out=dp[:B])   # :305-306
                 ops.mean_forward_backward(p_both[B:], 1.0, 1.0, losses[0:1], True, True, out=dp[B:])     # :311-315
@@ -343,9 +404,13 @@ class WGANTrainer(_GANBase):
         self.opt_G.zero_grad(memset=False)                                         # :324
         fake, ctxG = self._gen(gen_noise, True)                                    # :325-326
         fake_h = ops.nchw_to_nhwc(fake, CP, dt, out=both[B:])
+        if aug is not None:
+            fake_h = aug.forward(fake_h, self.aug_params, D.nc, dt, out=seen[B:])
         p_adv, c_adv = D.engine_forward(fake_h, B)                                 # :327
         dp_adv = ops.mean_forward_backward(p_adv, -1.0, 1.0, losses[1:2], False, True)   # :328
         d_fake = D._engine.backward(c_adv, dp_adv, True, sink, param_grads=not self.elide_dead_grads)   # :330
+        if aug is not None:
+            d_fake = aug.backward(d_fake, self.aug_params, D.nc, dt)
         self._gen_backward(ctxG, fake, d_fake, sink)
         if self._clip is not None:
             self._clip.clip("G")

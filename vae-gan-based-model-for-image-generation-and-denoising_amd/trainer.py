@@ -17,6 +17,7 @@ import torch
 from . import geometry as G
 from . import ops
 from .capture import CaptureRefused, HostMirrors, capture, replay
+from . import augment as A
 from .engine import GradSink
 from .gradclip import ClipOption
 
@@ -46,7 +47,7 @@ class VAEGANTrainer(ClipOption):
                  alpha_adv: float = 0.1, noise_sigma: float = 0.05, real_label: float = 0.9, fake_label: float = 0.1,
                  d_iters: int = 2, elide_dead_grads: bool = False, reducer=None, group_d_passes: bool = True,
                  sync_bn: bool = False, feat_layer: Optional[int] = None, alpha_feat: float = 0.0, alpha_pix: float = 1.0,
-                 alpha_ssim: float = 0.0, hole_weight: float = 1.0, ema=None, max_grad_norm=None):
+                 alpha_ssim: float = 0.0, hole_weight: float = 1.0, ema=None, max_grad_norm=None, augment=None):
         self.E, self.G, self.D = encoder, decoder, discriminator
         self.opt_E, self.opt_G, self.opt_D = opt_E, opt_Dec, opt_Dis
         self.alpha_kl, self.alpha_adv, self.sigma = alpha_kl, alpha_adv, noise_sigma          # :49-50, :91-92
@@ -89,6 +90,16 @@ class VAEGANTrainer(ClipOption):
         # [norm, coefficient]; D's is the last Discriminator update's) and loss_dict() report them.  None (the default): the
         # iteration launches exactly what it launched without it and nothing is allocated.
         self.max_grad_norm = max_grad_norm
+        # Differentiable augmentation (augment.DiffAugment or a policy string): after the [2B] buffer of
+        # noisy real / reconstructed images is filled, ONE table of per-image parameters is drawn from the noise stream (at the
+        # iteration the prologue just advanced to; reused across d_iters, as the reference reuses its instance noise) and every
+        # Discriminator pass -- the d_iters updates, the feature tap, the adversarial pass -- reads the augmented copy; image b
+        # and its reconstruction share row b.  The adversarial pass's input gradient goes back through the adjoint.  The table
+        # of the last iteration stays in aug_params ([B, 8] device tensor).  The noise stream then exists and advances also
+        # when all three eps are injected; the checkpoint's noise state determines the draws.  None (the default): the
+        # iteration launches exactly what it launched without it and nothing is allocated.
+        self.augment = A.DiffAugment.of(augment)
+        self.aug_params = None
         self.group_d_passes = group_d_passes       # run a D iteration's real+fake passes as one 2B-row launch chain
         # BCE + its gradient + the sigmoid / head backward as ONE launch per Discriminator pass (ops.head_backward;
         # bit-identical to the three separate launches, which False selects)
@@ -112,6 +123,8 @@ class VAEGANTrainer(ClipOption):
         if len(dts) != 1:
             raise ValueError("encoder / decoder / discriminator must share one engine dtype")
         self.dt = dts.pop()
+        if self.augment is not None:
+            A.check_dtype(self.dt)
         self.latent = encoder.latent_dim
         self.losses = None
         self.noise = None               # ops.NoiseStream for the in-kernel randn_like draws (created on first use)
@@ -156,7 +169,8 @@ class VAEGANTrainer(ClipOption):
                 self.elide_dead_grads, self.group_d_passes, self.fuse_head_backward, self.fuse_step_prologue,
                 self.merge_small_launches,
                 id(self.reducer), self.sync_bn, opts,
-                None if self.noise is None or inject else self.noise.state.data_ptr()) \
+                None if self.noise is None or (inject and self.augment is None) else self.noise.state.data_ptr()) \
+            + (self.augment.key() if self.augment is not None else ()) \
             + ((True, with_rects, self.hole_weight) if paired else ()) \
             + ((("ema",) + self.ema.key(),) if self.ema is not None else ()) + self._clip_key()
 
@@ -286,6 +300,8 @@ class VAEGANTrainer(ClipOption):
             eps_z = noise.draw(0) if eps_z is None else eps_z
             eps_real = noise.draw(1) if eps_real is None else eps_real
             eps_recon = noise.draw(2) if eps_recon is None else eps_recon
+        elif self.augment is not None:
+            noise = self._noise_stream(dev)         # the augmentation table is drawn from it (and it advances) all the same
         # one single-thread launch for everything that only counts: the noise iteration and the step counters / bias
         # corrections of the three Adam steps below (the Discriminator's second update prepares itself)
         prep = self.fuse_step_prologue and self.d_iters >= 1
@@ -332,6 +348,16 @@ class VAEGANTrainer(ClipOption):
             if Gn._engine.trace is not None:        # test instrumentation (engine.StackEngine.trace): the unfused tail
                 Gn._engine.trace.append(dict(stage=len(Gn._engine.stages) - 1, what="tail", pre=pre.clone(),
                                              img=recon.clone(), noisy=recon_noisy.clone()))
+        aug = self.augment
+        if aug is not None:
+            # one table per iteration, then everything D reads below is the augmented copy of `both`
+            if self.aug_params is None or self.aug_params.shape[0] != B or self.aug_params.device != dev:
+                if torch.cuda.is_current_stream_capturing():
+                    raise RuntimeError("the augmentation table would be allocated during graph capture; run a warm-up step first")
+                self.aug_params = torch.empty(B, 8, dtype=torch.float32, device=dev)
+            aug.draw(noise.state, B, both.shape[1], both.shape[2], out=self.aug_params)
+            both = aug.forward(both, self.aug_params, D.nc, dt)
+            real_noisy, recon_noisy = both[:B], both[B:]
         grouped = self.group_d_passes and D._engine.can_group(B, 2)
         fused_head = self.fuse_head_backward and 2 * B <= ops.HEAD_BWD_MAXROWS and D._engine.stages[-1].kind == "head"
 
@@ -396,6 +422,8 @@ class VAEGANTrainer(ClipOption):
         d_noisy = D._engine.backward(c_adv, dp_adv, True, sink, param_grads=not self.elide_dead_grads,
                                      head_loss=(self.real_label, 0.0, 1, self.alpha_adv, losses[2:3], False) if fused_head else None,
                                      feat=feat)
+        if aug is not None:
+            d_noisy = aug.backward(d_noisy, self.aug_params, D.nc, dt)      # back to the gradient of the un-augmented batch
         # d total / d recon = d MSE (+ d SSIM) + d adv through the instance-noise add (:92), then through tanh: one pass
         d_pre = ops.nchw_grad_add_to_nhwc(d_recon, d_noisy, recon, G.padc(Gn.nc, dt), dt)
         dz = Gn._engine.backward(ctxG, d_pre, True, sink, on_grads=self._grad_hook(self.opt_G, Gn))
@@ -459,7 +487,7 @@ class VAEGANTrainer(ClipOption):
         inject = eps_z is not None
         if inject and (eps_real is None or eps_recon is None):
             raise ValueError("inject all three noise tensors or none")
-        if not inject:
+        if not inject or self.augment is not None:
             self._noise_stream(real.device)         # exists (and is keyed on the current seed) before the key is formed
         key = self._capture_key(real, epoch, inject, noisy is not None, rects is not None)
         g = self._graph
