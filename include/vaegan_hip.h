@@ -48,7 +48,7 @@ extern "C" {
 #define VG_ACT_LRELU   2   /* nn.LeakyReLU(slope)    main_vae.py:25, gan_code.py:62-82 */
 #define VG_ACT_TANH    3   /* nn.Tanh()              gan_code.py:50 (vg_tnconv epilogue only) */
 
-#define VG_ABI_VERSION 25  /* 2: vg_pack_desc.tile_start, SyncBN / WGAN / data-path entry points; 3: in-kernel noise (vg_*_rng);
+#define VG_ABI_VERSION 26  /* 2: vg_pack_desc.tile_start, SyncBN / WGAN / data-path entry points; 3: in-kernel noise (vg_*_rng);
                              4: vg_bn_finalize_act_forward, vg_bn_backward_finalize_apply;
                              7: vg_bce_pair_forward_backward;
                              8: vg_head_backward; round-3 prune -- the opt-in experiments of ABI 5 / 6 that measured slower (input prologue of
@@ -71,7 +71,8 @@ extern "C" {
                              22: weight averaging: vg_ema_update;
                              23: vg_wgrad_plan / vg_wg_plan, vg_edge_wgrad_plan / vg_ew_plan replace vg_wgrad_ws_bytes / vg_edge_wgrad_ws_bytes;
                              24: gradient-norm clipping: vg_grad_norm_clip, vg_adam_apply_clip;
-                             25: differentiable augmentation: vg_diffaug_params, vg_diffaug_forward, vg_diffaug_backward (+ _ws_floats) */
+                             25: differentiable augmentation: vg_diffaug_params, vg_diffaug_forward, vg_diffaug_backward (+ _ws_floats);
+                             26: learning-rate schedules and decoupled weight decay: vg_lr_sched, vg_step_prologue_sched, vg_adamw_apply */
 int vg_abi_version(void);
 /* The library reads its optional kernel-selection switches (VG_* environment variables, DESIGN.md "Runtime switches")
  * ONCE, when it is loaded; nothing on a launch path calls getenv.  A process that changes one of them afterwards
@@ -953,6 +954,73 @@ int vg_adam_apply_clip(float* const* p, const float* const* g, float* const* m, 
                        const double* beta1, const double* beta2, const double* eps, const float* grad_scale,
                        const float* const* state /* prepared */, const float* const* coef /* device; entry may be NULL */,
                        int count /* 1 or 2 */, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Learning-rate schedules and decoupled weight decay (not in the reference; ABI 26): the learning rate of an iteration as a
+ * closed-form function of the optimizer's DEVICE-resident step count, evaluated in the prologue launch, so that a captured
+ * iteration replays a moving rate without being captured again; and torch.optim.AdamW's decay as one more multiply in the
+ * update kernel.
+ *
+ * vg_lr_sched: plain data, one record per optimizer.  With t = the step count AFTER this iteration's increment (1 for the
+ * first step) and lr the base rate, everything in double:
+ *     e    = (t - 1) / hold                                  integer division: the scheduler moves once per `hold` steps
+ *     w    = e < warmup ? warmup_start + (1 - warmup_start) * ((double)e / warmup) : 1
+ *     k    = max(e - decay_start, 0);   u = min(k, decay_len)
+ *     d    = VG_LRS_CONST  : 1
+ *            VG_LRS_LINEAR : 1 + (decay_param - 1) * ((double)u / decay_len)                  decay_param = the end factor
+ *            VG_LRS_COSINE : decay_param + (1 - decay_param) * 0.5 * (1 + cos(pi * u / decay_len))
+ *            VG_LRS_EXP    : pow(decay_param, k)                                              decay_param = gamma
+ *            VG_LRS_STEP   : pow(decay_param, k / decay_len)                                  integer division
+ *     lr_t = lr * (w * d)
+ * These are the closed forms of torch.optim.lr_scheduler.LinearLR (as the warm-up: start_factor = warmup_start, total_iters =
+ * warmup; as the decay: end_factor = decay_param, total_iters = decay_len), CosineAnnealingLR (T_max = decay_len, eta_min =
+ * lr * decay_param), ExponentialLR and StepLR (step_size = decay_len); SequentialLR([warm-up, decay], milestones=[warmup]) is
+ * decay_start = warmup; hold = the steps per epoch gives the scheduler stepped once per epoch.  Past decay_start + decay_len
+ * the LINEAR and COSINE factors STAY at decay_param (torch's CosineAnnealingLR is periodic there and rises again).
+ * The evaluation is compiled without floating-point contraction: every operation above is rounded on its own, so CONST, the
+ * warm-up and LINEAR (only + - * /) give on the device the bits the same double expression gives on a host; COSINE, EXP and
+ * STEP go through the device's cos / pow, a few double ulps from a host's.
+ *
+ * vg_step_prologue_sched: vg_step_prologue with one `const vg_lr_sched*` per optimizer; still ONE launch of VG_PROLOGUE_MAX
+ * lanes, one lane per optimizer.  For optimizer i with sched[i] != NULL:
+ *     state[0] = t, state[2] = sqrt(1 - beta2^t)          as vg_step_prologue writes them
+ *     state[1] = (float)(lr_t / (1 - beta1^t))
+ *     state[3] = (float)(1.0 - lr_t * weight_decay)       product and difference each rounded in double, narrowed once: the
+ *                                                         scalar of torch 2.10's param.mul_(1 - lr * weight_decay)
+ * sched[i] == NULL: lr_t = lr, state[3] is NOT written and the other three are vg_step_prologue's bits.
+ * Checked on the host before anything is launched, VG_EINVAL: everything vg_step_prologue checks; a NULL sched array with
+ * n > 0; in a record: hold < 1, warmup < 0, warmup_start outside [0, 1], an unknown decay_kind, decay_start < 0, decay_len < 1
+ * (LINEAR, COSINE, STEP; ignored for CONST and EXP), decay_param outside [0, 1] (LINEAR, COSINE) or outside (0, 1] (EXP,
+ * STEP; ignored for CONST), weight_decay negative or not finite (NaN fails every range).
+ *
+ * vg_adamw_apply: vg_adam_apply_clip -- arrays, grid per buffer, host checks, coef (an entry may be NULL), count 1 or 2 --
+ * whose per-element code first forms  p = p * state[i][3]  as ONE rounded f32 product (no contraction into what follows)
+ * and then runs the Adam update unchanged: torch 2.10 _single_tensor_adam with decoupled_weight_decay.  state[i][3] == 1.0f
+ * (weight_decay == 0) gives vg_adam_apply_clip's bits.  28 bytes of traffic per element, as vg_adam_apply_clip.
+ * ---------------------------------------------------------------------------------------- */
+#define VG_LRS_CONST  0
+#define VG_LRS_LINEAR 1
+#define VG_LRS_COSINE 2
+#define VG_LRS_EXP    3
+#define VG_LRS_STEP   4
+typedef struct vg_lr_sched {
+    int64_t hold;          /* >= 1: optimizer steps per scheduler step */
+    int64_t warmup;        /* >= 0: scheduler steps of linear warm-up */
+    int64_t decay_start;   /* >= 0: scheduler step at which the decay begins */
+    int64_t decay_len;     /* >= 1: scheduler steps of the decay (LINEAR, COSINE); the step size (STEP) */
+    double warmup_start;   /* [0, 1]: the factor at scheduler step 0 */
+    double decay_param;    /* the end factor in [0, 1] (LINEAR, COSINE); gamma in (0, 1] (EXP, STEP) */
+    double weight_decay;   /* >= 0, finite */
+    int32_t decay_kind;    /* VG_LRS_* */
+    int32_t reserved;      /* 0 */
+} vg_lr_sched;
+int vg_step_prologue_sched(uint64_t* rng, float* const* states, const double* lr, const double* beta1, const double* beta2,
+                           const vg_lr_sched* const* sched /* entry may be NULL */, int n, float* zero, int nzero,
+                           void* stream);
+int vg_adamw_apply(float* const* p, const float* const* g, float* const* m, float* const* v, const int64_t* n,
+                   const double* beta1, const double* beta2, const double* eps, const float* grad_scale,
+                   const float* const* state /* prepared by vg_step_prologue_sched */,
+                   const float* const* coef /* device; entry may be NULL */, int count /* 1 or 2 */, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Differentiable augmentation (not in the reference; Zhao et al., NeurIPS 2020, "DiffAugment"; ABI 25; csrc/diffaug.hip): a

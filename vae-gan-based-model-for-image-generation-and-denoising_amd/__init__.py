@@ -16,7 +16,9 @@ average of Encoder / Generator weights kept on the device, ``VAEGANTrainer(..., 
 Gradient-norm clipping (not in the reference): ``clip_grad_norm_`` / ``Adam.clip_grad_norm_`` -- torch's
 ``clip_grad_norm_`` with the coefficient kept on the device and applied inside the Adam step, ``max_grad_norm=`` on the four
 trainers.  Differentiable augmentation of the Discriminator's inputs (not in the reference): ``DiffAugment`` and
-``augment=`` on the three adversarial trainers.  Data path (dataset_code.py): ``data`` -- ``ResidentImages`` (``resized``: Resize +
+``augment=`` on the three adversarial trainers.  Learning-rate schedules and decoupled weight decay (not in the reference):
+``LRSchedule`` (``Adam(..., lr_schedule=)``: warm-up and linear / cosine / exponential / step decay, evaluated on the device from
+the step count, so a captured iteration replays a moving rate) and ``AdamW``.  Data path (dataset_code.py): ``data`` -- ``ResidentImages`` (``resized``: Resize +
 CenterCrop on the device), ``resample_coeffs``, ``resize_geometry``.
 """
 from . import data  # noqa: F401
@@ -33,7 +35,7 @@ from .latent import LatentPrior, encode_dataset, evaluate_generation, sample_ima
 from .metrics import FeatureStats, encoder_features, frechet_distance, kernel_distance, precision_recall
 from .losses import BCELoss, MSELoss, SSIMLoss
 from .nets import ConvBlock, Discriminator, Encoder, Generator, weights_init
-from .optim import Adam, clip_grad_norm_
+from .optim import Adam, AdamW, LRSchedule, clip_grad_norm_
 from .siblings import DCGANTrainer, VAETrainer, WGANTrainer
 from .trainer import LOSS_NAMES, VAEGANTrainer
 from .utils import configure_seed
@@ -42,5 +44,5 @@ __all__ = ["ConvBlock", "Encoder", "Generator", "Discriminator", "weights_init",
            "VAEGANTrainer", "LOSS_NAMES", "configure_seed", "geometry", "denoise_eval", "validation_epoch", "paired_test_epoch", "GradReducer", "data", "VAETrainer", "DCGANTrainer", "WGANTrainer", "graphed",
            "latent", "LatentPrior", "encode_dataset", "evaluate_generation", "sample_images",
            "ResidentImages", "resample_coeffs", "resize_geometry",
-           "EMA", "clip_grad_norm_", "DiffAugment",
+           "EMA", "clip_grad_norm_", "DiffAugment", "AdamW", "LRSchedule",
            "metrics", "FeatureStats", "frechet_distance", "precision_recall", "encoder_features", "kernel_distance"]

@@ -19,7 +19,9 @@ VG_MAX_PHASE = 4
 VG_EMA_MAX = 4
 VG_GNORM_MAX = 4
 VG_GNORM_PARTS = 512
-ABI_VERSION = 25
+VG_PROLOGUE_MAX = 4
+VG_LRS_CONST, VG_LRS_LINEAR, VG_LRS_COSINE, VG_LRS_EXP, VG_LRS_STEP = 0, 1, 2, 3, 4
+ABI_VERSION = 26
 
 VG_ENOSUP = -3
 _ERR = {-1: "VG_EINVAL (bad shape/size/flag)", -2: "VG_EALIGN (16-byte contract violated)",
@@ -107,6 +109,13 @@ class PackDesc(Structure):
                 ("tap_in_n", c_int32), ("KHW", c_int32), ("tile_start", c_int32)]
 
 
+class LRSched(Structure):
+    """vg_lr_sched."""
+    _fields_ = [("hold", c_int64), ("warmup", c_int64), ("decay_start", c_int64), ("decay_len", c_int64),
+                ("warmup_start", c_double), ("decay_param", c_double), ("weight_decay", c_double),
+                ("decay_kind", c_int32), ("reserved", c_int32)]
+
+
 # name -> (restype, argtypes); every symbol include/vaegan_hip.h declares
 _P, _F, _I, _L, _D, _U = c_void_p, c_float, c_int, c_int64, c_double, ctypes.c_uint64
 SIGNATURES = {
@@ -179,6 +188,8 @@ SIGNATURES = {
     "vg_ema_update": (c_int, [_P, _P, _P, _P, _P, _P, _I, _P]),
     "vg_grad_norm_clip": (c_int, [_P, _P, _P, _P, _I, _P, _P, _P]),
     "vg_adam_apply_clip": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
+    "vg_step_prologue_sched": (c_int, [_P, _P, _P, _P, _P, _P, _I, _P, _I, _P]),
+    "vg_adamw_apply": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
     "vg_diffaug_ws_floats": (c_int64, [_I, _I, _I]),
     "vg_diffaug_params": (c_int, [_P, _I, _I, _I, _I, _P, _P]),
     "vg_diffaug_forward": (c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _L, _I, _P]),

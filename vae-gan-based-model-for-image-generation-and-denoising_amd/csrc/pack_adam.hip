@@ -234,6 +234,62 @@ __global__ __launch_bounds__(VG_PROLOGUE_MAX) void step_prologue_kernel(const Pr
     }
 }
 
+// The scheduled learning rate (include/vaegan_hip.h "Learning-rate schedules"): lr_t of optimizer step t (counted from 1) in
+// double.  Contraction off, as in adam_grad below: every + - * / is rounded on its own, so the kinds without cos / pow give
+// the bits the same expression gives on a host.
+__device__ __forceinline__ double sched_lr(double lr, const vg_lr_sched& s, int64_t t) {
+#pragma clang fp contract(off)
+    const int64_t e = (t - 1) / s.hold;
+    double w = 1.0;
+    if (e < s.warmup) w = s.warmup_start + (1.0 - s.warmup_start) * ((double)e / (double)s.warmup);
+    const int64_t k = e > s.decay_start ? e - s.decay_start : 0;
+    const int64_t u = k < s.decay_len ? k : s.decay_len;
+    double d = 1.0;
+    switch (s.decay_kind) {
+        case VG_LRS_LINEAR: d = 1.0 + (s.decay_param - 1.0) * ((double)u / (double)s.decay_len); break;
+        case VG_LRS_COSINE:
+            d = s.decay_param + (1.0 - s.decay_param) * 0.5 * (1.0 + cos(3.14159265358979323846 * (double)u / (double)s.decay_len));
+            break;
+        case VG_LRS_EXP: d = pow(s.decay_param, (double)k); break;
+        case VG_LRS_STEP: d = pow(s.decay_param, (double)(k / s.decay_len)); break;
+        default: break;
+    }
+    return lr * (w * d);
+}
+// 1 - lr_t * weight_decay: the scalar of torch's param.mul_(1 - lr * weight_decay), product and difference rounded apart
+__device__ __forceinline__ double sched_decay(double lr_t, double weight_decay) {
+#pragma clang fp contract(off)
+    return 1.0 - lr_t * weight_decay;
+}
+
+// step_prologue_kernel with a schedule record per optimizer (has[i] == 0: none -- that lane is step_prologue_kernel's)
+struct PrologueSchedArgs {
+    PrologueArgs a;
+    vg_lr_sched sched[VG_PROLOGUE_MAX];
+    int has[VG_PROLOGUE_MAX];
+};
+__global__ __launch_bounds__(VG_PROLOGUE_MAX) void step_prologue_sched_kernel(const PrologueSchedArgs sa) {
+    const PrologueArgs& a = sa.a;
+    const int i = threadIdx.x;
+    if (blockIdx.x != 0) return;
+    if (i == 0) {
+        if (a.rng != nullptr) a.rng[1] += 1ull;
+        for (int k = 0; k < a.nzero; ++k) a.zero[k] = 0.f;
+    }
+    if (i < a.n) {
+        float* state = a.state[i];
+        const double t = (double)state[0] + 1.0;
+        state[0] = (float)t;
+        double lr_t = a.lr[i];
+        if (sa.has[i]) {
+            lr_t = sched_lr(a.lr[i], sa.sched[i], (int64_t)t);
+            state[3] = (float)sched_decay(lr_t, sa.sched[i].weight_decay);
+        }
+        state[1] = (float)(lr_t / (1.0 - pow(a.beta1[i], t)));
+        state[2] = (float)sqrt(1.0 - pow(a.beta2[i], t));
+    }
+}
+
 // g * grad_scale as a ROUNDED f32 product -- the gradient torch's Adam is handed after the all-reduce and the division by
 // the world size.  Contraction off (the pragma binds lexically): hipcc otherwise folds the product into the fma of
 // (g * scale - m), which moves exp_avg in the last bits of g for every scale that is no power of two.
@@ -262,10 +318,20 @@ __device__ __forceinline__ void adam_update(float& p, float g, float& m, float& 
     p = p - c.step_size * (m / denom);                         // addcdiv_(exp_avg, denom, -step_size)
 }
 
+// Decoupled weight decay (torch's param.mul_(1 - lr * weight_decay) ahead of the update): p * decay as a ROUNDED f32 product,
+// kept out of the fma of adam_update's last line for the reason given at adam_grad.
+__device__ __forceinline__ float adam_decay(float p, float decay) {
+#pragma clang fp contract(off)
+    return p * decay;
+}
+
 // Workgroup `bid` of the `nb` that walk one flat buffer: 16-byte vectors in a grid-stride loop, the tail past n / 4 * 4
-// element by element in workgroup 0.
+// element by element in workgroup 0.  WD: every parameter is first multiplied by `decay` (adamw_kernel); the instantiation
+// without it is the code of the Adam kernels as they were.
+template <bool WD = false>
 __device__ __forceinline__ void adam_span(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                          float* __restrict__ v, int64_t n, int bid, int nb, const AdamConsts& c) {
+                                          float* __restrict__ v, int64_t n, int bid, int nb, const AdamConsts& c,
+                                          float decay = 1.0f) {
     const int64_t n4 = n / 4;
     for (int64_t i = (int64_t)bid * blockDim.x + threadIdx.x; i < n4; i += (int64_t)nb * blockDim.x) {
         float4 pp = reinterpret_cast<float4*>(p)[i];
@@ -274,7 +340,10 @@ __device__ __forceinline__ void adam_span(float* __restrict__ p, const float* __
         float4 vv = reinterpret_cast<float4*>(v)[i];
         float* P = &pp.x; float* G = &gg.x; float* Mv = &mm.x; float* V = &vv.x;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) adam_update(P[k], G[k], Mv[k], V[k], c);
+        for (int k = 0; k < 4; ++k) {
+            if constexpr (WD) P[k] = adam_decay(P[k], decay);
+            adam_update(P[k], G[k], Mv[k], V[k], c);
+        }
         reinterpret_cast<float4*>(p)[i] = pp;
         reinterpret_cast<float4*>(m)[i] = mm;
         reinterpret_cast<float4*>(v)[i] = vv;
@@ -283,6 +352,7 @@ __device__ __forceinline__ void adam_span(float* __restrict__ p, const float* __
     if (bid == 0) {
         for (int64_t i = n4 * 4 + threadIdx.x; i < n; i += blockDim.x) {
             float pi = p[i], mi = m[i], vi = v[i];
+            if constexpr (WD) pi = adam_decay(pi, decay);
             adam_update(pi, g[i], mi, vi, c);
             p[i] = pi;
             m[i] = mi;
@@ -332,6 +402,21 @@ __global__ __launch_bounds__(256) void adam_clip_kernel(const AdamClipArgs ca) {
     const float s = coef != nullptr ? adam_grad(a.gscale[which], coef[0]) : a.gscale[which];
     const AdamConsts c{a.w1[which], a.beta2[which], a.w2[which], a.eps[which], s, a.state[which][1], a.state[which][2]};
     adam_span(a.p[which], a.g[which], a.m[which], a.v[which], a.n[which], bid, nb, c);
+}
+
+// AdamW (include/vaegan_hip.h "Learning-rate schedules and decoupled weight decay"): adam_clip_kernel whose elements are first
+// multiplied by state[3] = 1 - lr_t * weight_decay, which vg_step_prologue_sched left on the device -- uniform per buffer, no
+// byte more than adam_clip_kernel moves.
+__global__ __launch_bounds__(256) void adamw_kernel(const AdamClipArgs ca) {
+    const Adam2Args& a = ca.a;
+    const int which = blockIdx.x < a.nb0 ? 0 : 1;
+    const int bid = which == 0 ? blockIdx.x : blockIdx.x - a.nb0;
+    const int nb = which == 0 ? a.nb0 : (int)gridDim.x - a.nb0;
+    const float* coef = ca.coef[which];
+    const float s = coef != nullptr ? adam_grad(a.gscale[which], coef[0]) : a.gscale[which];
+    const float* state = a.state[which];
+    const AdamConsts c{a.w1[which], a.beta2[which], a.w2[which], a.eps[which], s, state[1], state[2]};
+    adam_span<true>(a.p[which], a.g[which], a.m[which], a.v[which], a.n[which], bid, nb, c, state[3]);
 }
 
 }  // namespace
@@ -430,9 +515,11 @@ extern "C" int vg_adam_apply2(float* const* p, const float* const* g, float* con
     return VG_LAUNCH_RC();
 }
 
-extern "C" int vg_adam_apply_clip(float* const* p, const float* const* g, float* const* m, float* const* v, const int64_t* n,
-                                  const double* beta1, const double* beta2, const double* eps, const float* grad_scale,
-                                  const float* const* state, const float* const* coef, int count, void* stream) {
+// vg_adam_apply_clip / vg_adamw_apply: one host path, the kernel apart.
+static int adam_clip_launch(void (*kernel)(const AdamClipArgs), float* const* p, const float* const* g, float* const* m,
+                            float* const* v, const int64_t* n, const double* beta1, const double* beta2, const double* eps,
+                            const float* grad_scale, const float* const* state, const float* const* coef, int count,
+                            void* stream) {
     VG_CHECK_ARG(count == 1 || count == 2, VG_EINVAL);
     VG_CHECK_ARG(coef != nullptr, VG_EINVAL);
     AdamClipArgs ca{};
@@ -441,8 +528,20 @@ extern "C" int vg_adam_apply_clip(float* const* p, const float* const* g, float*
     if (rc) return rc;
     for (int i = 0; i < count; ++i) ca.coef[i] = coef[i];
     ca.a.nb0 = nb[0];
-    hipLaunchKernelGGL(adam_clip_kernel, dim3(nb[0] + nb[1]), dim3(256), 0, vg_stream(stream), ca);
+    hipLaunchKernelGGL(kernel, dim3(nb[0] + nb[1]), dim3(256), 0, vg_stream(stream), ca);
     return VG_LAUNCH_RC();
+}
+
+extern "C" int vg_adam_apply_clip(float* const* p, const float* const* g, float* const* m, float* const* v, const int64_t* n,
+                                  const double* beta1, const double* beta2, const double* eps, const float* grad_scale,
+                                  const float* const* state, const float* const* coef, int count, void* stream) {
+    return adam_clip_launch(adam_clip_kernel, p, g, m, v, n, beta1, beta2, eps, grad_scale, state, coef, count, stream);
+}
+
+extern "C" int vg_adamw_apply(float* const* p, const float* const* g, float* const* m, float* const* v, const int64_t* n,
+                              const double* beta1, const double* beta2, const double* eps, const float* grad_scale,
+                              const float* const* state, const float* const* coef, int count, void* stream) {
+    return adam_clip_launch(adamw_kernel, p, g, m, v, n, beta1, beta2, eps, grad_scale, state, coef, count, stream);
 }
 
 extern "C" int vg_step_prologue(uint64_t* rng, float* const* states, const double* lr, const double* beta1,
@@ -459,5 +558,49 @@ extern "C" int vg_step_prologue(uint64_t* rng, float* const* states, const doubl
         a.state[i] = states[i]; a.lr[i] = lr[i]; a.beta1[i] = beta1[i]; a.beta2[i] = beta2[i];
     }
     hipLaunchKernelGGL(step_prologue_kernel, dim3(1), dim3(VG_PROLOGUE_MAX), 0, vg_stream(stream), a);
+    return VG_LAUNCH_RC();
+}
+
+// Host checks of one schedule record (include/vaegan_hip.h "Learning-rate schedules"); written so that a NaN fails them.
+static int sched_check(const vg_lr_sched& s) {
+    VG_CHECK_ARG(s.hold >= 1 && s.warmup >= 0 && s.decay_start >= 0, VG_EINVAL);
+    VG_CHECK_ARG(s.warmup_start >= 0.0 && s.warmup_start <= 1.0, VG_EINVAL);
+    VG_CHECK_ARG(s.weight_decay >= 0.0 && s.weight_decay <= 1.7976931348623157e308, VG_EINVAL);
+    switch (s.decay_kind) {
+        case VG_LRS_CONST: break;
+        case VG_LRS_LINEAR:
+        case VG_LRS_COSINE:
+            VG_CHECK_ARG(s.decay_len >= 1 && s.decay_param >= 0.0 && s.decay_param <= 1.0, VG_EINVAL);
+            break;
+        case VG_LRS_EXP: VG_CHECK_ARG(s.decay_param > 0.0 && s.decay_param <= 1.0, VG_EINVAL); break;
+        case VG_LRS_STEP: VG_CHECK_ARG(s.decay_len >= 1 && s.decay_param > 0.0 && s.decay_param <= 1.0, VG_EINVAL); break;
+        default: VG_CHECK_ARG(false, VG_EINVAL);
+    }
+    return 0;
+}
+
+extern "C" int vg_step_prologue_sched(uint64_t* rng, float* const* states, const double* lr, const double* beta1,
+                                      const double* beta2, const vg_lr_sched* const* sched, int n, float* zero, int nzero,
+                                      void* stream) {
+    VG_CHECK_ARG(n >= 0 && n <= VG_PROLOGUE_MAX && (n == 0 || (states && lr && beta1 && beta2 && sched)) && (rng || n > 0),
+                 VG_EINVAL);
+    VG_CHECK_ARG(nzero >= 0 && nzero <= 64 && (nzero == 0 || zero != nullptr), VG_EINVAL);
+    PrologueSchedArgs sa{};
+    PrologueArgs& a = sa.a;
+    a.rng = (unsigned long long*)rng;
+    a.zero = zero;
+    a.nzero = nzero;
+    a.n = n;
+    for (int i = 0; i < n; ++i) {
+        VG_CHECK_ARG(states[i] != nullptr && lr[i] >= 0.0, VG_EINVAL);
+        a.state[i] = states[i]; a.lr[i] = lr[i]; a.beta1[i] = beta1[i]; a.beta2[i] = beta2[i];
+        if (sched[i] != nullptr) {
+            const int rc = sched_check(*sched[i]);
+            if (rc) return rc;
+            sa.sched[i] = *sched[i];
+            sa.has[i] = 1;
+        }
+    }
+    hipLaunchKernelGGL(step_prologue_sched_kernel, dim3(1), dim3(VG_PROLOGUE_MAX), 0, vg_stream(stream), sa);
     return VG_LAUNCH_RC();
 }

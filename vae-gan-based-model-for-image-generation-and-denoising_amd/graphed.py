@@ -77,7 +77,7 @@ class GraphedStep:
         skey = tuple(sorted(scalars.items())) if self.scalar_key is None else self.scalar_key(**scalars)
         key = (tuple((tuple(t.shape), t.dtype) for t in tensors), skey,
                tuple(m.training for m in self.modules),
-               tuple((o.lr, o.betas, o.eps, o.grad_scale) for o in self.optimizers if hasattr(o, "grad_scale")))
+               tuple((o.capture_key(), o.betas, o.eps, o.grad_scale) for o in self.optimizers if hasattr(o, "grad_scale")))
         hit = self._graphs.get(key)
         if hit is not None:
             self._graphs.move_to_end(key)

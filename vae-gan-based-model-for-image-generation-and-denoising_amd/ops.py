@@ -1455,13 +1455,24 @@ def axpy(a, b, alpha, out=None):
 def step_prologue(noise, optimizers, zero=None) -> None:
     """Top of an iteration, one single-thread launch: noise.advance() (noise may be None), the step counters / bias
     corrections of `optimizers` (optim.Adam, at most 4) -- their step(prepared=True) then launches the update alone --
-    and, when given, the iteration's loss slots `zero` (f32, <= 64 elements) set to 0 (instead of a memset node)."""
+    and, when given, the iteration's loss slots `zero` (f32, <= 64 elements) set to 0 (instead of a memset node).
+    An optimizer with a learning-rate schedule or a decoupled weight decay (optim.LRSchedule, optim.AdamW) has its rate of this
+    step and its decay factor worked out in the same launch from the step count on the device."""
     import ctypes
     n = len(optimizers)
     states = (ctypes.c_void_p * max(n, 1))(*[o.state_dev.data_ptr() for o in optimizers])
     lr = (ctypes.c_double * max(n, 1))(*[o.lr for o in optimizers])
     b1 = (ctypes.c_double * max(n, 1))(*[o.betas[0] for o in optimizers])
     b2 = (ctypes.c_double * max(n, 1))(*[o.betas[1] for o in optimizers])
+    recs = [o.sched_record() if hasattr(o, "sched_record") else None for o in optimizers]
+    if any(r is not None for r in recs):
+        # some optimizer has a learning-rate schedule or a decoupled decay: the same launch evaluates them on the device
+        # (vg_step_prologue_sched; entries of the others are NULL -- vg_step_prologue's bits for those)
+        sched = (ctypes.c_void_p * n)(*[None if r is None else ctypes.addressof(r) for r in recs])
+        L.check(L.load().vg_step_prologue_sched(noise.state.data_ptr() if noise is not None else None, states, lr, b1, b2,
+                                                sched, n, L.ptr(zero), 0 if zero is None else zero.numel(), L.stream_ptr()),
+                "vg_step_prologue_sched")
+        return
     L.check(L.load().vg_step_prologue(noise.state.data_ptr() if noise is not None else None, states, lr, b1, b2, n,
                                       L.ptr(zero), 0 if zero is None else zero.numel(), L.stream_ptr()), "vg_step_prologue")
 
@@ -1534,7 +1545,9 @@ def grad_norm_clip(grads, grad_scales, max_norms, out, ws) -> None:
 def adam_apply_clip(opts, coefs) -> None:
     """The prepared update of ONE or TWO optim.Adam instances in one launch with the gradient scale grad_scale * coefs[i][0],
     the coefficient read from the device (vg_adam_apply_clip); coefs[i] None: grad_scale as it is, i.e. adam_apply2's /
-    adam_step(prepared=True)'s bits for that optimizer."""
+    adam_step(prepared=True)'s bits for that optimizer.  With an optim.AdamW among them the launch is vg_adamw_apply: each
+    optimizer's parameters are first multiplied by its state_dev[3] (1 - lr_t * weight_decay from the prologue; 1 for a plain
+    Adam)."""
     import ctypes
     k = len(opts)
     if len(coefs) != k:
@@ -1547,13 +1560,16 @@ def adam_apply_clip(opts, coefs) -> None:
             if c.dtype != torch.float32 or c.numel() < 1 or c.device != o.flat_p.device:
                 raise RuntimeError("adam_apply_clip: coefs[i] must be an f32 tensor on the optimizer's device (or None)")
     arr = lambda f: (ctypes.c_void_p * k)(*[f(o) for o in opts])       # noqa: E731
-    L.check(L.load().vg_adam_apply_clip(
+    # an AdamW in the launch: vg_adamw_apply, which multiplies every parameter by its optimizer's state_dev[3] first
+    decay = any(getattr(o, "_DECOUPLED", False) for o in opts)
+    fn, name = (L.load().vg_adamw_apply, "vg_adamw_apply") if decay else (L.load().vg_adam_apply_clip, "vg_adam_apply_clip")
+    L.check(fn(
         arr(lambda o: o.flat_p.data_ptr()), arr(lambda o: o.flat_g.data_ptr()), arr(lambda o: o.exp_avg.data_ptr()),
         arr(lambda o: o.exp_avg_sq.data_ptr()), (ctypes.c_int64 * k)(*[o.flat_p.numel() for o in opts]),
         (ctypes.c_double * k)(*[o.betas[0] for o in opts]), (ctypes.c_double * k)(*[o.betas[1] for o in opts]),
         (ctypes.c_double * k)(*[o.eps for o in opts]), (ctypes.c_float * k)(*[o.grad_scale for o in opts]),
         arr(lambda o: o.state_dev.data_ptr()), (ctypes.c_void_p * k)(*[None if c is None else c.data_ptr() for c in coefs]),
-        k, L.stream_ptr()), "vg_adam_apply_clip")
+        k, L.stream_ptr()), name)
 
 
 def launch_count() -> int:

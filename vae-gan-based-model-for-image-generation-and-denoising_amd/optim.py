@@ -13,10 +13,15 @@ and ``p.grad`` becomes a view into a matching flat gradient buffer, so:
     device and leaves the coefficient there; the gradients in ``flat_g`` / ``p.grad`` are NOT rewritten -- the next
     ``step()`` multiplies each gradient by the coefficient where it reads it (the second observable difference from torch:
     after the call ``p.grad`` still holds the unclipped gradient).
+  * a learning-rate schedule (``LRSchedule``, ``lr_schedule=``) is a closed-form function of the step count that lives on the
+    device: the iteration's prologue launch evaluates it there (vg_step_prologue_sched), so a captured iteration replays a
+    moving rate without being captured again.  ``AdamW`` adds torch.optim.AdamW's decoupled weight decay as one more
+    multiply in the update kernel (vg_adamw_apply).  DESIGN.md section 4.4k.
 Construct it AFTER ``.to(device)`` (as vaegan_code.py:29-44 does); moving the module afterwards
 would detach the parameters from the flat buffer.
 """
 import math
+import operator
 from typing import Iterable, Sequence, Union
 
 import torch
@@ -25,12 +30,124 @@ from . import ops
 from .engine import bump_weights_epoch
 
 
+class LRSchedule:
+    """A learning-rate schedule as a closed form of the optimizer's step count (include/vaegan_hip.h "Learning-rate
+    schedules"): linear warm-up from ``warmup_start`` to 1 over ``warmup`` scheduler steps, times a decay that begins at
+    scheduler step ``decay_start`` (None: at ``warmup``, torch's SequentialLR([warm-up, decay], milestones=[warmup])):
+
+      "constant"  1
+      "linear"    1 -> ``final`` over ``decay_steps``           torch LinearLR(end_factor=final, total_iters=decay_steps)
+      "cosine"    1 -> ``final`` over ``decay_steps``           torch CosineAnnealingLR(T_max=decay_steps, eta_min=lr * final);
+                                                                past the end the factor STAYS at final (torch's rises again)
+      "exp"       ``gamma`` ** k                                torch ExponentialLR(gamma)
+      "step"      ``gamma`` ** (k // ``decay_steps``)           torch StepLR(step_size=decay_steps, gamma)
+
+    The scheduler moves once per ``hold`` optimizer steps (hold = steps per epoch: the epoch-stepped usage).  The optimizer
+    evaluates the same formulas on the device, in double, from its device-resident step count; factor() / lr() evaluate them
+    here in Python floats.  Immutable; ValueError for anything the C side would reject."""
+    KINDS = ("constant", "linear", "cosine", "exp", "step")          # index = VG_LRS_*
+    __slots__ = ("hold", "warmup", "warmup_start", "decay", "decay_start", "decay_steps", "final", "gamma")
+
+    def __init__(self, warmup=0, warmup_start=0.0, decay="constant", decay_start=None, decay_steps=1, final=0.0, gamma=1.0,
+                 hold=1):
+        def integer(name, v, lo):
+            try:                                # any integer type (numpy's included: len(loader) arithmetic), no bool, no float
+                i = None if isinstance(v, bool) else operator.index(v)
+            except TypeError:
+                i = None
+            if i is None or i < lo:
+                raise ValueError(f"LRSchedule: {name} must be an integer >= {lo}, got {v!r}")
+            return i
+
+        def real(name, v, lo, hi, open_lo=False):
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not (lo <= v <= hi) or (open_lo and v == lo):
+                raise ValueError(f"LRSchedule: {name} must be a number in {'(' if open_lo else '['}{lo}, {hi}], got {v!r}")
+            return float(v)
+
+        if decay not in self.KINDS:
+            raise ValueError(f"LRSchedule: decay must be one of {', '.join(self.KINDS)}, got {decay!r}")
+        put = lambda name, value: object.__setattr__(self, name, value)       # noqa: E731
+        put("decay", decay)
+        put("hold", integer("hold", hold, 1))
+        put("warmup", integer("warmup", warmup, 0))
+        put("warmup_start", real("warmup_start", warmup_start, 0.0, 1.0))
+        put("decay_start", self.warmup if decay_start is None else integer("decay_start", decay_start, 0))
+        put("decay_steps", integer("decay_steps", decay_steps, 1))
+        put("final", real("final", final, 0.0, 1.0))
+        put("gamma", real("gamma", gamma, 0.0, 1.0, open_lo=True))
+
+    def __setattr__(self, name, value=None):
+        raise AttributeError("LRSchedule is immutable (its fields key captured graphs and its hash): build another one and "
+                             "hand it to Adam.set_schedule()")
+
+    __delattr__ = __setattr__
+
+    def factor(self, step: int) -> float:
+        """lr_t / lr of optimizer step number `step` (counted from 1: the count after that step's increment)."""
+        e = (max(int(step), 1) - 1) // self.hold
+        w = self.warmup_start + (1.0 - self.warmup_start) * (e / self.warmup) if e < self.warmup else 1.0
+        k = max(e - self.decay_start, 0)
+        u = min(k, self.decay_steps)
+        if self.decay == "linear":
+            d = 1.0 + (self.final - 1.0) * (u / self.decay_steps)
+        elif self.decay == "cosine":
+            d = self.final + (1.0 - self.final) * 0.5 * (1.0 + math.cos(math.pi * u / self.decay_steps))
+        elif self.decay == "exp":
+            d = math.pow(self.gamma, k)
+        elif self.decay == "step":
+            d = math.pow(self.gamma, k // self.decay_steps)
+        else:
+            d = 1.0
+        return w * d
+
+    def lr(self, base: float, step: int) -> float:
+        return float(base) * self.factor(step)
+
+    def key(self):
+        """What a captured iteration freezes of the schedule: every field (not the object's identity)."""
+        return (self.hold, self.warmup, self.warmup_start, self.decay, self.decay_start, self.decay_steps, self.final, self.gamma)
+
+    def state_dict(self):
+        return dict(warmup=self.warmup, warmup_start=self.warmup_start, decay=self.decay, decay_start=self.decay_start,
+                    decay_steps=self.decay_steps, final=self.final, gamma=self.gamma, hold=self.hold)
+
+    def __eq__(self, other):
+        return isinstance(other, LRSchedule) and self.key() == other.key()
+
+    def __hash__(self):
+        return hash(self.key())
+
+    def __reduce__(self):                       # copy / pickle rebuild it from its fields (nothing may be assigned)
+        return (_schedule_from, (self.state_dict(),))
+
+    def __repr__(self):
+        return "LRSchedule(" + ", ".join(f"{k}={v!r}" for k, v in self.state_dict().items()) + ")"
+
+
+def _schedule_from(fields):
+    return LRSchedule(**fields)
+
+
+def sched_record(schedule, weight_decay):
+    """The vg_lr_sched record of (schedule, weight_decay); schedule None: the constant schedule (the decay alone)."""
+    s = schedule if schedule is not None else LRSchedule()
+    kind = LRSchedule.KINDS.index(s.decay)
+    return ops.L.LRSched(hold=s.hold, warmup=s.warmup, decay_start=s.decay_start, decay_len=s.decay_steps,
+                         warmup_start=s.warmup_start, decay_param=s.gamma if s.decay in ("exp", "step") else s.final,
+                         weight_decay=float(weight_decay), decay_kind=kind, reserved=0)
+
+
 class Adam:
+    _DECOUPLED = False          # AdamW: weight_decay is the decoupled decay
+
     def __init__(self, params: Iterable[torch.Tensor], lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0,
-                 amsgrad=False):
-        if weight_decay != 0 or amsgrad:
+                 amsgrad=False, lr_schedule=None):
+        if amsgrad or (weight_decay != 0 and not self._DECOUPLED):
             raise NotImplementedError("only the torch.optim.Adam defaults used by the reference are implemented "
-                                      "(weight_decay=0, amsgrad=False)")
+                                      "(weight_decay=0, amsgrad=False); for decoupled weight decay use vaegan_amd.AdamW")
+        weight_decay = check_weight_decay(weight_decay)
+        if lr_schedule is not None and not isinstance(lr_schedule, LRSchedule):
+            raise ValueError(f"lr_schedule must be a vaegan_amd.LRSchedule or None, got {lr_schedule!r}")
         if lr < 0.0:
             raise ValueError(f"Invalid learning rate: {lr}")                  # torch.optim.Adam's own check and wording
         self.params = [p for p in params]
@@ -43,8 +160,10 @@ class Adam:
                                    "construct it after .to(device) as vaegan_code.py:29-44 does")
             if p.device != dev:
                 raise RuntimeError("all parameters of one optimizer must live on one device")
-        self.defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=0, amsgrad=False)
+        self.defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False)
         self.lr, self.betas, self.eps = float(lr), (float(betas[0]), float(betas[1])), float(eps)
+        # lr stays the BASE rate; the rate of step t is lr_schedule.lr(lr, t), evaluated on the device from state_dev[0]
+        self.weight_decay, self.lr_schedule = weight_decay, lr_schedule
         # Placement in the flat buffers.  Default: parameter order.  A parameter tagged `_vg_follows = other` (the
         # Encoder's fc_logvar after fc_mu, nets.py) is homed directly behind `other`, so that the pair forms one
         # contiguous [2N, ...] operand.  Indices in state_dict() stay those of self.params.
@@ -80,7 +199,9 @@ class Adam:
         self.flat_g = torch.zeros(n, dtype=torch.float32, device=dev)
         self.exp_avg = torch.zeros(n, dtype=torch.float32, device=dev)
         self.exp_avg_sq = torch.zeros(n, dtype=torch.float32, device=dev)
-        self.state_dev = torch.zeros(4, dtype=torch.float32, device=dev)   # [t, lr/(1-b1^t), sqrt(1-b2^t), -]
+        # [t, lr_t/(1-b1^t), sqrt(1-b2^t), 1 - lr_t * weight_decay]; the last is written only by a scheduled prologue and
+        # reads 1 until then, so that a plain Adam can share vg_adamw_apply's launch with an AdamW (step_pair)
+        self.state_dev = torch.tensor([0.0, 0.0, 0.0, 1.0], dtype=torch.float32, device=dev)
         with torch.no_grad():
             for p, o in zip(self.params, self.offsets):
                 self.flat_p[o:o + p.numel()].copy_(p.detach().reshape(-1))
@@ -98,9 +219,43 @@ class Adam:
         bump_weights_epoch(self.params)
 
     # -- torch.optim.Optimizer surface ---------------------------------------------------------------
+    def _group(self, params):
+        grp = dict(params=params, lr=self.lr, betas=self.betas, eps=self.eps, weight_decay=self.weight_decay, amsgrad=False)
+        if self.lr_schedule is not None:
+            grp["lr_schedule"] = self.lr_schedule.state_dict()
+        return grp
+
     @property
     def param_groups(self):
-        return [dict(params=self.params, lr=self.lr, betas=self.betas, eps=self.eps, weight_decay=0, amsgrad=False)]
+        return [self._group(self.params)]
+
+    @property
+    def scheduled(self) -> bool:
+        """The prologue of this optimizer is vg_step_prologue_sched's: it has a schedule, or it is an AdamW (whose
+        state_dev[3] is then rewritten every iteration, whatever is assigned to weight_decay)."""
+        return self.lr_schedule is not None or self._DECOUPLED
+
+    def sched_record(self):
+        """The vg_lr_sched record of this optimizer, None for a plain Adam without a schedule."""
+        return sched_record(self.lr_schedule, self.weight_decay) if self.scheduled else None
+
+    def capture_key(self):
+        """What a captured iteration freezes of the learning rate: the base rate, the schedule's fields and the decay --
+        not the rate of the step, which the device works out from its own step count."""
+        return (self.lr, None if self.lr_schedule is None else self.lr_schedule.key(), self.weight_decay)
+
+    def set_schedule(self, lr_schedule) -> None:
+        """Replace (or with None remove) the schedule.  The step count is kept: the next step uses the new schedule's rate
+        at that count.  A captured iteration is keyed on the schedule's fields and is captured again."""
+        if lr_schedule is not None and not isinstance(lr_schedule, LRSchedule):
+            raise ValueError(f"lr_schedule must be a vaegan_amd.LRSchedule or None, got {lr_schedule!r}")
+        self.lr_schedule = lr_schedule
+
+    @property
+    def current_lr(self) -> float:
+        """The learning rate of the last step taken (of the first one, before any), from the host's step count: no device
+        read.  Without a schedule: lr."""
+        return self.lr if self.lr_schedule is None else self.lr_schedule.lr(self.lr, max(self.steps, 1))
 
     def zero_grad(self, set_to_none: bool = True, memset: bool = True) -> None:
         """Gradients become zero (one memset).  memset=False only re-arms the 'overwrite on next write' flags --
@@ -128,15 +283,17 @@ class Adam:
         corrections of this optimizer on the device; only the update kernel is launched.
         Armed by clip_grad_norm_: the update multiplies every gradient by grad_scale * clip_dev[1], read from the device
         (vg_adam_apply_clip; unprepared: after a one-optimizer ops.step_prologue, the same two launches and double arithmetic
-        as vg_adam_step), and disarms."""
+        as vg_adam_step), and disarms.  With a schedule or a decay the unprepared step takes the same two-launch form (the
+        prologue is then vg_step_prologue_sched's); an AdamW's update is vg_adamw_apply."""
         if closure is not None:
             raise NotImplementedError("closure is not supported")
         self._rehome_grads()
-        if self._clip_armed:
+        if self._clip_armed or self.scheduled:
+            coef = self.clip_dev[1:] if self._clip_armed else None
             self._clip_armed = False
             if not prepared:
                 ops.step_prologue(None, [self])
-            ops.adam_apply_clip([self], [self.clip_dev[1:]])
+            ops.adam_apply_clip([self], [coef])
         else:
             ops.adam_step(self.flat_p, self.flat_g, self.exp_avg, self.exp_avg_sq, self.lr, self.betas[0],
                           self.betas[1], self.eps, self.grad_scale, self.state_dev, prepared=prepared)
@@ -146,13 +303,14 @@ class Adam:
     def step_pair(self, other: "Adam") -> None:
         """self.step(prepared=True); other.step(prepared=True) as ONE launch (both optimizers prepared by this iteration's
         ops.step_prologue); results are bit-identical to the two launches.  With either optimizer armed by clip_grad_norm_
-        the launch is vg_adam_apply_clip (an unarmed one of the pair steps unclipped) and both disarm."""
+        the launch is vg_adam_apply_clip (an unarmed one of the pair steps unclipped) and both disarm.  With an AdamW in the
+        pair it is vg_adamw_apply (a plain Adam's state_dev[3] reads 1)."""
         for o in (self, other):
             for p, off in zip(o.params, o.offsets):
                 g = p.grad
                 if g is None or g.data_ptr() != o.flat_g.data_ptr() + 4 * off:
                     raise RuntimeError("step_pair needs every .grad homed in the optimizer's flat gradient buffer")
-        if self._clip_armed or other._clip_armed:
+        if self._clip_armed or other._clip_armed or self._DECOUPLED or other._DECOUPLED:
             ops.adam_apply_clip([self, other], [o.clip_dev[1:] if o._clip_armed else None for o in (self, other)])
             self._clip_armed = other._clip_armed = False
         else:
@@ -172,14 +330,22 @@ class Adam:
             st[i] = dict(step=torch.tensor(float(self.steps)),
                          exp_avg=self.exp_avg[o:o + p.numel()].view(p.shape).clone(),
                          exp_avg_sq=self.exp_avg_sq[o:o + p.numel()].view(p.shape).clone())
-        grp = dict(lr=self.lr, betas=self.betas, eps=self.eps, weight_decay=0, amsgrad=False,
-                   params=list(range(len(self.params))))
-        return dict(state=st, param_groups=[grp])
+        return dict(state=st, param_groups=[self._group(list(range(len(self.params))))])
 
     def load_state_dict(self, sd):
-        """Accepts a torch.optim.Adam state_dict (same format as state_dict() returns)."""
+        """Accepts a torch.optim.Adam state_dict (same format as state_dict() returns).  "lr_schedule" in the group restores
+        the schedule; without the key the optimizer's own schedule is kept (a plain torch dict says nothing about it).  The
+        group's weight_decay, a key every torch dict has, is taken as torch takes it: an AdamW's decay becomes the dict's (0
+        from a plain torch Adam dict), and it must be 0 for an Adam.  No schedule state exists beyond the step
+        count, which is saved: the resumed run evaluates the same rates."""
         grp = sd["param_groups"][0]
+        wd = check_weight_decay(grp.get("weight_decay", 0))
+        if wd != 0 and not self._DECOUPLED:
+            raise NotImplementedError("this state_dict carries weight_decay != 0: load it into a vaegan_amd.AdamW")
         self.lr, self.betas, self.eps = float(grp["lr"]), tuple(float(b) for b in grp["betas"]), float(grp["eps"])
+        self.weight_decay = wd
+        if grp.get("lr_schedule") is not None:
+            self.lr_schedule = LRSchedule(**grp["lr_schedule"])
         steps = 0
         with torch.no_grad():
             for i, (p, o) in enumerate(zip(self.params, self.offsets)):
@@ -190,8 +356,32 @@ class Adam:
                 self.exp_avg_sq[o:o + p.numel()].copy_(s["exp_avg_sq"].reshape(-1))
                 steps = int(float(s["step"]))
             self.steps = steps
-            self.state_dev.zero_()
-            self.state_dev[0] = float(steps)
+            self.state_dev.copy_(torch.tensor([float(steps), 0.0, 0.0, 1.0]))
+
+
+class AdamW(Adam):
+    """torch.optim.AdamW: Adam with DECOUPLED weight decay (Loshchilov & Hutter) -- every parameter is multiplied by
+    1 - lr_t * weight_decay before the Adam update, inside the update kernel (vg_adamw_apply); lr_t is the scheduled rate."""
+    _DECOUPLED = True
+
+    def __init__(self, params: Iterable[torch.Tensor], lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2,
+                 amsgrad=False, lr_schedule=None):
+        super().__init__(params, lr, betas, eps, weight_decay, amsgrad, lr_schedule)
+
+
+def check_weight_decay(weight_decay) -> float:
+    """A weight decay as the optimizers accept it: a finite number >= 0.  ValueError otherwise (torch's wording)."""
+    if isinstance(weight_decay, bool) or not isinstance(weight_decay, (int, float)) or not 0.0 <= weight_decay < math.inf:
+        raise ValueError(f"Invalid weight_decay value: {weight_decay!r}")
+    return float(weight_decay)
+
+
+def lr_report(named_opts) -> dict:
+    """{"lr_<name>": current_lr} over {name: optimizer} when any of them has a schedule, {} otherwise (the trainers'
+    loss_dict / lr_dict)."""
+    if all(o.lr_schedule is None for o in named_opts.values()):
+        return {}
+    return {f"lr_{k}": o.current_lr for k, o in named_opts.items()}
 
 
 def check_max_norm(max_norm) -> float:

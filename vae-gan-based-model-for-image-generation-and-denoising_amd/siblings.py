@@ -21,6 +21,7 @@ from . import ops
 from .capture import HostMirrors, capture, replay
 from .engine import GradSink, bump_weights_epoch
 from .gradclip import ClipOption
+from .optim import lr_report
 
 
 class _Graphed(ClipOption):
@@ -45,6 +46,11 @@ class _Graphed(ClipOption):
         """Whatever else a subclass's captured iteration freezes."""
         return ()
 
+    def lr_dict(self):
+        """{"lr_<network>": the learning rate of the optimizer's last step} when any optimizer has an optim.LRSchedule, {}
+        otherwise; from the host's step counts (no device read).  Network names as in max_grad_norm."""
+        return lr_report(self._clip_opts())
+
     def _graphed_call(self, step, tensors, scalars, tag=None):
         """step(*tensors, **scalars) eagerly, then captured, then replayed; tag: whatever else the capture freezes."""
         # Draws that are not injected come from the per-device default NoiseStream, whose STATE BUFFER the captured
@@ -56,7 +62,8 @@ class _Graphed(ClipOption):
             dev = next(t for t in tensors if t is not None).device
             noise = ops.default_noise(dev)
         key = (tuple(None if t is None else tuple(t.shape) for t in tensors), tuple(sorted(scalars.items())),
-               tuple(n.training for n in self._nets), None if noise is None else noise.state.data_ptr()) \
+               tuple(n.training for n in self._nets), tuple(o.capture_key() for o in self._opts),
+               None if noise is None else noise.state.data_ptr()) \
             + (() if tag is None else (tag,)) + (() if self.ema is None else (("ema",) + self.ema.key(),)) \
             + self._clip_key() + self._extra_key()
         self._gnoise = noise

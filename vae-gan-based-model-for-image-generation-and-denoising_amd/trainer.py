@@ -20,6 +20,7 @@ from .capture import CaptureRefused, HostMirrors, capture, replay
 from . import augment as A
 from .engine import GradSink
 from .gradclip import ClipOption
+from .optim import lr_report
 
 LOSS_NAMES = ("recon_loss", "kl_loss", "g_loss_adv", "d_loss_1", "d_loss_2")
 # more than two periods of c10d's NCCL watchdog (ProcessGroupNCCL::kWatchdogThreadSleepMillis = 100): see _capture
@@ -160,8 +161,10 @@ class VAEGANTrainer(ClipOption):
     def _capture_key(self, real, epoch, inject, paired=False, with_rects=False):
         """Everything a captured graph freezes: shapes, every scalar kernel argument (loss weights, labels, noise
         sigma, Adam hyper-parameters, the data-parallel gradient scale), the schedule switches and the buffers the
-        launches point at.  A change in any of them re-captures instead of silently replaying stale values."""
-        opts = tuple((o.lr, o.betas, o.eps, o.grad_scale, o.flat_p.data_ptr()) for o in (self.opt_E, self.opt_G, self.opt_D))
+        launches point at.  A change in any of them re-captures instead of silently replaying stale values.  Of the learning
+        rate that is the base rate, the schedule's fields and the weight decay (Adam.capture_key): the rate of the step is
+        worked out on the device, so a scheduled run replays one graph while the rate moves."""
+        opts = tuple((o.capture_key(), o.betas, o.eps, o.grad_scale, o.flat_p.data_ptr()) for o in (self.opt_E, self.opt_G, self.opt_D))
         return (tuple(real.shape), float(self.alpha_kl * min(1.0, epoch / 50)), inject, self.E.training, self.G.training,
                 self.D.training, self.alpha_adv, self.alpha_feat, self.alpha_pix, self.alpha_ssim, self.feat_layer, self.sigma,
                 self.real_label,
@@ -653,6 +656,7 @@ class VAEGANTrainer(ClipOption):
                                                  # used the weighted term (slot 7 reads 0 after any other)
         if self._clip is not None:
             out.update(self._clip.report())      # grad_norm_E/G/D, clip_coef_E/G/D of the networks that are configured
+        out.update(lr_report(self._clip_opts()))  # lr_E/G/D, the rates of the last step, when any optimizer has a schedule
         if epoch is not None:
             out["total"] = self.alpha_pix * out["recon_loss"] + self.alpha_kl * min(1.0, epoch / 50) * out["kl_loss"] \
                 + self.alpha_adv * out["g_loss_adv"] + self.alpha_feat * v[5] + self.alpha_ssim * v[6]
