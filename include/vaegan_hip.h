@@ -48,7 +48,7 @@ extern "C" {
 #define VG_ACT_LRELU   2   /* nn.LeakyReLU(slope)    main_vae.py:25, gan_code.py:62-82 */
 #define VG_ACT_TANH    3   /* nn.Tanh()              gan_code.py:50 (vg_tnconv epilogue only) */
 
-#define VG_ABI_VERSION 26  /* 2: vg_pack_desc.tile_start, SyncBN / WGAN / data-path entry points; 3: in-kernel noise (vg_*_rng);
+#define VG_ABI_VERSION 27  /* 2: vg_pack_desc.tile_start, SyncBN / WGAN / data-path entry points; 3: in-kernel noise (vg_*_rng);
                              4: vg_bn_finalize_act_forward, vg_bn_backward_finalize_apply;
                              7: vg_bce_pair_forward_backward;
                              8: vg_head_backward; round-3 prune -- the opt-in experiments of ABI 5 / 6 that measured slower (input prologue of
@@ -72,7 +72,8 @@ extern "C" {
                              23: vg_wgrad_plan / vg_wg_plan, vg_edge_wgrad_plan / vg_ew_plan replace vg_wgrad_ws_bytes / vg_edge_wgrad_ws_bytes;
                              24: gradient-norm clipping: vg_grad_norm_clip, vg_adam_apply_clip;
                              25: differentiable augmentation: vg_diffaug_params, vg_diffaug_forward, vg_diffaug_backward (+ _ws_floats);
-                             26: learning-rate schedules and decoupled weight decay: vg_lr_sched, vg_step_prologue_sched, vg_adamw_apply */
+                             26: learning-rate schedules and decoupled weight decay: vg_lr_sched, vg_step_prologue_sched, vg_adamw_apply;
+                             27: vg_tnconv_plan / vg_tn_plan: the tiling vg_tnconv launches, as a host-only query */
 int vg_abi_version(void);
 /* The library reads its optional kernel-selection switches (VG_* environment variables, DESIGN.md "Runtime switches")
  * ONCE, when it is loaded; nothing on a launch path calls getenv.  A process that changes one of them afterwards
@@ -384,7 +385,7 @@ int vg_bias_grad(const void* dy, int64_t rows, int C, int NC, float* dbias, int 
  * act = VG_ACT_TANH applies tanh (gan_code.py:50) to both; with noise (eps NCHW f32, or rng+draw: in-kernel
  * N(0,1)) Y becomes act(.) + sigma*noise while Y_nchw stays act(.) -- vaegan_code.py:83 and :92 in one pass. */
 typedef struct vg_tn_desc {
-    const void* X;          /* [B][IH][IW][C] bf16, C = 32 or 64 */
+    const void* X;          /* [B][IH][IW][C] bf16, C = 16, 32 or 64 */
     const void* Wp;
     void* Y;                /* or NULL */
     float* Y_nchw;          /* or NULL */
@@ -396,7 +397,7 @@ typedef struct vg_tn_desc {
 } vg_tn_desc;
 /* Weight gradient of the edge layers, bf16 operands, f32 result:
  *     dW[c*s_c + n*s_n + kh*K + kw] (+)= sum_{b,py,px} Wd[b][py][px][c] * Nr[b][py*S - P + kh][px*S - P + kw][n]
- * Wd: the WIDE operand [B][WH][WW][C] (C = 32 | 64): dY of nn.Conv2d(N, C, K, S, P) (gan_code.py:61, main_vae.py:23 --
+ * Wd: the WIDE operand [B][WH][WW][C] (C = 16 | 32 | 64): dY of nn.Conv2d(N, C, K, S, P) (gan_code.py:61, main_vae.py:23 --
  * then dW is the [C][N][K][K] weight gradient, s_c = N*K*K, s_n = K*K) or the input of nn.ConvTranspose2d(C, N, K, S, P)
  * (gan_code.py:49 -- dW is [C][N][K][K] as well).  Nr: the 3-channel tensor on the other side, [B][NH][NW][8] bf16 with
  * channels >= N zero (the image, or the image gradient).  N <= 3, K = 3 | 4, S = 1 | 2.
@@ -428,6 +429,25 @@ typedef struct vg_ew_plan {
 int vg_edge_wgrad_plan(const vg_ew_desc* d, vg_ew_plan* out);
 int vg_tnconv_supported(const vg_tn_desc* d);     /* 0 if vg_tnconv takes this shape, else the error code */
 int vg_tnconv(const vg_tn_desc* d, void* stream);
+/* What vg_tnconv launches for a descriptor (host-only query; needs no GPU; ABI 27): the record the launcher builds and
+ * launches from.  The query validates the geometry like a launch; of the descriptor's pointers it reads only whether rng
+ * is NULL (in-kernel noise moves the column step of the tiling to 4) -- the NULL and alignment tests of X, Wp, Y and Y_nchw
+ * belong to the launch.  A shape the kernel does not take gives the launch's error code.  One workgroup per tile of
+ * ro x co output pixels; its input window is at most npix pixels, tc of them per row ((ro - 1 + K - 1) / S + 1 rows at most). */
+typedef struct vg_tn_plan {
+    int32_t nt;                /* tnconv_kernel<nt, kc, npix, K, S>: tiles of 16 (tap, n) columns, ceil(K*K*N / 16) = 1..4 */
+    int32_t kc;                /* chunks of 32 input channels: 1 (C = 16 | 32) | 2 (C = 64)                                */
+    int32_t npix;              /* input pixels of the LDS product tile: 512 (nt <= 2) | 256                                */
+    int32_t tc;                /* input columns per window row, a multiple of 16; tc == IW: whole rows (then tiles_x == 1) */
+    int32_t ro;                /* output rows per tile, a multiple of S (the last row tile may hold fewer)                 */
+    int32_t co;                /* output columns per tile (the last column tile may hold fewer); whole rows: OW            */
+    int32_t tiles_y;           /* ceil(OH / ro)                                                                            */
+    int32_t tiles_x;           /* ceil(OW / co)                                                                            */
+    int32_t grid;              /* workgroups: B * tiles_y * tiles_x                                                        */
+    int32_t quad_noise;        /* rng set and OW % 4 == 0: tile columns start and end on multiples of 4, and a launch
+                                  without eps draws its noise once per quad of lanes (else, with rng, once per element)  */
+} vg_tn_plan;
+int vg_tnconv_plan(const vg_tn_desc* d, vg_tn_plan* out);
 
 /* ------------------------------------------------------------------------------------------
  * Layout / pointwise / losses

@@ -176,7 +176,8 @@ EDGE_SHAPES = [("conv", 64, 4, 2, 1, 64, 3),     # Discriminator's first layer, 
                ("conv", 32, 4, 2, 0, 64, 2),    # Encoder's first layer: 31x31 outputs, p=0
                ("conv", 32, 4, 2, 1, 128, 1),   # S=128 members
                ("convT", 32, 3, 1, 1, 128, 1),
-               ("conv", 64, 4, 2, 1, 16, 5),    # many images per workgroup walk, tiny maps
+               ("conv", 64, 4, 2, 1, 16, 5),    # tiny maps: one 64-pixel tile per image (5 tiles on 5 workgroups -- like every row
+                                                # here, no workgroup walks; the walks are rows of _edge_ref.EW_CASES)
                ("conv", 16, 4, 2, 1, 256, 1),   # S=256 members: 16 channels on the wide side
                ("convT", 16, 3, 1, 1, 256, 1),  # (gan_code.py:49 and :61 as written)
                ("conv", 16, 4, 2, 1, 32, 3)]

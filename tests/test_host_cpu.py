@@ -197,6 +197,20 @@ def test_c_abi_rejects_bad_arguments_on_host():
     assert lib.vg_edge_wgrad_plan(ctypes.byref(e), None) == -1
     e = L.EWDesc(B=1, WH=8, WW=8, C=48, NH=16, NW=16, N=3, K=4, S=2, P=1)
     assert lib.vg_edge_wgrad_plan(ctypes.byref(e), ctypes.byref(ep)) == -3
+    # the transposed edge convolution's plan: validated like its launch, except that it looks at no pointer but rng
+    t, tp = L.TNDesc(), L.TNPlan()
+    assert lib.vg_tnconv_plan(ctypes.byref(t), ctypes.byref(tp)) == -1
+    geo = dict(B=1, IH=16, IW=16, C=64, N=3, K=3, S=1, P=1, OH=16, OW=16, OC=8, Wpitch=64)
+    t = L.TNDesc(**geo)
+    assert lib.vg_tnconv_plan(ctypes.byref(t), None) == -1
+    assert lib.vg_tnconv_plan(ctypes.byref(t), ctypes.byref(tp)) == 0 and (tp.nt, tp.kc, tp.grid, tp.quad_noise) == (2, 2, 1, 0)
+    assert lib.vg_tnconv_supported(ctypes.byref(t)) == -1 and lib.vg_tnconv(ctypes.byref(t), None) == -1      # NULL operands
+    for bad, rc in ((dict(C=48), -3), (dict(IW=24, OW=24), -3), (dict(N=5), -3), (dict(K=4), -3), (dict(Wpitch=32), -2),
+                    (dict(OW=17), -1), (dict(P=9, OH=0, OW=0), -1)):      # P = 9: a padding that leaves no output
+        t = L.TNDesc(**dict(geo, **bad))
+        assert lib.vg_tnconv_plan(ctypes.byref(t), ctypes.byref(tp)) == rc, bad
+        t.X = t.Wp = t.Y = 64                            # with operands in place the launch path gives the same code
+        assert lib.vg_tnconv_supported(ctypes.byref(t)) == rc and lib.vg_tnconv(ctypes.byref(t), None) == rc, bad
     assert lib.vg_adam_step(None, None, None, None, 0, 1e-3, 0.9, 0.999, 1e-8, 1.0, None, None) == -1
     # the iteration prologue: nothing to do at all, too many optimizers, a NULL state
     assert lib.vg_step_prologue(None, None, None, None, None, 0, None, 0, None) == -1

@@ -21,7 +21,7 @@ VG_GNORM_MAX = 4
 VG_GNORM_PARTS = 512
 VG_PROLOGUE_MAX = 4
 VG_LRS_CONST, VG_LRS_LINEAR, VG_LRS_COSINE, VG_LRS_EXP, VG_LRS_STEP = 0, 1, 2, 3, 4
-ABI_VERSION = 26
+ABI_VERSION = 27
 
 VG_ENOSUP = -3
 _ERR = {-1: "VG_EINVAL (bad shape/size/flag)", -2: "VG_EALIGN (16-byte contract violated)",
@@ -83,6 +83,11 @@ class TNDesc(Structure):
                 ("B", c_int32), ("IH", c_int32), ("IW", c_int32), ("C", c_int32), ("N", c_int32), ("K", c_int32),
                 ("S", c_int32), ("P", c_int32), ("OH", c_int32), ("OW", c_int32), ("OC", c_int32),
                 ("Wpitch", c_int32), ("act", c_int32)]
+
+
+class TNPlan(Structure):
+    """vg_tn_plan."""
+    _fields_ = [(n, c_int32) for n in ("nt", "kc", "npix", "tc", "ro", "co", "tiles_y", "tiles_x", "grid", "quad_noise")]
 
 
 class EWDesc(Structure):
@@ -227,6 +232,7 @@ SIGNATURES = {
     "vg_edge_wgrad_plan": (c_int, [POINTER(EWDesc), POINTER(EWPlan)]),
     "vg_tnconv_supported": (c_int, [POINTER(TNDesc)]),
     "vg_tnconv": (c_int, [POINTER(TNDesc), _P]),
+    "vg_tnconv_plan": (c_int, [POINTER(TNDesc), POINTER(TNPlan)]),
 }
 
 LIB_PATH = os.environ.get("VG_LIB_PATH") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libvaegan_hip.so")

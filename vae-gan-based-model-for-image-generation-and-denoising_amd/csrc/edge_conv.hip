@@ -44,8 +44,10 @@ template <int NT, int KC, int NPIX, int K, int S>
 __global__ __launch_bounds__(256) void tnconv_kernel(const vg_tn_desc d, const int RO, const int tiles_y, const int CO,
                                                      const int tiles_x, const int TC) {
     // Tile: output rows [oy_a, oy_b) x output columns [ox_a, ox_b); its input window is nrows x TC pixels (TC a multiple of
-    // 16: whole MFMA row groups per window row) starting at column c0.  tiles_x == 1: TC = IW, whole rows (every map up to
-    // 128 pixels wide); wider maps (S=256 members) are cut into column blocks with a K-1 halo on either side.
+    // 16: whole MFMA row groups per window row) starting at column c0.  tiles_x == 1: TC = IW, whole rows; else column blocks
+    // with a K-1 halo on either side.  Which of the two is the host's choice by halo cost (tn_plan; vg_tnconv_plan reports
+    // it): whole rows only for narrow maps -- the 16-wide ones, most 32-wide ones and some 48-wide ones; every map of 64
+    // pixels or more (the S = 64 members' included) is cut into 16- or 32-column blocks.
     constexpr int PS = NPIX + 4;                              // LDS row pitch of the product tile (floats)
     __shared__ __attribute__((aligned(16))) float Pm[NT * 16 * PS];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -196,32 +198,35 @@ __global__ __launch_bounds__(256) void tnconv_kernel(const vg_tn_desc d, const i
     }
 }
 
-struct TnPlan { int RO, tiles_y, NT, KC, NPIX, CO, tiles_x, TC; };
-
-inline int tn_plan(const vg_tn_desc* d, TnPlan* p) {
+// The launch record (vg_tn_plan, include/vaegan_hip.h).  ptrs: also hold the descriptor's pointers to the launch contract
+// (vg_tnconv, vg_tnconv_supported); the host-only query vg_tnconv_plan passes false and reads of them only whether rng is set.
+inline int tn_plan(const vg_tn_desc* d, vg_tn_plan* p, bool ptrs) {
     VG_CHECK_ARG(d != nullptr, VG_EINVAL);
-    VG_CHECK_ARG(d->X && d->Wp && (d->Y || d->Y_nchw), VG_EINVAL);
+    if (ptrs) VG_CHECK_ARG(d->X && d->Wp && (d->Y || d->Y_nchw), VG_EINVAL);
     VG_CHECK_ARG(d->B > 0 && d->IH > 0 && d->IW > 0 && d->P >= 0, VG_EINVAL);
     VG_CHECK_ARG((d->K == 3 && d->S == 1) || (d->K == 4 && d->S == 2), VG_ENOSUP);      // the two edge-layer forms
     VG_CHECK_ARG(d->N >= 1 && d->N <= 4 && d->OC == 8, VG_ENOSUP);
     VG_CHECK_ARG(d->C == 16 || d->C == 32 || d->C == 64, VG_ENOSUP);
     VG_CHECK_ARG(d->Wpitch >= ((d->C + 31) / 32) * 32 && d->Wpitch % 8 == 0, VG_EALIGN);     // whole 32-channel chunks (zero-padded)
     VG_CHECK_ARG(d->OH == (d->IH - 1) * d->S - 2 * d->P + d->K && d->OW == (d->IW - 1) * d->S - 2 * d->P + d->K, VG_EINVAL);
-    VG_CHECK_ARG(vg_aligned16(d->X) && vg_aligned16(d->Wp) && vg_aligned16(d->Y), VG_EALIGN);
+    VG_CHECK_ARG(d->OH > 0 && d->OW > 0, VG_EINVAL);                                    // (a padding that leaves no output)
+    if (ptrs) VG_CHECK_ARG(vg_aligned16(d->X) && vg_aligned16(d->Wp) && vg_aligned16(d->Y), VG_EALIGN);
     VG_CHECK_ARG(d->act == VG_ACT_NONE || d->act == VG_ACT_TANH, VG_EINVAL);
     VG_CHECK_ARG(d->draw >= 0 && d->draw < 256, VG_EINVAL);
     const int NJ = d->K * d->K * d->N;
     VG_CHECK_ARG(NJ <= 64, VG_ENOSUP);
-    p->NT = (NJ + 15) / 16;
-    p->KC = (d->C + 31) / 32;
+    p->nt = (NJ + 15) / 16;
+    p->kc = (d->C + 31) / 32;
     // product tile in LDS: NT*16 columns x NPIX pixels of f32; keep it <= ~66 KB so that two workgroups share a CU
     // (one's HBM loads under the other's col2im): 512 pixels for <= 32 columns, 256 beyond
-    p->NPIX = p->NT <= 2 ? 512 : 256;
+    p->npix = p->nt <= 2 ? 512 : 256;
     VG_CHECK_ARG(d->IW % 16 == 0, VG_ENOSUP);
-    // Window of input pixels per workgroup: nrows x TC <= NPIX with TC a multiple of 16.  Whole rows (TC = IW) when at
-    // least the rows behind one block of S output rows fit; otherwise (maps wider than ~128 pixels) column blocks.  Among
-    // the candidates the one with the least halo overhead (window pixels per output pixel) wins.
-    auto rows_for = [&](int tc) { return p->NPIX / tc; };
+    // Window of input pixels per workgroup: nrows x TC <= NPIX with TC a multiple of 16.  Candidates: whole rows (TC = IW,
+    // when at least the rows behind one block of S output rows fit) and column blocks of every TC that divides IW or is at
+    // most half of it.  The one with the least halo overhead (window pixels per output pixel) wins, whole rows on a near
+    // tie (0.02): a 64-wide k3 s1 map costs 1.33 in whole rows (8 x 64 window, 6 output rows) against 1.24 in 16-column
+    // blocks (32 x 16 window, 30 x 14 outputs), so only maps narrower than that keep whole rows.
+    auto rows_for = [&](int tc) { return p->npix / tc; };
     auto ro_for = [&](int max_rows) {               // largest block of output rows (a multiple of S) whose input rows fit
         int RO = 0;
         for (int r = d->S; r <= d->OH + d->S; r += d->S) {
@@ -244,7 +249,7 @@ inline int tn_plan(const vg_tn_desc* d, TnPlan* p) {
     };
     int best_tc = 0, best_ro = 0, best_co = 0;
     double best_cost = 1e30;
-    for (int tc = 16; tc <= d->IW && tc <= p->NPIX; tc += 16) {
+    for (int tc = 16; tc <= d->IW && tc <= p->npix; tc += 16) {
         const bool full = tc == d->IW;
         if (!full && d->IW % tc != 0 && tc * 2 > d->IW) continue;   // (a block that is neither the row nor a sensible fraction)
         int ro = ro_for(rows_for(tc));
@@ -257,27 +262,29 @@ inline int tn_plan(const vg_tn_desc* d, TnPlan* p) {
         if (cost < best_cost) { best_cost = cost; best_tc = tc; best_ro = ro; best_co = co; }
     }
     VG_CHECK_ARG(best_tc > 0, VG_ENOSUP);
-    p->TC = best_tc;
-    p->RO = best_ro;
-    p->CO = best_co;
-    p->tiles_y = (d->OH + p->RO - 1) / p->RO;
-    p->tiles_x = (d->OW + p->CO - 1) / p->CO;
+    p->tc = best_tc;
+    p->ro = best_ro;
+    p->co = best_co;
+    p->tiles_y = (d->OH + p->ro - 1) / p->ro;
+    p->tiles_x = (d->OW + p->co - 1) / p->co;
+    p->grid = d->B * p->tiles_y * p->tiles_x;
+    p->quad_noise = d->rng != nullptr && d->OW % 4 == 0;     // the column step above was 4: every tile's columns are whole quads
     return 0;
 }
 
 template <int NT, int KC>
-inline void tn_launch(const vg_tn_desc* d, const TnPlan& p, hipStream_t s) {
-    dim3 grid(d->B * p.tiles_y * p.tiles_x), block(256);
+inline void tn_launch(const vg_tn_desc* d, const vg_tn_plan& p, hipStream_t s) {
+    dim3 grid(p.grid), block(256);
     constexpr int NPIX = NT <= 2 ? 512 : 256;
-    if (d->K == 3) vg_launch_timed(2, (tnconv_kernel<NT, KC, NPIX, 3, 1>), grid, block, 0, s, *d, p.RO, p.tiles_y, p.CO, p.tiles_x, p.TC);
-    else vg_launch_timed(2, (tnconv_kernel<NT, KC, NPIX, 4, 2>), grid, block, 0, s, *d, p.RO, p.tiles_y, p.CO, p.tiles_x, p.TC);
+    if (d->K == 3) vg_launch_timed(2, (tnconv_kernel<NT, KC, NPIX, 3, 1>), grid, block, 0, s, *d, p.ro, p.tiles_y, p.co, p.tiles_x, p.tc);
+    else vg_launch_timed(2, (tnconv_kernel<NT, KC, NPIX, 4, 2>), grid, block, 0, s, *d, p.ro, p.tiles_y, p.co, p.tiles_x, p.tc);
 }
 
 
 // ---------------------------------------------------------------------------------------------------------------------
 // vg_edge_wgrad -- weight gradient of the edge layers (the Discriminator's / Encoder's first Conv2d, the Generator's
 // last ConvTranspose2d):   G[j = (kh*K + kw)*4 + n][c] = sum_pix  Nr[b][py*S - P + kh][px*S - P + kw][n] * Wd[b][py][px][c]
-// over the pixels (b, py, px) of the WIDE operand Wd (C = 32 | 64 channels: dY of the conv, the input of the convT);
+// over the pixels (b, py, px) of the WIDE operand Wd (C = 16 | 32 | 64 channels: dY of the conv, the input of the convT);
 // Nr is the 3-channel tensor on the other side (the image, or the image gradient), 8 bf16 per pixel, channel 3 is zero.
 // The generic wgrad kernel (wgrad.hip) runs this as a 128 x 128 tile of which 1/4 is used, gathers the narrow operand
 // in 16-byte granules through LDS-DMA and writes 17-33 MB of split slabs for a 3 K-element result.  Here:
@@ -469,21 +476,26 @@ inline int ew_plan(const vg_ew_desc* d, vg_ew_plan* p) {
 }  // namespace
 
 extern "C" int vg_tnconv_supported(const vg_tn_desc* d) {
-    TnPlan p;
-    return tn_plan(d, &p);
+    vg_tn_plan p;
+    return tn_plan(d, &p, true);
+}
+
+extern "C" int vg_tnconv_plan(const vg_tn_desc* d, vg_tn_plan* out) {
+    VG_CHECK_ARG(out != nullptr, VG_EINVAL);
+    return tn_plan(d, out, false);
 }
 
 extern "C" int vg_tnconv(const vg_tn_desc* d, void* stream) {
-    TnPlan p;
-    int rc = tn_plan(d, &p);
+    vg_tn_plan p;
+    int rc = tn_plan(d, &p, true);
     if (rc) return rc;
     hipStream_t s = vg_stream(stream);
-    if (p.KC == 1) {
-        if (p.NT == 1) tn_launch<1, 1>(d, p, s); else if (p.NT == 2) tn_launch<2, 1>(d, p, s);
-        else if (p.NT == 3) tn_launch<3, 1>(d, p, s); else tn_launch<4, 1>(d, p, s);
+    if (p.kc == 1) {
+        if (p.nt == 1) tn_launch<1, 1>(d, p, s); else if (p.nt == 2) tn_launch<2, 1>(d, p, s);
+        else if (p.nt == 3) tn_launch<3, 1>(d, p, s); else tn_launch<4, 1>(d, p, s);
     } else {
-        if (p.NT == 1) tn_launch<1, 2>(d, p, s); else if (p.NT == 2) tn_launch<2, 2>(d, p, s);
-        else if (p.NT == 3) tn_launch<3, 2>(d, p, s); else tn_launch<4, 2>(d, p, s);
+        if (p.nt == 1) tn_launch<1, 2>(d, p, s); else if (p.nt == 2) tn_launch<2, 2>(d, p, s);
+        else if (p.nt == 3) tn_launch<3, 2>(d, p, s); else tn_launch<4, 2>(d, p, s);
     }
     return VG_LAUNCH_RC();
 }

@@ -491,6 +491,17 @@ def edge_wgrad_plan(ew: EWSpec) -> dict:
     return {name: getattr(p, name) for name, _ in L.EWPlan._fields_}
 
 
+def tnconv_plan(tn: TNSpec, rng: bool = False) -> dict:
+    """What vg_tnconv launches for this geometry (vg_tnconv_plan: the record the launcher itself launches from).  Host
+    only, no GPU and no tensors.  rng: whether the noise is drawn in-kernel (tnconv with a NoiseDraw) -- the only pointer
+    of the descriptor the query looks at.  -> dict of the fields of vg_tn_plan, quad_noise as a bool."""
+    d = L.TNDesc(rng=_addr(bool(rng)), B=tn.B, IH=tn.IH, IW=tn.IW, C=tn.C, N=tn.N, K=tn.K, S=tn.S, P=tn.P, OH=tn.OH, OW=tn.OW,
+                 OC=tn.OC, Wpitch=tn.Wpitch)
+    p = L.TNPlan()
+    L.check(L.load().vg_tnconv_plan(byref(d), byref(p)), "vg_tnconv_plan")
+    return dict({name: getattr(p, name) for name, _ in L.TNPlan._fields_}, quad_noise=bool(p.quad_noise))
+
+
 def bn_finalize(stats, nparts, C, count, gamma, beta, running_mean, running_var, momentum, eps, device, groups=1,
                 sync=None):
     """-> coeffs tensor [groups][4][C]: mean, invstd, scale, shift.  With groups > 1 the slabs of group g are
