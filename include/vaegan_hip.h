@@ -48,7 +48,7 @@ extern "C" {
 #define VG_ACT_LRELU   2   /* nn.LeakyReLU(slope)    main_vae.py:25, gan_code.py:62-82 */
 #define VG_ACT_TANH    3   /* nn.Tanh()              gan_code.py:50 (vg_tnconv epilogue only) */
 
-#define VG_ABI_VERSION 27  /* 2: vg_pack_desc.tile_start, SyncBN / WGAN / data-path entry points; 3: in-kernel noise (vg_*_rng);
+#define VG_ABI_VERSION 28  /* 2: vg_pack_desc.tile_start, SyncBN / WGAN / data-path entry points; 3: in-kernel noise (vg_*_rng);
                              4: vg_bn_finalize_act_forward, vg_bn_backward_finalize_apply;
                              7: vg_bce_pair_forward_backward;
                              8: vg_head_backward; round-3 prune -- the opt-in experiments of ABI 5 / 6 that measured slower (input prologue of
@@ -73,7 +73,8 @@ extern "C" {
                              24: gradient-norm clipping: vg_grad_norm_clip, vg_adam_apply_clip;
                              25: differentiable augmentation: vg_diffaug_params, vg_diffaug_forward, vg_diffaug_backward (+ _ws_floats);
                              26: learning-rate schedules and decoupled weight decay: vg_lr_sched, vg_step_prologue_sched, vg_adamw_apply;
-                             27: vg_tnconv_plan / vg_tn_plan: the tiling vg_tnconv launches, as a host-only query */
+                             27: vg_tnconv_plan / vg_tn_plan: the tiling vg_tnconv launches, as a host-only query;
+                             28: Gaussian-mixture prior: vg_gmm_log_resp, vg_gmm_moments (+ _ws_bytes), vg_gmm_sample */
 int vg_abi_version(void);
 /* The library reads its optional kernel-selection switches (VG_* environment variables, DESIGN.md "Runtime switches")
  * ONCE, when it is loaded; nothing on a launch path calls getenv.  A process that changes one of them afterwards
@@ -714,6 +715,69 @@ int vg_latent_hist(const float* x, int64_t N, int D, int64_t row_stride, int n_b
 int vg_latent_sample(const float* edges, const double* cdf, int n_bins, int L, int64_t n, const double* u, const double* v,
                      const float* eps, const uint64_t* rng, float* mulv, void* z, int ZP, int dtype, void* stream);
 int vg_to_u8(const float* x, uint8_t* y, int B, int C, int H, int W, int grid_cols, void* stream);
+/* ------------------------------------------------------------------------------------------
+ * Gaussian-mixture prior (ex-post density estimation: Ghosh et al. 2020, "From Variational to Deterministic
+ * Autoencoders"; not in the reference, whose two priors are N(0, I) and the per-column histograms above).  A
+ * full-covariance mixture of K Gaussians fitted by EM to the Encoder's mu rows of the whole data set keeps the
+ * correlations between latent dimensions that the histogram prior discards.  The two GEMM-shaped phases of an EM
+ * iteration and the sampler run here; the K small D x D steps between them (weights, means, Cholesky, triangular
+ * inverse) are the caller's, in f64 on the host (latent.GaussianMixturePrior).
+ * Throughout: x f32 [N][D], rows `row_stride` elements apart (row_stride >= D: mulv[:, :L] is fitted without a copy);
+ * every parameter and every sum f64, 8-byte aligned (else VG_EALIGN); 1 <= N <= 2^31 - 1, 1 <= D <= 256, 1 <= K <= 64.
+ * Outside these limits, on a NULL required pointer or with too small a workspace: VG_EINVAL before any launch.
+ * Deterministic: no floating-point atomics, the same inputs give the same bits on every call.
+ *
+ * vg_gmm_log_resp (E-step): mean f64 [K][D]; prec_chol f64 [K][D][D], scikit-learn's precisions_cholesky_: UPPER
+ * triangular U_k with inverse(Sigma_k) = U_k U_k^T (entries below the diagonal are never read); log_coef f64 [K] =
+ * log w_k + sum_i log U_k[i][i] - D/2 log(2 pi).  Per row, d = (double)x - mean_k:
+ *     y_j        = sum_i d_i U_k[i][j]                   on v_mfma_f64_16x16x4_f64, D staged padded with zeros to 16
+ *     log_prob_k = log_coef_k - 0.5 * sum_j y_j^2        the sum of squares is the MFMA's epilogue
+ *     m          = max_k log_prob_k
+ *     log_norm   = m + log(sum_k exp(log_prob_k - m))    k ascending
+ *     resp_k     = exp(log_prob_k - log_norm)
+ * Outputs, each optional (NULL), at least one: log_prob f64 [N][K], log_norm f64 [N], resp f64 [N][K].  The order of the
+ * additions inside y and inside the sum of squares is the kernel's; where every intermediate is exactly representable
+ * the result is exact.  exp and log are the device library's f64 functions.  A NaN in a row makes its log_norm NaN.
+ * One launch: a workgroup owns up to 64 rows, whose x tile stays in LDS for all K components.
+ *
+ * vg_gmm_moments (M-step sums), with d = (double)x - shift_k (shift f64 [K][D]) and r = resp f64 [N][K]:
+ *     nk[k] = sum_n r_nk      s1[k][i] = sum_n r_nk d_i      s2[k][i][j] = sum_n r_nk d_i d_j      (f64 [K], [K][D], [K][D][D])
+ *     loglik_sum[0] = sum_n log_norm[n]      (both optional; loglik_sum needs log_norm)
+ * The outputs are OVERWRITTEN; s2 is the full matrix, exactly symmetric (the entries below the diagonal are copies).  The centred form is deliberate: with shift = the current
+ * means, Sigma_k = s2/nk - delta delta^T with delta = s1/nk loses nothing to cancellation as EM converges.
+ * The shape is (r * d)^T d on v_mfma_f64_16x16x4_f64 (r_nk * d_i is rounded once, then every product and sum is f64):
+ * the 16 x 16 blocks of the upper triangle of s2_k, one accumulator each, over a FIXED row split -- rows in ascending
+ * order inside a split, the splits' partials added in split order by a second launch, the scheme of vg_feat_stats_accum.
+ * For D <= 112 one workgroup holds all blocks of a component, so x is read once per component.  Two launches.
+ * ws: vg_gmm_moments_ws_bytes(N, D, K) bytes, 8-byte aligned = 8 * splits * (K * (256 NB + 16 TB + 1) + 1) with
+ * TB = ceil(D / 16), NB = TB (TB + 1) / 2 and the row split: s = min(max(1, 768 / (ceil(NB / 32) K)), ceil(N / 64)) parts
+ * asked for, rows_per_split = ceil(N / s) rounded up to a multiple of 16, splits = ceil(N / rows_per_split) <= s (N =
+ * 200 000, D = 100, K = 10: s = 76, 2 640 rows each, 76 splits; K = 1: s = 768, 272 rows each, 736 splits).  VG_EINVAL
+ * (negative) outside the limits.
+ *
+ * vg_gmm_sample: n draws.  cdf f64 [K] = cumulative weights; mean f64 [K][D]; cov_chol f64 [K][D][D]: the LOWER factor
+ * L_k of Sigma_k (entries above the diagonal are never read).  Per draw j, with u in [0, 1) and eps f32 [D]:
+ *     k     = first index with cdf[k] > u (np.searchsorted(cdf, u, side="right")), CLAMPED to K - 1
+ *     z64_i = mean_k[i] + s_i,   s_i = sum_{c <= i} L_k[i][c] * (double)eps_c, c ascending, each step one fused multiply-add
+ *     z32   = (float)z64, one rounding
+ * Draws: injected -- u f64 [n], eps f32 [n][D] -- or, where the pointer is NULL, generated from rng = {seed, counter}
+ * (device memory) like every other in-kernel draw: u = u01(word(VG_DRAW_GMM_U, j)), eps = element j*D + i of what
+ * vg_randn(out, n*D, rng, VG_DRAW_GMM_EPS) materialises (u01, word: "Degraded pairs" above).
+ * Outputs, each optional (NULL), at least one: comp int32 [n] = k; z32 f32 [n][D]; z [n][ZP] in dtype (VG_F32 / VG_BF16,
+ * ZP >= D, pad columns zero, 16-byte aligned): z32 cast to the engine dtype, the Generator's input.  One launch.
+ * ---------------------------------------------------------------------------------------- */
+#define VG_DRAW_GMM_U   40
+#define VG_DRAW_GMM_EPS 41
+int vg_gmm_log_resp(const float* x, int64_t N, int D, int64_t row_stride, int K, const double* mean,
+                    const double* prec_chol, const double* log_coef, double* log_prob, double* log_norm, double* resp,
+                    void* stream);
+int64_t vg_gmm_moments_ws_bytes(int64_t N, int D, int K);
+int vg_gmm_moments(const float* x, int64_t N, int D, int64_t row_stride, int K, const double* shift, const double* resp,
+                   const double* log_norm, double* nk, double* s1, double* s2, double* loglik_sum, void* ws,
+                   int64_t ws_bytes, void* stream);
+int vg_gmm_sample(const double* cdf, const double* mean, const double* cov_chol, int K, int D, int64_t n, const double* u,
+                  const float* eps, const uint64_t* rng, int32_t* comp, float* z32, void* z, int ZP, int dtype,
+                  void* stream);
 /* ------------------------------------------------------------------------------------------
  * Resize (dataset_code.py:26-30, CelebADatasetV0's transforms.Resize(image_size) + transforms.CenterCrop(image_size) on
  * the PIL image default_loader hands them): PIL's ImagingResample for 8-bit images with the triangle (BILINEAR) filter,

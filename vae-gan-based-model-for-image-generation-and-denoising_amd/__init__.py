@@ -9,7 +9,8 @@ reference-shaped step function).  The learned-similarity term of Larsen et al. (
 its code): ``VAEGANTrainer(..., feat_layer=, alpha_feat=, alpha_pix=)`` and ``Discriminator.features(x, layer)`` /
 ``Discriminator.feature_layers()``.  The SSIM reconstruction loss (1 - the SSIM the denoising passes report; not in the
 reference): ``SSIMLoss`` and ``VAEGANTrainer(..., alpha_ssim=)`` / ``VAETrainer(..., alpha_ssim=)``.  Generation (main_vae.py:415-641): ``latent`` -- ``encode_dataset``, ``LatentPrior``,
-``evaluate_generation``, ``sample_images``.  Feature-space metrics (fid.update / fid.compute of every evaluation loop,
+``evaluate_generation``, ``sample_images``, and ``GaussianMixturePrior`` (not in the reference): a full-covariance Gaussian
+mixture fitted to the Encoder's latents by EM on the device and sampled there, a drop-in ``prior=``.  Feature-space metrics (fid.update / fid.compute of every evaluation loop,
 README.md:22 precision / recall): ``metrics`` -- ``FeatureStats``, ``frechet_distance``, ``precision_recall``,
 ``encoder_features``, ``kernel_distance`` (KID).  Weight averaging (not in the reference): ``EMA`` -- an exponential moving
 average of Encoder / Generator weights kept on the device, ``VAEGANTrainer(..., ema=)`` and the sibling trainers.
@@ -31,7 +32,7 @@ from .ddp import GradReducer
 from .ema import EMA
 from .denoise import denoise_eval, paired_test_epoch, validation_epoch
 from .graphed import graphed
-from .latent import LatentPrior, encode_dataset, evaluate_generation, sample_images
+from .latent import GaussianMixturePrior, LatentPrior, encode_dataset, evaluate_generation, sample_images
 from .metrics import FeatureStats, encoder_features, frechet_distance, kernel_distance, precision_recall
 from .losses import BCELoss, MSELoss, SSIMLoss
 from .nets import ConvBlock, Discriminator, Encoder, Generator, weights_init
@@ -42,7 +43,7 @@ from .utils import configure_seed
 
 __all__ = ["ConvBlock", "Encoder", "Generator", "Discriminator", "weights_init", "Adam", "BCELoss", "MSELoss", "SSIMLoss",
            "VAEGANTrainer", "LOSS_NAMES", "configure_seed", "geometry", "denoise_eval", "validation_epoch", "paired_test_epoch", "GradReducer", "data", "VAETrainer", "DCGANTrainer", "WGANTrainer", "graphed",
-           "latent", "LatentPrior", "encode_dataset", "evaluate_generation", "sample_images",
+           "latent", "LatentPrior", "GaussianMixturePrior", "encode_dataset", "evaluate_generation", "sample_images",
            "ResidentImages", "resample_coeffs", "resize_geometry",
            "EMA", "clip_grad_norm_", "DiffAugment", "AdamW", "LRSchedule",
            "metrics", "FeatureStats", "frechet_distance", "precision_recall", "encoder_features", "kernel_distance"]

@@ -11,9 +11,15 @@ score.  The contracts -- f32 edges as numpy >= 2 computes them, the f64 cdf summ
 deviations -- are in include/vaegan_hip.h, "Latent prior".  All compute is HIP kernels.  FID and precision / recall / F1
 are computed in the feature space of a pluggable ``feature_fn`` (metrics.py; the project's own Encoder by default);
 InceptionV3 itself needs downloaded weights, so Inception Score is out of scope.
-"""
-from typing import Dict, Iterable, Optional, Tuple
 
+Beyond the reference: ``GaussianMixturePrior`` fits a full-covariance Gaussian mixture to the same latents by EM on the
+device (vg_gmm_log_resp, vg_gmm_moments; the K small D x D steps in numpy on the host) and samples it there
+(vg_gmm_sample) -- the histogram prior treats every latent dimension on its own, the mixture keeps their correlations.
+Either prior is a ``prior=`` of ``evaluate_generation`` / ``sample_images``.
+"""
+from typing import Dict, Iterable, Optional, Tuple, Union
+
+import numpy as np
 import torch
 
 from . import geometry as G
@@ -143,6 +149,220 @@ class LatentPrior:
                    int(sd["n_fitted"]))
 
 
+_GMM_TINY = 10 * np.finfo(np.float64).eps
+_GMM_KEYS = ("weights", "means", "covariances", "prec_chol", "cov_chol", "cdf")
+
+
+def _lower_inverse(low: np.ndarray) -> np.ndarray:
+    """Inverse of a lower-triangular matrix by forward substitution (exactly lower triangular, f64)."""
+    D = low.shape[0]
+    inv = np.zeros_like(low)
+    for i in range(D):
+        row = -(low[i, :i] @ inv[:i])
+        row[i] += 1.0
+        inv[i] = row / low[i, i]
+    return inv
+
+
+def _gmm_host_step(weights: np.ndarray, means: np.ndarray, cov: np.ndarray, reg_covar: float) -> Dict[str, np.ndarray]:
+    """The K small D x D steps of an M-step, numpy f64 on the host: Cholesky factor L_k of every covariance, the
+    precision factor U_k = inverse(L_k)^T (scikit-learn's precisions_cholesky_), log_coef and the cdf of the weights."""
+    K, D = means.shape
+    cov_chol, prec_chol = np.empty_like(cov), np.empty_like(cov)
+    for k in range(K):
+        try:
+            if not np.all(np.isfinite(cov[k])):
+                raise np.linalg.LinAlgError("not finite")
+            cov_chol[k] = np.linalg.cholesky(cov[k])
+        except np.linalg.LinAlgError:
+            raise RuntimeError(f"GaussianMixturePrior.fit: the covariance of component {k} is not positive definite "
+                               f"(a collapsed component or a degenerate latent column); increase reg_covar "
+                               f"(now {reg_covar})") from None
+        prec_chol[k] = _lower_inverse(cov_chol[k]).T
+    log_det = np.log(np.diagonal(prec_chol, axis1=1, axis2=2)).sum(axis=1)
+    log_coef = np.log(weights) + log_det - 0.5 * D * np.log(2.0 * np.pi)
+    return dict(weights=weights, means=means, covariances=cov, cov_chol=cov_chol, prec_chol=prec_chol, log_coef=log_coef,
+                cdf=np.cumsum(weights))
+
+
+class GaussianMixturePrior:
+    """A full-covariance Gaussian mixture fitted to the aggregate posterior (ex-post density estimation, Ghosh et al.
+    2020); not in the reference, whose histogram prior (``LatentPrior``) fits every latent dimension on its own and so
+    discards the correlations between them.  The two GEMM-shaped phases of EM and the sampler are HIP kernels
+    (include/vaegan_hip.h, "Gaussian-mixture prior"); the latents never leave the device.
+
+    Device tensors, all f64: ``weights`` [K], ``means`` [K, D], ``covariances`` [K, D, D], ``prec_chol`` [K, D, D] (upper
+    factors U_k, inverse(Sigma_k) = U_k U_k^T: scikit-learn's precisions_cholesky_), ``cov_chol`` [K, D, D] (lower factors
+    L_k of Sigma_k), ``cdf`` [K] (np.cumsum(weights)).  Python values: ``converged``, ``n_iter``, ``lower_bound`` (the mean
+    log-likelihood per row of the last E-step), ``n_fitted``, ``latent_dim``."""
+
+    def __init__(self, weights, means, covariances, prec_chol, cov_chol, cdf, converged: bool = True, n_iter: int = 0,
+                 lower_bound: float = float("nan"), n_fitted: int = 0):
+        ts = (weights, means, covariances, prec_chol, cov_chol, cdf)
+        for t in ts:
+            if not t.is_cuda:
+                raise RuntimeError("GaussianMixturePrior lives on the MI355X ('cuda'); there is no CPU path")
+        K, D = (means.shape[0], means.shape[1]) if means.dim() == 2 else (0, 0)
+        shapes = ((K,), (K, D), (K, D, D), (K, D, D), (K, D, D), (K,))
+        if K < 1 or D < 1 or any(t.dtype != torch.float64 or tuple(t.shape) != s for t, s in zip(ts, shapes)):
+            raise RuntimeError("GaussianMixturePrior: f64 weights [K], means [K,D], covariances / prec_chol / cov_chol "
+                               "[K,D,D], cdf [K]")
+        self.weights, self.means, self.covariances, self.prec_chol, self.cov_chol, self.cdf = (t.contiguous() for t in ts)
+        self.n_components, self.latent_dim = K, D
+        self.converged, self.n_iter = bool(converged), int(n_iter)
+        self.lower_bound, self.n_fitted = float(lower_bound), int(n_fitted)
+        self._log_coef = None                                           # f64 [K] on the device, made on first use
+
+    @classmethod
+    def fit(cls, x: torch.Tensor, n_components: int = 10, reg_covar: float = 1e-6, tol: float = 1e-3, max_iter: int = 100,
+            seed: int = 0, init_idx=None) -> "GaussianMixturePrior":
+        """EM on x f32 [N, D] on the device, possibly a strided view: fit on the ``mu`` columns of ``encode_dataset``'s
+        output, ``mulv[:, :L]`` (no copy is made).  Fitting on sampled z instead is out of scope.
+
+        Initialisation: ``init_idx`` (K distinct row numbers; default ``np.random.default_rng(seed).choice(N, K,
+        replace=False)``) names the rows that become the means; weights 1 / K; every precision diag(1 / (var + reg_covar))
+        with var the global per-column variance (one ``ops.gmm_moments`` call with K = 1, resp = 1).
+        Loop: exactly scikit-learn's ``GaussianMixture.fit`` -- E-step (``ops.gmm_log_resp``), lower_bound = mean
+        log-likelihood, M-step (``ops.gmm_moments`` around the current means, then the K small D x D steps in numpy f64 on
+        the host: weights, means, Sigma_k + reg_covar I, Cholesky, triangular inverse, log_coef, cdf -- the precedent of
+        ``metrics.frechet_distance``), stop when |change of lower_bound| < tol; nk gets + 10 eps.  Three launches and ONE
+        host sync per iteration.  Not converged after max_iter: ``converged`` is False, no warning.
+        RuntimeError: N < K, a bad init_idx, a failed Cholesky or a non-finite lower_bound (a NaN latent, a constant
+        column with reg_covar = 0): the message names reg_covar."""
+        if not x.is_cuda:
+            raise RuntimeError("GaussianMixturePrior.fit needs the latents on the MI355X ('cuda'); there is no CPU path")
+        if x.dim() != 2 or x.dtype != torch.float32:
+            raise RuntimeError("GaussianMixturePrior.fit: x must be f32 [N, D]")
+        N, D = x.shape
+        K = int(n_components)
+        if not (1 <= K <= ops.GMM_MAX_K and 1 <= D <= ops.GMM_MAX_D):
+            raise RuntimeError(f"GaussianMixturePrior.fit: needs 1 <= n_components <= {ops.GMM_MAX_K} and 1 <= D <= "
+                               f"{ops.GMM_MAX_D}")
+        if N < K:
+            raise RuntimeError(f"GaussianMixturePrior.fit: {N} rows cannot initialise {K} components (reg_covar does not "
+                               f"help here: give more rows or fewer components)")
+        if init_idx is None:
+            init_idx = np.random.default_rng(seed).choice(N, K, replace=False)
+        idx = np.asarray(init_idx)
+        if (idx.ndim != 1 or idx.size != K or not np.issubdtype(idx.dtype, np.integer) or idx.min() < 0 or idx.max() >= N
+                or np.unique(idx).size != K):
+            raise RuntimeError(f"GaussianMixturePrior.fit: init_idx must be {K} distinct row numbers in [0, {N})")
+        if max_iter < 1:
+            raise RuntimeError("GaussianMixturePrior.fit: max_iter must be >= 1")
+        dev = x.device
+        rows = x[torch.as_tensor(idx, dtype=torch.int64, device=dev)].double().contiguous()      # [K, D]
+        nk, s1, s2, _ = ops.gmm_moments(x, rows[:1].contiguous(), torch.ones(N, 1, dtype=torch.float64, device=dev))
+        nk0 = float(nk.item())
+        delta = s1[0].cpu().numpy() / nk0
+        var = np.diagonal(s2[0].cpu().numpy()) / nk0 - delta * delta
+        with np.errstate(divide="ignore", invalid="ignore"):
+            prec = 1.0 / (var + reg_covar)
+        if not np.all(np.isfinite(prec)) or np.any(prec <= 0.0):
+            raise RuntimeError(f"GaussianMixturePrior.fit: a latent column has no finite positive variance (a NaN, an "
+                               f"infinity or a constant column); increase reg_covar (now {reg_covar})")
+        weights = np.full(K, 1.0 / K)
+        means = rows.cpu().numpy()
+        log_coef = np.log(weights) + np.log(np.sqrt(prec)).sum() - 0.5 * D * np.log(2.0 * np.pi)
+        up = lambda a: torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float64).to(dev)      # noqa: E731
+        d_means, d_prec, d_coef = rows, up(np.tile(np.diag(np.sqrt(prec)), (K, 1, 1))), up(log_coef)
+        lower, converged, n_iter, p = -np.inf, False, 0, None
+        for n_iter in range(1, int(max_iter) + 1):
+            prev = lower
+            _, ln, resp = ops.gmm_log_resp(x, d_means, d_prec, d_coef)
+            nk, s1, s2, ll = ops.gmm_moments(x, d_means, resp, ln)
+            flat = torch.cat([ll, nk, s1.reshape(-1), s2.reshape(-1)]).cpu().numpy()               # the one host sync
+            lower = float(flat[0]) / N
+            if not np.isfinite(lower):
+                raise RuntimeError(f"GaussianMixturePrior.fit: the log-likelihood is not finite in iteration {n_iter} (a "
+                                   f"NaN or infinite latent, or a collapsed component); check the latents or increase "
+                                   f"reg_covar (now {reg_covar})")
+            nk_h = flat[1:1 + K] + _GMM_TINY
+            s1_h = flat[1 + K:1 + K + K * D].reshape(K, D)
+            s2_h = flat[1 + K + K * D:].reshape(K, D, D)
+            weights = nk_h / N
+            weights = weights / weights.sum()
+            delta = s1_h / nk_h[:, None]
+            means = means + delta
+            cov = s2_h / nk_h[:, None, None] - delta[:, :, None] * delta[:, None, :]
+            cov = 0.5 * (cov + cov.transpose(0, 2, 1))
+            cov[:, np.arange(D), np.arange(D)] += reg_covar
+            p = _gmm_host_step(weights, means, cov, reg_covar)
+            d_means, d_prec, d_coef = up(p["means"]), up(p["prec_chol"]), up(p["log_coef"])
+            if abs(lower - prev) < tol:
+                converged = True
+                break
+        out = cls(*(up(p[k]) for k in _GMM_KEYS), converged=converged, n_iter=n_iter, lower_bound=lower, n_fitted=N)
+        out._log_coef = d_coef
+        return out
+
+    def _state(self, need: bool):
+        if not need:
+            return None
+        ns = ops.default_noise(self.means.device)
+        ns.advance()
+        return ns.state
+
+    def sample(self, n: int, u: Optional[torch.Tensor] = None, eps: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """n draws -> f32 [n, D].  u f64 [n] picks the component (np.searchsorted(cdf, u, side="right")), eps f32 [n, D] is
+        the normal draw of z = mean_k + L_k eps; by default both come from the device stream, which advances by one step
+        per call."""
+        _, z32, _ = ops.gmm_sample(self.cdf, self.means, self.cov_chol, n, u, eps, self._state(u is None or eps is None))
+        return z32
+
+    def sample_z(self, n: int, dtype_of=None, u=None, eps=None, return_comp: bool = False):
+        """n draws in ONE launch, in the input layout of the decoder ``dtype_of`` ([n, 1, 1, ZP] in its engine dtype, pad
+        columns zero; f32 when dtype_of is None).  return_comp: -> (z, comp int32 [n])."""
+        D = self.latent_dim
+        dt = G.F32 if dtype_of is None else dtype_of._dt
+        nz = D if dtype_of is None else dtype_of.nz
+        if nz != D:
+            raise RuntimeError(f"GaussianMixturePrior.sample_z: the decoder takes nz = {nz} inputs, the prior has {D} "
+                               f"dimensions")
+        comp, _, z = ops.gmm_sample(self.cdf, self.means, self.cov_chol, n, u, eps, self._state(u is None or eps is None),
+                                    want_comp=return_comp, want_z32=False, z=(G.padc(nz, dt), dt))
+        return (z, comp) if return_comp else z
+
+    def score_samples(self, x: torch.Tensor) -> torch.Tensor:
+        """log p(x) of every row of x f32 [N, D] (device) -> f64 [N]: the E-step's log_norm."""
+        if x.dim() != 2 or x.shape[1] != self.latent_dim:
+            raise RuntimeError(f"GaussianMixturePrior.score_samples: x must be [N, {self.latent_dim}]")
+        if self._log_coef is None:                                      # a loaded prior: K values, once, on the host
+            log_det = np.log(np.diagonal(self.prec_chol.cpu().numpy(), axis1=1, axis2=2)).sum(axis=1)
+            coef = np.log(self.weights.cpu().numpy()) + log_det - 0.5 * self.latent_dim * np.log(2.0 * np.pi)
+            self._log_coef = torch.as_tensor(coef, dtype=torch.float64).to(self.means.device)
+        _, ln, _ = ops.gmm_log_resp(x, self.means, self.prec_chol, self._log_coef, want_resp=False)
+        return ln
+
+    def score(self, x: torch.Tensor) -> float:
+        """Mean log-likelihood per row (scikit-learn's GaussianMixture.score); one host sync."""
+        ln = self.score_samples(x)
+        # The sum of the N values is vg_gmm_moments' loglik_sum -- f64, fixed order, the same bits on every call, what fit's
+        # lower_bound is made of -- asked of ONE column with K = 1, so the moments that come with it cost next to nothing.
+        col = x[:, :1]
+        ones = torch.ones(x.shape[0], 1, dtype=torch.float64, device=x.device)
+        ll = ops.gmm_moments(col, torch.zeros(1, 1, dtype=torch.float64, device=x.device), ones, ln)[3]
+        return float(ll.item()) / x.shape[0]
+
+    def state_dict(self) -> Dict[str, torch.Tensor]:
+        """Plain tensors: save a fitted prior beside the decoder checkpoint and sample without the data set."""
+        sd = {k: getattr(self, k) for k in _GMM_KEYS}
+        sd.update(converged=torch.tensor(self.converged), n_iter=torch.tensor(self.n_iter),
+                  lower_bound=torch.tensor(self.lower_bound, dtype=torch.float64), n_fitted=torch.tensor(self.n_fitted))
+        return sd
+
+    def load_state_dict(self, sd: Dict[str, torch.Tensor]) -> "GaussianMixturePrior":
+        """Replace this prior's parameters by those of ``sd`` (a ``state_dict()``, e.g. from torch.load), moved to its device."""
+        dev = self.means.device
+        self.__init__(*(sd[k].to(dev) for k in _GMM_KEYS), converged=bool(sd["converged"]), n_iter=int(sd["n_iter"]),
+                      lower_bound=float(sd["lower_bound"]), n_fitted=int(sd["n_fitted"]))
+        return self
+
+    @classmethod
+    def from_state_dict(cls, sd: Dict[str, torch.Tensor], device="cuda") -> "GaussianMixturePrior":
+        return cls(*(sd[k].to(device) for k in _GMM_KEYS), converged=bool(sd["converged"]), n_iter=int(sd["n_iter"]),
+                   lower_bound=float(sd["lower_bound"]), n_fitted=int(sd["n_fitted"]))
+
+
 def _device_of(decoder, what: str):
     dev = next(decoder.parameters()).device
     if dev.type != "cuda":
@@ -175,7 +395,8 @@ def _normal_z(decoder, b: int, eps: Optional[torch.Tensor]) -> torch.Tensor:
 
 
 @torch.no_grad()
-def evaluate_generation(decoder, val_loader: Iterable[torch.Tensor], prior: Optional[LatentPrior] = None,
+def evaluate_generation(decoder, val_loader: Iterable[torch.Tensor],
+                        prior: Optional[Union[LatentPrior, GaussianMixturePrior]] = None,
                         noise_fn=None, feature_fn=None, k: int = 3, real_stats=None, kid_subsets: Optional[int] = None,
                         kid_subset_size: int = 1000, kid_seed: int = 0) -> Dict[str, float]:
     """The generation-evaluation loops of the reference:
@@ -183,13 +404,15 @@ def evaluate_generation(decoder, val_loader: Iterable[torch.Tensor], prior: Opti
         decoder.eval()                                                                  (main_vae.py:476 / :546)
         for real in val_loader:   b = real.size(0)
             prior given  (:482-489): mu, logvar ~ histogram prior; z = mu + exp(logvar / 2) * randn; fake = G(z)
+            mixture prior (a GaussianMixturePrior; not in the reference): z ~ the fitted mixture; fake = G(z)
             prior=None   (:552-554): z = randn(b, latent); fake = G(z)
             ssim.update((fake + 1) / 2, (real + 1) / 2)                                 (:492-496 / :557-561)
         ssim.compute()                                                   (mean over all images, ragged batch weighted)
 
     val_loader yields device batches [b,C,S,S] in [-1,1] (data.DeviceLoader).  noise_fn(i, b) injects the draws of batch
     i (parity tests): with a prior it returns (u, v, eps) -- f64 [b,2L], f64 [b,2L], f32 [b,L], see LatentPrior.sample_z --
-    and without one the f32 [b, nz] z itself; by default everything is drawn on the device.  SSIM: torchmetrics recipe,
+    with a GaussianMixturePrior (u, eps) -- f64 [b], f32 [b,L], see GaussianMixturePrior.sample_z -- and without a prior
+    the f32 [b, nz] z itself; by default everything is drawn on the device.  SSIM: torchmetrics recipe,
     parity unpinned (the package is not installed), as in denoise.py.  Deviation: the logvar clamp of sample_z.
     Accumulation stays on the device; ONE host sync at the end of the pass.  Returns python numbers: ssim, samples,
     batches.
@@ -221,7 +444,10 @@ def evaluate_generation(decoder, val_loader: Iterable[torch.Tensor], prior: Opti
         real = real.contiguous()
         b = real.shape[0]
         inj = noise_fn(i, b) if noise_fn is not None else None
-        if prior is not None:
+        if isinstance(prior, GaussianMixturePrior):
+            u, eps = inj if inj is not None else (None, None)
+            z = prior.sample_z(b, decoder, u, eps)
+        elif prior is not None:
             u, v, eps = inj if inj is not None else (None, None, None)
             z = prior.sample_z(b, decoder, u, v, eps)
         else:
@@ -250,13 +476,15 @@ def evaluate_generation(decoder, val_loader: Iterable[torch.Tensor], prior: Opti
 
 
 @torch.no_grad()
-def sample_images(decoder, z: Optional[torch.Tensor] = None, n: int = 64, prior: Optional[LatentPrior] = None,
+def sample_images(decoder, z: Optional[torch.Tensor] = None, n: int = 64,
+                  prior: Optional[Union[LatentPrior, GaussianMixturePrior]] = None,
                   grid_cols: int = 0) -> torch.Tensor:
     """Generated images as uint8 on the device ((fake + 1) / 2 * 255, clamped and truncated: main_vae.py:492,498-499), the
     decoder in eval mode:
         z=None, prior=None: n images from z ~ N(0, I)                        (sample_vae_decoder, main_vae.py:364-366)
         z f32 [n, nz, 1, 1]: the images of that z -- the per-epoch ``decoder(fixed_noise)`` picture, vaegan_code.py:40, 209-216
         prior:              n images from the histogram prior                (sample_vae, main_vae.py:619-626)
+                            or from a GaussianMixturePrior (any object with ``sample_z(n, decoder)``)
     grid_cols == 0: [n, C, S, S]; grid_cols > 0: ONE [rows*S, grid_cols*S, C] picture, image i at tile (i // grid_cols,
     i % grid_cols), ready for ``PIL.Image.fromarray(out.cpu().numpy())``."""
     decoder.eval()

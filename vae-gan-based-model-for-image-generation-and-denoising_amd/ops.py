@@ -1012,6 +1012,104 @@ def _feature_rows(x, what: str, name: str = "x"):
     return N, D, stride
 
 
+# draw ids of the Gaussian-mixture prior (include/vaegan_hip.h "Gaussian-mixture prior")
+DRAW_GMM_U, DRAW_GMM_EPS = 40, 41
+GMM_MAX_D, GMM_MAX_K = 256, 64
+
+
+def _gmm_params(what, K, D, **tensors):
+    """The f64 parameter tensors of a mixture: on the device, contiguous, of the stated shape."""
+    for name, (t, shape) in tensors.items():
+        if not t.is_cuda:
+            raise RuntimeError("vaegan_amd ops need tensors on the MI355X (cuda) device; there is no CPU path")
+        if t.dtype != torch.float64 or tuple(t.shape) != shape or not t.is_contiguous():
+            raise RuntimeError(f"{what}: {name} must be a contiguous f64 tensor of shape {list(shape)}")
+    if not (1 <= K <= GMM_MAX_K and 1 <= D <= GMM_MAX_D):
+        raise RuntimeError(f"{what}: needs 1 <= K <= {GMM_MAX_K} components and 1 <= D <= {GMM_MAX_D} dimensions")
+
+
+def gmm_log_resp(x, mean, prec_chol, log_coef, want_log_prob=False, want_log_norm=True, want_resp=True):
+    """E-step of a full-covariance Gaussian mixture on the device (vg_gmm_log_resp).  x f32 [N,D] (may be a view whose
+    rows are further apart than D); mean f64 [K,D], prec_chol f64 [K,D,D] (upper triangular, scikit-learn's
+    precisions_cholesky_), log_coef f64 [K].  -> (log_prob f64 [N,K], log_norm f64 [N], resp f64 [N,K]), None for what
+    was not asked for.  One launch, no host sync."""
+    N, D, stride = _feature_rows(x, "gmm_log_resp")
+    if N < 1:
+        raise RuntimeError("gmm_log_resp: x must hold at least one row")
+    K = mean.shape[0] if mean.dim() == 2 else 0
+    _gmm_params("gmm_log_resp", K, D, mean=(mean, (K, D)), prec_chol=(prec_chol, (K, D, D)), log_coef=(log_coef, (K,)))
+    if not (want_log_prob or want_log_norm or want_resp):
+        raise RuntimeError("gmm_log_resp: ask for at least one output")
+    dev = x.device
+    lp = torch.empty(N, K, dtype=torch.float64, device=dev) if want_log_prob else None
+    ln = torch.empty(N, dtype=torch.float64, device=dev) if want_log_norm else None
+    rs = torch.empty(N, K, dtype=torch.float64, device=dev) if want_resp else None
+    L.check(L.load().vg_gmm_log_resp(x.data_ptr(), N, D, stride, K, mean.data_ptr(), prec_chol.data_ptr(),
+                                     log_coef.data_ptr(), L.ptr(lp), L.ptr(ln), L.ptr(rs), L.stream_ptr()),
+            "vg_gmm_log_resp")
+    return lp, ln, rs
+
+
+def gmm_moments(x, shift, resp, log_norm=None):
+    """M-step sums of a Gaussian mixture on the device (vg_gmm_moments), d = x - shift_k: nk f64 [K] = sum r, s1 f64 [K,D]
+    = sum r d, s2 f64 [K,D,D] = sum r d d^T, loglik f64 [1] = sum log_norm (None without log_norm).  x f32 [N,D] (may be
+    a strided view), shift f64 [K,D], resp f64 [N,K], log_norm f64 [N].  Deterministic; two launches, no host sync.
+    -> (nk, s1, s2, loglik)."""
+    N, D, stride = _feature_rows(x, "gmm_moments")
+    if N < 1:
+        raise RuntimeError("gmm_moments: x must hold at least one row")
+    K = shift.shape[0] if shift.dim() == 2 else 0
+    _gmm_params("gmm_moments", K, D, shift=(shift, (K, D)), resp=(resp, (N, K)))
+    if log_norm is not None:
+        _gmm_params("gmm_moments", K, D, log_norm=(log_norm, (N,)))
+    lib = L.load()
+    nbytes = _ws_query(lib.vg_gmm_moments_ws_bytes(N, D, K), "vg_gmm_moments_ws_bytes")
+    dev = x.device
+    nk = torch.empty(K, dtype=torch.float64, device=dev)
+    s1 = torch.empty(K, D, dtype=torch.float64, device=dev)
+    s2 = torch.empty(K, D, D, dtype=torch.float64, device=dev)
+    ll = torch.empty(1, dtype=torch.float64, device=dev) if log_norm is not None else None
+    ws = WS.get("gmm", nbytes, dev)
+    L.check(lib.vg_gmm_moments(x.data_ptr(), N, D, stride, K, shift.data_ptr(), resp.data_ptr(), L.ptr(log_norm),
+                               nk.data_ptr(), s1.data_ptr(), s2.data_ptr(), L.ptr(ll), ws.data_ptr(), ws.numel() * 4,
+                               L.stream_ptr()), "vg_gmm_moments")
+    return nk, s1, s2, ll
+
+
+def gmm_sample(cdf, mean, cov_chol, n, u=None, eps=None, state=None, want_comp=False, want_z32=True, z=None):
+    """n draws from a Gaussian mixture (vg_gmm_sample).  cdf f64 [K] (cumulative weights), mean f64 [K,D], cov_chol f64
+    [K,D,D] (lower factors).  u: f64 [n] picks the component, eps: f32 [n,D] is the normal draw; whatever is None is drawn
+    in the kernel from state = int64[2] {seed, counter}.  z: None or (ZP, dtype) -> also the Generator's input [n,1,1,ZP].
+    -> (comp int32 [n] or None, z32 f32 [n,D] or None, z or None).  One launch, no host sync."""
+    _need_cuda(cdf, mean, cov_chol, u, eps, state)
+    n = int(n)
+    K, D = (mean.shape[0], mean.shape[1]) if mean.dim() == 2 else (0, 0)
+    _gmm_params("gmm_sample", K, D, cdf=(cdf, (K,)), mean=(mean, (K, D)), cov_chol=(cov_chol, (K, D, D)))
+    if n < 1:
+        raise RuntimeError("gmm_sample: n must be >= 1")
+    if u is not None and (u.dtype != torch.float64 or u.numel() != n):
+        raise RuntimeError("gmm_sample: u must be f64 [n]")
+    if eps is not None and (eps.dtype != torch.float32 or eps.numel() != n * D):
+        raise RuntimeError("gmm_sample: eps must be f32 [n,D]")
+    if state is not None and (state.dtype != torch.int64 or state.numel() != 2):
+        raise RuntimeError("gmm_sample: state must be int64[2] = {seed, counter}")
+    if state is None and (u is None or eps is None):
+        raise RuntimeError("gmm_sample: whatever is not injected (u, eps) needs the generator state")
+    if not (want_comp or want_z32 or z is not None):
+        raise RuntimeError("gmm_sample: ask for at least one output")
+    dev = mean.device
+    comp = torch.empty(n, dtype=torch.int32, device=dev) if want_comp else None
+    z32 = torch.empty(n, D, dtype=torch.float32, device=dev) if want_z32 else None
+    ZP, dtype, zt = 0, F32, None
+    if z is not None:
+        ZP, dtype = z
+        zt = empty_act((n, 1, 1, ZP), dtype, dev)
+    L.check(L.load().vg_gmm_sample(cdf.data_ptr(), mean.data_ptr(), cov_chol.data_ptr(), K, D, n, L.ptr(u), L.ptr(eps),
+                                   L.ptr(state), L.ptr(comp), L.ptr(z32), L.ptr(zt), ZP, dtype, L.stream_ptr()),
+            "vg_gmm_sample")
+    return comp, z32, zt
+
+
 def feat_stats_accum(x, sum, outer):
     """FID's running statistics on the device (vg_feat_stats_accum): sum f64 [D] += column sums of x, outer f64 [D,D] +=
     x^T x, every product and addition in f64 on the exactly converted f32 rows of x f32 [n,D] (n >= 0; x may be a view
