@@ -48,7 +48,7 @@ extern "C" {
 #define VG_ACT_LRELU   2   /* nn.LeakyReLU(slope)    main_vae.py:25, gan_code.py:62-82 */
 #define VG_ACT_TANH    3   /* nn.Tanh()              gan_code.py:50 (vg_tnconv epilogue only) */
 
-#define VG_ABI_VERSION 28  /* 2: vg_pack_desc.tile_start, SyncBN / WGAN / data-path entry points; 3: in-kernel noise (vg_*_rng);
+#define VG_ABI_VERSION 29  /* 2: vg_pack_desc.tile_start, SyncBN / WGAN / data-path entry points; 3: in-kernel noise (vg_*_rng);
                              4: vg_bn_finalize_act_forward, vg_bn_backward_finalize_apply;
                              7: vg_bce_pair_forward_backward;
                              8: vg_head_backward; round-3 prune -- the opt-in experiments of ABI 5 / 6 that measured slower (input prologue of
@@ -74,7 +74,8 @@ extern "C" {
                              25: differentiable augmentation: vg_diffaug_params, vg_diffaug_forward, vg_diffaug_backward (+ _ws_floats);
                              26: learning-rate schedules and decoupled weight decay: vg_lr_sched, vg_step_prologue_sched, vg_adamw_apply;
                              27: vg_tnconv_plan / vg_tn_plan: the tiling vg_tnconv launches, as a host-only query;
-                             28: Gaussian-mixture prior: vg_gmm_log_resp, vg_gmm_moments (+ _ws_bytes), vg_gmm_sample */
+                             28: Gaussian-mixture prior: vg_gmm_log_resp, vg_gmm_moments (+ _ws_bytes), vg_gmm_sample;
+                             29: tiled denoising of images larger than the network: vg_tile_gather, vg_tile_blend */
 int vg_abi_version(void);
 /* The library reads its optional kernel-selection switches (VG_* environment variables, DESIGN.md "Runtime switches")
  * ONCE, when it is loaded; nothing on a launch path calls getenv.  A process that changes one of them afterwards
@@ -1171,6 +1172,51 @@ int vg_diffaug_forward(const void* in, void* out, const float* params, int N, in
                        int cut_w, float* ws, int64_t ws_capacity, int dtype, void* stream);
 int vg_diffaug_backward(const void* in, void* out, const float* params, int N, int PB, int H, int W, int C, int CP, int cut_h,
                         int cut_w, float* ws, int64_t ws_capacity, int dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Tiled denoising (not in the reference, whose networks only take S x S images; ABI 29; csrc/tiling.hip; host plan: tiling.py):
+ * an H x W image is cut into ny x nx overlapping S x S tiles, the tiles go through Encoder -> reparameterise -> Generator in
+ * batches, and the reconstructions are blended back with a separable window.  Tile t of the global list N * ny * nx belongs to
+ * image n = t / (ny nx) and has k = t % (ny nx), ky = k / nx, kx = k % nx, origin (oy[ky], ox[kx]).  No padding: every tile lies
+ * inside the image (0 <= oy <= H - S, 0 <= ox <= W - S).
+ *
+ * Tables (device memory, 4-byte aligned, uploaded once per plan): oy int32 [ny], ox int32 [nx]; per axis and coordinate p the
+ * contiguous range of covering tiles first[p], count[p] (int32 [H] / [W]) and their coefficients coef f32 [H][wy] / [W][wx]
+ * (row p, slot j belongs to tile first[p] + j; unused slots 0), 1 <= wy, wx <= VG_TILE_MAX_COVER.  The host normalises:
+ * coef[p][j] = w[p - o_k] / sum_k w[p - o_k] in f64, rounded once to f32.  The kernels never divide.
+ *
+ * vg_tile_gather: tiles [t0, t0 + B) as the Encoder's input, out [B][S][S][CP] in dtype (VG_F32 | VG_BF16), pad channels zero:
+ * the layout vg_nchw_to_nhwc writes.  Exactly one source: src_u8 [N][H][W][C], the resident set, with exactly
+ * vg_gather_normalize_u8's arithmetic (u/255 - 0.5)/0.5; or src_f32 [N][C][H][W], copied (rounded once to bf16).  A chunk may
+ * straddle two images and may be shorter than the engine batch.  One launch.
+ *
+ * vg_tile_blend: out f32 [N][C][H][W] from tiles f32 [N ny nx][C][S][S] (what vg_nhwc_to_nchw writes per chunk, into slices of
+ * one buffer), in gather form -- each output element sums its covering tiles, so there are no atomics, no zero-fill, and the
+ * result is the same bits on every launch:
+ *     inner_ky     = ((0 + cx_0 * r_0) + cx_1 * r_1) + ...      kx = first_x[x] + j ascending, cx_j = coef_x[x][j],
+ *                                                               r_j = tiles[n (ny nx) + ky nx + kx][c][y - oy[ky]][x - ox[kx]]
+ *     out[n,c,y,x] = ((0 + cy_0 * inner_0) + cy_1 * inner_1) + ...   ky = first_y[y] + j ascending, cy_j = coef_y[y][j]
+ * all f32, every product and sum rounded on its own (no contraction into an fma).  One launch; stores are 16-byte vectors
+ * aligned to the output row where W % 4 == 0 and out is 16-byte aligned, single floats otherwise; tile rows are read at
+ * whatever x origin they have.
+ *
+ * Table safety.  The host cannot see the tables at launch, so the kernels range-check every index read from them in integer
+ * arithmetic before an address is formed from it: count is clamped to [0, width], a tile index outside [0, ny) / [0, nx) or a
+ * local coordinate outside [0, S) drops that term (blend), an origin outside the image writes a zero tile (gather).  No content
+ * of a table can cause an out-of-range access.
+ *
+ * Checked on the host before anything is launched.  VG_EINVAL: a NULL pointer (gather: not exactly one source); N, C, S, ny, nx
+ * or B < 1; H < S or W < S; ny > H - S + 1 or nx > W - S + 1; N ny nx or N C >= 2^31; S > 32768, H > 262140 or
+ * W > 16776960 (the launch grids); t0 < 0 or t0 + B > N ny nx; CP < C; wy or wx
+ * outside [1, VG_TILE_MAX_COVER]; tiles == out.  VG_ENOSUP: a dtype other than f32 / bf16.  VG_EALIGN: a pixel that is not whole
+ * 16-byte units (CP % 4 for f32, CP % 8 for bf16), the gather's out not 16-byte aligned, an f32 / int32 pointer not 4-byte aligned.
+ * ---------------------------------------------------------------------------------------- */
+#define VG_TILE_MAX_COVER 8     /* most tiles covering one coordinate of an axis: ceil(S / stride) + 1 for the plans of tiling.py */
+int vg_tile_gather(const uint8_t* src_u8, const float* src_f32, int N, int C, int H, int W, int S, int ny, int nx,
+                   const int32_t* oy, const int32_t* ox, int64_t t0, int B, void* out, int CP, int dtype, void* stream);
+int vg_tile_blend(const float* tiles, float* out, int N, int C, int H, int W, int S, int ny, int nx,
+                  const int32_t* oy, const int32_t* ox, const int32_t* first_y, const int32_t* count_y, const float* coef_y,
+                  int wy, const int32_t* first_x, const int32_t* count_x, const float* coef_x, int wx, void* stream);
 
 #ifdef __cplusplus
 }

@@ -20,7 +20,9 @@ trainers.  Differentiable augmentation of the Discriminator's inputs (not in the
 ``augment=`` on the three adversarial trainers.  Learning-rate schedules and decoupled weight decay (not in the reference):
 ``LRSchedule`` (``Adam(..., lr_schedule=)``: warm-up and linear / cosine / exponential / step decay, evaluated on the device from
 the step count, so a captured iteration replays a moving rate) and ``AdamW``.  Data path (dataset_code.py): ``data`` -- ``ResidentImages`` (``resized``: Resize +
-CenterCrop on the device), ``resample_coeffs``, ``resize_geometry``.
+CenterCrop on the device), ``resample_coeffs``, ``resize_geometry``.  Tiled denoising of images larger than the networks
+(not in the reference): ``denoise_tiled``, ``tiled_denoise_eval``, ``tiled_test_epoch`` and ``tiling`` -- ``tile_plan`` /
+``TilePlan``: overlapping S x S tiles cut and blended back on the device with a separable window.
 """
 from . import data  # noqa: F401
 from . import geometry  # noqa: F401
@@ -30,7 +32,10 @@ from .data import ResidentImages, resample_coeffs, resize_geometry
 from .augment import DiffAugment
 from .ddp import GradReducer
 from .ema import EMA
-from .denoise import denoise_eval, paired_test_epoch, validation_epoch
+from . import tiling  # noqa: F401
+from .denoise import (denoise_eval, denoise_tiled, paired_test_epoch, tiled_denoise_eval, tiled_test_epoch,
+                      validation_epoch)
+from .tiling import TilePlan, tile_plan
 from .graphed import graphed
 from .latent import GaussianMixturePrior, LatentPrior, encode_dataset, evaluate_generation, sample_images
 from .metrics import FeatureStats, encoder_features, frechet_distance, kernel_distance, precision_recall
@@ -46,4 +51,5 @@ __all__ = ["ConvBlock", "Encoder", "Generator", "Discriminator", "weights_init",
            "latent", "LatentPrior", "GaussianMixturePrior", "encode_dataset", "evaluate_generation", "sample_images",
            "ResidentImages", "resample_coeffs", "resize_geometry",
            "EMA", "clip_grad_norm_", "DiffAugment", "AdamW", "LRSchedule",
+           "tiling", "TilePlan", "tile_plan", "denoise_tiled", "tiled_denoise_eval", "tiled_test_epoch",
            "metrics", "FeatureStats", "frechet_distance", "precision_recall", "encoder_features", "kernel_distance"]

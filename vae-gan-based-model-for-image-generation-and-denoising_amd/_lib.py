@@ -20,8 +20,9 @@ VG_EMA_MAX = 4
 VG_GNORM_MAX = 4
 VG_GNORM_PARTS = 512
 VG_PROLOGUE_MAX = 4
+VG_TILE_MAX_COVER = 8
 VG_LRS_CONST, VG_LRS_LINEAR, VG_LRS_COSINE, VG_LRS_EXP, VG_LRS_STEP = 0, 1, 2, 3, 4
-ABI_VERSION = 28
+ABI_VERSION = 29
 
 VG_ENOSUP = -3
 _ERR = {-1: "VG_EINVAL (bad shape/size/flag)", -2: "VG_EALIGN (16-byte contract violated)",
@@ -215,6 +216,8 @@ SIGNATURES = {
     "vg_gmm_moments_ws_bytes": (c_int64, [_L, _I, _I]),
     "vg_gmm_moments": (c_int, [_P, _L, _I, _L, _I, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P]),
     "vg_gmm_sample": (c_int, [_P, _P, _P, _I, _I, _L, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
+    "vg_tile_gather": (c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _L, _I, _P, _I, _I, _P]),
+    "vg_tile_blend": (c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _P]),
     "vg_resize_u8_lds_bytes": (c_int64, [_I, _I, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I]),
     "vg_resize_u8_band": (c_int, [_I, _I, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I]),
     "vg_resize_u8": (c_int, [_P, _L, _I, _I, _I, _P, _I, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _P, _I, _I, _I, _P]),

@@ -12,6 +12,7 @@ import torch
 
 from . import geometry as G
 from . import ops
+from . import tiling
 from .metrics import FeaturePass
 
 
@@ -245,3 +246,143 @@ def paired_test_epoch(encoder, decoder, loader: Iterable, n_samples: Optional[in
                         "psnr_hole" + suffix: psnr(m_hole), "psnr_valid" + suffix: psnr(m_valid),
                         "hole_fraction" + suffix: n_hole / (n_hole + n_valid)})
     return out
+
+
+def _psnr(mse: float) -> float:
+    mse01 = mse / 4.0                                                      # ((a+1)/2 - (b+1)/2)^2 = (a-b)^2 / 4
+    return float("inf") if mse01 == 0 else 10.0 * math.log10(1.0 / mse01)
+
+
+@torch.no_grad()
+def denoise_tiled(encoder, decoder, images, *, stride: Optional[int] = None, window: str = "hann", batch: int = 128,
+                  sample: bool = True, eps_z: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Denoise images LARGER than the networks (not in the reference, whose networks take S x S only): cut every image into
+    overlapping S x S tiles (``tiling.tile_plan``: origins every ``stride``, default S // 2, the last tile flush with the
+    edge, no padding), run Encoder -> reparameterise -> Generator on chunks of at most ``batch`` tiles, and blend the
+    reconstructions with a separable ``window`` ("hann" | "tri" | "box") whose normalised coefficients the plan holds.
+    images: f32 [N,C,H,W] on the MI355X in [-1,1], or the resident uint8 set (``data.ResidentImages``, or a uint8 [N,H,W,C]
+    tensor / slice of one), normalised as ``ResidentImages.batch`` does.  Returns f32 [N,C,H,W].
+    Both networks are put in eval mode (as validation_epoch does): BatchNorm then does not depend on how the tiles fall into
+    chunks.  sample=True draws the reparameterisation noise per tile from the device noise stream (the reference's behaviour
+    per image); sample=False uses z = mu; eps_z f32 [N * ny * nx, latent_dim] injects the draws (tile t = (n * ny + ky) * nx + kx).
+    Per chunk: ops.tile_gather -> the two engines -> ops.nhwc_to_nchw(tanh) into its slice of the tile buffer; then ONE
+    ops.tile_blend launch.  No host synchronisation inside."""
+    if isinstance(images, torch.Tensor):
+        src = images
+    elif isinstance(getattr(images, "images", None), torch.Tensor):
+        src = images.images
+    else:
+        raise RuntimeError("denoise_tiled: images must be a device tensor or a resident uint8 set")
+    if not src.is_cuda:
+        raise RuntimeError("denoise_tiled needs the images on the MI355X ('cuda'); there is no CPU path")
+    if src.dim() != 4 or src.dtype not in (torch.uint8, torch.float32):
+        raise RuntimeError("denoise_tiled: images must be float32 [N,C,H,W] or uint8 [N,H,W,C]")
+    src = src.contiguous()
+    u8 = src.dtype == torch.uint8
+    N, H, W, C = src.shape if u8 else (src.shape[0], src.shape[2], src.shape[3], src.shape[1])
+    S, dt, L = encoder._img, encoder._dt, encoder.latent_dim
+    if decoder.img_size != S or decoder._dt != dt or decoder.nc != C:
+        raise RuntimeError("denoise_tiled: encoder, decoder and images disagree on the tile size, dtype or channel count")
+    if int(batch) < 1 or N < 1:
+        raise RuntimeError("denoise_tiled: batch and the number of images must be at least 1")
+    plan = tiling.cached_plan(H, W, S, stride, window)
+    T = N * plan.tiles_per_image
+    dev = src.device
+    if eps_z is not None:
+        if not eps_z.is_cuda or eps_z.dtype != torch.float32 or tuple(eps_z.shape) != (T, L):
+            raise RuntimeError(f"denoise_tiled: eps_z must be a device f32 [{T}, {L}] tensor (one row per tile)")
+        eps_z = eps_z.contiguous()
+    elif sample:
+        ns = ops.default_noise(dev)                      # HIP Philox draws keyed by torch's device seed
+        ns.advance()
+        eps_z = ns.randn((T, L), 1)
+    else:
+        eps_z = ops.zeros_f32(T * L, dev).view(T, L)     # z = mu
+    encoder.eval(), decoder.eval()
+    CP, ZP = G.padc(C, dt), G.padc(decoder.nz, dt)
+    tiles = torch.empty(T, C, S, S, dtype=torch.float32, device=dev)
+    for t0 in range(0, T, int(batch)):
+        b = min(int(batch), T - t0)
+        x = ops.tile_gather(src, plan, t0, b, CP, dt)
+        mulv, _ = encoder._engine.forward(x, b, False, keep=False)
+        z, _ = ops.reparam_forward(mulv.view(b, -1), eps_z[t0:t0 + b], L, ZP, dt)
+        pre, _ = decoder._engine.forward(z, b, False, keep=False)
+        ops.nhwc_to_nchw(pre, C, dt, apply_tanh=True, out=tiles[t0:t0 + b])
+    return ops.tile_blend(tiles, plan)
+
+
+def _tile_count(encoder, img, tiling_kw) -> int:
+    plan = tiling.cached_plan(img.shape[2], img.shape[3], encoder._img, tiling_kw.get("stride"), tiling_kw.get("window", "hann"))
+    return img.shape[0] * plan.tiles_per_image
+
+
+@torch.no_grad()
+def tiled_denoise_eval(encoder, decoder, img: torch.Tensor, sigma: float = 0.05, eps: Optional[torch.Tensor] = None,
+                       noisy: Optional[torch.Tensor] = None, **tiling_kw) -> Dict[str, object]:
+    """denoise_eval at full resolution.  img: f32 [N,C,H,W] on the MI355X in [-1,1], H, W >= the networks' S.  The noise is
+    added ONCE to the whole image, noisy = clamp(img + sigma*eps, -1, 1) (eps: injected draws of img's shape, else generated
+    on the device), so overlapping tiles see the same noisy pixel; ``noisy`` given: used instead, sigma / eps ignored.  Then
+    ``denoise_tiled(encoder, decoder, noisy, **tiling_kw)`` (stride, window, batch, sample, eps_z).
+    Returns noisy, recon (NCHW f32) and python floats: recon_loss (mean squared error of recon vs img), psnr, ssim, and
+    noisy_loss, psnr_noisy, ssim_noisy of the input, all on the H x W tensors ([0,1]-rescaled for PSNR / SSIM, as
+    denoise_eval), plus tiles.  One host sync."""
+    if not img.is_cuda:
+        raise RuntimeError("tiled_denoise_eval needs the batch on the MI355X ('cuda'); there is no CPU path")
+    if img.dim() != 4 or img.dtype != torch.float32:
+        raise RuntimeError("tiled_denoise_eval: img must be float32 [N,C,H,W]")
+    img = img.contiguous()
+    dt = encoder._dt
+    if noisy is not None:
+        if not noisy.is_cuda or noisy.shape != img.shape:
+            raise RuntimeError("tiled_denoise_eval: noisy must be a device batch of img's shape")
+        noisy = noisy.contiguous()
+    else:
+        if eps is None:
+            ns = ops.default_noise(img.device)
+            ns.advance()
+            eps = ns.randn(tuple(img.shape), 0)
+        _, noisy = ops.noisy_clamp_to_nhwc(img, eps, sigma, G.padc(img.shape[1], dt), dt)
+    recon = denoise_tiled(encoder, decoder, noisy, **tiling_kw)
+    scal = ops.zeros_f32(4, img.device)                  # [mse(recon), mse(noisy), ssim(recon), ssim(noisy)]
+    ops.mse_forward_backward(recon, img, 1.0, scal[0:1], False)
+    ops.mse_forward_backward(noisy, img, 1.0, scal[1:2], False)
+    ops.axpy(scal[2:3], ops.ssim(recon, img), 1.0, out=scal[2:3])
+    ops.axpy(scal[3:4], ops.ssim(noisy, img), 1.0, out=scal[3:4])
+    mse_r, mse_n, ssim_r, ssim_n = (float(v) for v in scal.tolist())       # the one host sync
+    return {"noisy": noisy, "recon": recon, "recon_loss": mse_r, "psnr": _psnr(mse_r), "ssim": ssim_r,
+            "noisy_loss": mse_n, "psnr_noisy": _psnr(mse_n), "ssim_noisy": ssim_n, "tiles": _tile_count(encoder, img, tiling_kw)}
+
+
+@torch.no_grad()
+def tiled_test_epoch(encoder, decoder, pairs: Iterable, **tiling_kw) -> Dict[str, float]:
+    """paired_test_epoch at full resolution: ``pairs`` yields (noisy, clean) device batches f32 [b,C,H,W] in [-1,1], each
+    denoised with ``denoise_tiled(encoder, decoder, noisy, **tiling_kw)``.  Accumulation stays on the device (per batch the
+    mean squared error and the mean SSIM, weighed by the batch's image count); ONE host sync at the end.  Returns python
+    floats: psnr, ssim, recon_loss (mean squared error per element) of recon vs clean, psnr_noisy, ssim_noisy of the input,
+    samples, tiles."""
+    acc = None                                           # sum over batches of b * [mse(recon), ssim(recon), mse(noisy), ssim(noisy)]
+    seen = tiles = 0
+    for noisy, clean in pairs:
+        if not (noisy.is_cuda and clean.is_cuda):
+            raise RuntimeError("tiled_test_epoch needs device pairs; there is no CPU path")
+        dev = clean.device
+        acc = ops.zeros_f32(4, dev) if acc is None else acc
+        if noisy.shape != clean.shape or clean.dim() != 4:
+            raise RuntimeError("tiled_test_epoch: noisy and clean must be [b,C,H,W] batches of one shape")
+        noisy, clean = noisy.contiguous(), clean.contiguous()
+        b = clean.shape[0]
+        recon = denoise_tiled(encoder, decoder, noisy, **tiling_kw)
+        scal = torch.empty(2, dtype=torch.float32, device=dev)
+        ops.mse_forward_backward(recon, clean, 1.0, scal[0:1], False)
+        ops.mse_forward_backward(noisy, clean, 1.0, scal[1:2], False)
+        ops.axpy(acc[0:1], scal[0:1], float(b), out=acc[0:1])
+        ops.axpy(acc[1:2], ops.ssim(recon, clean), float(b), out=acc[1:2])
+        ops.axpy(acc[2:3], scal[1:2], float(b), out=acc[2:3])
+        ops.axpy(acc[3:4], ops.ssim(noisy, clean), float(b), out=acc[3:4])
+        seen += b
+        tiles += _tile_count(encoder, clean, tiling_kw)
+    if seen == 0:
+        raise RuntimeError("tiled_test_epoch: pairs yielded no batch")
+    mse_r, ssim_r, mse_n, ssim_n = (float(v) / seen for v in acc.tolist())  # the one host sync
+    return {"psnr": _psnr(mse_r), "ssim": ssim_r, "recon_loss": mse_r, "psnr_noisy": _psnr(mse_n), "ssim_noisy": ssim_n,
+            "samples": seen, "tiles": tiles}

@@ -1242,12 +1242,56 @@ def ssim(a, b):
     return out
 
 
-def nhwc_to_nchw(x, C, dtype, apply_tanh=False):
-    _need_cuda(x)
+def nhwc_to_nchw(x, C, dtype, apply_tanh=False, out=None):
+    """out: an f32 [B,C,H,W] tensor to write into (a slice of a larger buffer), else a new one."""
+    _need_cuda(x, out)
     B, H, W, CP = x.shape
-    y = torch.empty(B, C, H, W, dtype=torch.float32, device=x.device)
+    if out is not None and (out.dtype != torch.float32 or tuple(out.shape) != (B, C, H, W)):
+        raise RuntimeError("nhwc_to_nchw: out must be f32 [B,C,H,W]")
+    y = out if out is not None else torch.empty(B, C, H, W, dtype=torch.float32, device=x.device)
     L.check(L.load().vg_nhwc_to_nchw(x.data_ptr(), y.data_ptr(), B, C, H, W, CP, 1 if apply_tanh else 0, dtype,
                                      L.stream_ptr()), "vg_nhwc_to_nchw")
+    return y
+
+
+def tile_gather(images, plan, t0, B, CP, dtype, out=None):
+    """Tiles [t0, t0 + B) of ``plan`` (tiling.TilePlan) over ``images`` -- a resident uint8 [N,H,W,C] set (normalised as
+    gather_normalize_u8 does) or an f32 [N,C,H,W] batch -- as the Encoder's NHWC input [B,S,S,CP] (vg_tile_gather)."""
+    _need_cuda(images, out)
+    u8 = images.dtype == torch.uint8
+    if images.dim() != 4 or not (u8 or images.dtype == torch.float32):
+        raise RuntimeError("tile_gather: images must be uint8 [N,H,W,C] or float32 [N,C,H,W]")
+    N, H, W, C = images.shape if u8 else (images.shape[0], images.shape[2], images.shape[3], images.shape[1])
+    if (H, W) != (plan.H, plan.W):
+        raise RuntimeError(f"tile_gather: the plan is for {plan.H} x {plan.W} images, got {H} x {W}")
+    S = plan.S
+    y = out if out is not None else empty_act((B, S, S, CP), dtype, images.device)
+    if y.numel() != B * S * S * CP or y.dtype != TORCH_DT[dtype]:
+        raise RuntimeError("tile_gather: out must be [B,S,S,CP] in the engine dtype")
+    t = plan.device_tables(images.device)
+    L.check(L.load().vg_tile_gather(images.data_ptr() if u8 else None, None if u8 else images.data_ptr(), N, C, H, W, S,
+                                    plan.ny, plan.nx, t["oy"].data_ptr(), t["ox"].data_ptr(), int(t0), int(B), y.data_ptr(),
+                                    CP, dtype, L.stream_ptr()), "vg_tile_gather")
+    return y
+
+
+def tile_blend(tiles, plan, out=None):
+    """f32 [N,C,H,W] from the reconstruction tiles f32 [N * ny * nx, C, S, S] of ``plan``, blended with the plan's
+    coefficient tables in one launch (vg_tile_blend): no atomics, the same bits on every launch."""
+    _need_cuda(tiles, out)
+    S, per = plan.S, plan.ny * plan.nx
+    if tiles.dtype != torch.float32 or tiles.dim() != 4 or tuple(tiles.shape[2:]) != (S, S) or tiles.shape[0] % per != 0 \
+            or tiles.shape[0] == 0:
+        raise RuntimeError(f"tile_blend: tiles must be f32 [N * {per}, C, {S}, {S}]")
+    N, C = tiles.shape[0] // per, tiles.shape[1]
+    y = out if out is not None else torch.empty(N, C, plan.H, plan.W, dtype=torch.float32, device=tiles.device)
+    if y.dtype != torch.float32 or tuple(y.shape) != (N, C, plan.H, plan.W):
+        raise RuntimeError("tile_blend: out must be f32 [N,C,H,W]")
+    t = plan.device_tables(tiles.device)
+    L.check(L.load().vg_tile_blend(tiles.data_ptr(), y.data_ptr(), N, C, plan.H, plan.W, S, plan.ny, plan.nx,
+                                   t["oy"].data_ptr(), t["ox"].data_ptr(), t["first_y"].data_ptr(), t["count_y"].data_ptr(),
+                                   t["coef_y"].data_ptr(), plan.cover_y, t["first_x"].data_ptr(), t["count_x"].data_ptr(),
+                                   t["coef_x"].data_ptr(), plan.cover_x, L.stream_ptr()), "vg_tile_blend")
     return y
 
 
