@@ -48,7 +48,7 @@ extern "C" {
 #define VG_ACT_LRELU   2   /* nn.LeakyReLU(slope)    main_vae.py:25, gan_code.py:62-82 */
 #define VG_ACT_TANH    3   /* nn.Tanh()              gan_code.py:50 (vg_tnconv epilogue only) */
 
-#define VG_ABI_VERSION 29  /* 2: vg_pack_desc.tile_start, SyncBN / WGAN / data-path entry points; 3: in-kernel noise (vg_*_rng);
+#define VG_ABI_VERSION 30  /* 2: vg_pack_desc.tile_start, SyncBN / WGAN / data-path entry points; 3: in-kernel noise (vg_*_rng);
                              4: vg_bn_finalize_act_forward, vg_bn_backward_finalize_apply;
                              7: vg_bce_pair_forward_backward;
                              8: vg_head_backward; round-3 prune -- the opt-in experiments of ABI 5 / 6 that measured slower (input prologue of
@@ -75,7 +75,9 @@ extern "C" {
                              26: learning-rate schedules and decoupled weight decay: vg_lr_sched, vg_step_prologue_sched, vg_adamw_apply;
                              27: vg_tnconv_plan / vg_tn_plan: the tiling vg_tnconv launches, as a host-only query;
                              28: Gaussian-mixture prior: vg_gmm_log_resp, vg_gmm_moments (+ _ws_bytes), vg_gmm_sample;
-                             29: tiled denoising of images larger than the network: vg_tile_gather, vg_tile_blend */
+                             29: tiled denoising of images larger than the network: vg_tile_gather, vg_tile_blend;
+                             30: k-means: vg_kmeans_assign, vg_kmeans_update (+ _ws_bytes), vg_kmeans_seed (+ _ws_bytes),
+                                 vg_kmeans_plan / vg_km_plan */
 int vg_abi_version(void);
 /* The library reads its optional kernel-selection switches (VG_* environment variables, DESIGN.md "Runtime switches")
  * ONCE, when it is loaded; nothing on a launch path calls getenv.  A process that changes one of them afterwards
@@ -779,6 +781,84 @@ int vg_gmm_moments(const float* x, int64_t N, int D, int64_t row_stride, int K, 
 int vg_gmm_sample(const double* cdf, const double* mean, const double* cov_chol, int K, int D, int64_t n, const double* u,
                   const float* eps, const uint64_t* rng, int32_t* comp, float* z32, void* z, int ZP, int dtype,
                   void* stream);
+/* ------------------------------------------------------------------------------------------
+ * K-means (not in the reference; ABI 30; csrc/kmeans.hip): Lloyd's two phases and the k-means++ seeding over rows that
+ * already sit in HBM -- the k-means start of the mixture prior above (scikit-learn's init_params="kmeans") and the bins of
+ * the NDB metric (Richardson & Weiss 2018, "On GANs and GMMs").  Conventions of the Gaussian-mixture section: x f32 [N][D],
+ * rows `row_stride` elements apart (row_stride >= D); centres and every sum f64, 8-byte aligned (else VG_EALIGN);
+ * 1 <= N <= 2^31 - 1, 1 <= D <= 256, 1 <= K <= 1024.  Outside these limits, on a NULL required pointer or with too small
+ * a workspace: VG_EINVAL before any launch.  Deterministic: no floating-point atomics, the same inputs give the same bits
+ * on every call.  No launch waits on another workgroup of the same launch.
+ *
+ * vg_kmeans_assign (one launch, plus a 4-byte memset where `changed` is asked for).  center f64 [K][D].  Per row n:
+ *     h_k      = 0.5 * sum_i c_ki^2                       per workgroup, from the centre loads of the product (no workspace)
+ *     s_k      = h_k - sum_i (double)x_i * c_ki           the N x K x D product on v_mfma_f64_16x16x4_f64
+ *     label[n] = the LOWEST k with minimal s_k            (first strict `<` wins)
+ *     dist2[n] = sum_i ((double)x_i - c_label,i)^2        direct form, no cancellation
+ * A row with a NaN gets label 0 and a NaN dist2.  Outputs, each optional (NULL), at least one: label int32 [N]; dist2 f64
+ * [N]; resp f64 [N][K], the one-hot row vg_gmm_moments consumes; changed int32 [1] TOGETHER WITH prev_label int32 [N] (one
+ * without the other: VG_EINVAL): the number of rows whose label differs from prev_label, zeroed by the entry and counted
+ * with an integer atomic.  The order of the additions inside a sum is the kernel's (the product: columns in groups of 16,
+ * D padded with zeros, inside a group i = 4 q + s with q the MFMA's k index and s ascending; h: per q over the groups, then
+ * (q0 + q1) + (q2 + q3); dist2: 256 / rows lanes per row, lane q the columns q, q + lanes, ..., then a xor tree); where every
+ * intermediate is exactly representable the result is exact.  A workgroup owns 64 rows (32 where D > 224), whose x tile
+ * stays in LDS for all K centres; the four waves split the 16-centre tiles, or the rows where K <= 48 (vg_km_plan).
+ *
+ * vg_kmeans_update (three launches: main, reduce, and a one-workgroup launch for stats, which needs every centre; only
+ * two where stats is NULL).  From label int32 [N], over a FIXED row split whose partials are added in split order:
+ *     count[k]  = #{n : label[n] = k}                                            int64 [K], required
+ *     sum[k][i] = sum_{label[n] = k} (double)x_ni                                rows ascending inside a split; f64 [K][D]
+ *     center[k] = count[k] > 0 ? sum[k] / count[k] (one IEEE division) : old[k]  f64 [K][D]; must not alias old
+ *     stats[0]  = sum_k (sum_i (center_ki - old_ki)^2)                           k, i ascending; 0 where center is NULL
+ *     stats[1]  = sum_n dist2[n]                                                 0 where dist2 is NULL
+ * Rows whose label is outside [0, K) are skipped (the kernel never indexes with such a label; callers mask rows this way).
+ * sum, center, stats, dist2 are optional; old is required with center, stats with dist2.  An empty cluster keeps its old
+ * centre (scikit-learn relocates it: a stated deviation).  stats[1]: per split, thread t of 256 adds the rows r0 + t +
+ * 256 j, j ascending, the 256 values meet in a halving tree (t += t + 128, t + 64, ...), the splits in split order.
+ * Main launch: a workgroup owns (row split, chunk of clusters), chunk = min(K, 49152 / (8 D)) so that the f64 accumulators
+ * fit in LDS; thread i owns column i; only the chunk that owns a row's label reads that row of x.
+ * ws: vg_kmeans_update_ws_bytes(N, D, K) bytes, 8-byte aligned = 8 * (splits * (K D + K + 1) + K) with chunks =
+ * ceil(K / chunk), cap = min(1024, max(128, 16 MiB / (8 K D))) (the partial sums stay at 16 MiB, or at 128 splits),
+ * s = max(1, min(cap, 1024 / chunks, ceil(N / 256))), rows_per_split = ceil(N / s) rounded up to a multiple of 256,
+ * splits = ceil(N / rows_per_split) (N = 200 000, D = 100, K = 200: chunk 61, 4 chunks, 112 splits of 1 792 rows, 18 MB;
+ * K = 10: one chunk, 782 splits of 256 rows, 6 MB).  VG_EINVAL (negative) outside the limits.
+ *
+ * vg_kmeans_seed: plain k-means++ (Arthur & Vassilvitskii 2007: one trial per step, not scikit-learn's greedy variant),
+ * no host sync.  u f64 [K] injected, or (u NULL) drawn from rng = {seed, counter} (device memory) as
+ * u_j = u01(word(VG_DRAW_KMEANS_U, j)) (u01, word: "Degraded pairs" above):
+ *     idx[0] = min((int64)(u_0 * N), N - 1);          mind2[n] = sum_i ((double)x_ni - (double)x_idx0,i)^2, i ascending
+ *     for j = 1 .. K - 1:  total = sum mind2;  idx[j] = first n with cum[n] > u_j * total, N - 1 if there is none;
+ *                          mind2 = min(mind2, |x - x_idx[j]|^2)
+ * cum is a two-level sum with blocks of 256 rows: a block's total adds its rows in ascending order, total adds the block
+ * totals in ascending order, and cum[n] = (the totals of the blocks below n's, added in that order) + (the rows of n's
+ * block up to n, added in ascending order from 0): two sums and ONE addition of the two.  Each step is two launches -- the mind2 update with block
+ * totals, then a one-workgroup pick that leaves idx[j] in device memory for the next update: 2 K - 1 launches.
+ * Outputs: idx int32 [K], center f64 [K][D] (the chosen rows).  ws: vg_kmeans_seed_ws_bytes(N, D, K) = 8 * (N +
+ * ceil(N / 256)) bytes, 8-byte aligned; its first N doubles are mind2 after the last step.  A picked row has mind2 = 0
+ * only when total = 0 (fewer than K distinct rows): the result then holds duplicate centres.
+ *
+ * vg_kmeans_plan (host-only, needs no GPU): the record the three launchers above launch from.
+ * ---------------------------------------------------------------------------------------- */
+#define VG_DRAW_KMEANS_U 42
+typedef struct vg_km_plan {
+    int32_t assign_rows;          /* rows per workgroup of the assign kernel: 64, or 32 where D > 224 */
+    int32_t assign_tile;          /* centres per MFMA tile: 16 */
+    int32_t assign_row_split;     /* 1: fewer than four centre tiles, the waves split the rows; 0: they split the tiles */
+    int32_t assign_lds_bytes;
+    int32_t update_splits, update_chunks, update_chunk;
+    int32_t seed_block;           /* rows per block of the seed's cumulative sum: 256 */
+    int64_t assign_grid, update_rows_per_split, seed_blocks, update_ws_bytes, seed_ws_bytes;
+} vg_km_plan;
+int vg_kmeans_plan(int64_t N, int D, int K, vg_km_plan* out);
+int vg_kmeans_assign(const float* x, int64_t N, int D, int64_t row_stride, int K, const double* center, int32_t* label,
+                     double* dist2, double* resp, const int32_t* prev_label, int32_t* changed, void* stream);
+int64_t vg_kmeans_update_ws_bytes(int64_t N, int D, int K);
+int vg_kmeans_update(const float* x, int64_t N, int D, int64_t row_stride, int K, const int32_t* label, const double* dist2,
+                     const double* old, int64_t* count, double* sum, double* center, double* stats, void* ws,
+                     int64_t ws_bytes, void* stream);
+int64_t vg_kmeans_seed_ws_bytes(int64_t N, int D, int K);
+int vg_kmeans_seed(const float* x, int64_t N, int D, int64_t row_stride, int K, const double* u, const uint64_t* rng,
+                   int32_t* idx, double* center, void* ws, int64_t ws_bytes, void* stream);
 /* ------------------------------------------------------------------------------------------
  * Resize (dataset_code.py:26-30, CelebADatasetV0's transforms.Resize(image_size) + transforms.CenterCrop(image_size) on
  * the PIL image default_loader hands them): PIL's ImagingResample for 8-bit images with the triangle (BILINEAR) filter,

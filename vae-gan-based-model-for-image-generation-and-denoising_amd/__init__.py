@@ -12,7 +12,9 @@ reference): ``SSIMLoss`` and ``VAEGANTrainer(..., alpha_ssim=)`` / ``VAETrainer(
 ``evaluate_generation``, ``sample_images``, and ``GaussianMixturePrior`` (not in the reference): a full-covariance Gaussian
 mixture fitted to the Encoder's latents by EM on the device and sampled there, a drop-in ``prior=``.  Feature-space metrics (fid.update / fid.compute of every evaluation loop,
 README.md:22 precision / recall): ``metrics`` -- ``FeatureStats``, ``frechet_distance``, ``precision_recall``,
-``encoder_features``, ``kernel_distance`` (KID).  Weight averaging (not in the reference): ``EMA`` -- an exponential moving
+``encoder_features``, ``kernel_distance`` (KID), ``ndb`` (number of statistically different bins over k-means bins of the
+real features; no classifier needed; ``evaluate_generation_ndb`` adds it to a generation pass).  K-means on the device (not in the reference): ``cluster`` -- ``KMeans`` (Lloyd's
+iteration with k-means++ seeding), also the k-means start of ``GaussianMixturePrior.fit(init="kmeans")``.  Weight averaging (not in the reference): ``EMA`` -- an exponential moving
 average of Encoder / Generator weights kept on the device, ``VAEGANTrainer(..., ema=)`` and the sibling trainers.
 Gradient-norm clipping (not in the reference): ``clip_grad_norm_`` / ``Adam.clip_grad_norm_`` -- torch's
 ``clip_grad_norm_`` with the coefficient kept on the device and applied inside the Adam step, ``max_grad_norm=`` on the four
@@ -24,6 +26,7 @@ CenterCrop on the device), ``resample_coeffs``, ``resize_geometry``.  Tiled deno
 (not in the reference): ``denoise_tiled``, ``tiled_denoise_eval``, ``tiled_test_epoch`` and ``tiling`` -- ``tile_plan`` /
 ``TilePlan``: overlapping S x S tiles cut and blended back on the device with a separable window.
 """
+from . import cluster  # noqa: F401
 from . import data  # noqa: F401
 from . import geometry  # noqa: F401
 from . import latent  # noqa: F401
@@ -37,8 +40,10 @@ from .denoise import (denoise_eval, denoise_tiled, paired_test_epoch, tiled_deno
                       validation_epoch)
 from .tiling import TilePlan, tile_plan
 from .graphed import graphed
-from .latent import GaussianMixturePrior, LatentPrior, encode_dataset, evaluate_generation, sample_images
-from .metrics import FeatureStats, encoder_features, frechet_distance, kernel_distance, precision_recall
+from .latent import (GaussianMixturePrior, LatentPrior, encode_dataset, evaluate_generation, evaluate_generation_ndb,
+                     sample_images)
+from .cluster import KMeans
+from .metrics import FeatureStats, encoder_features, frechet_distance, kernel_distance, ndb, precision_recall
 from .losses import BCELoss, MSELoss, SSIMLoss
 from .nets import ConvBlock, Discriminator, Encoder, Generator, weights_init
 from .optim import Adam, AdamW, LRSchedule, clip_grad_norm_
@@ -52,4 +57,5 @@ __all__ = ["ConvBlock", "Encoder", "Generator", "Discriminator", "weights_init",
            "ResidentImages", "resample_coeffs", "resize_geometry",
            "EMA", "clip_grad_norm_", "DiffAugment", "AdamW", "LRSchedule",
            "tiling", "TilePlan", "tile_plan", "denoise_tiled", "tiled_denoise_eval", "tiled_test_epoch",
-           "metrics", "FeatureStats", "frechet_distance", "precision_recall", "encoder_features", "kernel_distance"]
+           "metrics", "FeatureStats", "frechet_distance", "precision_recall", "encoder_features", "kernel_distance",
+           "cluster", "KMeans", "ndb", "evaluate_generation_ndb"]

@@ -22,7 +22,7 @@ VG_GNORM_PARTS = 512
 VG_PROLOGUE_MAX = 4
 VG_TILE_MAX_COVER = 8
 VG_LRS_CONST, VG_LRS_LINEAR, VG_LRS_COSINE, VG_LRS_EXP, VG_LRS_STEP = 0, 1, 2, 3, 4
-ABI_VERSION = 29
+ABI_VERSION = 30
 
 VG_ENOSUP = -3
 _ERR = {-1: "VG_EINVAL (bad shape/size/flag)", -2: "VG_EALIGN (16-byte contract violated)",
@@ -103,6 +103,14 @@ class EWDesc(Structure):
 class EWPlan(Structure):
     """vg_ew_plan."""
     _fields_ = [(n, c_int32) for n in ("ct", "jt", "rows_per_tile", "tiles_per_img", "ntiles", "grid")] + [("ws_bytes", c_int64)]
+
+
+class KMPlan(Structure):
+    """vg_km_plan."""
+    _fields_ = [(n, c_int32) for n in ("assign_rows", "assign_tile", "assign_row_split", "assign_lds_bytes", "update_splits",
+                                       "update_chunks", "update_chunk", "seed_block")] + \
+               [(n, c_int64) for n in ("assign_grid", "update_rows_per_split", "seed_blocks", "update_ws_bytes",
+                                       "seed_ws_bytes")]
 
 
 class PackDesc(Structure):
@@ -216,6 +224,12 @@ SIGNATURES = {
     "vg_gmm_moments_ws_bytes": (c_int64, [_L, _I, _I]),
     "vg_gmm_moments": (c_int, [_P, _L, _I, _L, _I, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P]),
     "vg_gmm_sample": (c_int, [_P, _P, _P, _I, _I, _L, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
+    "vg_kmeans_plan": (c_int, [_L, _I, _I, POINTER(KMPlan)]),
+    "vg_kmeans_assign": (c_int, [_P, _L, _I, _L, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "vg_kmeans_update_ws_bytes": (c_int64, [_L, _I, _I]),
+    "vg_kmeans_update": (c_int, [_P, _L, _I, _L, _I, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P]),
+    "vg_kmeans_seed_ws_bytes": (c_int64, [_L, _I, _I]),
+    "vg_kmeans_seed": (c_int, [_P, _L, _I, _L, _I, _P, _P, _P, _P, _P, _L, _P]),
     "vg_tile_gather": (c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _L, _I, _P, _I, _I, _P]),
     "vg_tile_blend": (c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _P]),
     "vg_resize_u8_lds_bytes": (c_int64, [_I, _I, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I]),

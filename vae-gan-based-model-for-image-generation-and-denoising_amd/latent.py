@@ -24,7 +24,8 @@ import torch
 
 from . import geometry as G
 from . import ops
-from .metrics import FeaturePass, _pr_result
+from .cluster import KMeans
+from .metrics import FeaturePass, _pr_result, ndb_statistics
 
 
 def _loader_samples(loader) -> int:
@@ -215,13 +216,19 @@ class GaussianMixturePrior:
 
     @classmethod
     def fit(cls, x: torch.Tensor, n_components: int = 10, reg_covar: float = 1e-6, tol: float = 1e-3, max_iter: int = 100,
-            seed: int = 0, init_idx=None) -> "GaussianMixturePrior":
+            seed: int = 0, init_idx=None, init="random") -> "GaussianMixturePrior":
         """EM on x f32 [N, D] on the device, possibly a strided view: fit on the ``mu`` columns of ``encode_dataset``'s
         output, ``mulv[:, :L]`` (no copy is made).  Fitting on sampled z instead is out of scope.
 
         Initialisation: ``init_idx`` (K distinct row numbers; default ``np.random.default_rng(seed).choice(N, K,
         replace=False)``) names the rows that become the means; weights 1 / K; every precision diag(1 / (var + reg_covar))
-        with var the global per-column variance (one ``ops.gmm_moments`` call with K = 1, resp = 1).
+        with var the global per-column variance (one ``ops.gmm_moments`` call with K = 1, resp = 1).  That is
+        ``init="random"``, the default.  ``init="kmeans"`` (a ``cluster.KMeans`` fitted here by k-means++ from ``seed``) or
+        ``init=<a fitted KMeans>`` of the same K and D is scikit-learn's default ``init_params="kmeans"``: one
+        ``ops.kmeans_assign`` gives the one-hot responsibilities, ``ops.gmm_moments`` around the centres their sums, and the
+        host M-step of the loop below the starting weights, means and covariances (``_initialize_parameters`` followed by
+        ``_initialize``); from there EM needs fewer iterations and ends in better optima.  ``init_idx`` belongs to
+        ``init="random"`` and is refused with a k-means start; so is a start that leaves a cluster empty.
         Loop: exactly scikit-learn's ``GaussianMixture.fit`` -- E-step (``ops.gmm_log_resp``), lower_bound = mean
         log-likelihood, M-step (``ops.gmm_moments`` around the current means, then the K small D x D steps in numpy f64 on
         the host: weights, means, Sigma_k + reg_covar I, Cholesky, triangular inverse, log_coef, cdf -- the precedent of
@@ -241,15 +248,43 @@ class GaussianMixturePrior:
         if N < K:
             raise RuntimeError(f"GaussianMixturePrior.fit: {N} rows cannot initialise {K} components (reg_covar does not "
                                f"help here: give more rows or fewer components)")
-        if init_idx is None:
-            init_idx = np.random.default_rng(seed).choice(N, K, replace=False)
-        idx = np.asarray(init_idx)
-        if (idx.ndim != 1 or idx.size != K or not np.issubdtype(idx.dtype, np.integer) or idx.min() < 0 or idx.max() >= N
-                or np.unique(idx).size != K):
-            raise RuntimeError(f"GaussianMixturePrior.fit: init_idx must be {K} distinct row numbers in [0, {N})")
+        kmeans_start = not (isinstance(init, str) and init == "random")
+        if kmeans_start:
+            if not (isinstance(init, KMeans) or (isinstance(init, str) and init == "kmeans")):
+                raise RuntimeError(f"GaussianMixturePrior.fit: init must be 'random', 'kmeans' or a fitted KMeans, got "
+                                   f"{init!r}")
+            if init_idx is not None:
+                raise RuntimeError("GaussianMixturePrior.fit: init_idx names the rows of init='random'; a k-means start "
+                                   "takes its centres from the clustering")
+            if isinstance(init, KMeans) and (init.n_clusters, init.dim) != (K, D):
+                raise RuntimeError(f"GaussianMixturePrior.fit: the KMeans has {init.n_clusters} clusters of {init.dim} "
+                                   f"dimensions, the mixture {K} components of {D}")
+        else:
+            if init_idx is None:
+                init_idx = np.random.default_rng(seed).choice(N, K, replace=False)
+            idx = np.asarray(init_idx)
+            if (idx.ndim != 1 or idx.size != K or not np.issubdtype(idx.dtype, np.integer) or idx.min() < 0
+                    or idx.max() >= N or np.unique(idx).size != K):
+                raise RuntimeError(f"GaussianMixturePrior.fit: init_idx must be {K} distinct row numbers in [0, {N})")
         if max_iter < 1:
             raise RuntimeError("GaussianMixturePrior.fit: max_iter must be >= 1")
         dev = x.device
+        up = lambda a: torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float64).to(dev)      # noqa: E731
+
+        def m_step(nk_raw, s1_h, s2_h, means):
+            nk_h = nk_raw + _GMM_TINY
+            weights = nk_h / N
+            weights = weights / weights.sum()
+            delta = s1_h / nk_h[:, None]
+            means = means + delta
+            cov = s2_h / nk_h[:, None, None] - delta[:, :, None] * delta[:, None, :]
+            cov = 0.5 * (cov + cov.transpose(0, 2, 1))
+            cov[:, np.arange(D), np.arange(D)] += reg_covar
+            return _gmm_host_step(weights, means, cov, reg_covar)
+
+        if kmeans_start:
+            return cls._fit_loop(x, K, reg_covar, tol, max_iter, m_step, up,
+                                 *cls._kmeans_start(x, K, seed, init, m_step, up))
         rows = x[torch.as_tensor(idx, dtype=torch.int64, device=dev)].double().contiguous()      # [K, D]
         nk, s1, s2, _ = ops.gmm_moments(x, rows[:1].contiguous(), torch.ones(N, 1, dtype=torch.float64, device=dev))
         nk0 = float(nk.item())
@@ -263,8 +298,32 @@ class GaussianMixturePrior:
         weights = np.full(K, 1.0 / K)
         means = rows.cpu().numpy()
         log_coef = np.log(weights) + np.log(np.sqrt(prec)).sum() - 0.5 * D * np.log(2.0 * np.pi)
-        up = lambda a: torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float64).to(dev)      # noqa: E731
         d_means, d_prec, d_coef = rows, up(np.tile(np.diag(np.sqrt(prec)), (K, 1, 1))), up(log_coef)
+        return cls._fit_loop(x, K, reg_covar, tol, max_iter, m_step, up, means, d_means, d_prec, d_coef)
+
+    @staticmethod
+    def _kmeans_start(x, K, seed, init, m_step, up):
+        """scikit-learn's init_params="kmeans": -> (means, d_means, d_prec, d_coef) of the M-step on one-hot
+        responsibilities."""
+        N = x.shape[0]
+        km = init if isinstance(init, KMeans) else KMeans.fit(x, K, seed=seed)
+        centres = km.cluster_centers_
+        _, _, resp, _ = ops.kmeans_assign(x, centres, want_label=False, want_resp=True)
+        nk, s1, s2, _ = ops.gmm_moments(x, centres, resp)
+        D = centres.shape[1]
+        flat = torch.cat([nk, s1.reshape(-1), s2.reshape(-1), centres.reshape(-1)]).cpu().numpy()
+        nk_h = flat[:K]
+        if np.any(nk_h == 0.0):
+            raise RuntimeError(f"GaussianMixturePrior.fit: the k-means start leaves cluster {int(np.argmin(nk_h))} of {K} "
+                               f"empty ({N} rows); ask for fewer components or use init='random'")
+        p = m_step(nk_h, flat[K:K + K * D].reshape(K, D), flat[K + K * D:K + K * D + K * D * D].reshape(K, D, D),
+                   flat[K + K * D + K * D * D:].reshape(K, D))
+        return p["means"], up(p["means"]), up(p["prec_chol"]), up(p["log_coef"])
+
+    @classmethod
+    def _fit_loop(cls, x, K, reg_covar, tol, max_iter, m_step, up, means, d_means, d_prec, d_coef):
+        """The EM loop of ``fit`` from a start: host means f64 [K, D] and their device twins."""
+        N, D = x.shape
         lower, converged, n_iter, p = -np.inf, False, 0, None
         for n_iter in range(1, int(max_iter) + 1):
             prev = lower
@@ -276,17 +335,8 @@ class GaussianMixturePrior:
                 raise RuntimeError(f"GaussianMixturePrior.fit: the log-likelihood is not finite in iteration {n_iter} (a "
                                    f"NaN or infinite latent, or a collapsed component); check the latents or increase "
                                    f"reg_covar (now {reg_covar})")
-            nk_h = flat[1:1 + K] + _GMM_TINY
-            s1_h = flat[1 + K:1 + K + K * D].reshape(K, D)
-            s2_h = flat[1 + K + K * D:].reshape(K, D, D)
-            weights = nk_h / N
-            weights = weights / weights.sum()
-            delta = s1_h / nk_h[:, None]
-            means = means + delta
-            cov = s2_h / nk_h[:, None, None] - delta[:, :, None] * delta[:, None, :]
-            cov = 0.5 * (cov + cov.transpose(0, 2, 1))
-            cov[:, np.arange(D), np.arange(D)] += reg_covar
-            p = _gmm_host_step(weights, means, cov, reg_covar)
+            p = m_step(flat[1:1 + K], flat[1 + K:1 + K + K * D].reshape(K, D), flat[1 + K + K * D:].reshape(K, D, D), means)
+            means = p["means"]
             d_means, d_prec, d_coef = up(p["means"]), up(p["prec_chol"]), up(p["log_coef"])
             if abs(lower - prev) < tol:
                 converged = True
@@ -430,7 +480,37 @@ def evaluate_generation(decoder, val_loader: Iterable[torch.Tensor],
     kid_subsets (default None: nothing changes; needs feature_fn, else RuntimeError): the Kernel Inception Distance of the
     pass's features (``metrics.kernel_distance``: ``kid_subsets`` subset pairs of ``kid_subset_size`` rows drawn on the host
     with ``kid_seed``, degree 3, gamma 1 / D, coef 1); the result gains ``kid_mean`` and ``kid_std`` (population standard
-    deviation), read in the same host sync.  Not in the reference; single process, like precision / recall."""
+    deviation), read in the same host sync.  Not in the reference; single process, like precision / recall.
+
+    NDB of the pass's features: ``evaluate_generation_ndb`` (this function's keyword list is pinned)."""
+    return _evaluate_generation(decoder, val_loader, prior, noise_fn, feature_fn, k, real_stats, kid_subsets,
+                                kid_subset_size, kid_seed, None)
+
+
+@torch.no_grad()
+def evaluate_generation_ndb(decoder, val_loader: Iterable[torch.Tensor], ndb_bins: int = 100, ndb_alpha: float = 0.05,
+                            ndb_seed: int = 0, **kwargs) -> Dict[str, float]:
+    """``evaluate_generation(decoder, val_loader, **kwargs)`` whose result also holds ``ndb``, ``ndb_over_k`` and
+    ``js_divergence`` (``metrics.ndb``: ``ndb_bins`` k-means bins of the pass's kept REAL features, k-means++ from
+    ``ndb_seed``, two-proportion z-test at level ``ndb_alpha``).  Needs ``feature_fn=``, else RuntimeError, like
+    ``kid_subsets``.  The k-means fit adds one host sync per Lloyd iteration to the pass; the bin counts are read in the
+    pass's final sync.  Not in the reference; single process."""
+    if kwargs.get("feature_fn") is None:
+        raise RuntimeError("evaluate_generation_ndb: ndb_bins needs a feature_fn (NDB is a feature-space metric)")
+    names = ("prior", "noise_fn", "feature_fn", "k", "real_stats", "kid_subsets", "kid_subset_size", "kid_seed")
+    unknown = sorted(set(kwargs) - set(names))
+    if unknown:
+        raise TypeError(f"evaluate_generation_ndb: unknown keyword(s) {unknown}")
+    defaults = dict(prior=None, noise_fn=None, feature_fn=None, k=3, real_stats=None, kid_subsets=None, kid_subset_size=1000,
+                    kid_seed=0)
+    defaults.update(kwargs)
+    return _evaluate_generation(decoder, val_loader, *(defaults[n] for n in names),
+                                (int(ndb_bins), float(ndb_alpha), int(ndb_seed)))
+
+
+def _evaluate_generation(decoder, val_loader, prior, noise_fn, feature_fn, k, real_stats, kid_subsets, kid_subset_size,
+                         kid_seed, ndb):
+    """The pass behind ``evaluate_generation`` (ndb None) and ``evaluate_generation_ndb`` (ndb = (bins, alpha, seed))."""
     if kid_subsets is not None and feature_fn is None:
         raise RuntimeError("evaluate_generation: kid_subsets needs a feature_fn (KID is a feature-space metric)")
     decoder.eval()
@@ -466,12 +546,20 @@ def evaluate_generation(decoder, val_loader: Iterable[torch.Tensor],
     parts = [acc.double(), counts.double()]
     if kid_subsets is not None:
         parts.append(feats.kid(int(kid_subsets), int(kid_subset_size), int(kid_seed)))
+    if ndb is not None:
+        parts.append(feats.ndb_counts(ndb[0], ndb[2]).double().reshape(-1))            # exact: counts are below 2^53
     ssim_sum, fake_in_real, real_in_fake, *kid = torch.cat(parts).tolist()             # the one host sync
+    if ndb is not None:
+        bins = np.asarray(kid[len(kid) - 2 * ndb[0]:]).reshape(2, ndb[0])
+        kid = kid[:len(kid) - 2 * ndb[0]]
     out = {"ssim": ssim_sum / seen, "samples": seen, "batches": batches, "fid": feats.fid(), "feature_dim": feats.D}
     pr = _pr_result(int(fake_in_real), int(real_in_fake), seen, seen, int(k))
     out.update(precision=pr["precision"], recall=pr["recall"], f1=pr["f1"])
     if kid:
         out.update(kid_mean=kid[0], kid_std=kid[1])
+    if ndb is not None:
+        st = ndb_statistics(bins[0], bins[1], ndb[1])
+        out.update(ndb=st["ndb"], ndb_over_k=st["ndb_over_k"], js_divergence=st["js_divergence"])
     return out
 
 

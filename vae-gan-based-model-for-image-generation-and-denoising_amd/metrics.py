@@ -1,4 +1,4 @@
-"""Feature-space generation metrics on the device: FID, the k-nearest-neighbour precision / recall / F1 and KID.
+"""Feature-space generation metrics on the device: FID, the k-nearest-neighbour precision / recall / F1, KID and NDB.
 
 Every evaluation loop of the reference ends in ``fid.update(real, real=True); fid.update(fake, real=False); fid.compute()``
 (vaegan_code.py:143-185, gan_code.py:111-145, main_vae.py:472-512, :540-574), and its README.md:22 lists Precision /
@@ -10,6 +10,7 @@ exists; the three kernels behind it are stated in include/vaegan_hip.h, "Feature
     precision_recall         vg_knn_radius2        k-th neighbour radius of every sample, exact-f32 MFMA
                              vg_manifold_cover     is a sample inside some ball of the other set
     kernel_distance          vg_kid_scores         polynomial-kernel MMD^2 over random subsets (KID), f64 MFMA
+    ndb                      vg_kmeans_*           k-means bins of the real features (cluster.KMeans), the fake rows' bin counts
 
 The feature extractor is pluggable: ``feature_fn(images_u8 [b,C,S,S] uint8 device) -> f32 [b, D] device``.
 ``encoder_features`` wraps the project's own Encoder (no download); a user who has InceptionV3 weights passes a callable of
@@ -23,12 +24,14 @@ biased in N).  Deviations from torchmetrics' KernelInceptionDistanc
 same reason: the subsets are drawn on the HOST by numpy's PCG64 (``kid_subsets``), the arithmetic is f64 and ``kid_std``
 is the population standard deviation (torch.std's default is the sample one).
 """
+import math
 from typing import Callable, Dict, Optional
 
 import numpy as np
 import torch
 
 from . import ops
+from .cluster import KMeans
 
 
 def _check_feats(f, D: Optional[int], what: str) -> None:
@@ -232,6 +235,68 @@ def kernel_distance(real_feats: torch.Tensor, fake_feats: torch.Tensor, subsets:
     return (out, scores) if return_scores else out
 
 
+def ndb_statistics(count_real, count_fake, alpha: float = 0.05) -> Dict[str, object]:
+    """The host arithmetic of ``ndb`` on two K-length bin histograms (integer counts), numpy f64.  Per bin, with n, m the
+    sample counts and P, Q the proportions: pooled p = (n P + m Q) / (n + m), se = sqrt(p (1 - p) (1 / n + 1 / m)),
+    z = (P - Q) / se (0 where se = 0), two-sided p-value erfc(|z| / sqrt(2)); the bin is statistically different where
+    p-value < alpha.  js_divergence = 0.5 KL(P || M) + 0.5 KL(Q || M), M = (P + Q) / 2, natural log, 0 log 0 = 0.
+    -> ndb, ndb_over_k, js_divergence, bins (bool [K]), p_values, z, real_proportions, fake_proportions, n_real, n_fake."""
+    cr, cf = np.asarray(count_real, dtype=np.float64), np.asarray(count_fake, dtype=np.float64)
+    if cr.ndim != 1 or cr.shape != cf.shape or cr.size < 1:
+        raise ValueError("ndb_statistics: two histograms of the same length K >= 1")
+    n, m = cr.sum(), cf.sum()
+    if n < 1 or m < 1:
+        raise ValueError("ndb_statistics: both histograms need at least one sample")
+    P, Q = cr / n, cf / m
+    pooled = (n * P + m * Q) / (n + m)
+    se = np.sqrt(pooled * (1.0 - pooled) * (1.0 / n + 1.0 / m))
+    z = np.zeros_like(P)
+    np.divide(P - Q, se, out=z, where=se > 0)
+    pv = np.array([math.erfc(abs(v) / math.sqrt(2.0)) for v in z])
+    bins = pv < float(alpha)
+    M = 0.5 * (P + Q)
+
+    def kl(a):
+        nz = a > 0
+        return float(np.sum(a[nz] * np.log(a[nz] / M[nz])))
+
+    return {"ndb": int(bins.sum()), "ndb_over_k": float(bins.sum()) / P.size, "js_divergence": 0.5 * kl(P) + 0.5 * kl(Q),
+            "bins": bins, "p_values": pv, "z": z, "real_proportions": P, "fake_proportions": Q, "n_real": int(n),
+            "n_fake": int(m)}
+
+
+def _ndb_device(real_feats, fake_feats, n_bins, seed, kmeans):
+    """-> (the KMeans of the real rows, int64 [2, K] on the device: real and fake bin counts)."""
+    _check_feats(fake_feats, None, "ndb")
+    if kmeans is None:
+        _check_feats(real_feats, fake_feats.shape[1], "ndb")
+        kmeans = KMeans.fit(real_feats, int(n_bins), seed=int(seed))
+    elif not isinstance(kmeans, KMeans) or kmeans.dim != fake_feats.shape[1]:
+        raise RuntimeError(f"ndb: kmeans must be a fitted cluster.KMeans over {fake_feats.shape[1]}-dimensional rows")
+    if fake_feats.shape[0] < 1:
+        raise RuntimeError("ndb: fake_feats must hold at least one row")
+    fake_count = ops.kmeans_update(fake_feats, kmeans.predict(fake_feats), kmeans.n_clusters)[0]
+    return kmeans, torch.stack([kmeans.counts_, fake_count])
+
+
+def ndb(real_feats: Optional[torch.Tensor], fake_feats: torch.Tensor, n_bins: int = 100, alpha: float = 0.05, seed: int = 0,
+        kmeans: Optional[KMeans] = None) -> Dict[str, object]:
+    """Number of statistically Different Bins (Richardson & Weiss 2018, "On GANs and GMMs"): k-means clusters the REAL
+    features into ``n_bins`` bins (``cluster.KMeans.fit``, k-means++ from ``seed``), every fake row goes to its nearest
+    centre, and a two-proportion z-test per bin counts the bins whose shares differ at level ``alpha``
+    (``ndb_statistics``).  It needs no classifier and says WHICH modes a Generator dropped: ``bins`` marks them.
+    real_feats f32 [Nr, D], fake_feats f32 [Nf, D] on the device.  kmeans: a ``KMeans`` of the real side fitted earlier
+    (returned by every call as ``kmeans``) -- cluster the real features once per training run; real_feats may then be None
+    and n_bins / seed are not read.  -> the keys of ``ndb_statistics`` plus ``kmeans``.  Besides the fit (one host sync per
+    Lloyd iteration): two launches for the fake side and one host sync of 2 K integers.  No feature whitening; single
+    process, like precision / recall."""
+    kmeans, counts = _ndb_device(real_feats, fake_feats, n_bins, seed, kmeans)
+    c = counts.cpu().numpy()                                                           # the one host sync
+    out = ndb_statistics(c[0], c[1], alpha)
+    out["kmeans"] = kmeans
+    return out
+
+
 _ARANGE = {}
 
 
@@ -318,3 +383,10 @@ class FeaturePass:
             raise RuntimeError("FeaturePass.kid needs the features of the pass: construct it with keep=True")
         return _kid_device(torch.cat(self.real_feats), torch.cat(self.fake_feats), subsets, subset_size, 3, None, 1.0, seed,
                            None, None)[1]
+
+    def ndb_counts(self, n_bins: int, seed: int = 0) -> torch.Tensor:
+        """int64 [2, n_bins] on the device: the real and fake bin counts of the pass's features (``keep=True``); the
+        k-means fit inside costs one host sync per Lloyd iteration."""
+        if not self.keep:
+            raise RuntimeError("FeaturePass.ndb_counts needs the features of the pass: construct it with keep=True")
+        return _ndb_device(torch.cat(self.real_feats), torch.cat(self.fake_feats), n_bins, seed, None)[1]

@@ -1110,6 +1110,120 @@ def gmm_sample(cdf, mean, cov_chol, n, u=None, eps=None, state=None, want_comp=F
     return comp, z32, zt
 
 
+# draw id of the k-means++ seeding (include/vaegan_hip.h "K-means")
+DRAW_KMEANS_U = 42
+KMEANS_MAX_D, KMEANS_MAX_K = 256, 1024
+
+
+def _kmeans_shape(what, N, D, K):
+    if N < 1:
+        raise RuntimeError(f"{what}: x must hold at least one row")
+    if not (1 <= K <= KMEANS_MAX_K and 1 <= D <= KMEANS_MAX_D):
+        raise RuntimeError(f"{what}: needs 1 <= K <= {KMEANS_MAX_K} clusters and 1 <= D <= {KMEANS_MAX_D} dimensions")
+
+
+def _kmeans_tensor(what, name, t, dtype, shape):
+    if not t.is_cuda:
+        raise RuntimeError("vaegan_amd ops need tensors on the MI355X (cuda) device; there is no CPU path")
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise RuntimeError(f"{what}: {name} must be a contiguous {str(dtype).replace('torch.', '')} tensor of shape "
+                           f"{list(shape)}")
+
+
+def kmeans_plan(N: int, D: int, K: int) -> dict:
+    """What the k-means launchers launch for N rows, D columns and K clusters (vg_kmeans_plan; host-only, needs no GPU):
+    rows per workgroup / centre tile / row-split flag / LDS bytes / grid of the assign kernel, splits / rows per split /
+    cluster chunk / chunks / workspace bytes of the update, block size / blocks / workspace bytes of the seed."""
+    p = L.KMPlan()
+    L.check(L.load().vg_kmeans_plan(int(N), int(D), int(K), L.byref(p)), "vg_kmeans_plan")
+    return {n: int(getattr(p, n)) for n, _ in L.KMPlan._fields_}
+
+
+def kmeans_assign(x, center, want_label=True, want_dist2=False, want_resp=False, prev_label=None):
+    """Nearest centre of every row on the device (vg_kmeans_assign): label int32 [N] = the LOWEST k minimising
+    0.5 |c_k|^2 - x . c_k (f64 MFMA), dist2 f64 [N] = |x - c_label|^2 in direct form, resp f64 [N, K] one-hot (what
+    ``gmm_moments`` consumes), changed int32 [1] = rows whose label differs from ``prev_label`` int32 [N].  x f32 [N, D]
+    (may be a strided view), center f64 [K, D].  One launch, no host sync.  -> (label, dist2, resp, changed), None for
+    what was not asked for."""
+    N, D, stride = _feature_rows(x, "kmeans_assign")
+    K = center.shape[0] if center.dim() == 2 else 0
+    _kmeans_tensor("kmeans_assign", "center", center, torch.float64, (K, D))
+    _kmeans_shape("kmeans_assign", N, D, K)
+    if prev_label is not None:
+        _kmeans_tensor("kmeans_assign", "prev_label", prev_label, torch.int32, (N,))
+    if not (want_label or want_dist2 or want_resp or prev_label is not None):
+        raise RuntimeError("kmeans_assign: ask for at least one output")
+    dev = x.device
+    label = torch.empty(N, dtype=torch.int32, device=dev) if want_label else None
+    dist2 = torch.empty(N, dtype=torch.float64, device=dev) if want_dist2 else None
+    resp = torch.empty(N, K, dtype=torch.float64, device=dev) if want_resp else None
+    changed = torch.empty(1, dtype=torch.int32, device=dev) if prev_label is not None else None
+    L.check(L.load().vg_kmeans_assign(x.data_ptr(), N, D, stride, K, center.data_ptr(), L.ptr(label), L.ptr(dist2),
+                                      L.ptr(resp), L.ptr(prev_label), L.ptr(changed), L.stream_ptr()), "vg_kmeans_assign")
+    return label, dist2, resp, changed
+
+
+def kmeans_update(x, label, K, old=None, dist2=None, want_sum=False, want_stats=None):
+    """Cluster counts, sums and new centres from the labels on the device (vg_kmeans_update): count int64 [K]; sum f64
+    [K, D] (``want_sum``); center f64 [K, D] = sum / count, an empty cluster keeping ``old`` f64 [K, D] (centres are made
+    only where ``old`` is given); stats f64 [2] = (sum of squared centre shifts, sum of ``dist2`` f64 [N]) -- made where
+    ``old`` or ``dist2`` is given unless ``want_stats=False``.  Rows whose label is outside [0, K) are skipped.  x f32
+    [N, D] (may be a strided view), label int32 [N].  Deterministic; two or three launches, no host sync.
+    -> (count, sum, center, stats), None for what was not made."""
+    N, D, stride = _feature_rows(x, "kmeans_update")
+    K = int(K)
+    _kmeans_shape("kmeans_update", N, D, K)
+    _kmeans_tensor("kmeans_update", "label", label, torch.int32, (N,))
+    if old is not None:
+        _kmeans_tensor("kmeans_update", "old", old, torch.float64, (K, D))
+    if dist2 is not None:
+        _kmeans_tensor("kmeans_update", "dist2", dist2, torch.float64, (N,))
+    if want_stats is None:
+        want_stats = old is not None or dist2 is not None
+    if dist2 is not None and not want_stats:
+        raise RuntimeError("kmeans_update: dist2 is only read for stats")
+    lib = L.load()
+    nbytes = _ws_query(lib.vg_kmeans_update_ws_bytes(N, D, K), "vg_kmeans_update_ws_bytes")
+    dev = x.device
+    count = torch.empty(K, dtype=torch.int64, device=dev)
+    sm = torch.empty(K, D, dtype=torch.float64, device=dev) if want_sum else None
+    center = torch.empty(K, D, dtype=torch.float64, device=dev) if old is not None else None
+    stats = torch.empty(2, dtype=torch.float64, device=dev) if want_stats else None
+    ws = WS.get("kmeans", nbytes, dev)
+    L.check(lib.vg_kmeans_update(x.data_ptr(), N, D, stride, K, label.data_ptr(), L.ptr(dist2), L.ptr(old), count.data_ptr(),
+                                 L.ptr(sm), L.ptr(center), L.ptr(stats), ws.data_ptr(), ws.numel() * 4, L.stream_ptr()),
+            "vg_kmeans_update")
+    return count, sm, center, stats
+
+
+def kmeans_seed(x, K, u=None, state=None):
+    """Plain k-means++ seeding on the device with no host sync (vg_kmeans_seed): idx int32 [K] (row numbers), center f64
+    [K, D] (those rows), mind2 f64 [N] (squared distance of every row to its nearest chosen row).  u: f64 [K] in [0, 1)
+    picks the rows; None: drawn in the kernel from state = int64[2] {seed, counter} with draw id DRAW_KMEANS_U.  x f32
+    [N, D] (may be a strided view).  2 K - 1 launches.  With fewer than K distinct rows the centres hold duplicates.
+    -> (idx, center, mind2)."""
+    N, D, stride = _feature_rows(x, "kmeans_seed")
+    K = int(K)
+    _kmeans_shape("kmeans_seed", N, D, K)
+    if u is not None:
+        _kmeans_tensor("kmeans_seed", "u", u, torch.float64, (K,))
+    if state is not None:
+        _need_cuda(state)
+        if state.dtype != torch.int64 or state.numel() != 2:
+            raise RuntimeError("kmeans_seed: state must be int64[2] = {seed, counter}")
+    if u is None and state is None:
+        raise RuntimeError("kmeans_seed: u is not injected, so the draws need the generator state")
+    lib = L.load()
+    nbytes = _ws_query(lib.vg_kmeans_seed_ws_bytes(N, D, K), "vg_kmeans_seed_ws_bytes")
+    dev = x.device
+    idx = torch.empty(K, dtype=torch.int32, device=dev)
+    center = torch.empty(K, D, dtype=torch.float64, device=dev)
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+    L.check(lib.vg_kmeans_seed(x.data_ptr(), N, D, stride, K, L.ptr(u), L.ptr(state), idx.data_ptr(), center.data_ptr(),
+                               ws.data_ptr(), nbytes, L.stream_ptr()), "vg_kmeans_seed")
+    return idx, center, ws[:N]
+
+
 def feat_stats_accum(x, sum, outer):
     """FID's running statistics on the device (vg_feat_stats_accum): sum f64 [D] += column sums of x, outer f64 [D,D] +=
     x^T x, every product and addition in f64 on the exactly converted f32 rows of x f32 [n,D] (n >= 0; x may be a view
