@@ -48,7 +48,7 @@ extern "C" {
 #define VG_ACT_LRELU   2   /* nn.LeakyReLU(slope)    main_vae.py:25, gan_code.py:62-82 */
 #define VG_ACT_TANH    3   /* nn.Tanh()              gan_code.py:50 (vg_tnconv epilogue only) */
 
-#define VG_ABI_VERSION 30  /* 2: vg_pack_desc.tile_start, SyncBN / WGAN / data-path entry points; 3: in-kernel noise (vg_*_rng);
+#define VG_ABI_VERSION 31  /* 2: vg_pack_desc.tile_start, SyncBN / WGAN / data-path entry points; 3: in-kernel noise (vg_*_rng);
                              4: vg_bn_finalize_act_forward, vg_bn_backward_finalize_apply;
                              7: vg_bce_pair_forward_backward;
                              8: vg_head_backward; round-3 prune -- the opt-in experiments of ABI 5 / 6 that measured slower (input prologue of
@@ -77,7 +77,9 @@ extern "C" {
                              28: Gaussian-mixture prior: vg_gmm_log_resp, vg_gmm_moments (+ _ws_bytes), vg_gmm_sample;
                              29: tiled denoising of images larger than the network: vg_tile_gather, vg_tile_blend;
                              30: k-means: vg_kmeans_assign, vg_kmeans_update (+ _ws_bytes), vg_kmeans_seed (+ _ws_bytes),
-                                 vg_kmeans_plan / vg_km_plan */
+                                 vg_kmeans_plan / vg_km_plan;
+                             31: decoded prior samples as the third Discriminator stream: vg_prior_forward (+ _rng),
+                                 vg_head_backward_g, vg_nhwc_grad_tanh_to_nhwc */
 int vg_abi_version(void);
 /* The library reads its optional kernel-selection switches (VG_* environment variables, DESIGN.md "Runtime switches")
  * ONCE, when it is loaded; nothing on a launch path calls getenv.  A process that changes one of them afterwards
@@ -484,11 +486,24 @@ int vg_nchw_grad_to_nhwc(const float* dy, const float* tanh_out, void* dx,
  * input gradient through the instance-noise add (NHWC) -- one pass instead of layout change + add + layout change. */
 int vg_nchw_grad_add_to_nhwc(const float* dy, const void* add_nhwc, const float* tanh_out, void* dx,
                              int B, int C, int H, int W, int CP, int dtype, void* stream);
+/* The tail backward of a Generator output that has no MSE branch (ABI 31; the decoded prior samples, DESIGN.md section
+ * 4.4o): dx = add_nhwc * (1 - t*t), t the NCHW f32 Tanh output, add_nhwc / dx in the engine layout, pad channels of dx
+ * zero.  Bit-identical in value to vg_nchw_grad_add_to_nhwc on dy == 0 (a zero may differ in sign) without reading a zero
+ * tensor: H * W % 4 == 0 and a 16-byte aligned t take four pixels per thread (16-byte loads of t), anything else one pixel
+ * per thread.  VG_EINVAL: a NULL pointer, a size <= 0, CP < C; VG_EALIGN: CP % 4 != 0 or add_nhwc / dx not 16-byte
+ * aligned; VG_ENOSUP: an unknown dtype. */
+int vg_nhwc_grad_tanh_to_nhwc(const void* add_nhwc, const float* tanh_out, void* dx,
+                              int B, int C, int H, int W, int CP, int dtype, void* stream);
 /* Reparameterisation (vaegan_code.py:75-77): lv=clamp(logvar,-10,10); z=mu+exp(.5 lv)*eps.
  * mulv: [B][MP] dtype, the fused fc_mu|fc_logvar output (main_vae.py:55-56): columns [0,L) = mu,
  * [L,2L) = logvar.  eps: [B][L] f32.  z: [B][ZP] dtype (pad = 0).  lv_clamped: [B][L] f32. */
 int vg_reparam_forward(const void* mulv, const float* eps, void* z, float* lv_clamped,
                        int B, int L, int MP, int ZP, int dtype, void* stream);
+/* The prior latent in the Generator's input layout (ABI 31): z [B][ZP] dtype = eps [B][L] f32, pad
+ * columns zero -- vg_reparam_forward on mu = 0, logvar = 0 bit for bit (f32 exact, bf16 round-to-nearest-even), without the
+ * mulv and lv_clamped tensors.  One 16 / 8-byte store per four columns.  VG_EINVAL: a NULL pointer, B or L <= 0, ZP < L;
+ * VG_EALIGN: ZP % 4 != 0 or z not 16-byte aligned; VG_ENOSUP: an unknown dtype or B * ZP >= 2^31. */
+int vg_prior_forward(const float* eps, void* z, int B, int L, int ZP, int dtype, void* stream);
 /* KL (vaegan_code.py:114): out[0] = -0.5*sum(1+lv-mu^2-exp(lv)) / divisor. */
 int vg_kl_forward(const void* mulv, const float* lv_clamped, int B, int L, int MP, float divisor,
                   float* out, int dtype, void* stream);
@@ -523,6 +538,16 @@ int vg_bce_pair_forward_backward(const float* p, float target0, float target1, i
 int vg_head_backward(const float* p, const void* x, const void* w, void* dx, float* dw, float* dlogit, int B, int groups,
                      float target0, float target1, float gscale, float* loss, int accumulate_loss, int accumulate_dw,
                      int K, int C, int HW, int dtype, void* stream);
+/* vg_head_backward for groups in 1..3 with one target per group (ABI 31; the Discriminator update of the prior stream,
+ * p = [B real | B reconstructed | B decoded prior samples]): rows [g B, (g + 1) B) are held against
+ * target<g>; targets of groups that do not exist are ignored.  loss[0] (+)= the sum of the groups' BCE means, added in group
+ * order; dlogit, dx and dw as documented for vg_head_backward.  Bit-identical to `groups` calls of vg_bce_forward_backward
+ * (the later ones accumulating) followed by vg_dot_sigmoid_backward and vg_dot_wgrad over all groups * B rows; for
+ * groups <= 2 bit-identical to vg_head_backward, which forwards to it.  VG_EINVAL: a NULL p / x / w / loss, B <= 0, groups
+ * outside 1..3, C * HW != K; VG_EALIGN: K % 4 != 0; VG_ENOSUP: B * groups > 4096 or an unknown dtype. */
+int vg_head_backward_g(const float* p, const void* x, const void* w, void* dx, float* dw, float* dlogit, int B, int groups,
+                       float target0, float target1, float target2, float gscale, float* loss, int accumulate_loss,
+                       int accumulate_dw, int K, int C, int HW, int dtype, void* stream);
 /* Sibling loop train_wgan (gan_code.py:306-315, :328): loss[0] (+)= sign*mean_b p[b]; dp[b] = sign*gscale/B. */
 int vg_mean_forward_backward(const float* p, float sign, int B, float gscale,
                              float* loss, int accumulate, float* dp, void* stream);
@@ -619,6 +644,9 @@ int vg_nhwc_tanh_to_nchw_noisy_rng(const void* x, float* y_nchw, const uint64_t*
                                    void* stream);                                             /* vaegan_code.py:83,92 */
 int vg_reparam_forward_rng(const void* mulv, const uint64_t* rng, int draw, void* z, float* lv_clamped,
                            int B, int L, int MP, int ZP, int dtype, void* stream);            /* vaegan_code.py:75-78 */
+/* vg_prior_forward on draw `draw` of the current iteration (ABI 31): equal to the injected form fed what vg_randn
+ * materialises for that draw.  VG_EINVAL also for draw outside [0, 256). */
+int vg_prior_forward_rng(const uint64_t* rng, int draw, void* z, int B, int L, int ZP, int dtype, void* stream);
 int vg_reparam_kl_backward_rng(const void* mulv, const float* lv_clamped, const uint64_t* rng, int draw,
                                const void* dz, float kl_scale, void* dmulv, int B, int L, int MP, int ZP,
                                int dtype, void* stream);

@@ -22,7 +22,7 @@ VG_GNORM_PARTS = 512
 VG_PROLOGUE_MAX = 4
 VG_TILE_MAX_COVER = 8
 VG_LRS_CONST, VG_LRS_LINEAR, VG_LRS_COSINE, VG_LRS_EXP, VG_LRS_STEP = 0, 1, 2, 3, 4
-ABI_VERSION = 30
+ABI_VERSION = 31
 
 VG_ENOSUP = -3
 _ERR = {-1: "VG_EINVAL (bad shape/size/flag)", -2: "VG_EALIGN (16-byte contract violated)",
@@ -181,6 +181,10 @@ SIGNATURES = {
     "vg_bce_forward_backward": (c_int, [_P, _F, _I, _F, _P, _I, _P, _P]),
     "vg_bce_pair_forward_backward": (c_int, [_P, _F, _F, _I, _F, _P, _I, _P, _P]),
     "vg_head_backward": (c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _F, _F, _F, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "vg_head_backward_g": (c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _F, _F, _F, _F, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "vg_prior_forward": (c_int, [_P, _P, _I, _I, _I, _I, _P]),
+    "vg_prior_forward_rng": (c_int, [_P, _I, _P, _I, _I, _I, _I, _P]),
+    "vg_nhwc_grad_tanh_to_nhwc": (c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "vg_mean_forward_backward": (c_int, [_P, _F, _I, _F, _P, _I, _P, _P]),
     "vg_clamp": (c_int, [_P, _L, _F, _F, _P]),
     "vg_mse_forward_backward": (c_int, [_P, _P, _L, _F, _P, _P, _P, _I, _P]),

@@ -213,6 +213,51 @@ __global__ __launch_bounds__(256) void nchw_grad_to_nhwc_kernel(const float* __r
     }
 }
 
+// The prior stream's tail backward: x_p = tanh(G(z_p)) has no MSE branch, so the gradient that
+// reaches it is the Discriminator's input gradient alone, dx = add * (1 - t^2) -- nchw_grad_to_nhwc_kernel on dy == 0
+// without the pass over a zero tensor.  X4: four consecutive pixels of one image per thread (H*W % 4 == 0), t read as
+// one 16-byte load per channel; else one pixel per thread, the ragged form.  Pad channels are written as zeros.
+template <int DT, bool X4>
+__global__ __launch_bounds__(256) void nhwc_grad_tanh_kernel(const void* __restrict__ add, const float* __restrict__ t,
+                                                             void* __restrict__ dx, int64_t nitems, int C, int HW, int CP) {
+    constexpr int P = X4 ? 4 : 1;
+    for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < nitems; q += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t i0 = q * P;
+        const int64_t b = i0 / HW;
+        const int64_t hw = i0 - b * HW;
+        for (int c0 = 0; c0 < CP; c0 += 4) {
+            float d[4][P];                                   // 1 - t^2 per (channel, pixel); pad channels: unused
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int c = c0 + k;
+#pragma unroll
+                for (int p = 0; p < P; ++p) d[k][p] = 0.f;
+                if (c < C) {
+                    const int64_t src = (b * C + c) * HW + hw;
+                    if constexpr (X4) {
+                        const float4 tv = *reinterpret_cast<const float4*>(t + src);
+                        d[k][0] = 1.f - tv.x * tv.x; d[k][1] = 1.f - tv.y * tv.y;
+                        d[k][2] = 1.f - tv.z * tv.z; d[k][3] = 1.f - tv.w * tv.w;
+                    } else {
+                        const float tv = t[src];
+                        d[k][0] = 1.f - tv * tv;
+                    }
+                }
+            }
+#pragma unroll
+            for (int p = 0; p < P; ++p) {
+                const float4 a = load4<DT>(add, (i0 + p) * CP + c0);
+                float4 o;
+                o.x = c0 + 0 < C ? a.x * d[0][p] : 0.f;
+                o.y = c0 + 1 < C ? a.y * d[1][p] : 0.f;
+                o.z = c0 + 2 < C ? a.z * d[2][p] : 0.f;
+                o.w = c0 + 3 < C ? a.w * d[3][p] : 0.f;
+                store4<DT>(dx, (i0 + p) * CP + c0, o);
+            }
+        }
+    }
+}
+
 // ---- reparameterisation / KL ----------------------------------------------------------------------
 template <int DT>
 __global__ void reparam_fwd_kernel(const void* __restrict__ mulv, const NoiseSrc eps, void* __restrict__ z,
@@ -229,6 +274,30 @@ __global__ void reparam_fwd_kernel(const void* __restrict__ mulv, const NoiseSrc
             zv = mu + expf(0.5f * lv) * noise_at(eps, b * L + j);
         }
         store1<DT>(z, i, zv);
+    }
+}
+
+// z_p = eps_prior in the layout reparam_fwd_kernel writes (vaegan_code.py:77 on mu = 0, logvar = 0: z = 0 + exp(0) * eps),
+// four columns -- one 16 / 8-byte store -- per thread; quad: rows of eps are whole 16-byte units (L % 4 == 0, injected
+// eps 16-byte aligned), so a thread's four draws are one 16-byte load or one Philox block.
+template <int DT>
+__global__ __launch_bounds__(256) void prior_fwd_kernel(const NoiseSrc eps, void* __restrict__ z, int B, int L, int ZP,
+                                                        int quad) {
+    const int Q = ZP >> 2;
+    const int total = B * Q;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
+        const int b = i / Q, j = (i - b * Q) * 4;
+        float v[4] = {0.f, 0.f, 0.f, 0.f};
+        if (quad && j + 4 <= L) {
+            const Normal4 n = noise4_at(eps, (int64_t)b * L + j);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) v[k] = 0.f + n.v[k];
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (j + k < L) v[k] = 0.f + noise_at(eps, (int64_t)b * L + j + k);
+        }
+        store4<DT>(z, (int64_t)b * ZP + j, float4{v[0], v[1], v[2], v[3]});
     }
 }
 
@@ -404,23 +473,24 @@ __device__ __forceinline__ float bce_term(float pv, float target) {
 // What vaegan_code.py:99-104 / :115,133 run behind the head: bce (loss + dL/dp), sigmoid backward, the head's data
 // gradient dx[b,k] = dlogit[b] * w[k] and its weight gradient dw[k] = sum_b dlogit[b] * x[b,k] were three launches
 // (bce[_pair]_kernel, dot_sigmoid_bwd_kernel, dot_wgrad_kernel).  Here a workgroup owns 64 columns k for ALL rows: it
-// re-derives dlogit[0..groups*B) into LDS (B*groups floats; the arithmetic of the three kernels, operation for operation),
+// re-derives dlogit[0..groups*B) into LDS (B*groups floats, groups <= 3 with one target each; the arithmetic of the three
+// kernels, operation for operation),
 // forms its dw columns with dot_wgrad_kernel's lane mapping and summation order and writes its dx columns; workgroup 0
-// also writes the loss with bce_pair_kernel's mapping -- every output is bit-identical to the three-launch path.
+// also writes the loss with bce_[pair_]kernel's mapping per group -- every output is bit-identical to the three-launch path.
 constexpr int HB_MAXROWS = 4096;
 template <int DT>
 __global__ __launch_bounds__(1024) void head_bwd_kernel(const float* __restrict__ p, const void* __restrict__ x,
                                                         const void* __restrict__ w, void* __restrict__ dx,
                                                         float* __restrict__ dw, float* __restrict__ dlogit_out, int B,
-                                                        int groups, float t0, float t1, float gscale,
+                                                        int groups, float t0, float t1, float t2, float gscale,
                                                         float* __restrict__ loss, int accumulate_loss, int accumulate_dw,
                                                         int K, int C, int HW) {
     __shared__ float dl[HB_MAXROWS];
     __shared__ float red[16][64];
-    __shared__ double lred[2][4];
+    __shared__ double lred[3][4];
     const int R = B * groups;
     for (int r = threadIdx.x; r < R; r += 1024) {
-        const float target = r < B ? t0 : t1;
+        const float target = r < B ? t0 : (r < 2 * B ? t1 : t2);
         const float pv = p[r];
         const float dpv = gscale * ((pv - target) / fmaxf((1.f - pv) * pv, 1e-12f)) / (float)B;     // bce_kernel
         const float d = dpv * (pv * (1.f - pv));                                                     // dot_sigmoid_bwd_kernel
@@ -429,7 +499,7 @@ __global__ __launch_bounds__(1024) void head_bwd_kernel(const float* __restrict_
     }
     if (blockIdx.x == 0 && threadIdx.x < 256) {             // the loss: bce_pair_kernel's 256-thread mapping per half
         for (int h = 0; h < groups; ++h) {
-            const float target = h == 0 ? t0 : t1;
+            const float target = h == 0 ? t0 : (h == 1 ? t1 : t2);
             double sacc = 0.0;
             for (int b = threadIdx.x; b < B; b += 256) {
                 sacc += (double)bce_term(p[h * B + b], target);
@@ -442,7 +512,8 @@ __global__ __launch_bounds__(1024) void head_bwd_kernel(const float* __restrict_
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         const float v0 = (float)((lred[0][0] + lred[0][1] + lred[0][2] + lred[0][3]) / (double)B);
         float out = accumulate_loss ? loss[0] + v0 : v0;
-        if (groups == 2) out = out + (float)((lred[1][0] + lred[1][1] + lred[1][2] + lred[1][3]) / (double)B);
+        for (int h = 1; h < groups; ++h)            // as the accumulating launches of bce_kernel add them, in group order
+            out = out + (float)((lred[h][0] + lred[h][1] + lred[h][2] + lred[h][3]) / (double)B);
         loss[0] = out;
     }
     // ---- dw: 64 columns x 16 batch lanes, four loads in flight, fixed-order combine (dot_wgrad_kernel) ----
@@ -807,6 +878,27 @@ extern "C" int vg_nchw_grad_add_to_nhwc(const float* dy, const void* add_nhwc, c
     return VG_LAUNCH_RC();
 }
 
+extern "C" int vg_nhwc_grad_tanh_to_nhwc(const void* add_nhwc, const float* tanh_out, void* dx, int B, int C, int H, int W,
+                                         int CP, int dtype, void* stream) {
+    CHECK_DT();
+    VG_CHECK_ARG(add_nhwc && tanh_out && dx && B > 0 && C > 0 && H > 0 && W > 0 && CP >= C, VG_EINVAL);
+    VG_CHECK_ARG(CP % 4 == 0 && vg_aligned16(add_nhwc) && vg_aligned16(dx), VG_EALIGN);
+    const int64_t npix = (int64_t)B * H * W;
+    const int HW = H * W;
+    if (HW % 4 == 0 && vg_aligned16(tanh_out)) {
+        if (dtype == VG_F32) hipLaunchKernelGGL((nhwc_grad_tanh_kernel<VG_F32, true>), dim3(blocks_for(npix / 4)), dim3(256), 0,
+                                                vg_stream(stream), add_nhwc, tanh_out, dx, npix / 4, C, HW, CP);
+        else hipLaunchKernelGGL((nhwc_grad_tanh_kernel<VG_BF16, true>), dim3(blocks_for(npix / 4)), dim3(256), 0,
+                                vg_stream(stream), add_nhwc, tanh_out, dx, npix / 4, C, HW, CP);
+    } else {
+        if (dtype == VG_F32) hipLaunchKernelGGL((nhwc_grad_tanh_kernel<VG_F32, false>), dim3(blocks_for(npix)), dim3(256), 0,
+                                                vg_stream(stream), add_nhwc, tanh_out, dx, npix, C, HW, CP);
+        else hipLaunchKernelGGL((nhwc_grad_tanh_kernel<VG_BF16, false>), dim3(blocks_for(npix)), dim3(256), 0,
+                                vg_stream(stream), add_nhwc, tanh_out, dx, npix, C, HW, CP);
+    }
+    return VG_LAUNCH_RC();
+}
+
 extern "C" int vg_nchw_grad_to_nhwc(const float* dy, const float* tanh_out, void* dx, int B, int C, int H, int W,
                                     int CP, int dtype, void* stream) {
     CHECK_DT();
@@ -833,6 +925,26 @@ extern "C" int vg_reparam_forward_rng(const void* mulv, const uint64_t* rng, int
     DISPATCH_DT(reparam_fwd_kernel, dim3(blocks_for((int64_t)B * ZP)), dim3(256), vg_stream(stream), mulv,
                 (NoiseSrc{nullptr, (const unsigned long long*)rng, (uint32_t)draw}), z, lv_clamped, B, L, MP, ZP);
     return VG_LAUNCH_RC();
+}
+
+static int prior_forward(const NoiseSrc src, void* z, int B, int L, int ZP, int dtype, void* stream) {
+    VG_CHECK_ARG(ZP % 4 == 0 && vg_aligned16(z), VG_EALIGN);
+    VG_CHECK_ARG((int64_t)B * ZP < (int64_t)1 << 31 && (int64_t)B * L < (int64_t)1 << 31, VG_ENOSUP);
+    const int quad = L % 4 == 0 && (src.eps == nullptr || vg_aligned16(src.eps));
+    DISPATCH_DT(prior_fwd_kernel, dim3(blocks_for((int64_t)B * (ZP / 4))), dim3(256), vg_stream(stream), src, z, B, L, ZP, quad);
+    return VG_LAUNCH_RC();
+}
+
+extern "C" int vg_prior_forward(const float* eps, void* z, int B, int L, int ZP, int dtype, void* stream) {
+    CHECK_DT();
+    VG_CHECK_ARG(eps && z && B > 0 && L > 0 && ZP >= L, VG_EINVAL);
+    return prior_forward(NoiseSrc{eps, nullptr, 0u}, z, B, L, ZP, dtype, stream);
+}
+
+extern "C" int vg_prior_forward_rng(const uint64_t* rng, int draw, void* z, int B, int L, int ZP, int dtype, void* stream) {
+    CHECK_DT();
+    VG_CHECK_ARG(rng && z && draw >= 0 && draw < 256 && B > 0 && L > 0 && ZP >= L, VG_EINVAL);
+    return prior_forward(NoiseSrc{nullptr, (const unsigned long long*)rng, (uint32_t)draw}, z, B, L, ZP, dtype, stream);
 }
 
 extern "C" int vg_kl_forward(const void* mulv, const float* lv_clamped, int B, int L, int MP, float divisor, float* out,
@@ -927,16 +1039,24 @@ extern "C" int vg_bce_pair_forward_backward(const float* p, float target0, float
     return VG_LAUNCH_RC();
 }
 
+extern "C" int vg_head_backward_g(const float* p, const void* x, const void* w, void* dx, float* dw, float* dlogit, int B,
+                                  int groups, float target0, float target1, float target2, float gscale, float* loss,
+                                  int accumulate_loss, int accumulate_dw, int K, int C, int HW, int dtype, void* stream) {
+    CHECK_DT();
+    VG_CHECK_ARG(p && x && w && loss && B > 0 && groups >= 1 && groups <= 3 && K > 0 && C > 0 && HW > 0 && C * HW == K, VG_EINVAL);
+    VG_CHECK_ARG(K % 4 == 0, VG_EALIGN);
+    VG_CHECK_ARG((int64_t)B * groups <= HB_MAXROWS, VG_ENOSUP);
+    DISPATCH_DT(head_bwd_kernel, dim3((K + 63) / 64), dim3(1024), vg_stream(stream), p, x, w, dx, dw, dlogit, B, groups,
+                target0, target1, target2, gscale, loss, accumulate_loss, accumulate_dw, K, C, HW);
+    return VG_LAUNCH_RC();
+}
+
 extern "C" int vg_head_backward(const float* p, const void* x, const void* w, void* dx, float* dw, float* dlogit, int B,
                                 int groups, float target0, float target1, float gscale, float* loss, int accumulate_loss,
                                 int accumulate_dw, int K, int C, int HW, int dtype, void* stream) {
-    CHECK_DT();
-    VG_CHECK_ARG(p && x && w && loss && B > 0 && (groups == 1 || groups == 2) && K > 0 && C > 0 && HW > 0 && C * HW == K, VG_EINVAL);
-    VG_CHECK_ARG(K % 4 == 0, VG_EALIGN);
-    VG_CHECK_ARG(B * groups <= HB_MAXROWS, VG_ENOSUP);
-    DISPATCH_DT(head_bwd_kernel, dim3((K + 63) / 64), dim3(1024), vg_stream(stream), p, x, w, dx, dw, dlogit, B, groups,
-                target0, target1, gscale, loss, accumulate_loss, accumulate_dw, K, C, HW);
-    return VG_LAUNCH_RC();
+    VG_CHECK_ARG(groups == 1 || groups == 2, dtype == VG_F32 || dtype == VG_BF16 ? VG_EINVAL : VG_ENOSUP);
+    return vg_head_backward_g(p, x, w, dx, dw, dlogit, B, groups, target0, target1, 0.f, gscale, loss, accumulate_loss,
+                              accumulate_dw, K, C, HW, dtype, stream);
 }
 
 extern "C" int vg_mean_forward_backward(const float* p, float sign, int B, float gscale, float* loss, int accumulate,

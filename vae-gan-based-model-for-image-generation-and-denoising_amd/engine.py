@@ -470,7 +470,7 @@ class StackEngine:
         return out
 
     def backward(self, ctxpack, dout: torch.Tensor, need_dx: bool, sink: GradSink, param_grads: bool = True,
-                 on_grads=None, head_loss=None, feat=None):
+                 on_grads=None, head_loss=None, feat=None, weight_grad_groups: int = 1):
         """dout: gradient w.r.t. forward()'s output.  Returns the gradient w.r.t. the NHWC input (or None).
         param_grads=False skips every weight/bias/BN-parameter gradient (legal when the caller discards
         them, e.g. the generator-loss pass through the discriminator).
@@ -479,11 +479,17 @@ class StackEngine:
         head_loss = (target0, target1, groups, gscale, loss_slot, accumulate): instead of `dout`, for a stack that ends
         in the Discriminator's head -- the BCE of its output probabilities against target0 (first group of rows) / target1
         (second group), its gradient, the sigmoid backward and the head's data / weight gradients run as ONE launch
-        (ops.head_backward; vaegan_code.py:99-104, :115); loss_slot[0] (+)= the loss.
+        (ops.head_backward; vaegan_code.py:99-104, :115); loss_slot[0] (+)= the loss.  groups = 3 takes a seventh entry,
+        target2 (third group of rows; ops.head_backward_g: the prior stream's Discriminator update).
         feat = (l, f_real, gscale, loss_slot): the Discriminator-feature reconstruction loss at stage l (check_feat_stage):
         when the loop reaches stage l, BEFORE its BatchNorm backward, ops.feat_mse_forward_backward writes
         loss_slot[0] = mean((A_l - f_real)^2) and adds gscale * 2 (A_l - f_real) / n onto dA in place (A_l = ctx[l + 1]["x"],
         the activation this pass stored; f_real a constant of the same shape) -- dA then carries both branches.
+        weight_grad_groups = g > 1, for a grouped pass (forward(groups=g)): every convolution / head WEIGHT gradient is formed
+        group after group over that group's rows, the later ones accumulating -- the launches, and therefore the bits, of g
+        separate passes (one launch over all rows sums in another order).  Everything else of a grouped backward already is
+        what separate passes compute, bit for bit: the BatchNorm backward and its parameter gradients are per group, a data
+        gradient's rows do not mix.
         Everything runs on the current stream: forking weight gradients onto a second stream (three schedules, rounds 1
         and 2) measured slower every time and is gone ("Concurrency does not pay")."""
         ctx, B, train = ctxpack
@@ -500,13 +506,23 @@ class StackEngine:
             want_dx = need_dx or i > 0
             if st.kind == "head" and head_loss is not None:
                 K = st.hin * st.hin * G.padc(st.cin, dt)
-                t0, t1, grp, gscale, slot, acc_loss = head_loss
+                t0, t1, grp, gscale, slot, acc_loss = head_loss[:6]
                 gw, acc = sink.get(st.conv.weight) if param_grads else (None, False)
-                dA = ops.head_backward(c["p"], c["x"], packs[i]["fprop"], B // grp, grp, t0, t1, gscale, slot, acc_loss, gw,
-                                       acc, K, G.padc(st.cin, dt), st.hin * st.hin, dt, want_dx)
+                if grp == 3:
+                    split = gw is not None and weight_grad_groups > 1     # the launch leaves dlogit, the weight gradient follows
+                    dlogit = torch.empty_like(c["p"]) if split else None
+                    dA = ops.head_backward_g(c["p"], c["x"], packs[i]["fprop"], B // grp, (t0, t1, head_loss[6]), gscale, slot,
+                                             acc_loss, None if split else gw, acc, K, G.padc(st.cin, dt), st.hin * st.hin, dt,
+                                             want_dx, dlogit=dlogit)
+                    if split:
+                        self._head_wgrad(st, c["x"], dlogit, gw, acc, B, K, weight_grad_groups)
+                else:
+                    dA = ops.head_backward(c["p"], c["x"], packs[i]["fprop"], B // grp, grp, t0, t1, gscale, slot, acc_loss,
+                                           gw, acc, K, G.padc(st.cin, dt), st.hin * st.hin, dt, want_dx)
                 if self.trace is not None:
                     self.trace.append(dict(stage=i, what="head_bwd", p=c["p"].clone(), x=c["x"].clone(), dp=None,
-                                           bce=(t0, t1, grp, gscale), dX=None if dA is None else dA.clone(), acc=acc,
+                                           bce=(t0, t1, grp, gscale) + tuple(head_loss[6:7]),
+                                           dX=None if dA is None else dA.clone(), acc=acc,
                                            gw=None if gw is None else gw.clone()))
                 if param_grads and on_grads is not None:
                     on_grads(i)
@@ -517,7 +533,7 @@ class StackEngine:
                 gw, acc = None, False
                 if param_grads:
                     gw, acc = sink.get(st.conv.weight)
-                    ops.dot_wgrad(c["x"], dlogit, gw, B, K, G.padc(st.cin, dt), st.hin * st.hin, acc, dt)
+                    self._head_wgrad(st, c["x"], dlogit, gw, acc, B, K, weight_grad_groups)
                     if on_grads is not None:
                         on_grads(i)
                 if self.trace is not None:
@@ -531,12 +547,15 @@ class StackEngine:
             dA = dA.view(yshape) if dA.shape != yshape else dA
             if feat is not None and i == feat[0]:
                 _, f_real, fscale, fslot = feat
-                f_fake = ctx[i + 1]["x"]
-                dA_in = dA.clone() if self.trace is not None else None
-                ops.feat_mse_forward_backward(f_fake, f_real.view(f_fake.shape), dA, fscale, fslot, False, dt)
+                # f_real has the rows the loss is taken over: all of this pass's, or the leading group of a grouped pass (the
+                # reconstruction's half of the prior stream's [reconstruction | decoded prior samples] pass)
+                nf = f_real.shape[0]
+                f_fake, dA_f = ctx[i + 1]["x"][:nf], dA[:nf]
+                dA_in = dA_f.clone() if self.trace is not None else None
+                ops.feat_mse_forward_backward(f_fake, f_real.view(f_fake.shape), dA_f, fscale, fslot, False, dt)
                 if self.trace is not None:
                     self.trace.append(dict(stage=i, what="feat", f_fake=f_fake.clone(), f_real=f_real.clone(), dA_in=dA_in,
-                                           dA=dA.clone(), gscale=fscale, loss=fslot.clone()))
+                                           dA=dA_f.clone(), gscale=fscale, loss=fslot.clone()))
             gg_, gb_, acc_g = None, None, False
             if st.bn is not None:
                 if param_grads:
@@ -557,7 +576,7 @@ class StackEngine:
             masked = False
             if param_grads:
                 acc_before = st.conv.weight.grad is not None and not getattr(st.conv.weight, "_vg_fresh", False)
-                self._param_grads(i, st, c, dY, B, rows, OC, sink)
+                self._param_grads(i, st, c, dY, B, rows, OC, sink, weight_grad_groups)
                 if on_grads is not None:
                     on_grads(i)
                 if self.trace is not None:
@@ -591,8 +610,30 @@ class StackEngine:
                 dA = None
         return dA
 
-    def _param_grads(self, i, st, c, dY, B, rows, OC, sink):
+    def _head_wgrad(self, st, x, dlogit, gw, acc, B, K, groups=1):
+        """The head's weight gradient over B rows, as `groups` accumulating launches over B / groups rows each."""
+        Bg, dt = B // groups, self.dtype
+        for g in range(groups):
+            rows = slice(g * Bg, (g + 1) * Bg)
+            ops.dot_wgrad(x[rows], dlogit[rows], gw, Bg, K, G.padc(st.cin, dt), st.hin * st.hin, acc or g > 0, dt)
+
+    def _param_grads(self, i, st, c, dY, B, rows, OC, sink, groups=1):
         dt = self.dtype
+        if groups > 1:
+            # a grouped pass, weight gradient group after group (backward: weight_grad_groups).  Only bias-free convolutions
+            # run grouped (the Discriminator, can_group)
+            if st.kind != "conv" or st.has_bias:
+                raise RuntimeError("weight_grad_groups needs a stack of bias-free convolutions")
+            gw, acc = sink.get(st.conv.weight)
+            Bg = B // groups
+            wg, ew = self.spec(i, Bg, "wgrad"), self.edge_wg(i, Bg)
+            for g in range(groups):
+                dYg, xg = dY[g * Bg:(g + 1) * Bg], c["x"][g * Bg:(g + 1) * Bg]
+                if ew is not None and gw.is_contiguous():
+                    ops.edge_wgrad(ew, dYg, xg, gw, acc or g > 0, alg=st.alg(Bg, dt))
+                else:
+                    ops.wgrad(wg, dYg, xg, gw, acc or g > 0, dt, alg=st.alg(Bg, dt))
+            return
         wg = self.spec(i, B, "wgrad")
         if st.kind == "linear2":
             # one wgrad / one bias reduction for the fused [fc_mu | fc_logvar] head, written straight into the pair's

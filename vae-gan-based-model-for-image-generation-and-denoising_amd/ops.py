@@ -1439,6 +1439,19 @@ def nchw_grad_add_to_nhwc(dy, add_nhwc, tanh_out, CP, dtype):
     return dx
 
 
+def nhwc_grad_tanh_to_nhwc(add_nhwc, tanh_out, CP, dtype):
+    """dx NHWC = add_nhwc * (1 - tanh_out^2): nchw_grad_add_to_nhwc for an image without an MSE branch (dy == 0), i.e. the
+    decoded prior samples; tanh_out NCHW f32, add_nhwc [B, H, W, CP] in the engine dtype."""
+    _need_cuda(add_nhwc, tanh_out)
+    B, C, H, W = tanh_out.shape
+    if tanh_out.dtype != torch.float32 or add_nhwc.dtype != TORCH_DT[dtype] or add_nhwc.numel() != B * H * W * CP or CP < C:
+        raise RuntimeError("nhwc_grad_tanh_to_nhwc: tanh_out f32 [B,C,H,W], add_nhwc [B,H,W,CP] in the engine dtype")
+    dx = empty_act((B, H, W, CP), dtype, tanh_out.device)
+    L.check(L.load().vg_nhwc_grad_tanh_to_nhwc(add_nhwc.data_ptr(), tanh_out.data_ptr(), dx.data_ptr(), B, C, H, W, CP, dtype,
+                                               L.stream_ptr()), "vg_nhwc_grad_tanh_to_nhwc")
+    return dx
+
+
 def nchw_grad_to_nhwc(dy, tanh_out, CP, dtype):
     _need_cuda(dy, tanh_out)
     B, C, H, W = dy.shape
@@ -1462,6 +1475,29 @@ def reparam_forward(mulv, eps, L_dim, ZP, dtype):
     L.check(L.load().vg_reparam_forward(mulv.data_ptr(), eps.data_ptr(), z.data_ptr(), lvc.data_ptr(), B, L_dim, MP,
                                         ZP, dtype, L.stream_ptr()), "vg_reparam_forward")
     return z, lvc
+
+
+def prior_forward(eps, B, L_dim, ZP, dtype):
+    """z_p [B, 1, 1, ZP] in the engine dtype = eps [B, L_dim] (f32 tensor, or a NoiseDraw generated in the kernel), pad columns
+    zero: the Generator's input for a latent drawn from the prior N(0, I) (vg_prior_forward; reparam_forward on mu = 0,
+    logvar = 0 bit for bit)."""
+    rng = isinstance(eps, NoiseDraw)
+    if rng:
+        dev = eps.state.device
+    else:
+        _need_cuda(eps)
+        if eps.dtype != torch.float32 or eps.numel() != B * L_dim:
+            raise RuntimeError("prior_forward: eps must be f32 [B, L]")
+        dev = eps.device
+    if B <= 0 or L_dim <= 0 or ZP < L_dim or ZP % 4 != 0:
+        raise ValueError("prior_forward: B, L > 0 and ZP >= L, a multiple of 4 (geometry.padc)")
+    z = empty_act((B, 1, 1, ZP), dtype, dev)
+    if rng:
+        L.check(L.load().vg_prior_forward_rng(eps.state.data_ptr(), eps.draw, z.data_ptr(), B, L_dim, ZP, dtype,
+                                              L.stream_ptr()), "vg_prior_forward_rng")
+        return z
+    L.check(L.load().vg_prior_forward(eps.data_ptr(), z.data_ptr(), B, L_dim, ZP, dtype, L.stream_ptr()), "vg_prior_forward")
+    return z
 
 
 def kl_forward(mulv, lvc, L_dim, divisor, dtype, out=None, mse=None):
@@ -1529,6 +1565,30 @@ def head_backward(p, x, w, B, groups, target0, target1, gscale, loss, accumulate
     L.check(L.load().vg_head_backward(p.data_ptr(), x.data_ptr(), w.data_ptr(), L.ptr(dx), L.ptr(dw), 0, B, groups,
                                       target0, target1, gscale, loss.data_ptr(), 1 if accumulate_loss else 0,
                                       1 if accumulate_dw else 0, K, C, HW, dtype, L.stream_ptr()), "vg_head_backward")
+    return dx
+
+
+def head_backward_g(p, x, w, B, targets, gscale, loss, accumulate_loss, dw, accumulate_dw, K, C, HW, dtype, need_dx,
+                    dlogit=None):
+    """head_backward for len(targets) in 1..3 groups of B rows with one target each (vg_head_backward_g; the prior stream's
+    Discriminator update holds [real | reconstruction | decoded prior samples] against three targets in one launch).
+    dlogit (f32 [groups * B], optional): receives the gradient w.r.t. the logits."""
+    _need_cuda(p, x, w, loss, dw, dlogit)
+    groups = len(targets)
+    if not 1 <= groups <= 3:
+        raise ValueError("head_backward_g: one to three groups")
+    if p.dtype != torch.float32 or p.numel() != groups * B or x.numel() != groups * B * K or w.numel() < K:
+        raise RuntimeError("head_backward_g: p must be f32 [groups * B], x [groups * B, K], w [K]")
+    if x.dtype != TORCH_DT[dtype] or w.dtype != TORCH_DT[dtype] or loss.dtype != torch.float32 or \
+            (dw is not None and (dw.dtype != torch.float32 or dw.numel() != C * HW)):
+        raise RuntimeError("head_backward_g: x / w in the engine dtype, loss and dw (C * HW elements) f32")
+    if dlogit is not None and (dlogit.dtype != torch.float32 or dlogit.numel() != groups * B):
+        raise RuntimeError("head_backward_g: dlogit must be f32 [groups * B]")
+    t = [float(v) for v in targets] + [0.0] * (3 - groups)
+    dx = torch.empty_like(x) if need_dx else None
+    L.check(L.load().vg_head_backward_g(p.data_ptr(), x.data_ptr(), w.data_ptr(), L.ptr(dx), L.ptr(dw), L.ptr(dlogit), B, groups, t[0],
+                                        t[1], t[2], gscale, loss.data_ptr(), 1 if accumulate_loss else 0,
+                                        1 if accumulate_dw else 0, K, C, HW, dtype, L.stream_ptr()), "vg_head_backward_g")
     return dx
 
 

@@ -23,6 +23,9 @@ from .gradclip import ClipOption
 from .optim import lr_report
 
 LOSS_NAMES = ("recon_loss", "kl_loss", "g_loss_adv", "d_loss_1", "d_loss_2")
+# draw ids of the prior stream in the iteration's noise stream (0, 1, 2: eps_z, eps_real, eps_recon): the prior latent and the
+# instance noise of the decoded prior samples
+DRAW_PRIOR, DRAW_XP = 3, 4
 # more than two periods of c10d's NCCL watchdog (ProcessGroupNCCL::kWatchdogThreadSleepMillis = 100): see _capture
 WATCHDOG_PASS_SECONDS = 0.25
 
@@ -48,7 +51,8 @@ class VAEGANTrainer(ClipOption):
                  alpha_adv: float = 0.1, noise_sigma: float = 0.05, real_label: float = 0.9, fake_label: float = 0.1,
                  d_iters: int = 2, elide_dead_grads: bool = False, reducer=None, group_d_passes: bool = True,
                  sync_bn: bool = False, feat_layer: Optional[int] = None, alpha_feat: float = 0.0, alpha_pix: float = 1.0,
-                 alpha_ssim: float = 0.0, hole_weight: float = 1.0, ema=None, max_grad_norm=None, augment=None):
+                 alpha_ssim: float = 0.0, hole_weight: float = 1.0, ema=None, max_grad_norm=None, augment=None,
+                 prior_stream: bool = False):
         self.E, self.G, self.D = encoder, decoder, discriminator
         self.opt_E, self.opt_G, self.opt_D = opt_E, opt_Dec, opt_Dis
         self.alpha_kl, self.alpha_adv, self.sigma = alpha_kl, alpha_adv, noise_sigma          # :49-50, :91-92
@@ -101,6 +105,18 @@ class VAEGANTrainer(ClipOption):
         # iteration launches exactly what it launched without it and nothing is allocated.
         self.augment = A.DiffAugment.of(augment)
         self.aug_params = None
+        # Decoded prior samples as the third Discriminator stream (Larsen et al. 2016, algorithm 1):
+        # z_p ~ N(0, I) (draw 3), x_p = G(z_p) in a second train-mode Generator forward after the reconstruction's, xp_noisy =
+        # x_p + sigma eps_xp (draw 4); every Discriminator update adds BCE(D(xp_noisy.detach()), fake_label) and the Generator
+        # loss adds alpha_adv * BCE(D(xp_noisy), real_label) (slot 8 of the loss tensor, g_loss_adv_prior).  Its gradient
+        # reaches the Generator only, summed with the reconstruction's in the flat gradient buffer.  False (the default): the
+        # iteration launches exactly what it launched without it and returns 8 slots.
+        if not isinstance(prior_stream, bool):
+            raise ValueError("prior_stream must be True or False")
+        if prior_stream and (decoder.nc != discriminator.nc or decoder.nz != encoder.latent_dim):
+            raise ValueError("prior_stream=True needs a Generator that decodes the Encoder's latent into the Discriminator's "
+                             "image channels")
+        self.prior_stream = prior_stream
         self.group_d_passes = group_d_passes       # run a D iteration's real+fake passes as one 2B-row launch chain
         # BCE + its gradient + the sigmoid / head backward as ONE launch per Discriminator pass (ops.head_backward;
         # bit-identical to the three separate launches, which False selects)
@@ -170,7 +186,7 @@ class VAEGANTrainer(ClipOption):
                 self.real_label,
                 self.fake_label, self.d_iters,
                 self.elide_dead_grads, self.group_d_passes, self.fuse_head_backward, self.fuse_step_prologue,
-                self.merge_small_launches,
+                self.merge_small_launches, self.prior_stream,
                 id(self.reducer), self.sync_bn, opts,
                 None if self.noise is None or (inject and self.augment is None) else self.noise.state.data_ptr()) \
             + (self.augment.key() if self.augment is not None else ()) \
@@ -252,11 +268,14 @@ class VAEGANTrainer(ClipOption):
     def train_step(self, real: torch.Tensor, epoch: int, eps_z: Optional[torch.Tensor] = None,
                    eps_real: Optional[torch.Tensor] = None, eps_recon: Optional[torch.Tensor] = None, *,
                    noisy: Optional[torch.Tensor] = None, noisy_nhwc: Optional[torch.Tensor] = None,
-                   rects: Optional[torch.Tensor] = None) -> torch.Tensor:
+                   rects: Optional[torch.Tensor] = None, eps_prior: Optional[torch.Tensor] = None,
+                   eps_xp: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One iteration.  Returns a device tensor [recon_loss, kl_loss, g_loss_adv, d_loss_1, d_loss_2, feat_loss, ssim_loss,
         hole_mse]: slot 5 holds the Discriminator-feature reconstruction loss (unweighted, like recon_loss) when alpha_feat
         != 0, slot 6 the SSIM reconstruction loss 1 - SSIM(recon, real) (unweighted) when alpha_ssim != 0; each reads 0 when
-        its term is off.
+        its term is off.  With prior_stream=True there is a ninth slot, g_loss_adv_prior = BCE(D(xp_noisy), real_label)
+        (unweighted), the d_loss slots hold the three-term loss, and eps_prior ([B, L] f32) / eps_xp ([B, C, S, S] f32) inject
+        the prior latent and the instance noise of the decoded prior samples (None: draws 3 / 4 of the noise stream).
         noisy (device f32 of real's shape): the PAIRED step on a degraded pair -- the Encoder reads `noisy` as it is (no
         clamp, no noise added); everything else (the Discriminator's real batch, the MSE / SSIM / Dis_l targets) reads
         `real`, the clean image.  noisy_nhwc: the same batch already in the Encoder's input layout ([B, H, W, padc(C)] in
@@ -265,9 +284,11 @@ class VAEGANTrainer(ClipOption):
         MSE; slot 0 then holds L_w and slot 7 the mean squared error inside the holes (0 otherwise)."""
         if noisy is None and (rects is not None or noisy_nhwc is not None):
             raise ValueError("rects / noisy_nhwc belong to the paired step: pass noisy= as well")
+        if not self.prior_stream and (eps_prior is not None or eps_xp is not None):
+            raise ValueError("eps_prior / eps_xp belong to the prior stream: build the trainer with prior_stream=True")
         steps = [o.steps for o in (self.opt_E, self.opt_G, self.opt_D)]
         try:
-            return self._train_step(real, epoch, eps_z, eps_real, eps_recon, noisy, noisy_nhwc, rects)
+            return self._train_step(real, epoch, eps_z, eps_real, eps_recon, noisy, noisy_nhwc, rects, eps_prior, eps_xp)
         except BaseException:
             # The step prologue advances the DEVICE step counters / bias corrections of all three optimizers at the top of
             # the iteration, the host mirrors (opt.steps) move with the updates at its end.  An eager iteration that dies
@@ -283,7 +304,26 @@ class VAEGANTrainer(ClipOption):
                             pass
             raise
 
-    def _train_step(self, real, epoch, eps_z, eps_real, eps_recon, noisy=None, noisy_nhwc=None, rects=None) -> torch.Tensor:
+    def _decode(self, z, B, eps, out_noisy, CP):
+        """One train-mode Generator forward of z: -> (tanh image NCHW f32, ctx), with image + sigma * eps written into
+        out_noisy in the Discriminator's layout (:83 and :92; the reconstruction, and the prior stream's decoded samples)."""
+        Gn, D, dt = self.G, self.D, self.dt
+        if Gn.nc == D.nc and G.padc(Gn.nc, dt) == CP and Gn.fused_tail(B):
+            # the last ConvTranspose2d's kernel applies Tanh and writes the NCHW image AND image + sigma*eps in D's layout
+            return Gn.engine_forward(z, B, tail=dict(noise=eps, sigma=self.sigma, out_noisy=out_noisy))
+        pre, ctxG = Gn.engine_forward(z, B)
+        if Gn.nc == D.nc and pre.shape[-1] == CP:
+            img = ops.nhwc_tanh_to_nchw_noisy(pre, Gn.nc, eps, self.sigma, out_noisy, dt)      # :83 and :92 in one pass
+        else:
+            img = ops.nhwc_to_nchw(pre, Gn.nc, dt, apply_tanh=True)
+            ops.nchw_to_nhwc(img, CP, dt, eps=eps, sigma=self.sigma, out=out_noisy)
+        if Gn._engine.trace is not None:        # test instrumentation (engine.StackEngine.trace): the unfused tail
+            Gn._engine.trace.append(dict(stage=len(Gn._engine.stages) - 1, what="tail", pre=pre.clone(),
+                                         img=img.clone(), noisy=out_noisy.clone()))
+        return img, ctxG
+
+    def _train_step(self, real, epoch, eps_z, eps_real, eps_recon, noisy=None, noisy_nhwc=None, rects=None, eps_prior=None,
+                    eps_xp=None) -> torch.Tensor:
         if not real.is_cuda:
             raise RuntimeError("train_step needs the batch on the MI355X ('cuda'); there is no CPU path")
         E, Gn, D, dt = self.E, self.G, self.D, self.dt
@@ -296,13 +336,18 @@ class VAEGANTrainer(ClipOption):
         weighted = self._weighted(noisy, rects)
         self.last_step_weighted = weighted
         noise = None
-        if eps_z is None or eps_real is None or eps_recon is None:
+        ps = self.prior_stream
+        if eps_z is None or eps_real is None or eps_recon is None or (ps and (eps_prior is None or eps_xp is None)):
             # the three randn_like draws (:77, :91, :92) are generated inside the kernels that consume them
-            # (Philox keyed by torch's device seed; the iteration counter is bumped on the device, also under replay)
+            # (Philox keyed by torch's device seed; the iteration counter is bumped on the device, also under replay);
+            # the prior stream's two draws likewise
             noise = self._noise_stream(dev)
             eps_z = noise.draw(0) if eps_z is None else eps_z
             eps_real = noise.draw(1) if eps_real is None else eps_real
             eps_recon = noise.draw(2) if eps_recon is None else eps_recon
+            if ps:
+                eps_prior = noise.draw(DRAW_PRIOR) if eps_prior is None else eps_prior
+                eps_xp = noise.draw(DRAW_XP) if eps_xp is None else eps_xp
         elif self.augment is not None:
             noise = self._noise_stream(dev)         # the augmentation table is drawn from it (and it advances) all the same
         # one single-thread launch for everything that only counts: the noise iteration and the step counters / bias
@@ -311,7 +356,8 @@ class VAEGANTrainer(ClipOption):
         # slots 0..4 are written (not accumulated) below when d_iters >= 2; with d_iters = 1 slot 4 (d_loss_2) is never
         # written and with d_iters > 2 it holds the LAST iteration's loss -- zeroed so that it reads 0, not stale memory.
         # With the prologue launch the zeroing rides on it (no memset node in the captured iteration).
-        losses = torch.empty(8, dtype=torch.float32, device=dev) if prep else ops.zeros_f32(8, dev)
+        nslots = 9 if ps else 8                     # slot 8: g_loss_adv_prior
+        losses = torch.empty(nslots, dtype=torch.float32, device=dev) if prep else ops.zeros_f32(nslots, dev)
         if prep:
             ops.step_prologue(noise, [self.opt_D, self.opt_G, self.opt_E], zero=losses)
         elif noise is not None:
@@ -324,7 +370,8 @@ class VAEGANTrainer(ClipOption):
         # statistics, running stats updated real-then-fake as the reference's two calls do).  The Encoder's input and the
         # Discriminator's noisy real batch are the same images: one pass over `real` writes both (round 4).
         CP = G.padc(D.nc, dt)
-        both = ops.empty_act((2 * B, real.shape[2], real.shape[3], CP), dt, dev)
+        ngrp = 3 if ps else 2                       # prior stream: [real_noisy | recon_noisy | xp_noisy]
+        both = ops.empty_act((ngrp * B, real.shape[2], real.shape[3], CP), dt, dev)
         if noisy is None:
             pair = ops.nchw_to_nhwc_pair(real, CP, dt, eps_real, self.sigma, both[:B]) \
                 if (self.merge_small_launches and G.padc(real.shape[1], dt) == CP) else None
@@ -337,20 +384,12 @@ class VAEGANTrainer(ClipOption):
         z, lvc = ops.reparam_forward(mulv, eps_z, L, ZP, dt)
         real_noisy = both[:B] if pair is not None else \
             ops.nchw_to_nhwc(real, CP, dt, eps=eps_real, sigma=self.sigma, out=both[:B])
-        recon_noisy = both[B:]
-        if Gn.nc == D.nc and G.padc(Gn.nc, dt) == CP and Gn.fused_tail(B):
-            # the last ConvTranspose2d's kernel applies Tanh and writes the NCHW image AND image + sigma*eps in D's layout
-            recon, ctxG = Gn.engine_forward(z, B, tail=dict(noise=eps_recon, sigma=self.sigma, out_noisy=recon_noisy))
-        else:
-            pre, ctxG = Gn.engine_forward(z, B)
-            if Gn.nc == D.nc and pre.shape[-1] == CP:
-                recon = ops.nhwc_tanh_to_nchw_noisy(pre, Gn.nc, eps_recon, self.sigma, recon_noisy, dt)   # :83 and :92 in one pass
-            else:
-                recon = ops.nhwc_to_nchw(pre, Gn.nc, dt, apply_tanh=True)
-                ops.nchw_to_nhwc(recon, CP, dt, eps=eps_recon, sigma=self.sigma, out=recon_noisy)
-            if Gn._engine.trace is not None:        # test instrumentation (engine.StackEngine.trace): the unfused tail
-                Gn._engine.trace.append(dict(stage=len(Gn._engine.stages) - 1, what="tail", pre=pre.clone(),
-                                             img=recon.clone(), noisy=recon_noisy.clone()))
+        recon_noisy = both[B:2 * B]
+        recon, ctxG = self._decode(z, B, eps_recon, recon_noisy, CP)
+        if ps:
+            # the second Generator forward, on a latent from the prior: its BatchNorm buffers see recon, then prior
+            z_p = ops.prior_forward(eps_prior, B, L, ZP, dt)
+            x_p, ctxG_p = self._decode(z_p, B, eps_xp, both[2 * B:], CP)
         aug = self.augment
         if aug is not None:
             # one table per iteration, then everything D reads below is the augmented copy of `both`
@@ -360,15 +399,37 @@ class VAEGANTrainer(ClipOption):
                 self.aug_params = torch.empty(B, 8, dtype=torch.float32, device=dev)
             aug.draw(noise.state, B, both.shape[1], both.shape[2], out=self.aug_params)
             both = aug.forward(both, self.aug_params, D.nc, dt)
-            real_noisy, recon_noisy = both[:B], both[B:]
-        grouped = self.group_d_passes and D._engine.can_group(B, 2)
+            real_noisy, recon_noisy = both[:B], both[B:2 * B]
+        xp_noisy = both[2 * B:] if ps else None
+        grouped = self.group_d_passes and D._engine.can_group(B, ngrp)
         fused_head = self.fuse_head_backward and 2 * B <= ops.HEAD_BWD_MAXROWS and D._engine.stages[-1].kind == "head"
 
         # ---- Discriminator updates (:95-105) ----
         for it in range(self.d_iters):
             slot = losses[3 + min(it, 1):4 + min(it, 1)]
             self.opt_D.zero_grad(memset=False)
-            if grouped:
+            if ps:
+                # three terms: BCE(D(real_noisy), real) + BCE(D(recon_noisy), fake) + BCE(D(xp_noisy), fake), three train-mode
+                # calls in that order (one grouped 3B pass: per-group BatchNorm statistics, running stats updated in order,
+                # weight gradients formed group after group -- the bits of the three separate passes below)
+                targets = (self.real_label, self.fake_label, self.fake_label)
+                if grouped:
+                    p_all, c_all = D.engine_forward(both, B, groups=3)
+                    if fused_head and 3 * B <= ops.HEAD_BWD_MAXROWS:
+                        D._engine.backward(c_all, None, False, sink, on_grads=self._grad_hook(self.opt_D, D),
+                                           head_loss=targets[:2] + (3, 1.0, slot, False, targets[2]), weight_grad_groups=3)
+                    else:
+                        dp = torch.empty_like(p_all)
+                        for g, t in enumerate(targets):
+                            rows = slice(g * B, (g + 1) * B)
+                            ops.bce_forward_backward(p_all[rows], t, 1.0, slot, g > 0, True, out=dp[rows])
+                        D._engine.backward(c_all, dp, False, sink, on_grads=self._grad_hook(self.opt_D, D), weight_grad_groups=3)
+                else:
+                    passes = [D.engine_forward(x, B) for x in (real_noisy, recon_noisy, xp_noisy)]
+                    dps = [ops.bce_forward_backward(p, targets[g], 1.0, slot, g > 0, True) for g, (p, _) in enumerate(passes)]
+                    for g, (_, c) in enumerate(passes):       # the later passes accumulate, the last one carries the hook
+                        D._engine.backward(c, dps[g], False, sink, on_grads=self._grad_hook(self.opt_D, D) if g == 2 else None)
+            elif grouped:
                 p_both, c_both = D.engine_forward(both, B, groups=2)                           # .detach(): no dx below
                 if fused_head:
                     # :98-104: the two BCE terms, their gradient and the head's backward in one launch
@@ -397,7 +458,17 @@ class VAEGANTrainer(ClipOption):
             # the pass on the reconstruction (BatchNorm buffers see real, then fake); nothing kept but the tapped activation
             _, _, f_real = D.engine_forward(real_noisy, B, keep=False, tap=self.feat_layer)
             feat = (self.feat_layer, f_real, self.alpha_feat, losses[5:6])
-        p_adv, c_adv = D.engine_forward(recon_noisy, B)
+        # prior stream: D sees recon, then prior -- as ONE grouped 2B pass over [recon_noisy | xp_noisy] where that is legal.  The
+        # two BCE terms go to different slots (2 and 8), so a grouped pass takes the single-target BCE launches (the fused head
+        # launch sums its groups into one slot); separate passes keep one fused launch each.
+        group_g = ps and self.group_d_passes and D._engine.can_group(B, 2)
+        c_pr = None
+        if group_g:
+            p_adv, c_adv = D.engine_forward(both[B:], B, groups=2)
+        else:
+            p_adv, c_adv = D.engine_forward(recon_noisy, B)
+            if ps:
+                p_pr, c_pr = D.engine_forward(xp_noisy, B)
         if weighted:
             # alpha_pix * L_w: the region-weighted MSE writes slot 0, the holes' own MSE (slot 7) and d_recon in full
             d_recon = ops.region_mse_forward_backward(recon, real, rects, self.hole_weight, self.alpha_pix, losses[0:1],
@@ -414,19 +485,40 @@ class VAEGANTrainer(ClipOption):
             # 1 - SSIM(recon, real) and its gradient, added onto the MSE's in d_recon (which that launch wrote in full, also
             # with alpha_pix = 0)
             ops.ssim_loss_forward_backward(recon, real, self.alpha_ssim, losses[6:7], False, d_recon)
-        dp_adv = None
-        if not fused_head:
+        dp_adv, dp_pr = None, None
+        if group_g:
+            dp_adv = torch.empty_like(p_adv)                  # [2B]: :115 on the reconstruction's half, the same on the prior's
+            ops.bce_forward_backward(p_adv[:B], self.real_label, self.alpha_adv, losses[2:3], False, True, out=dp_adv[:B])
+            ops.bce_forward_backward(p_adv[B:], self.real_label, self.alpha_adv, losses[8:9], False, True, out=dp_adv[B:])
+        elif not fused_head:
             dp_adv = ops.bce_forward_backward(p_adv, self.real_label, self.alpha_adv, losses[2:3], False, True)  # :115
+            if ps:
+                dp_pr = ops.bce_forward_backward(p_pr, self.real_label, self.alpha_adv, losses[8:9], False, True)
 
         # ---- backward of total = a_pix*recon + a_kl*min(1,epoch/50)*kl + a_adv*adv (+ a_feat*feat) (+ a_ssim*ssim), then E and G steps
         # (:131-135) ----
         self.opt_E.zero_grad(memset=False)
         self.opt_G.zero_grad(memset=False)
+        head_g = fused_head and not group_g
         d_noisy = D._engine.backward(c_adv, dp_adv, True, sink, param_grads=not self.elide_dead_grads,
-                                     head_loss=(self.real_label, 0.0, 1, self.alpha_adv, losses[2:3], False) if fused_head else None,
+                                     head_loss=(self.real_label, 0.0, 1, self.alpha_adv, losses[2:3], False) if head_g else None,
                                      feat=feat)
+        if c_pr is not None:
+            d_xp = D._engine.backward(c_pr, dp_pr, True, sink, param_grads=not self.elide_dead_grads,
+                                      head_loss=(self.real_label, 0.0, 1, self.alpha_adv, losses[8:9], False) if head_g else None)
         if aug is not None:
             d_noisy = aug.backward(d_noisy, self.aug_params, D.nc, dt)      # back to the gradient of the un-augmented batch
+            if c_pr is not None:
+                d_xp = aug.backward(d_xp, self.aug_params, D.nc, dt)
+        if ps:
+            # the prior half first, without a hook: through the instance-noise add and Tanh into the backward of the SECOND
+            # Generator context (its own saved batch statistics).  It writes the Generator's gradients; the reconstruction's
+            # backward below accumulates onto them and carries the bucket hook, so a bucket leaves once, after its last
+            # contribution.  Nothing of it reaches the Encoder (z_p is an input).
+            if group_g:
+                d_noisy, d_xp = d_noisy[:B], d_noisy[B:]
+            d_pre_p = ops.nhwc_grad_tanh_to_nhwc(d_xp, x_p, G.padc(Gn.nc, dt), dt)
+            Gn._engine.backward(ctxG_p, d_pre_p, False, sink)
         # d total / d recon = d MSE (+ d SSIM) + d adv through the instance-noise add (:92), then through tanh: one pass
         d_pre = ops.nchw_grad_add_to_nhwc(d_recon, d_noisy, recon, G.padc(Gn.nc, dt), dt)
         dz = Gn._engine.backward(ctxG, d_pre, True, sink, on_grads=self._grad_hook(self.opt_G, Gn))
@@ -467,7 +559,8 @@ class VAEGANTrainer(ClipOption):
     def train_step_graphed(self, real: torch.Tensor, epoch: int, eps_z: Optional[torch.Tensor] = None,
                            eps_real: Optional[torch.Tensor] = None,
                            eps_recon: Optional[torch.Tensor] = None, *, noisy: Optional[torch.Tensor] = None,
-                           noisy_nhwc: Optional[torch.Tensor] = None, rects: Optional[torch.Tensor] = None) -> torch.Tensor:
+                           noisy_nhwc: Optional[torch.Tensor] = None, rects: Optional[torch.Tensor] = None,
+                           eps_prior: Optional[torch.Tensor] = None, eps_xp: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Same iteration as train_step, replayed from captured hipGraphs (~220 kernel launches become one graph
         launch per segment).  The returned tensor is the graph's STATIC output buffer: the next call overwrites it
         (clone it to keep a history of losses).  Every call performs exactly one training iteration: the first call with a new
@@ -478,7 +571,9 @@ class VAEGANTrainer(ClipOption):
         where gradients are handed to the reducer (one cut per gradient bucket, ddp.py) and, in SyncBN mode, at every
         BatchNorm's statistics all-reduce; the collectives run eagerly between the segment replays.
         noisy / rects: the paired step (train_step); both become static inputs (graph_noisy_input, graph_rects_input) and the
-        captured iteration converts the static NCHW `noisy` itself: noisy_nhwc is eager-only (ValueError)."""
+        captured iteration converts the static NCHW `noisy` itself: noisy_nhwc is eager-only (ValueError).
+        prior_stream=True: the injected form takes eps_prior and eps_xp as well (all five tensors or none); they become two
+        more static inputs."""
         if noisy_nhwc is not None:
             raise ValueError("train_step_graphed: noisy_nhwc is eager-only (the captured step converts its static noisy input)")
         if noisy is None and rects is not None:
@@ -490,6 +585,11 @@ class VAEGANTrainer(ClipOption):
         inject = eps_z is not None
         if inject and (eps_real is None or eps_recon is None):
             raise ValueError("inject all three noise tensors or none")
+        ps = self.prior_stream
+        if not ps and (eps_prior is not None or eps_xp is not None):
+            raise ValueError("eps_prior / eps_xp belong to the prior stream: build the trainer with prior_stream=True")
+        if ps and ((eps_prior is not None) != inject or (eps_xp is not None) != inject):
+            raise ValueError("prior_stream: inject all five noise tensors (eps_z, eps_real, eps_recon, eps_prior, eps_xp) or none")
         if not inject or self.augment is not None:
             self._noise_stream(real.device)         # exists (and is keyed on the current seed) before the key is formed
         key = self._capture_key(real, epoch, inject, noisy is not None, rects is not None)
@@ -505,6 +605,8 @@ class VAEGANTrainer(ClipOption):
                     sin[4].copy_(noisy)
                 if rects is not None and rects.data_ptr() != sin[5].data_ptr():
                     sin[5].copy_(rects)
+            if ps and inject:
+                sin[6].copy_(eps_prior), sin[7].copy_(eps_xp)
             self._replay(g)
             self.last_step_weighted = self._weighted(noisy, rects)
             self.losses = g.out
@@ -512,10 +614,13 @@ class VAEGANTrainer(ClipOption):
         if self._warm_key != key:
             self._warm_key = key
             self._graph = None
-            return self.train_step(real, epoch, eps_z, eps_real, eps_recon, noisy=noisy, rects=rects)
+            return self.train_step(real, epoch, eps_z, eps_real, eps_recon, noisy=noisy, rects=rects, eps_prior=eps_prior,
+                                   eps_xp=eps_xp)
         sin = [real.clone()] + ([eps_z.clone(), eps_real.clone(), eps_recon.clone()] if inject else [None] * 3)
-        if noisy is not None:
-            sin += [noisy.clone(), None if rects is None else rects.clone()]
+        if noisy is not None or (ps and inject):
+            sin += [None if noisy is None else noisy.clone(), None if rects is None else rects.clone()]
+        if ps and inject:                           # entries 6, 7; 4 and 5 stay the paired step's (None when unpaired)
+            sin += [eps_prior.clone(), eps_xp.clone()]
         # Collectives INSIDE the graph (round 4): RCCL's all-reduces are capturable on this stack (PyTorch 2.10 / RCCL 2.26:
         # tools/rccl_capture_probe.py) -- the asynchronous bucket launches fork onto RCCL's stream and the waits join it
         # back, all as graph dependencies, so the iteration stays ONE graph and no hand-off costs a graph boundary (a cut
@@ -574,8 +679,13 @@ class VAEGANTrainer(ClipOption):
         mirrors = HostMirrors([m._engine for m in (self.E, self.G, self.D)], (self.opt_E, self.opt_G, self.opt_D),
                               self.reducer, replay_reducer=inline)
         try:
-            return capture(lambda *s: self.train_step(s[0], epoch, *s[1:4], noisy=s[4], rects=s[5]) if len(s) > 4
-                           else self.train_step(s[0], epoch, *s[1:]), sin, mirrors, sin[0].device, key=key,
+            def step(*s):                           # s = sin: [real, 3 eps][, noisy, rects][, eps_prior, eps_xp]
+                kw = dict(noisy=s[4], rects=s[5]) if len(s) > 4 else {}
+                if len(s) > 6:
+                    kw.update(eps_prior=s[6], eps_xp=s[7])
+                return self.train_step(s[0], epoch, *s[1:4], **kw)
+
+            return capture(step, sin, mirrors, sin[0].device, key=key,
                            pool=torch.cuda.graph_pool_handle(), error_mode="thread_local", pre_capture=quiesce,
                            install_cut=set_cut_hook)
         except CaptureRefused:
@@ -644,13 +754,15 @@ class VAEGANTrainer(ClipOption):
 
     def loss_dict(self, losses: Optional[torch.Tensor] = None, epoch: Optional[int] = None) -> Dict[str, float]:
         """Host copy of the last step's losses (one device sync, like the reference's .item() calls :125-127)."""
-        v = (losses if losses is not None else self.losses)[:8].tolist()
-        v += [0.0] * (8 - len(v))                # a caller's five-slot slice
+        v = (losses if losses is not None else self.losses)[:9].tolist()
+        v += [0.0] * (9 - len(v))                # a caller's five-slot slice; slot 8 exists with the prior stream only
         out = dict(zip(LOSS_NAMES, v))
         if self.alpha_feat != 0.0:
             out["feat_loss"] = v[5]
         if self.alpha_ssim != 0.0:
             out["ssim_loss"] = v[6]
+        if self.prior_stream:
+            out["g_loss_adv_prior"] = v[8]       # BCE(D(xp_noisy), real_label), unweighted like g_loss_adv
         if self.last_step_weighted:
             out["hole_mse"] = v[7]               # mean squared error inside the occlusion rectangles: only after a step that
                                                  # used the weighted term (slot 7 reads 0 after any other)
@@ -659,5 +771,6 @@ class VAEGANTrainer(ClipOption):
         out.update(lr_report(self._clip_opts()))  # lr_E/G/D, the rates of the last step, when any optimizer has a schedule
         if epoch is not None:
             out["total"] = self.alpha_pix * out["recon_loss"] + self.alpha_kl * min(1.0, epoch / 50) * out["kl_loss"] \
-                + self.alpha_adv * out["g_loss_adv"] + self.alpha_feat * v[5] + self.alpha_ssim * v[6]
+                + self.alpha_adv * out["g_loss_adv"] + self.alpha_feat * v[5] + self.alpha_ssim * v[6] \
+                + (self.alpha_adv * v[8] if self.prior_stream else 0.0)
         return out
