@@ -79,7 +79,9 @@ extern "C" {
                              30: k-means: vg_kmeans_assign, vg_kmeans_update (+ _ws_bytes), vg_kmeans_seed (+ _ws_bytes),
                                  vg_kmeans_plan / vg_km_plan;
                              31: decoded prior samples as the third Discriminator stream: vg_prior_forward (+ _rng),
-                                 vg_head_backward_g, vg_nhwc_grad_tanh_to_nhwc */
+                                 vg_head_backward_g, vg_nhwc_grad_tanh_to_nhwc;
+                                 (added within 31, nothing changed) multi-scale SSIM loss: vg_msssim_loss_forward_backward
+                                 (+ _ws_bytes); timing family 5 */
 int vg_abi_version(void);
 /* The library reads its optional kernel-selection switches (VG_* environment variables, DESIGN.md "Runtime switches")
  * ONCE, when it is loaded; nothing on a launch path calls getenv.  A process that changes one of them afterwards
@@ -87,7 +89,9 @@ int vg_abi_version(void);
 int vg_reload_switches(void);
 /* Live kernel timing for the roofline report: while enabled, gather-GEMM (family 0) and wgrad (family 1)
  * launches carry a HIP start/stop event pair on their stream (hipExtLaunchKernelGGL); collect() synchronises,
- * sums the kernel times in ms, returns the launch count and resets the family.  Do not enable during capture. */
+ * sums the kernel times in ms, returns the launch count and resets the family.  Do not enable during capture.
+ * Further families: 2 edge layers, 3 fp8 gather-GEMM, 4 BatchNorm / activation passes, 5 every launch of the multi-scale
+ * SSIM loss (csrc/msssim.hip).  VG_EINVAL for a family outside 0 .. 5. */
 int vg_timing_enable(int on);
 /* Kernel launches issued by this library since it was loaded (every hipLaunchKernelGGL / hipExtLaunchKernelGGL of csrc/;
  * memsets and copies are runtime calls, not counted).  bench.py: launches per training iteration. */
@@ -582,6 +586,36 @@ int vg_feat_mse_forward_backward(const void* f_fake, const void* f_real, void* d
 int vg_ssim_loss_forward_backward(const float* a, const float* b, float* d, int B, int C, int H, int W, float gscale,
                                   float* loss, int accumulate_loss, float* ws, int ws_capacity, void* stream);
 int64_t vg_ssim_loss_ws_floats(int B, int C, int H, int W);      /* VG_EINVAL (negative) for sizes outside the contract */
+/* Multi-scale SSIM reconstruction loss (csrc/msssim.hip; an addition within ABI 31): the maps of the SSIM loss above over a
+ * 2x pyramid (Wang, Simoncelli & Bovik 2003).  a (reconstruction) and b (target, a constant): NCHW f32 [B][C][H][W] in
+ * [-1, 1]; M scales, 1 <= M <= 5, with weights w_0 .. w_{M-1} (host memory, read at call time, each finite and > 0).
+ *   Pyramid: a_0 = a, b_0 = b; level j + 1 is the 2 x 2 mean of level j, stride 2, no padding: H_{j+1} = floor(H_j / 2),
+ *     W_{j+1} = floor(W_j / 2), a trailing odd row / column is dropped (F.avg_pool2d(x, 2)); f32: ((x00 + x01) + (x10 + x11))
+ *     * 0.25f, every level rounded to f32 and the next formed from the rounded one.  Every level needs H_j, W_j >= 11.
+ *   Per level, on u = (a_j + 1) / 2, v = (b_j + 1) / 2 over the interior [5, H_j - 5) x [5, W_j - 5), with the Gaussian, c1, c2,
+ *     A1, A2, B1, B2 of the block above:  cs = A2 / B2,  S = (A1 / B1)(A2 / B2).  No padding is ever read.
+ *   m_{b,j} = mean of cs (j < M - 1) or of S (j = M - 1) over the channels and interior pixels of IMAGE b at level j (per image,
+ *     not per channel), n_j = C (H_j - 10)(W_j - 10).
+ *   P_b = prod_j m_{b,j}^{w_j} if every m_{b,j} > 0, else 0 (the "relu" normalisation);
+ *   loss[0] (+)= 1 - (1 / B) sum_b P_b                               (accumulate_loss != 0: added to what the slot holds)
+ *   k_{b,j} = w_j P_b / (m_{b,j} B n_j) if every m_{b,.} > 0, else 0: an image on the clamp contributes the value 0 and a
+ *     gradient of exactly 0; no NaN or Inf comes out of 0^(w - 1).
+ *   g_j = -k_{b,j} d(sum_p map_j(p)) / d a_j over every pixel of the level-j plane (the closed form of the block above; for
+ *     the cs levels Du = -cs / B2, Dc = 2 / B2, Dm = -2 mu_u Du - mu_v Dc);
+ *   d[q] += gscale sum_j 4^-j g_j[q >> j]   over the levels whose plane contains q >> j: the adjoint of the floor-pooling
+ *     chain; base pixels in dropped trailing rows / columns get no coarse contribution.             (d NULL: forward only)
+ * Maps in f32 with one constant per 32 x 32 tile and input subtracted before the moments at every level (as ssimloss.hip);
+ * per-image sums, P_b and k in f64, summed in a fixed order.  No atomics: the same inputs give the same bits, run to run and
+ * eagerly vs. replayed from a graph; no host synchronisation.  Identical images give m = 1 exactly at every level, loss 0.
+ * Launches: pyramid (M > 1), forward tiles of all levels, finalize, and with d backward tiles of all levels and the collapse
+ * onto d: 3 without and 5 with the gradient (2 and 4 at M = 1), whatever M.
+ * per_scale: f32 [B][M] receives the m_{b,j}; NULL skips it.  ws: vg_msssim_ws_bytes(B, C, H, W, M) bytes (pyramids of a, b
+ * and of the gradient, tile partials, coefficients), 8-byte aligned (VG_EALIGN).  VG_EINVAL: a, b, loss or weights_host NULL,
+ * B or C < 1, M outside 1 .. 5, a level under 11 x 11, a weight <= 0 or not finite, ws NULL or too small. */
+int vg_msssim_loss_forward_backward(const float* a, const float* b, float* d, int B, int C, int H, int W, int M,
+                                    const float* weights_host, float gscale, float* loss, int accumulate_loss,
+                                    float* per_scale, void* ws, int64_t ws_bytes, void* stream);
+int64_t vg_msssim_ws_bytes(int B, int C, int H, int W, int M);   /* VG_EINVAL (negative) for sizes outside the contract */
 /* Region-weighted reconstruction MSE (ABI 18; csrc/regionloss.hip): the pixel MSE of a reconstruction a against the clean
  * image b (a constant), both NCHW f32 [B][C][H][W], split by each image's occlusion rectangle, for training on and evaluating
  * degraded pairs.  rects: f32 [B][8] in the layout vg_degrade_params writes; entries 2..5 = {rect_h, rect_w, x, y} are read;

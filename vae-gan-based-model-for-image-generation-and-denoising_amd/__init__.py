@@ -8,7 +8,8 @@ vaegan_code.py:42-44), ``BCELoss`` / ``MSELoss`` (vaegan_code.py:46-47), ``confi
 reference-shaped step function).  The learned-similarity term of Larsen et al. (the reference README's eq. 2, absent from
 its code): ``VAEGANTrainer(..., feat_layer=, alpha_feat=, alpha_pix=)`` and ``Discriminator.features(x, layer)`` /
 ``Discriminator.feature_layers()``.  The SSIM reconstruction loss (1 - the SSIM the denoising passes report; not in the
-reference): ``SSIMLoss`` and ``VAEGANTrainer(..., alpha_ssim=)`` / ``VAETrainer(..., alpha_ssim=)``.  Generation (main_vae.py:415-641): ``latent`` -- ``encode_dataset``, ``LatentPrior``,
+reference): ``SSIMLoss`` and ``VAEGANTrainer(..., alpha_ssim=)`` / ``VAETrainer(..., alpha_ssim=)``; its multi-scale form (MS-SSIM over a 2x
+pyramid): ``MSSSIMLoss``, ``msssim_weights``, ``ssim_scales=`` on the two trainers and ``ms_ssim=True`` on the denoising passes.  Generation (main_vae.py:415-641): ``latent`` -- ``encode_dataset``, ``LatentPrior``,
 ``evaluate_generation``, ``sample_images``, and ``GaussianMixturePrior`` (not in the reference): a full-covariance Gaussian
 mixture fitted to the Encoder's latents by EM on the device and sampled there, a drop-in ``prior=``.  Feature-space metrics (fid.update / fid.compute of every evaluation loop,
 README.md:22 precision / recall): ``metrics`` -- ``FeatureStats``, ``frechet_distance``, ``precision_recall``,
@@ -44,7 +45,7 @@ from .latent import (GaussianMixturePrior, LatentPrior, encode_dataset, evaluate
                      sample_images)
 from .cluster import KMeans
 from .metrics import FeatureStats, encoder_features, frechet_distance, kernel_distance, ndb, precision_recall
-from .losses import BCELoss, MSELoss, SSIMLoss
+from .losses import BCELoss, MSELoss, MSSSIMLoss, SSIMLoss, msssim_weights
 from .nets import ConvBlock, Discriminator, Encoder, Generator, weights_init
 from .optim import Adam, AdamW, LRSchedule, clip_grad_norm_
 from .siblings import DCGANTrainer, VAETrainer, WGANTrainer
@@ -58,4 +59,4 @@ __all__ = ["ConvBlock", "Encoder", "Generator", "Discriminator", "weights_init",
            "EMA", "clip_grad_norm_", "DiffAugment", "AdamW", "LRSchedule",
            "tiling", "TilePlan", "tile_plan", "denoise_tiled", "tiled_denoise_eval", "tiled_test_epoch",
            "metrics", "FeatureStats", "frechet_distance", "precision_recall", "encoder_features", "kernel_distance",
-           "cluster", "KMeans", "ndb", "evaluate_generation_ndb"]
+           "cluster", "KMeans", "ndb", "evaluate_generation_ndb", "MSSSIMLoss", "msssim_weights"]

@@ -191,6 +191,8 @@ SIGNATURES = {
     "vg_feat_mse_forward_backward": (c_int, [_P, _P, _P, _L, _F, _P, _I, _P, _I, _I, _P]),
     "vg_ssim_loss_forward_backward": (c_int, [_P, _P, _P, _I, _I, _I, _I, _F, _P, _I, _P, _I, _P]),
     "vg_ssim_loss_ws_floats": (c_int64, [_I, _I, _I, _I]),
+    "vg_msssim_loss_forward_backward": (c_int, [_P, _P, _P, _I, _I, _I, _I, _I, POINTER(c_float), _F, _P, _I, _P, _P, _L, _P]),
+    "vg_msssim_ws_bytes": (c_int64, [_I, _I, _I, _I, _I]),
     "vg_region_mse_forward_backward": (c_int, [_P, _P, _P, _I, _I, _I, _I, _F, _F, _P, _P, _P, _P, _P, _I, _P]),
     "vg_region_mse_ws_doubles": (c_int, [_I, _I, _I, _I]),
     "vg_ssim": (c_int, [_P, _P, _I, _I, _I, _I, _P, _P, _I, _P]),

@@ -19,9 +19,11 @@ from .metrics import FeaturePass
 @torch.no_grad()
 def denoise_eval(encoder, decoder, img: torch.Tensor, sigma: float = 0.05, eps: Optional[torch.Tensor] = None,
                  eps_z: Optional[torch.Tensor] = None, alpha_kl: float = 0.1,
-                 noisy: Optional[torch.Tensor] = None) -> Dict[str, object]:
+                 noisy: Optional[torch.Tensor] = None, ms_ssim: bool = False) -> Dict[str, object]:
     """img: [B,C,S,S] float32 on the MI355X in [-1,1].  Returns the noisy input, the reconstruction (both NCHW
     f32) and a dict of device scalars + host floats: recon_loss, kl_loss (sum), val_loss, psnr, ssim.
+    ms_ssim=True (default False: exactly the keys and the launches above) adds ``ms_ssim``, the multi-scale SSIM of the
+    reconstruction (ops.ms_ssim with the default scales of the image size), read in the host sync that reads ssim.
     noisy: an already degraded input batch (the ``noisy`` half of a data.DeviceLoader pair) used INSTEAD of
     clamp(img + sigma*eps): sigma / eps are then ignored, img is the clean target.
     The caller puts encoder / decoder in eval mode (vaegan_code.py:147-148) -- or not: BatchNorm follows
@@ -56,14 +58,20 @@ def denoise_eval(encoder, decoder, img: torch.Tensor, sigma: float = 0.05, eps: 
     recon_loss, kl = (float(v) for v in scal[:2].tolist())
     mse01 = recon_loss / 4.0                                                # ((a+1)/2 - (b+1)/2)^2 = (a-b)^2 / 4
     psnr = float("inf") if mse01 == 0 else 10.0 * math.log10(1.0 / mse01)
-    return {"noisy": noisy, "recon": recon, "recon_loss": recon_loss, "kl_loss": kl,
-            "val_loss": recon_loss + alpha_kl * kl, "psnr": psnr, "ssim": float(ssim_t.item())}
+    out = {"noisy": noisy, "recon": recon, "recon_loss": recon_loss, "kl_loss": kl,
+           "val_loss": recon_loss + alpha_kl * kl, "psnr": psnr}
+    if ms_ssim:
+        out["ssim"], out["ms_ssim"] = torch.cat([ssim_t, ops.ms_ssim(recon, img)]).tolist()
+    else:
+        out["ssim"] = float(ssim_t.item())
+    return out
 
 
 @torch.no_grad()
 def validation_epoch(encoder, decoder, loader: Iterable[torch.Tensor], n_samples: Optional[int] = None,
                      sigma: float = 0.05, alpha_kl: float = 0.1, noise_fn=None, feature_fn=None,
-                     kid_subsets: Optional[int] = None, kid_subset_size: int = 1000, kid_seed: int = 0) -> Dict[str, float]:
+                     kid_subsets: Optional[int] = None, kid_subset_size: int = 1000, kid_seed: int = 0,
+                     ms_ssim: bool = False) -> Dict[str, float]:
     """The per-epoch validation loop of the reference trainer, vaegan_code.py:147-191:
 
         encoder.eval(); decoder.eval()                                   (:147-148; the discriminator is not used)
@@ -89,12 +97,15 @@ def validation_epoch(encoder, decoder, loader: Iterable[torch.Tensor], n_samples
     device and the result gains ``kid_mean`` and ``kid_std``, the Kernel Inception Distance between the clean images and
     the reconstructions (``metrics.kernel_distance``: ``kid_subsets`` subset pairs of ``kid_subset_size`` rows drawn on the
     host with ``kid_seed``; population standard deviation).  Not in the reference; single process; one more host read of
-    two doubles."""
+    two doubles.
+    ms_ssim=True (default False: nothing changes): the result gains ``ms_ssim``, the multi-scale SSIM (ops.ms_ssim, the
+    default scales of the image size) accumulated like ssim -- the batch's value times its image count, on the device -- and
+    read in the same host sync."""
     if kid_subsets is not None and feature_fn is None:
         raise RuntimeError("validation_epoch: kid_subsets needs a feature_fn (KID is a feature-space metric)")
     encoder.eval(), decoder.eval()                                                   # :147-148
     dev = next(encoder.parameters()).device
-    acc = ops.zeros_f32(4, dev)                # [sum(recon + a*kl), sum(b * ssim_b), sum(b * mse_b), sum(kl)]
+    acc = ops.zeros_f32(5 if ms_ssim else 4, dev)  # [sum(recon + a*kl), sum(b * ssim_b), sum(b * mse_b), sum(kl)(, sum(b * ms_ssim_b))]
     seen = batches = 0
     dt, L = encoder._dt, encoder.latent_dim
     feats = FeaturePass(feature_fn, kid_subsets is not None) if feature_fn is not None else None
@@ -124,6 +135,8 @@ def validation_epoch(encoder, decoder, loader: Iterable[torch.Tensor], n_samples
         ops.axpy(acc[1:2], ssim_b, float(b), out=acc[1:2])
         ops.axpy(acc[2:3], scal[0:1], float(b), out=acc[2:3])
         ops.axpy(acc[3:4], scal[1:2], 1.0, out=acc[3:4])
+        if ms_ssim:
+            ops.axpy(acc[4:5], ops.ms_ssim(recon, img), float(b), out=acc[4:5])
         if feats is not None:
             feats.update(img, recon)
         seen += b
@@ -131,12 +144,14 @@ def validation_epoch(encoder, decoder, loader: Iterable[torch.Tensor], n_samples
     if batches == 0:
         raise RuntimeError("validation_epoch: the loader yielded no batch")
     kid = feats.kid(int(kid_subsets), int(kid_subset_size), int(kid_seed)) if kid_subsets is not None else None
-    val_sum, ssim_sum, mse_sum, kl_sum = (float(v) for v in acc.tolist())           # the one host sync
+    val_sum, ssim_sum, mse_sum, kl_sum, *ms_sum = (float(v) for v in acc.tolist())  # the one host sync
     n = seen if n_samples is None else int(n_samples)
     mse01 = mse_sum / seen / 4.0
     out = {"val_loss": val_sum / n, "ssim": ssim_sum / seen,
            "psnr": float("inf") if mse01 == 0 else 10.0 * math.log10(1.0 / mse01),
            "recon_loss": mse_sum / seen, "kl_loss": kl_sum / batches, "samples": seen, "batches": batches}
+    if ms_ssim:
+        out["ms_ssim"] = ms_sum[0] / seen
     if feats is not None:
         out["fid"] = feats.fid()
     if kid is not None:
@@ -146,7 +161,7 @@ def validation_epoch(encoder, decoder, loader: Iterable[torch.Tensor], n_samples
 
 @torch.no_grad()
 def paired_test_epoch(encoder, decoder, loader: Iterable, n_samples: Optional[int] = None, noise_fn=None,
-                      regions: bool = False) -> Dict[str, float]:
+                      regions: bool = False, ms_ssim: bool = False) -> Dict[str, float]:
     """The reference's test pass over (noisy, clean) pairs, main_vae.py:251-266:
 
         encoder.eval(); decoder.eval()                                                 (:251-252)
@@ -170,7 +185,10 @@ def paired_test_epoch(encoder, decoder, loader: Iterable, n_samples: Optional[in
     element inside / outside the occlusion rectangles), psnr_hole, psnr_valid and hole_fraction (hole elements / all
     elements) of ``recon`` vs ``clean``, and the same five suffixed ``_noisy`` for the input, each set from one f64[4]
     tensor that ops.region_mse_forward_backward accumulates over the pass (w_hole = 1, no gradient).  An empty region
-    reports mse 0.0 and psnr inf.  Still one host sync."""
+    reports mse 0.0 and psnr inf.  Still one host sync.
+    ms_ssim=True (default False: nothing changes): the result gains ``ms_ssim`` and ``ms_ssim_noisy``, the multi-scale SSIM
+    (ops.ms_ssim, the default scales of the image size) of ``recon`` and of ``noisy`` vs ``clean``, accumulated like ssim and
+    read in the same host sync."""
     if regions and not (hasattr(loader, "want_rects") and getattr(loader, "degrade", None) is not None and loader.degrade.pairs):
         raise RuntimeError("paired_test_epoch: regions=True needs a degraded data.DeviceLoader (want_rects)")
     encoder.eval(), decoder.eval()                                                   # :251-252
@@ -178,6 +196,7 @@ def paired_test_epoch(encoder, decoder, loader: Iterable, n_samples: Optional[in
     dt, L = encoder._dt, encoder.latent_dim
     # [sum(mse_sum + kl), sum(b * ssim(recon)), sum(b * mse_mean(recon)), sum(kl), sum(b * ssim(noisy)), sum(b * mse_mean(noisy))]
     acc = ops.zeros_f32(6, dev)
+    acc_ms = ops.zeros_f32(2, dev) if ms_ssim else None                              # [sum(b * ms_ssim(recon)), sum(b * ms_ssim(noisy))]
     seen = batches = numel = 0
     offers = hasattr(loader, "want_nhwc") and getattr(loader, "degrade", None) is not None and loader.degrade.pairs
     if offers:
@@ -219,6 +238,9 @@ def paired_test_epoch(encoder, decoder, loader: Iterable, n_samples: Optional[in
             ops.axpy(acc[3:4], scal[1:2], 1.0, out=acc[3:4])
             ops.axpy(acc[4:5], ssim_n, float(b), out=acc[4:5])
             ops.axpy(acc[5:6], scal[2:3], float(b), out=acc[5:6])
+            if ms_ssim:
+                ops.axpy(acc_ms[0:1], ops.ms_ssim(recon, clean), float(b), out=acc_ms[0:1])
+                ops.axpy(acc_ms[1:2], ops.ms_ssim(noisy, clean), float(b), out=acc_ms[1:2])
             seen += b
             batches += 1
     finally:
@@ -228,7 +250,10 @@ def paired_test_epoch(encoder, decoder, loader: Iterable, n_samples: Optional[in
             loader.want_rects(rects_were_on)
     if batches == 0:
         raise RuntimeError("paired_test_epoch: the loader yielded no batch")
-    host = torch.cat([acc.double(), stats.flatten()]).tolist() if regions else acc.tolist()   # the one host sync
+    parts = [acc.double(), stats.flatten()] if regions else [acc]
+    if ms_ssim:
+        parts = [p.double() for p in parts] + [acc_ms.double()]                      # (f32 -> f64 is exact)
+    host = (torch.cat(parts) if len(parts) > 1 else acc).tolist()                    # the one host sync
     tot, ssim_sum, mse_sum, kl_sum, ssim_n_sum, mse_n_sum = (float(v) for v in host[:6])
     n = seen if n_samples is None else int(n_samples)
 
@@ -238,6 +263,8 @@ def paired_test_epoch(encoder, decoder, loader: Iterable, n_samples: Optional[in
     out = {"test_loss": tot / n, "recon_loss": mse_sum / seen, "kl_loss": kl_sum / seen, "ssim": ssim_sum / seen,
            "psnr": psnr(mse_sum / seen), "ssim_noisy": ssim_n_sum / seen, "psnr_noisy": psnr(mse_n_sum / seen),
            "samples": seen, "batches": batches}
+    if ms_ssim:
+        out["ms_ssim"], out["ms_ssim_noisy"] = host[-2] / seen, host[-1] / seen
     if regions:
         for suffix, (s_hole, s_valid, n_hole, n_valid) in (("", host[6:10]), ("_noisy", host[10:14])):
             m_hole = s_hole / n_hole if n_hole > 0 else 0.0
@@ -318,14 +345,15 @@ def _tile_count(encoder, img, tiling_kw) -> int:
 
 @torch.no_grad()
 def tiled_denoise_eval(encoder, decoder, img: torch.Tensor, sigma: float = 0.05, eps: Optional[torch.Tensor] = None,
-                       noisy: Optional[torch.Tensor] = None, **tiling_kw) -> Dict[str, object]:
+                       noisy: Optional[torch.Tensor] = None, ms_ssim: bool = False, **tiling_kw) -> Dict[str, object]:
     """denoise_eval at full resolution.  img: f32 [N,C,H,W] on the MI355X in [-1,1], H, W >= the networks' S.  The noise is
     added ONCE to the whole image, noisy = clamp(img + sigma*eps, -1, 1) (eps: injected draws of img's shape, else generated
     on the device), so overlapping tiles see the same noisy pixel; ``noisy`` given: used instead, sigma / eps ignored.  Then
     ``denoise_tiled(encoder, decoder, noisy, **tiling_kw)`` (stride, window, batch, sample, eps_z).
     Returns noisy, recon (NCHW f32) and python floats: recon_loss (mean squared error of recon vs img), psnr, ssim, and
     noisy_loss, psnr_noisy, ssim_noisy of the input, all on the H x W tensors ([0,1]-rescaled for PSNR / SSIM, as
-    denoise_eval), plus tiles.  One host sync."""
+    denoise_eval), plus tiles.  One host sync.  ms_ssim=True (default False: nothing changes) adds ``ms_ssim`` and
+    ``ms_ssim_noisy`` (ops.ms_ssim on the H x W tensors, the default scales of that size), read in the same sync."""
     if not img.is_cuda:
         raise RuntimeError("tiled_denoise_eval needs the batch on the MI355X ('cuda'); there is no CPU path")
     if img.dim() != 4 or img.dtype != torch.float32:
@@ -343,30 +371,37 @@ def tiled_denoise_eval(encoder, decoder, img: torch.Tensor, sigma: float = 0.05,
             eps = ns.randn(tuple(img.shape), 0)
         _, noisy = ops.noisy_clamp_to_nhwc(img, eps, sigma, G.padc(img.shape[1], dt), dt)
     recon = denoise_tiled(encoder, decoder, noisy, **tiling_kw)
-    scal = ops.zeros_f32(4, img.device)                  # [mse(recon), mse(noisy), ssim(recon), ssim(noisy)]
+    scal = ops.zeros_f32(6 if ms_ssim else 4, img.device)    # [mse(recon), mse(noisy), ssim(recon), ssim(noisy)(, ms_ssim(recon), ms_ssim(noisy))]
     ops.mse_forward_backward(recon, img, 1.0, scal[0:1], False)
     ops.mse_forward_backward(noisy, img, 1.0, scal[1:2], False)
     ops.axpy(scal[2:3], ops.ssim(recon, img), 1.0, out=scal[2:3])
     ops.axpy(scal[3:4], ops.ssim(noisy, img), 1.0, out=scal[3:4])
-    mse_r, mse_n, ssim_r, ssim_n = (float(v) for v in scal.tolist())       # the one host sync
-    return {"noisy": noisy, "recon": recon, "recon_loss": mse_r, "psnr": _psnr(mse_r), "ssim": ssim_r,
-            "noisy_loss": mse_n, "psnr_noisy": _psnr(mse_n), "ssim_noisy": ssim_n, "tiles": _tile_count(encoder, img, tiling_kw)}
+    if ms_ssim:
+        ops.axpy(scal[4:5], ops.ms_ssim(recon, img), 1.0, out=scal[4:5])
+        ops.axpy(scal[5:6], ops.ms_ssim(noisy, img), 1.0, out=scal[5:6])
+    mse_r, mse_n, ssim_r, ssim_n, *ms = (float(v) for v in scal.tolist())  # the one host sync
+    out = {"noisy": noisy, "recon": recon, "recon_loss": mse_r, "psnr": _psnr(mse_r), "ssim": ssim_r,
+           "noisy_loss": mse_n, "psnr_noisy": _psnr(mse_n), "ssim_noisy": ssim_n, "tiles": _tile_count(encoder, img, tiling_kw)}
+    if ms_ssim:
+        out["ms_ssim"], out["ms_ssim_noisy"] = ms
+    return out
 
 
 @torch.no_grad()
-def tiled_test_epoch(encoder, decoder, pairs: Iterable, **tiling_kw) -> Dict[str, float]:
+def tiled_test_epoch(encoder, decoder, pairs: Iterable, ms_ssim: bool = False, **tiling_kw) -> Dict[str, float]:
     """paired_test_epoch at full resolution: ``pairs`` yields (noisy, clean) device batches f32 [b,C,H,W] in [-1,1], each
     denoised with ``denoise_tiled(encoder, decoder, noisy, **tiling_kw)``.  Accumulation stays on the device (per batch the
     mean squared error and the mean SSIM, weighed by the batch's image count); ONE host sync at the end.  Returns python
     floats: psnr, ssim, recon_loss (mean squared error per element) of recon vs clean, psnr_noisy, ssim_noisy of the input,
-    samples, tiles."""
+    samples, tiles.  ms_ssim=True (default False: nothing changes) adds ``ms_ssim`` and ``ms_ssim_noisy`` (ops.ms_ssim, the
+    default scales of the image size), accumulated like ssim and read in the same sync."""
     acc = None                                           # sum over batches of b * [mse(recon), ssim(recon), mse(noisy), ssim(noisy)]
     seen = tiles = 0
     for noisy, clean in pairs:
         if not (noisy.is_cuda and clean.is_cuda):
             raise RuntimeError("tiled_test_epoch needs device pairs; there is no CPU path")
         dev = clean.device
-        acc = ops.zeros_f32(4, dev) if acc is None else acc
+        acc = ops.zeros_f32(6 if ms_ssim else 4, dev) if acc is None else acc
         if noisy.shape != clean.shape or clean.dim() != 4:
             raise RuntimeError("tiled_test_epoch: noisy and clean must be [b,C,H,W] batches of one shape")
         noisy, clean = noisy.contiguous(), clean.contiguous()
@@ -379,10 +414,16 @@ def tiled_test_epoch(encoder, decoder, pairs: Iterable, **tiling_kw) -> Dict[str
         ops.axpy(acc[1:2], ops.ssim(recon, clean), float(b), out=acc[1:2])
         ops.axpy(acc[2:3], scal[1:2], float(b), out=acc[2:3])
         ops.axpy(acc[3:4], ops.ssim(noisy, clean), float(b), out=acc[3:4])
+        if ms_ssim:
+            ops.axpy(acc[4:5], ops.ms_ssim(recon, clean), float(b), out=acc[4:5])
+            ops.axpy(acc[5:6], ops.ms_ssim(noisy, clean), float(b), out=acc[5:6])
         seen += b
         tiles += _tile_count(encoder, clean, tiling_kw)
     if seen == 0:
         raise RuntimeError("tiled_test_epoch: pairs yielded no batch")
-    mse_r, ssim_r, mse_n, ssim_n = (float(v) / seen for v in acc.tolist())  # the one host sync
-    return {"psnr": _psnr(mse_r), "ssim": ssim_r, "recon_loss": mse_r, "psnr_noisy": _psnr(mse_n), "ssim_noisy": ssim_n,
-            "samples": seen, "tiles": tiles}
+    mse_r, ssim_r, mse_n, ssim_n, *ms = (float(v) / seen for v in acc.tolist())  # the one host sync
+    out = {"psnr": _psnr(mse_r), "ssim": ssim_r, "recon_loss": mse_r, "psnr_noisy": _psnr(mse_n), "ssim_noisy": ssim_n,
+           "samples": seen, "tiles": tiles}
+    if ms_ssim:
+        out["ms_ssim"], out["ms_ssim_noisy"] = ms
+    return out

@@ -96,3 +96,62 @@ class SSIMLoss(nn.Module):
         if target.requires_grad:
             raise NotImplementedError("vaegan_amd.SSIMLoss treats the target as a constant; detach it")
         return _SSIMFn.apply(input, target)
+
+
+msssim_weights = ops.msssim_weights
+
+
+def trainer_scales(ssim_scales, H, W):
+    """The trainers' ``ssim_scales`` argument (not None) -> the weight tuple for H x W images: True or "auto" = the
+    default scales of the image size (``msssim_weights(H, W)``), an int or a sequence of weights as ``msssim_weights``
+    takes them."""
+    if ssim_scales is True or (isinstance(ssim_scales, str) and ssim_scales == "auto"):
+        return msssim_weights(H, W)
+    if ssim_scales is None or ssim_scales is False or isinstance(ssim_scales, str):
+        raise ValueError(f"ssim_scales must be None, True / 'auto', an int or a sequence of weights, got {ssim_scales!r}")
+    return msssim_weights(H, W, ssim_scales)
+
+
+class _MSSSIMFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, a, b, weights):
+        loss = torch.empty(1, dtype=torch.float32, device=a.device)
+        da = torch.zeros_like(a, memory_format=torch.contiguous_format)
+        ops.msssim_loss_forward_backward(a.contiguous(), b.contiguous(), weights, 1.0, loss, False, da)
+        ctx.save_for_backward(da)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        (da,) = ctx.saved_tensors
+        return da * g, None, None
+
+
+class MSSSIMLoss(nn.Module):
+    """1 - MS-SSIM(input, target) (Wang, Simoncelli & Bovik 2003) of two [B,C,H,W] f32 image batches in [-1, 1] on the
+    device: the SSIM maps of ``SSIMLoss`` over a 2x average-pooling pyramid, the contrast-structure mean of every level
+    but the last and the SSIM mean of the last, each raised to its scale's weight, multiplied per image and averaged over
+    the batch; an image with a non-positive mean at any level counts 0 and gets no gradient.  ``scales``: None = as many
+    of the five published scales as the image holds (3 at 64, 4 at 128, 5 at 256; weights renormalised), an int, or 1 - 5
+    weights (``msssim_weights``).  At most five HIP launches whatever the number of scales; ``target`` is a constant.
+    Parity with the torchmetrics / pytorch-msssim packages is unpinned (neither is installed where this is tested): the
+    tests restate the formulas in f64."""
+
+    def __init__(self, scales=None):
+        super().__init__()
+        msssim_weights(1 << 14, 1 << 14, scales)          # a bad count / weight fails here
+        self.scales = scales
+
+    def forward(self, input, target):
+        for name, t in (("input", input), ("target", target)):
+            if not t.is_cuda:
+                raise RuntimeError(f"vaegan_amd.MSSSIMLoss needs {name} on the MI355X ('cuda'); there is no CPU path")
+            if t.dtype != torch.float32:
+                raise TypeError(f"vaegan_amd.MSSSIMLoss supports float32 images only, got {name} of {t.dtype}")
+        if input.dim() != 4 or input.shape != target.shape:
+            raise ValueError(f"vaegan_amd.MSSSIMLoss needs input and target of one [B,C,H,W] shape, got {tuple(input.shape)} "
+                             f"and {tuple(target.shape)}")
+        weights = msssim_weights(input.shape[2], input.shape[3], self.scales)      # ValueError: too small for the scales
+        if target.requires_grad:
+            raise NotImplementedError("vaegan_amd.MSSSIMLoss treats the target as a constant; detach it")
+        return _MSSSIMFn.apply(input, target, weights)

@@ -4,6 +4,7 @@ Each function takes torch CUDA tensors (used only as device-memory handles), fil
 descriptor struct, and launches on torch's current HIP stream.  No computation happens in
 Python/ATen here.  All functions raise RuntimeError when the library rejects the arguments.
 """
+import ctypes
 import math
 import os
 from ctypes import byref, c_int
@@ -1678,6 +1679,84 @@ def ssim_loss_forward_backward(a, b, gscale, loss, accumulate, d=None):
                                               1 if accumulate else 0, ws.data_ptr(), nws, L.stream_ptr()),
             "vg_ssim_loss_forward_backward")
     return d
+
+
+MSSSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)      # Wang, Simoncelli & Bovik 2003
+
+
+def msssim_weights(H, W, scales=None):
+    """The scale weights of the multi-scale SSIM for H x W images, as a tuple of floats (host only).
+    scales None: M = the largest number <= 5 of 2x levels whose smaller side min(H, W) >> (M - 1) still holds the 11 x 11
+    window (3 at 64, 4 at 128, 5 at 256), and the first M of (0.0448, 0.2856, 0.3001, 0.2363, 0.1333) divided by their sum;
+    an int: that M by the same rule (ValueError if the image is too small for it); a sequence of 1 - 5 positive finite
+    weights: used as given, not renormalised (ValueError if the image is too small for that many levels)."""
+    H, W = int(H), int(W)
+    side = min(H, W)
+    if side < 11:
+        raise ValueError(f"msssim_weights: images of at least 11 x 11 pixels (the 11 x 11 window), got {H} x {W}")
+    fit = max(m for m in range(1, 6) if (side >> (m - 1)) >= 11)
+    if scales is None or (isinstance(scales, int) and not isinstance(scales, bool)):
+        M = fit if scales is None else scales
+        if not 1 <= M <= 5:
+            raise ValueError(f"msssim_weights: 1 to 5 scales, got {M}")
+        if M > fit:
+            raise ValueError(f"msssim_weights: {M} scales need min(H, W) >> {M - 1} >= 11, got {H} x {W} (at most {fit})")
+        s = math.fsum(MSSSIM_WEIGHTS[:M])
+        return tuple(w / s for w in MSSSIM_WEIGHTS[:M])
+    try:
+        if isinstance(scales, (str, bytes)):
+            raise TypeError
+        w = tuple(float(x) for x in scales)
+    except TypeError:
+        raise ValueError(f"msssim_weights: scales must be None, an int or a sequence of weights, got {scales!r}") from None
+    if not 1 <= len(w) <= 5 or not all(math.isfinite(x) and x > 0 for x in w):
+        raise ValueError(f"msssim_weights: 1 to 5 positive finite weights, got {w}")
+    if len(w) > fit:
+        raise ValueError(f"msssim_weights: {len(w)} scales need min(H, W) >> {len(w) - 1} >= 11, got {H} x {W} (at most {fit})")
+    return w
+
+
+def msssim_loss_forward_backward(a, b, weights, gscale, loss, accumulate, d=None, per_scale=None):
+    """Multi-scale SSIM reconstruction loss (vg_msssim_loss_forward_backward): loss[0] (+)= 1 - mean_b prod_j m_{b,j}^{w_j}
+    over a 2x pyramid of len(weights) levels (NCHW f32 in [-1, 1]; contrast-structure means below the last level, the SSIM
+    mean at it; an image with a non-positive mean contributes 0) and, when d is given (same shape as a), d += gscale *
+    d loss / da IN PLACE: the gradient joins the one already there; b is a constant.  per_scale: f32 [B, M] receives the
+    per-image, per-level means.  Returns d."""
+    _need_cuda(a, b, loss, d, per_scale)
+    if a.dtype != torch.float32 or b.dtype != torch.float32 or (d is not None and d.dtype != torch.float32):
+        raise RuntimeError("msssim_loss_forward_backward: tensors must all be torch.float32")
+    if a.dim() != 4 or a.shape != b.shape or (d is not None and d.shape != a.shape):
+        raise RuntimeError("msssim_loss_forward_backward: a, b and d must be [B,C,H,W] tensors of one shape")
+    B, C, H, W = a.shape
+    w = tuple(float(x) for x in weights)
+    M = len(w)
+    if not 1 <= M <= 5 or not all(math.isfinite(x) and x > 0 for x in w):
+        raise RuntimeError(f"msssim_loss_forward_backward: 1 to 5 positive finite weights, got {w}")
+    if per_scale is not None and (per_scale.dtype != torch.float32 or tuple(per_scale.shape) != (B, M)
+                                  or not per_scale.is_contiguous()):
+        raise RuntimeError("msssim_loss_forward_backward: per_scale must be a contiguous f32 [B, M] tensor")
+    lib = L.load()
+    nbytes = _ws_query(lib.vg_msssim_ws_bytes(B, C, H, W, M),
+                       f"vg_msssim_ws_bytes (needs B, C >= 1 and H, W >= 11 at every one of the {M} levels)")
+    ws = WS.get("msssim", nbytes, a.device)
+    wh = (ctypes.c_float * M)(*w)
+    L.check(lib.vg_msssim_loss_forward_backward(a.data_ptr(), b.data_ptr(), L.ptr(d), B, C, H, W, M, wh, gscale,
+                                                loss.data_ptr(), 1 if accumulate else 0, L.ptr(per_scale), ws.data_ptr(),
+                                                ws.numel() * 4, L.stream_ptr()), "vg_msssim_loss_forward_backward")
+    return d
+
+
+def ms_ssim(a, b, weights=None):
+    """Multi-scale SSIM of two NCHW f32 batches in [-1, 1] -> device tensor [1]: 1 - the loss above (forward only).
+    weights None: msssim_weights(H, W)."""
+    _need_cuda(a, b)
+    if a.dim() != 4:
+        raise RuntimeError("ms_ssim: a and b must be [B,C,H,W] tensors")
+    if weights is None:
+        weights = msssim_weights(a.shape[2], a.shape[3])
+    out = torch.empty(1, dtype=torch.float32, device=a.device)
+    msssim_loss_forward_backward(a, b, weights, 1.0, out, False)
+    return torch.sub(1.0, out, out=out)
 
 
 def region_mse_forward_backward(a, b, rects, w_hole, gscale, loss=None, hole_mse=None, want_grad=False, stats=None):

@@ -21,6 +21,7 @@ from . import ops
 from .capture import HostMirrors, capture, replay
 from .engine import GradSink, bump_weights_epoch
 from .gradclip import ClipOption
+from .losses import trainer_scales
 from .optim import lr_report
 
 
@@ -113,7 +114,7 @@ class VAETrainer(_Graphed):
     LOSS_NAMES = ("recon_loss", "kl_loss", "total")
 
     def __init__(self, encoder, decoder, optimizer, noise_max_std: float = 0.5, kl_weight: float = 1e-5,
-                 alpha_ssim: float = 0.0, hole_weight: float = 1.0, ema=None, max_grad_norm=None):
+                 alpha_ssim: float = 0.0, hole_weight: float = 1.0, ema=None, max_grad_norm=None, ssim_scales=None):
         """max_grad_norm: the one optimizer holds both networks, so its one norm is the network "EG" (a number, or
         {"EG": number}); reported in grad_norms[0]."""
         self.E, self.G, self.opt = encoder, decoder, optimizer
@@ -123,6 +124,14 @@ class VAETrainer(_Graphed):
         # SSIM reconstruction loss (not in the reference): total += alpha_ssim * (1 - SSIM(recon,
         # img)), the gradient added onto the MSE's.  Off (0, the default): the iteration launches what it launched before.
         self.alpha_ssim = float(alpha_ssim)
+        # Its multi-scale form: ssim_scales not None makes the term 1 - MS-SSIM(recon, img) over a 2x
+        # pyramid (csrc/msssim.hip), same slot; True / "auto", an int or 1 - 5 weights as VAEGANTrainer takes them.  None
+        # (the default): the single-scale launch, exactly.
+        if ssim_scales is not None:
+            if self.alpha_ssim == 0.0:
+                raise ValueError("ssim_scales needs alpha_ssim != 0 (it selects the form of the SSIM term)")
+            trainer_scales(ssim_scales, 1 << 14, 1 << 14)
+        self.ssim_scales = ssim_scales
         # Training on degraded pairs: train_step(img, ..., noisy=, rects=) feeds `noisy` to the
         # Encoder; with hole_weight != 1 and rects the reconstruction term is the region-weighted MSE (csrc/regionloss.hip).
         self.hole_weight = float(hole_weight)
@@ -133,6 +142,10 @@ class VAETrainer(_Graphed):
 
     def _clip_opts(self):
         return {"EG": self.opt}
+
+    def _extra_key(self):
+        s = self.ssim_scales
+        return () if s is None else (("msssim", s if isinstance(s, (bool, int, str)) else tuple(float(x) for x in s)),)
 
     def train(self):
         self.E.train(), self.G.train()                                             # :98-99
@@ -186,7 +199,11 @@ class VAETrainer(_Graphed):
         w = min(epoch / 50, 1.0) * self.kl_weight                                  # :121
         torch.add(losses[0:1], losses[1:2], alpha=w, out=losses[2:3])
         if self.alpha_ssim != 0.0:
-            ops.ssim_loss_forward_backward(recon, img, self.alpha_ssim, losses[3:4], False, d_recon)
+            if self.ssim_scales is None:
+                ops.ssim_loss_forward_backward(recon, img, self.alpha_ssim, losses[3:4], False, d_recon)
+            else:
+                ops.msssim_loss_forward_backward(recon, img, trainer_scales(self.ssim_scales, *img.shape[2:]),
+                                                 self.alpha_ssim, losses[3:4], False, d_recon)
             torch.add(losses[2:3], losses[3:4], alpha=self.alpha_ssim, out=losses[2:3])
         self.opt.zero_grad(memset=False)                                           # :124
         d_pre = ops.nchw_grad_to_nhwc(d_recon, recon, G.padc(Gn.nc, dt), dt)

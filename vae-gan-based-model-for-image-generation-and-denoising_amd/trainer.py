@@ -20,6 +20,7 @@ from .capture import CaptureRefused, HostMirrors, capture, replay
 from . import augment as A
 from .engine import GradSink
 from .gradclip import ClipOption
+from .losses import trainer_scales
 from .optim import lr_report
 
 LOSS_NAMES = ("recon_loss", "kl_loss", "g_loss_adv", "d_loss_1", "d_loss_2")
@@ -52,7 +53,7 @@ class VAEGANTrainer(ClipOption):
                  d_iters: int = 2, elide_dead_grads: bool = False, reducer=None, group_d_passes: bool = True,
                  sync_bn: bool = False, feat_layer: Optional[int] = None, alpha_feat: float = 0.0, alpha_pix: float = 1.0,
                  alpha_ssim: float = 0.0, hole_weight: float = 1.0, ema=None, max_grad_norm=None, augment=None,
-                 prior_stream: bool = False):
+                 prior_stream: bool = False, ssim_scales=None):
         self.E, self.G, self.D = encoder, decoder, discriminator
         self.opt_E, self.opt_G, self.opt_D = opt_E, opt_Dec, opt_Dis
         self.alpha_kl, self.alpha_adv, self.sigma = alpha_kl, alpha_adv, noise_sigma          # :49-50, :91-92
@@ -75,6 +76,16 @@ class VAEGANTrainer(ClipOption):
         # MSE's in the buffer that launch wrote (csrc/ssimloss.hip, one launch for forward and backward).  Off (0, the
         # default): the iteration launches exactly what it launched without it.
         self.alpha_ssim = float(alpha_ssim)
+        # Multi-scale form of that term: with ssim_scales not None the structural term is 1 - MS-SSIM(recon,
+        # real) over a 2x pyramid (csrc/msssim.hip; at most five launches whatever the number of scales) -- same place in the
+        # iteration, same loss slot, same "ssim_loss" key.  ssim_scales: True or "auto" = the default scales of the image size
+        # (ops.msssim_weights), an int = that many, a sequence of 1 - 5 weights = those.  None (the default): the single-scale
+        # launches above, exactly.
+        if ssim_scales is not None:
+            if self.alpha_ssim == 0.0:
+                raise ValueError("ssim_scales needs alpha_ssim != 0 (it selects the form of the SSIM term)")
+            trainer_scales(ssim_scales, 1 << 14, 1 << 14)          # a bad count / weight fails here, not in the first step
+        self.ssim_scales = ssim_scales
         # Training on degraded pairs: train_step(clean, ..., noisy=, rects=) feeds `noisy` to the
         # Encoder and, with hole_weight != 1, replaces the pixel MSE by the region-weighted one (csrc/regionloss.hip): the
         # squared error inside each image's occlusion rectangle counts hole_weight times.  1 (the default) or no rects:
@@ -191,6 +202,7 @@ class VAEGANTrainer(ClipOption):
                 None if self.noise is None or (inject and self.augment is None) else self.noise.state.data_ptr()) \
             + (self.augment.key() if self.augment is not None else ()) \
             + ((True, with_rects, self.hole_weight) if paired else ()) \
+            + ((("msssim",) + trainer_scales(self.ssim_scales, *real.shape[2:]),) if self.ssim_scales is not None else ()) \
             + ((("ema",) + self.ema.key(),) if self.ema is not None else ()) + self._clip_key()
 
     # ---- data-parallel gradient hand-off (ddp.GradReducer) -------------------------------------------------------
@@ -484,7 +496,11 @@ class VAEGANTrainer(ClipOption):
         if self.alpha_ssim != 0.0:
             # 1 - SSIM(recon, real) and its gradient, added onto the MSE's in d_recon (which that launch wrote in full, also
             # with alpha_pix = 0)
-            ops.ssim_loss_forward_backward(recon, real, self.alpha_ssim, losses[6:7], False, d_recon)
+            if self.ssim_scales is None:
+                ops.ssim_loss_forward_backward(recon, real, self.alpha_ssim, losses[6:7], False, d_recon)
+            else:
+                ops.msssim_loss_forward_backward(recon, real, trainer_scales(self.ssim_scales, *real.shape[2:]),
+                                                 self.alpha_ssim, losses[6:7], False, d_recon)
         dp_adv, dp_pr = None, None
         if group_g:
             dp_adv = torch.empty_like(p_adv)                  # [2B]: :115 on the reconstruction's half, the same on the prior's
