@@ -81,7 +81,9 @@ extern "C" {
                              31: decoded prior samples as the third Discriminator stream: vg_prior_forward (+ _rng),
                                  vg_head_backward_g, vg_nhwc_grad_tanh_to_nhwc;
                                  (added within 31, nothing changed) multi-scale SSIM loss: vg_msssim_loss_forward_backward
-                                 (+ _ws_bytes); timing family 5 */
+                                 (+ _ws_bytes); timing family 5;
+                                 (added within 31, nothing changed) test-time latent refinement: vg_bn_act_backward_eval,
+                                 vg_masked_mse_rows (+ _ws_doubles), vg_latent_adam / VG_LATENT_* */
 int vg_abi_version(void);
 /* The library reads its optional kernel-selection switches (VG_* environment variables, DESIGN.md "Runtime switches")
  * ONCE, when it is loaded; nothing on a launch path calls getenv.  A process that changes one of them afterwards
@@ -640,6 +642,72 @@ int vg_region_mse_forward_backward(const float* a, const float* b, const float* 
                                    float w_hole, float gscale, float* loss, float* hole_mse, float* d_a, double* stats,
                                    double* ws, int ws_doubles, void* stream);
 int vg_region_mse_ws_doubles(int B, int C, int H, int W);        /* <= 0 (VG_EINVAL) for B, C, H or W < 1 */
+/* ------------------------------------------------------------------------------------------
+ * Test-time latent refinement (csrc/refine.hip; additions within ABI 31): descend on the latent z of
+ * frozen, eval-mode networks so that G(z) matches a degraded input outside its occlusion rectangle (GAN-inversion inpainting,
+ * Yeh et al. 2017).  The reference never differentiates an eval-mode network; these are the three launches that the forward
+ * and data-gradient chains above lack for it.
+ * ---------------------------------------------------------------------------------------- */
+/* Backward of y = act(scale[c] x + shift[c]) with CONSTANT coefficients -- the eval-mode BatchNorm that vg_bn_eval_coeffs feeds
+ * to vg_bn_act_forward (groups = 1):  dx = dy act'(z) scale[c],  z = fmaf(scale[c], x, shift[c]) in f32, the expression of
+ * vg_bn_act_forward, so the activation mask agrees with the forward pass bit for bit; act' as in vg_bn_act_backward_reduce:
+ * ReLU passes dy where z > 0 and 0 elsewhere (z == 0 and a NaN z included), LeakyReLU passes dy where z > 0 and dy * slope
+ * elsewhere, VG_ACT_NONE passes dy.  Every product is an f32 product; the result is rounded once to the storage type.
+ * x, dy, dx: [rows][C] in dtype (VG_F32 | VG_BF16), C the padded channel count; dx may alias dy.  One streaming launch with the
+ * thread -> (row, channel column) mapping of vg_bn_act_backward_apply: 16-byte vectors (4 f32; 8 bf16 where C % 8 == 0 and x,
+ * dy, dx are 16-byte aligned), else 8-byte vectors of 4 bf16; a ragged last block of 256 columns.  Three tensor-sized streams
+ * (12 B per element f32, 6 B bf16), HBM-bound; timing family 4.  VG_EINVAL: a NULL pointer, rows or C < 1, an activation
+ * other than NONE / RELU / LRELU; VG_ENOSUP: an unknown dtype; VG_EALIGN: C % 4 != 0, x / dy / dx not aligned to the narrowest
+ * vector (16 bytes f32, 8 bytes bf16), scale / shift not 16-byte aligned.  All checked before the launch. */
+int vg_bn_act_backward_eval(const void* x, const void* dy, void* dx, const float* scale, const float* shift, int64_t rows,
+                            int C, int act, float slope, int dtype, void* stream);
+/* Per-image context loss: the mean squared error of a against b (a constant), both NCHW f32 [B][C][H][W], over the elements
+ * OUTSIDE image i's occlusion rectangle, one value per image, and its gradient.  rects and the hole rule are those of
+ * vg_region_mse_forward_backward, word for word: f32 [B][8], entries 2..5 = {rect_h, rect_w, x, y}; pixel (h, w) is in the
+ * hole iff y <= h < y + rect_h and x <= w < x + rect_w in every channel, compared in f32; an empty rectangle has no hole, a
+ * rectangle past the image is clipped by it, a NaN entry makes every comparison false (no hole), rects == NULL: no image has
+ * a hole; the rectangle enters comparisons only, no address is formed from it.  With d = a - b in f32, q = d d in f32
+ * accumulated in f64 into S_valid_i, and n_valid_i the exact count of image i's elements outside its hole:
+ *   loss_rows[i] = (float)(S_valid_i / n_valid_i), 0 when n_valid_i == 0                          NULL skips it
+ *   d_a[e]       = (float)(2 (double)gscale / n_valid_i) * d outside the hole, exactly 0 inside   written in full; NULL skips it
+ * (the gradient of gscale * loss_rows[i]; images do not share a term, so gscale is NOT divided by B).
+ * Two launches: a grid of (workgroups per image, B) -- a workgroup's f64 partial in ws is of ONE image -- and one wave per
+ * image for the final pass; fixed summation order, no atomics: the same inputs give the same bits eagerly and replayed.  With
+ * loss_rows NULL only the first runs.  16-byte loads along W where W % 4 == 0 and a, b, d_a are 16-byte aligned, one element per
+ * lane otherwise.  ws: at least vg_masked_mse_rows_ws_doubles(B, C, H, W) doubles; ws_doubles is its capacity.  VG_EINVAL: a or
+ * b NULL, a size < 1, B > 65535, C H W >= 2^31 - 2^19, gscale not finite, both outputs NULL, ws NULL or too small; VG_EALIGN:
+ * rects or ws not 8-byte aligned, a tensor not 4-byte aligned.  HBM-bound: 12 B per element with the gradient, 8 B without. */
+int vg_masked_mse_rows(const float* a, const float* b, const float* rects, int B, int C, int H, int W, float gscale,
+                       float* loss_rows, float* d_a, double* ws, int ws_doubles, void* stream);
+int vg_masked_mse_rows_ws_doubles(int B, int C, int H, int W);   /* <= 0 (VG_EINVAL) for sizes outside the contract */
+/* The optimiser over latents: objective, keep-best and one Adam step per image row, one wave per row, no value leaves the
+ * device.  State per row (all f32 but t): master z [B][L], m [B][L], v [B][L], the row's own step count t [B] (int32: rows
+ * do not share a counter), best_loss [B], best_z [B][L].  dz, z_in, z_out: [B][ZP] in dtype (the Generator's stage-0 data
+ * gradient / input, ZP the padded latent width); loss_rows [B] (vg_masked_mse_rows); p [B]: the Discriminator's
+ * probabilities, or NULL (no adversarial term).
+ *   VG_LATENT_INIT    z = best_z = (float)z_in, m = v = 0, t = 0, best_loss = +inf; z_out (optional) = z_in, padding lanes 0.
+ *   VG_LATENT_UPDATE  1. J = loss_rows[i] + alpha_adv (-max(log p_i, -100)) [p given] + prior_weight (1 / (2 L)) sum_l z_l^2
+ *                        (nn.BCELoss' clamp; formed in f64, rounded to f32); objective[i] = J when objective != NULL;
+ *                     2. J < best_loss[i] (strict: a tie keeps the earlier iterate, a NaN never wins): best_loss[i] = J,
+ *                        best_z[i] = the z that was just evaluated;
+ *                     3. g = (float)dz + prior_weight z / L; torch.optim.Adam (no weight decay, no amsgrad) with bias
+ *                        corrections from t_i + 1: m = beta1 m + (1 - beta1) g, v = beta2 v + (1 - beta2) g g,
+ *                        z -= lr / (1 - beta1^(t+1)) * m / (sqrt(v) / sqrt(1 - beta2^(t+1)) + eps); t_i += 1;
+ *                     4. z_out = z in dtype, padding lanes 0.
+ *                     Each stored value (m, v, z) is formed in f64 from the f32 state and rounded once; beta^(t+1) is formed by
+ *                     square-and-multiply in f64 (r = 1; while n: if n odd r *= b; b *= b; n >>= 1), not by pow().
+ *   VG_LATENT_TRACK   steps 1 and 2 only (the last iterate's objective, after the loop).
+ * One launch of B waves.  VG_EINVAL: an unknown mode, B or L < 1, ZP < L, a NULL pointer the mode reads or writes (z,
+ * best_loss, best_z always; m, v, t, z_in for INIT; loss_rows for UPDATE / TRACK; m, v, t, dz, z_out for UPDATE), lr or eps
+ * negative or not finite, a beta outside [0, 1) (UPDATE), alpha_adv or prior_weight negative or not finite; VG_ENOSUP: an unknown
+ * dtype; VG_EALIGN: ZP % 4 != 0, dz / z_in / z_out not aligned to an element. */
+#define VG_LATENT_INIT   0
+#define VG_LATENT_UPDATE 1
+#define VG_LATENT_TRACK  2
+int vg_latent_adam(float* z, float* m, float* v, int* t, float* best_loss, float* best_z, const void* dz,
+                   const float* loss_rows, const float* p, const void* z_in, void* z_out, float* objective, int B, int L,
+                   int ZP, double lr, double beta1, double beta2, double eps, float alpha_adv, float prior_weight, int mode,
+                   int dtype, void* stream);
 /* Mean SSIM of two NCHW f32 image batches in [-1,1] (rescaled to [0,1] as vaegan_code.py:170-174 does):
  * gaussian 11x11, sigma 1.5, k1 .01, k2 .03, data_range 1, 5-pixel border cropped.  out[0] = mean. */
 int vg_ssim(const float* a, const float* b, int B, int C, int H, int W, float* out, float* ws, int ws_capacity,

@@ -25,7 +25,9 @@ trainers.  Differentiable augmentation of the Discriminator's inputs (not in the
 the step count, so a captured iteration replays a moving rate) and ``AdamW``.  Data path (dataset_code.py): ``data`` -- ``ResidentImages`` (``resized``: Resize +
 CenterCrop on the device), ``resample_coeffs``, ``resize_geometry``.  Tiled denoising of images larger than the networks
 (not in the reference): ``denoise_tiled``, ``tiled_denoise_eval``, ``tiled_test_epoch`` and ``tiling`` -- ``tile_plan`` /
-``TilePlan``: overlapping S x S tiles cut and blended back on the device with a separable window.
+``TilePlan``: overlapping S x S tiles cut and blended back on the device with a separable window.  Test-time latent
+refinement (not in the reference; GAN-inversion denoising / inpainting): ``LatentRefiner`` -- Adam on the latent of the frozen
+networks against the input outside its occlusion rectangle, and ``paired_test_epoch(..., refine=)``.
 """
 from . import cluster  # noqa: F401
 from . import data  # noqa: F401
@@ -37,7 +39,7 @@ from .augment import DiffAugment
 from .ddp import GradReducer
 from .ema import EMA
 from . import tiling  # noqa: F401
-from .denoise import (denoise_eval, denoise_tiled, paired_test_epoch, tiled_denoise_eval, tiled_test_epoch,
+from .denoise import (LatentRefiner, denoise_eval, denoise_tiled, paired_test_epoch, tiled_denoise_eval, tiled_test_epoch,
                       validation_epoch)
 from .tiling import TilePlan, tile_plan
 from .graphed import graphed
@@ -59,4 +61,4 @@ __all__ = ["ConvBlock", "Encoder", "Generator", "Discriminator", "weights_init",
            "EMA", "clip_grad_norm_", "DiffAugment", "AdamW", "LRSchedule",
            "tiling", "TilePlan", "tile_plan", "denoise_tiled", "tiled_denoise_eval", "tiled_test_epoch",
            "metrics", "FeatureStats", "frechet_distance", "precision_recall", "encoder_features", "kernel_distance",
-           "cluster", "KMeans", "ndb", "evaluate_generation_ndb", "MSSSIMLoss", "msssim_weights"]
+           "cluster", "KMeans", "ndb", "evaluate_generation_ndb", "MSSSIMLoss", "msssim_weights", "LatentRefiner"]

@@ -21,6 +21,7 @@ VG_GNORM_MAX = 4
 VG_GNORM_PARTS = 512
 VG_PROLOGUE_MAX = 4
 VG_TILE_MAX_COVER = 8
+VG_LATENT_INIT, VG_LATENT_UPDATE, VG_LATENT_TRACK = 0, 1, 2
 VG_LRS_CONST, VG_LRS_LINEAR, VG_LRS_COSINE, VG_LRS_EXP, VG_LRS_STEP = 0, 1, 2, 3, 4
 ABI_VERSION = 31
 
@@ -195,6 +196,10 @@ SIGNATURES = {
     "vg_msssim_ws_bytes": (c_int64, [_I, _I, _I, _I, _I]),
     "vg_region_mse_forward_backward": (c_int, [_P, _P, _P, _I, _I, _I, _I, _F, _F, _P, _P, _P, _P, _P, _I, _P]),
     "vg_region_mse_ws_doubles": (c_int, [_I, _I, _I, _I]),
+    "vg_bn_act_backward_eval": (c_int, [_P, _P, _P, _P, _P, _L, _I, _I, _F, _I, _P]),
+    "vg_masked_mse_rows": (c_int, [_P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _I, _P]),
+    "vg_masked_mse_rows_ws_doubles": (c_int, [_I, _I, _I, _I]),
+    "vg_latent_adam": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _D, _D, _D, _D, _F, _F, _I, _I, _P]),
     "vg_ssim": (c_int, [_P, _P, _I, _I, _I, _I, _P, _P, _I, _P]),
     "vg_axpy": (c_int, [_P, _P, _F, _P, _L, _P]),
     "vg_bn_backward_onepass_supported": (c_int, [_L, _I, _I, _I]),

@@ -13,6 +13,8 @@ import torch
 from . import geometry as G
 from . import ops
 from . import tiling
+from .capture import HostMirrors, capture, replay
+from .engine import GradSink
 from .metrics import FeaturePass
 
 
@@ -161,7 +163,7 @@ def validation_epoch(encoder, decoder, loader: Iterable[torch.Tensor], n_samples
 
 @torch.no_grad()
 def paired_test_epoch(encoder, decoder, loader: Iterable, n_samples: Optional[int] = None, noise_fn=None,
-                      regions: bool = False, ms_ssim: bool = False) -> Dict[str, float]:
+                      regions: bool = False, ms_ssim: bool = False, refine=None) -> Dict[str, float]:
     """The reference's test pass over (noisy, clean) pairs, main_vae.py:251-266:
 
         encoder.eval(); decoder.eval()                                                 (:251-252)
@@ -188,9 +190,27 @@ def paired_test_epoch(encoder, decoder, loader: Iterable, n_samples: Optional[in
     reports mse 0.0 and psnr inf.  Still one host sync.
     ms_ssim=True (default False: nothing changes): the result gains ``ms_ssim`` and ``ms_ssim_noisy``, the multi-scale SSIM
     (ops.ms_ssim, the default scales of the image size) of ``recon`` and of ``noisy`` vs ``clean``, accumulated like ssim and
-    read in the same host sync."""
-    if regions and not (hasattr(loader, "want_rects") and getattr(loader, "degrade", None) is not None and loader.degrade.pairs):
-        raise RuntimeError("paired_test_epoch: regions=True needs a degraded data.DeviceLoader (want_rects)")
+    read in the same host sync.
+    refine (default None: exactly the keys and the launches above): a ``LatentRefiner`` built on these networks, or a dict of
+    its keywords (``discriminator=`` among them) from which one is built.  Every batch is ALSO refined at test time --
+    ``refine.refine(noisy, rects=loader.last_rects)`` from the Encoder's mean, the occlusion rectangle left out of its loss
+    -- and the result gains ``recon_loss_refined``, ``ssim_refined`` and ``psnr_refined`` of the refined reconstruction vs
+    ``clean`` (with regions=True also the five region keys suffixed ``_refined``), accumulated on the device and read in the
+    same host sync.  The loader must offer ``want_rects``, which the pass turns on and restores as regions=True does."""
+    refiner = None
+    if refine is not None:
+        if isinstance(refine, LatentRefiner):
+            refiner = refine
+        elif isinstance(refine, dict):
+            refiner = LatentRefiner(encoder, decoder, **refine)
+        else:
+            raise ValueError("paired_test_epoch: refine must be a LatentRefiner or a dict of its keywords")
+        if refiner.E is not encoder or refiner.G is not decoder:
+            raise ValueError("paired_test_epoch: the LatentRefiner was built on other networks")
+    need_rects = regions or refiner is not None
+    if need_rects and not (hasattr(loader, "want_rects") and getattr(loader, "degrade", None) is not None and loader.degrade.pairs):
+        raise RuntimeError(f"paired_test_epoch: {'regions=True' if regions else 'refine'} needs a degraded data.DeviceLoader "
+                           f"(want_rects)")
     encoder.eval(), decoder.eval()                                                   # :251-252
     dev = next(encoder.parameters()).device
     dt, L = encoder._dt, encoder.latent_dim
@@ -202,10 +222,14 @@ def paired_test_epoch(encoder, decoder, loader: Iterable, n_samples: Optional[in
     if offers:
         loader.want_nhwc(G.padc(loader.dataset.image_shape[0], dt), dt)
     stats = None
-    if regions:
+    if need_rects:
         rects_were_on = bool(getattr(loader, "_rects", False))
         loader.want_rects(True)
+    if regions:
         stats = torch.zeros(2, 4, dtype=torch.float64, device=dev)                   # {S_hole, S_valid, n_hole, n_valid} of recon, noisy
+    if refiner is not None:
+        acc_ref = ops.zeros_f32(2, dev)                                              # [sum(b * ssim(refined)), sum(b * mse_mean(refined))]
+        stats_ref = torch.zeros(4, dtype=torch.float64, device=dev) if regions else None
     try:
         for i, (noisy, clean) in enumerate(loader):
             if not (noisy.is_cuda and clean.is_cuda):
@@ -241,19 +265,32 @@ def paired_test_epoch(encoder, decoder, loader: Iterable, n_samples: Optional[in
             if ms_ssim:
                 ops.axpy(acc_ms[0:1], ops.ms_ssim(recon, clean), float(b), out=acc_ms[0:1])
                 ops.axpy(acc_ms[1:2], ops.ms_ssim(noisy, clean), float(b), out=acc_ms[1:2])
+            if refiner is not None:
+                refined = refiner.refine(noisy, rects=loader.last_rects)["recon"]
+                mse_ref = torch.empty(1, dtype=torch.float32, device=dev)
+                ops.mse_forward_backward(refined, clean, 1.0, mse_ref, False)
+                ops.axpy(acc_ref[0:1], ops.ssim(refined, clean), float(b), out=acc_ref[0:1])
+                ops.axpy(acc_ref[1:2], mse_ref, float(b), out=acc_ref[1:2])
+                if regions:
+                    ops.region_mse_forward_backward(refined, clean, loader.last_rects, 1.0, 1.0, stats=stats_ref)
             seen += b
             batches += 1
     finally:
         if offers:
             loader.want_nhwc(None)
-        if regions:
+        if need_rects:
             loader.want_rects(rects_were_on)
     if batches == 0:
         raise RuntimeError("paired_test_epoch: the loader yielded no batch")
     parts = [acc.double(), stats.flatten()] if regions else [acc]
     if ms_ssim:
         parts = [p.double() for p in parts] + [acc_ms.double()]                      # (f32 -> f64 is exact)
+    if refiner is not None:
+        parts = [p.double() for p in parts] + [acc_ref.double()] + ([stats_ref] if regions else [])
     host = (torch.cat(parts) if len(parts) > 1 else acc).tolist()                    # the one host sync
+    if refiner is not None:                                                          # the refined tail, then today's layout
+        nref = 6 if regions else 2
+        host, host_ref = host[:-nref], host[-nref:]
     tot, ssim_sum, mse_sum, kl_sum, ssim_n_sum, mse_n_sum = (float(v) for v in host[:6])
     n = seen if n_samples is None else int(n_samples)
 
@@ -272,12 +309,253 @@ def paired_test_epoch(encoder, decoder, loader: Iterable, n_samples: Optional[in
             out.update({"mse_hole" + suffix: m_hole, "mse_valid" + suffix: m_valid,
                         "psnr_hole" + suffix: psnr(m_hole), "psnr_valid" + suffix: psnr(m_valid),
                         "hole_fraction" + suffix: n_hole / (n_hole + n_valid)})
+    if refiner is not None:
+        out.update({"recon_loss_refined": host_ref[1] / seen, "ssim_refined": host_ref[0] / seen,
+                    "psnr_refined": psnr(host_ref[1] / seen)})
+        if regions:
+            s_hole, s_valid, n_hole, n_valid = host_ref[2:6]
+            m_hole = s_hole / n_hole if n_hole > 0 else 0.0
+            m_valid = s_valid / n_valid if n_valid > 0 else 0.0
+            out.update({"mse_hole_refined": m_hole, "mse_valid_refined": m_valid, "psnr_hole_refined": psnr(m_hole),
+                        "psnr_valid_refined": psnr(m_valid), "hole_fraction_refined": n_hole / (n_hole + n_valid)})
     return out
 
 
 def _psnr(mse: float) -> float:
     mse01 = mse / 4.0                                                      # ((a+1)/2 - (b+1)/2)^2 = (a-b)^2 / 4
     return float("inf") if mse01 == 0 else 10.0 * math.log10(1.0 / mse01)
+
+
+def _finite_nonneg(name: str, v) -> float:
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or not (math.isfinite(v) and v >= 0.0):
+        raise ValueError(f"{name} must be finite and >= 0")
+    return float(v)
+
+
+class LatentRefiner:
+    """Test-time latent refinement (not in the reference; GAN-inversion denoising / inpainting, Yeh et al. 2017, "Semantic
+    image inpainting with deep generative models"): keep the trained networks frozen, start from the Encoder's latent and
+    run Adam on z so that G(z) matches the degraded input OUTSIDE its occlusion rectangle, optionally with the Discriminator
+    as a realism prior and a Gaussian prior on z.  Per image i the objective is
+
+        J_i = mse_valid_i(G(z_i), noisy_i) + alpha_adv * (-max(log D(G(z_i)), -100)) + prior_weight * |z_i|^2 / (2 L)
+
+    (mse_valid_i: mean squared error over the elements outside image i's rectangle).  The adversarial term DESCENDS along the
+    gradient of BCE(D(G(z)), 0.9) -- the trainer's smoothed "real" label -- while J reports the unsmoothed -log D.
+    All arithmetic is eval-mode (BatchNorm on the running statistics, whatever ``module.training`` says; the flags are left
+    alone): rows are independent, no parameter, buffer, ``num_batches_tracked`` or ``.grad`` is touched, no weight gradient
+    is formed.  One iteration = G forward (kept), ops.masked_mse_rows, [D forward, head launch, D data gradients,
+    ops.nchw_grad_add_to_nhwc |  ops.nchw_grad_to_nhwc], G data gradients, ops.latent_adam -- DESIGN.md section 4.4q.
+    graphed=True replays ONE captured iteration ``steps`` times (capture.capture / capture.replay); a capture is keyed by the
+    batch size and by what the engines key their packed operands by, so a refiner used between training steps captures
+    again.  encoder=None builds a refiner that only takes an injected start (``init=`` a tensor; the Encoder needs images of
+    at least 64 x 64, the other two networks go down to 16 x 16).  keep_best=True returns, per image, the iterate with the lowest objective seen (the start included)."""
+
+    REAL_LABEL = 0.9                        # VAEGANTrainer's real_label default (vaegan_code.py:88)
+
+    def __init__(self, encoder, decoder, discriminator=None, *, steps: int = 50, lr: float = 0.05, betas=(0.9, 0.999),
+                 eps: float = 1e-8, alpha_adv: float = 0.0, prior_weight: float = 0.0, keep_best: bool = True,
+                 graphed: bool = True):
+        if isinstance(steps, bool) or not isinstance(steps, int) or steps < 0:
+            raise ValueError("steps must be an integer >= 0")
+        self.steps = steps
+        self.lr = _finite_nonneg("lr", lr)
+        try:
+            b1, b2 = (float(b) for b in betas)
+        except (TypeError, ValueError):
+            raise ValueError("betas must be two numbers in [0, 1)") from None
+        if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
+            raise ValueError("betas must be two numbers in [0, 1)")
+        self.betas = (b1, b2)
+        self.eps = _finite_nonneg("eps", eps)
+        self.alpha_adv = _finite_nonneg("alpha_adv", alpha_adv)
+        self.prior_weight = _finite_nonneg("prior_weight", prior_weight)
+        for name, flag in (("keep_best", keep_best), ("graphed", graphed)):
+            if not isinstance(flag, bool):
+                raise ValueError(f"{name} must be True or False")
+        self.keep_best, self.graphed = keep_best, graphed
+        if self.alpha_adv != 0.0 and discriminator is None:
+            raise ValueError("alpha_adv != 0 needs a discriminator")
+        nets = [n for n in (encoder, decoder, discriminator) if n is not None]
+        if len({n._dt for n in nets}) != 1:
+            raise ValueError("encoder / decoder / discriminator must share one engine dtype")
+        if encoder is not None and (decoder.nz != encoder.latent_dim or decoder.img_size != encoder._img or
+                                    decoder.nc != encoder._engine.in_ch):
+            raise ValueError("LatentRefiner needs a Generator that decodes the Encoder's latent into the Encoder's image shape")
+        if discriminator is not None and (discriminator.nc != decoder.nc or discriminator.img_size != decoder.img_size):
+            raise ValueError("LatentRefiner needs a Discriminator of the Generator's image shape")
+        # a Discriminator without an adversarial weight has no term in J: it is not run
+        self.E, self.G, self.D = encoder, decoder, discriminator if self.alpha_adv != 0.0 else None
+        self.dt, self.latent = decoder._dt, decoder.nz
+        self._bufs = {}                     # B -> the static buffers of that batch size
+        self._caps = {}                     # B -> capture.Captured of one iteration
+        self.captures = 0                   # captures made so far (a replayed call adds none)
+
+    # ---- pieces of one iteration ------------------------------------------------------------------------------------
+    def _buffers(self, B: int, dev):
+        buf = self._bufs.get(B)
+        if buf is None or buf["noisy"].device != dev:
+            Gn, dt = self.G, self.dt
+            f32 = dict(dtype=torch.float32, device=dev)
+            buf = dict(state=ops.latent_state(B, self.latent, dev),
+                       z_eng=ops.empty_act((B, 1, 1, G.padc(Gn.nz, dt)), dt, dev),
+                       noisy=torch.empty(B, Gn.nc, Gn.img_size, Gn.img_size, **f32), rects=torch.empty(B, 8, **f32),
+                       loss_rows=torch.empty(B, **f32), objective=torch.empty(B, **f32), objective0=torch.empty(B, **f32),
+                       slot=torch.empty(1, **f32))
+            self._bufs[B] = buf
+            self._caps.pop(B, None)
+        return buf
+
+    def _evaluate(self, buf, B: int, want_grad: bool):
+        """G(z_eng), the context loss rows against the static input and, with a Discriminator, its probabilities.
+        -> (recon NCHW f32, G's context, d loss / d recon or None, p or None, D's context)"""
+        Gn, D, dt = self.G, self.D, self.dt
+        CP = G.padc(Gn.nc, dt)
+        d_in = None
+        if Gn.fused_tail(B):
+            tail = {}
+            if D is not None:               # the last layer's kernel writes the image in D's layout as well (no noise added)
+                d_in = ops.empty_act((B, Gn.img_size, Gn.img_size, CP), dt, buf["noisy"].device)
+                tail = dict(out_noisy=d_in)
+            recon, ctxG = Gn._engine.forward(buf["z_eng"], B, False, keep=want_grad, tail=tail)
+        else:
+            pre, ctxG = Gn._engine.forward(buf["z_eng"], B, False, keep=want_grad)
+            recon = ops.nhwc_to_nchw(pre, Gn.nc, dt, apply_tanh=True)
+            if D is not None:
+                d_in = ops.nchw_to_nhwc(recon, CP, dt)
+        d_recon = ops.masked_mse_rows(recon, buf["noisy"], buf["rects"], 1.0, buf["loss_rows"], want_grad)
+        p = ctxD = None
+        if D is not None:
+            p, ctxD = D._engine.forward(d_in, B, False, keep=want_grad)
+        return recon, ctxG, d_recon, p, ctxD
+
+    def _iterate(self, buf, B: int) -> None:
+        """One refinement iteration on the static buffers; no host value, no allocation outside torch's allocator."""
+        Gn, D, dt = self.G, self.D, self.dt
+        recon, ctxG, d_recon, p, ctxD = self._evaluate(buf, B, True)
+        sink = GradSink(direct=False)       # never asked: no parameter gradient is formed
+        CP = G.padc(Gn.nc, dt)
+        if D is not None:
+            # gradient scale alpha_adv * B against the launch's 1 / B: every image gets the gradient of ITS term
+            gscale = self.alpha_adv * B
+            if B <= ops.HEAD_BWD_MAXROWS and D._engine.stages[-1].kind == "head":
+                d_img = D._engine.backward(ctxD, None, True, sink, param_grads=False,
+                                           head_loss=(self.REAL_LABEL, 0.0, 1, gscale, buf["slot"], False))
+            else:
+                dp = ops.bce_forward_backward(p, self.REAL_LABEL, gscale, buf["slot"], False, True)
+                d_img = D._engine.backward(ctxD, dp, True, sink, param_grads=False)
+            d_pre = ops.nchw_grad_add_to_nhwc(d_recon, d_img, recon, CP, dt)     # both image gradients, through Tanh
+        else:
+            d_pre = ops.nchw_grad_to_nhwc(d_recon, recon, CP, dt)
+        dz = Gn._engine.backward(ctxG, d_pre, True, sink, param_grads=False)
+        ops.latent_adam("update", buf["state"], dt, buf["z_eng"].shape[-1], dz=dz, loss_rows=buf["loss_rows"], p=p,
+                        z_out=buf["z_eng"], objective=buf["objective"], lr=self.lr, betas=self.betas, eps=self.eps,
+                        alpha_adv=self.alpha_adv, prior_weight=self.prior_weight)
+
+    def _decode(self, z_eng, B: int) -> torch.Tensor:
+        Gn, dt = self.G, self.dt
+        if Gn.fused_tail(B):
+            return Gn._engine.forward(z_eng, B, False, keep=False, tail={})[0]
+        pre, _ = Gn._engine.forward(z_eng, B, False, keep=False)
+        return ops.nhwc_to_nchw(pre, Gn.nc, dt, apply_tanh=True)
+
+    def _engines(self):
+        return [n._engine for n in (self.G, self.D) if n is not None]
+
+    def _capture_key(self, B: int):
+        """The batch size and, per engine in the iteration, what its packed operands are valid for and where they live."""
+        for e in self._engines():
+            e._ensure_packed()              # the weights are constants of the loop: packed before, never inside, a capture
+        return (B,) + tuple((e.pack_key(), e._pack_ptrs, id(e._packs)) for e in self._engines())
+
+    # ---- the public call ----------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def refine(self, noisy: torch.Tensor, rects: Optional[torch.Tensor] = None, init="mu",
+               eps_z: Optional[torch.Tensor] = None) -> Dict[str, object]:
+        """noisy: f32 [B,C,S,S] on the MI355X in [-1,1], the degraded input.  rects: f32 [B, 8] in ops.degrade_params' layout
+        (``DeviceLoader.last_rects``), the occlusion rectangle of each image -- excluded from the context loss; None: no holes.
+        init: "mu" (z0 = the Encoder's mean), "sample" (z0 = mu + exp(logvar / 2) * eps_z; eps_z f32 [B, L] injects the draw,
+        else it comes from the device noise stream) or an f32 [B, L] device tensor.
+        Returns device tensors: recon (NCHW f32, decoded from z), z [B, L] f32 (the best iterate with keep_best, else the
+        last), z0, recon0 (the one-shot reconstruction from z0), objective0 and objective ([B] each: J at z0 and at z), and
+        steps (int).  No host synchronisation (the first call of a batch size under graphed=True captures, which has one)."""
+        what = "LatentRefiner.refine"
+        E, Gn, dt = self.E, self.G, self.dt
+        if not isinstance(noisy, torch.Tensor) or not noisy.is_cuda:
+            raise RuntimeError(f"{what} needs the batch on the MI355X ('cuda'); there is no CPU path")
+        if noisy.dim() != 4 or noisy.dtype != torch.float32 or tuple(noisy.shape[1:]) != (Gn.nc, Gn.img_size, Gn.img_size):
+            raise RuntimeError(f"{what}: noisy must be float32 [B,{Gn.nc},{Gn.img_size},{Gn.img_size}]")
+        B, L, dev = noisy.shape[0], self.latent, noisy.device
+        if rects is not None and (not rects.is_cuda or rects.dtype != torch.float32 or tuple(rects.shape) != (B, 8)):
+            raise RuntimeError(f"{what}: rects must be a device f32 [B, 8] tensor (ops.degrade_params)")
+        if isinstance(init, str) and init not in ("mu", "sample"):
+            raise ValueError(f"{what}: init must be 'mu', 'sample' or an f32 [B, L] device tensor, got {init!r}")
+        if not isinstance(init, str) and not (isinstance(init, torch.Tensor) and init.is_cuda and
+                                              init.dtype == torch.float32 and tuple(init.shape) == (B, L)):
+            raise ValueError(f"{what}: init must be 'mu', 'sample' or an f32 [B, L] device tensor")
+        if isinstance(init, str) and E is None:
+            raise ValueError(f"{what}: a refiner built without an encoder needs init= an f32 [B, L] device tensor")
+        if eps_z is not None:
+            if not (isinstance(init, str) and init == "sample"):
+                raise ValueError(f"{what}: eps_z belongs to init='sample'")
+            if not eps_z.is_cuda or eps_z.dtype != torch.float32 or tuple(eps_z.shape) != (B, L):
+                raise RuntimeError(f"{what}: eps_z must be a device f32 [{B}, {L}] tensor")
+        ZP = G.padc(Gn.nz, dt)
+        buf = self._buffers(B, dev)
+        st = buf["state"]
+        buf["noisy"].copy_(noisy)
+        if rects is None:
+            buf["rects"].fill_(float("nan"))            # a NaN row: no comparison holds, that image has no hole
+        else:
+            buf["rects"].copy_(rects)
+        # ---- z0 in the engine layout ----
+        if isinstance(init, str):
+            noisy_h = ops.nchw_to_nhwc(buf["noisy"], G.padc(Gn.nc, dt), dt)
+            mulv, _ = E._engine.forward(noisy_h, B, False, keep=False)
+            if init == "mu":
+                eps_z = ops.zeros_f32(B * L, dev).view(B, L)
+            elif eps_z is None:
+                ns = ops.default_noise(dev)             # HIP Philox draws keyed by torch's device seed
+                ns.advance()
+                eps_z = ns.randn((B, L), 1)
+            z0_eng, _ = ops.reparam_forward(mulv.view(B, -1), eps_z.contiguous(), L, ZP, dt)
+        else:
+            z0_eng = ops.prior_forward(init.contiguous(), B, L, ZP, dt)
+
+        def start():
+            ops.latent_adam("init", st, dt, ZP, z_in=z0_eng, z_out=buf["z_eng"])
+
+        cap = None
+        if self.graphed and self.steps > 0:
+            key = self._capture_key(B)
+            cap = self._caps.get(B)
+            if cap is None or cap.key != key:
+                start()
+                self._iterate(buf, B)                   # eager warm-up: the workspaces reach their size outside the capture
+                cap = capture(lambda: self._iterate(buf, B), [], HostMirrors([], []), dev, key=key, keep=buf)
+                self._caps[B] = cap
+                self.captures += 1
+        start()
+        z0 = st["z"].clone()
+        recon0 = self._decode(buf["z_eng"], B)
+        for k in range(self.steps):                     # no host value inside: `steps` launches sequences / replays in a row
+            if cap is not None:
+                replay(cap)
+            else:
+                self._iterate(buf, B)
+            if k == 0:
+                buf["objective0"].copy_(buf["objective"])
+        # the last iterate's objective (the loop evaluated every iterate but the one its last step produced)
+        _, _, _, p, _ = self._evaluate(buf, B, False)
+        ops.latent_adam("track", st, dt, ZP, loss_rows=buf["loss_rows"], p=p, objective=buf["objective"],
+                        alpha_adv=self.alpha_adv, prior_weight=self.prior_weight)
+        if self.steps == 0:
+            buf["objective0"].copy_(buf["objective"])
+        z = (st["best_z"] if self.keep_best else st["z"]).clone()
+        objective = (st["best_loss"] if self.keep_best else buf["objective"]).clone()
+        recon = self._decode(ops.prior_forward(z, B, L, ZP, dt), B)
+        return {"recon": recon, "z": z, "z0": z0, "recon0": recon0, "objective0": buf["objective0"].clone(),
+                "objective": objective, "steps": self.steps}
 
 
 @torch.no_grad()

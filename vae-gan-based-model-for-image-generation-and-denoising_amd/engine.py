@@ -237,9 +237,14 @@ class StackEngine:
     def invalidate(self) -> None:
         self._pack_key = None
 
+    def pack_key(self):
+        """What the packed operand copies are valid for: every parameter's (optimizer epoch, torch version) and where the
+        first weight lives.  A caller that captures launches reading the packs keys its capture by it (denoise.LatentRefiner)."""
+        return (tuple((getattr(p, "_vg_epoch", 0), p._version) for p in self.params()),
+                self.stages[0].conv.weight.data_ptr())
+
     def _ensure_packed(self) -> Dict:
-        key = (tuple((getattr(p, "_vg_epoch", 0), p._version) for p in self.params()),
-               self.stages[0].conv.weight.data_ptr())
+        key = self.pack_key()
         if self._packs is not None and key == self._pack_key:
             return self._packs
         ptr_key = tuple(p.data_ptr() for p in self.params())
@@ -490,11 +495,21 @@ class StackEngine:
         separate passes (one launch over all rows sums in another order).  Everything else of a grouped backward already is
         what separate passes compute, bit for bit: the BatchNorm backward and its parameter gradients are per group, a data
         gradient's rows do not mix.
+        A context of forward(train=False, keep=True) is accepted with param_grads=False only: every BatchNorm stage then runs
+        ops.bn_act_backward_eval on the constant coefficients its forward used (no statistics pass, no parameter gradient), the
+        rest of the chain is the train-mode one; sync / feat / weight_grad_groups are refused (ValueError), param_grads=True
+        raises the RuntimeError it always raised.
         Everything runs on the current stream: forking weight gradients onto a second stream (three schedules, rounds 1
         and 2) measured slower every time and is gone ("Concurrency does not pay")."""
         ctx, B, train = ctxpack
         if not train:
-            raise RuntimeError("backward through an eval-mode network is not supported (the reference never does it)")
+            # a context of forward(train=False, keep=True): data gradients only (test-time latent refinement, DESIGN.md 4.4q).
+            # BatchNorm is then a constant per-channel scale and shift, whose backward needs no statistics pass
+            if param_grads:
+                raise RuntimeError("backward through an eval-mode network is not supported (the reference never does it)")
+            if self.bn_sync is not None or feat is not None or weight_grad_groups != 1:
+                raise ValueError("an eval-mode backward takes no SyncBN, no feat and no weight_grad_groups: its BatchNorm "
+                                 "has no batch statistics and it forms no weight gradient")
         if feat is not None:
             self.check_feat_stage(feat[0])
         packs = self._ensure_packed()
@@ -557,7 +572,9 @@ class StackEngine:
                     self.trace.append(dict(stage=i, what="feat", f_fake=f_fake.clone(), f_real=f_real.clone(), dA_in=dA_in,
                                            dA=dA_f.clone(), gscale=fscale, loss=fslot.clone()))
             gg_, gb_, acc_g = None, None, False
-            if st.bn is not None:
+            if st.bn is not None and not train:
+                dY = ops.bn_act_backward_eval(Y, dA, c["coeffs"], rows, OC, st.act, st.slope, dt)
+            elif st.bn is not None:
                 if param_grads:
                     gg_, acc_g = sink.get(st.bn.weight)
                     gb_, acc_b = sink.get(st.bn.bias)

@@ -1790,6 +1790,103 @@ def region_mse_forward_backward(a, b, rects, w_hole, gscale, loss=None, hole_mse
     return da
 
 
+# ---- test-time latent refinement (csrc/refine.hip; denoise.LatentRefiner) -----------------------------------------------
+def bn_act_backward_eval(x, dy, coeffs, rows, C, act, slope, dtype, out=None):
+    """Backward of eval-mode BatchNorm + activation (vg_bn_act_backward_eval): dx = dy * act'(scale x + shift) * scale with the
+    constant coefficients bn_eval_coeffs made (coeffs [1][4][C]: rows 2 and 3).  x, dy: [rows][C] in the engine dtype."""
+    _need_cuda(x, dy, coeffs, out)
+    if coeffs is None or coeffs.dim() != 3 or coeffs.shape[0] != 1 or coeffs.shape[1] != 4 or coeffs.shape[2] != C or \
+            coeffs.dtype != torch.float32:
+        raise RuntimeError("bn_act_backward_eval: coeffs must be the f32 [1, 4, C] tensor of bn_eval_coeffs (one group)")
+    if x.dtype != TORCH_DT[dtype] or dy.dtype != TORCH_DT[dtype] or x.numel() != rows * C or dy.numel() != rows * C:
+        raise RuntimeError("bn_act_backward_eval: x and dy must be [rows, C] tensors in the engine dtype")
+    dx = out if out is not None else torch.empty_like(x)
+    if dx.dtype != x.dtype or dx.numel() != x.numel():
+        raise RuntimeError("bn_act_backward_eval: out must have x's dtype and size")
+    _bn_bytes(3, x.numel(), dtype)
+    L.check(L.load().vg_bn_act_backward_eval(x.data_ptr(), dy.data_ptr(), dx.data_ptr(), coeffs[0, 2].data_ptr(),
+                                             coeffs[0, 3].data_ptr(), rows, C, act, slope, dtype, L.stream_ptr()),
+            "vg_bn_act_backward_eval")
+    return dx
+
+
+def masked_mse_rows(a, b, rects, gscale=1.0, loss_rows=None, want_grad=False, out=None):
+    """Per-image MSE outside each image's occlusion rectangle (vg_masked_mse_rows): a, b NCHW f32 of one shape (b a
+    constant), rects f32 [B, 8] in ops.degrade_params' layout (None: no image has a hole; a NaN row: that image has none).
+    loss_rows f32 [B] = S_valid_i / n_valid_i (written; None skips it), and with want_grad the gradient of gscale *
+    loss_rows[i] w.r.t. a (exactly 0 inside the holes), written in full into ``out`` or a new tensor.  -> d_a or None."""
+    what = "masked_mse_rows"
+    _need_cuda(a, b, rects, loss_rows, out)
+    if a.dtype != torch.float32 or b.dtype != torch.float32 or a.dim() != 4 or a.shape != b.shape:
+        raise RuntimeError(f"{what}: a and b must be f32 [B,C,H,W] tensors of one shape")
+    B, C, H, W = a.shape
+    if rects is not None and (rects.dtype != torch.float32 or tuple(rects.shape) != (B, 8)):
+        raise RuntimeError(f"{what}: rects must be f32 [B, 8] (ops.degrade_params)")
+    if loss_rows is not None and (loss_rows.dtype != torch.float32 or loss_rows.numel() != B):
+        raise RuntimeError(f"{what}: loss_rows must be f32 [B]")
+    if out is not None and (not want_grad or out.dtype != torch.float32 or out.shape != a.shape):
+        raise RuntimeError(f"{what}: out is the gradient tensor (want_grad=True), f32 of a's shape")
+    if not math.isfinite(gscale):
+        raise RuntimeError(f"{what}: gscale must be finite")
+    if loss_rows is None and not want_grad:
+        raise RuntimeError(f"{what}: nothing to compute (every output is None)")
+    lib = L.load()
+    nws = _ws_query(lib.vg_masked_mse_rows_ws_doubles(B, C, H, W),
+                    "vg_masked_mse_rows_ws_doubles (needs B, C, H, W >= 1, B <= 65535, C H W < 2^31 - 2^19)")
+    ws = WS.get("maskedmse", nws * 8, a.device)
+    da = (out if out is not None else torch.empty_like(a)) if want_grad else None
+    L.check(lib.vg_masked_mse_rows(a.data_ptr(), b.data_ptr(), L.ptr(rects), B, C, H, W, float(gscale), L.ptr(loss_rows),
+                                   L.ptr(da), ws.data_ptr(), nws, L.stream_ptr()), "vg_masked_mse_rows")
+    return da
+
+
+LATENT_MODE = {"init": L.VG_LATENT_INIT, "update": L.VG_LATENT_UPDATE, "track": L.VG_LATENT_TRACK}
+
+
+def latent_state(B, L_dim, device):
+    """The optimiser state of vg_latent_adam for B latent rows: dict(z, m, v, best_z f32 [B, L]; t int32 [B]; best_loss f32 [B]).
+    Uninitialised: latent_adam("init", ...) fills it."""
+    f = dict(dtype=torch.float32, device=device)
+    return dict(z=torch.empty(B, L_dim, **f), m=torch.empty(B, L_dim, **f), v=torch.empty(B, L_dim, **f),
+                best_z=torch.empty(B, L_dim, **f), best_loss=torch.empty(B, **f),
+                t=torch.empty(B, dtype=torch.int32, device=device))
+
+
+def latent_adam(mode, state, dtype, ZP, *, dz=None, loss_rows=None, p=None, z_in=None, z_out=None, objective=None,
+                lr=0.0, betas=(0.9, 0.999), eps=1e-8, alpha_adv=0.0, prior_weight=0.0):
+    """Objective, keep-best and one Adam step over latent rows (vg_latent_adam).  mode: "init" (state from z_in [B, ZP] in the
+    engine dtype), "update" (objective of the z just evaluated from loss_rows [B] (+ p [B]), keep-best, Adam on dz [B, ZP],
+    z_out [B, ZP] = the next Generator input) or "track" (objective and keep-best only).  objective f32 [B]: receives J."""
+    what = "latent_adam"
+    if mode not in LATENT_MODE:
+        raise ValueError(f"{what}: mode must be 'init', 'update' or 'track', got {mode!r}")
+    z = state["z"]
+    B, L_dim = z.shape
+    _need_cuda(*state.values(), dz, loss_rows, p, z_in, z_out, objective)
+    for k in ("z", "m", "v", "best_z"):
+        if state[k].dtype != torch.float32 or tuple(state[k].shape) != (B, L_dim):
+            raise RuntimeError(f"{what}: state['{k}'] must be f32 [B, L]")
+    if state["best_loss"].dtype != torch.float32 or state["best_loss"].numel() != B or state["t"].dtype != torch.int32 or \
+            state["t"].numel() != B:
+        raise RuntimeError(f"{what}: state['best_loss'] must be f32 [B] and state['t'] int32 [B]")
+    for name, t in (("dz", dz), ("z_in", z_in), ("z_out", z_out)):
+        if t is not None and (t.dtype != TORCH_DT[dtype] or t.numel() != B * ZP):
+            raise RuntimeError(f"{what}: {name} must be [B, ZP] in the engine dtype")
+    for name, t in (("loss_rows", loss_rows), ("p", p), ("objective", objective)):
+        if t is not None and (t.dtype != torch.float32 or t.numel() != B):
+            raise RuntimeError(f"{what}: {name} must be f32 [B]")
+    need = {"init": (("z_in", z_in),), "update": (("dz", dz), ("loss_rows", loss_rows), ("z_out", z_out)),
+            "track": (("loss_rows", loss_rows),)}[mode]
+    for name, t in need:
+        if t is None:
+            raise RuntimeError(f"{what}: mode '{mode}' needs {name}")
+    L.check(L.load().vg_latent_adam(z.data_ptr(), state["m"].data_ptr(), state["v"].data_ptr(), state["t"].data_ptr(),
+                                    state["best_loss"].data_ptr(), state["best_z"].data_ptr(), L.ptr(dz), L.ptr(loss_rows),
+                                    L.ptr(p), L.ptr(z_in), L.ptr(z_out), L.ptr(objective), B, L_dim, ZP, float(lr),
+                                    float(betas[0]), float(betas[1]), float(eps), float(alpha_adv), float(prior_weight),
+                                    LATENT_MODE[mode], dtype, L.stream_ptr()), "vg_latent_adam")
+
+
 # draw id of the augmentation table (include/vaegan_hip.h "Differentiable augmentation"): outside 0..2, 16..18 and 32..34
 DRAW_AUGMENT = 48
 AUG_BRIGHTNESS, AUG_SATURATION, AUG_CONTRAST, AUG_TRANSLATION, AUG_CUTOUT = 1, 2, 4, 8, 16
