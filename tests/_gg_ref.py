@@ -337,6 +337,7 @@ PATCH = [  # 2 x 2-tap phases of the transposed form / the direct k4 s2 convolut
     Case("ggp<2>", "conv_dgrad", 2, 32, 72, 32, epi="ml"),
     Case("ggp<4>", "convT_dgrad", 2, 16, 130, 32, epi="s", env=P256),                 # direct, 256-row tile = one image
     Case("ggp<4>", "convT", 2, 32, 32, 72, epi="b+r", env=P256),                      # transposed, 32 x 32 grid: a tile is 8 of 32 rows
+    Case("ggp<4>", "conv_dgrad", 2, 32, 72, 32, epi="ml", env=P256),                  # transposed, 16 x 16 grid, the mask on the 8-wave tile
     Case("ggp<4,64>", "convT", 8, 8, 64, 40, epi="b+s", env=P256),                    # 4 images per tile
     Case("ggp<4,64>", "conv", 2, 64, 32, 64, epi="mr", env=P256),                     # direct, a tile is 8 of 32 rows
     Case("ggp<2,64>", "convT", 16, 4, 32, 48, epi="b+s"),                             # 4 x 4 grid: 8 images, 200 patch pixels
@@ -345,6 +346,7 @@ PATCH = [  # 2 x 2-tap phases of the transposed form / the direct k4 s2 convolut
     Case("ggp<2,64,3>", "conv_dgrad", 4, 16, 40, 64, epi="b+ml"),                     # transposed, 8 x 8 grid: 2 images
     Case("ggp<2,32>", "conv", 1, 64, 32, 32, epi="b+s"),                              # direct, 32-wide grid, exactly 32 columns
     Case("ggp<2,32>", "convT_dgrad", 8, 8, 32, 64, epi="mr"),
+    Case("ggp<2,32>", "conv_dgrad", 2, 16, 32, 64, epi="b+ml"),                       # transposed, 8 x 8 grid: 128 rows (no 4-phase tile), sub-pixel scatter
 ]
 
 SPLITK = [

@@ -19,6 +19,13 @@ made -- which descriptor each query saw:
   tile_m_stats  ops.gather_gemm_tile_m's protocol (engine.can_group, the layerwise test): non-NULL `stats`, nothing else
   plan          ops.gather_gemm_plan(g, dtype, bias, want_stats, act, mask): placeholder workspace and the zero page
 
+Rows added to tests/_gg_ref.ALL_CASES after ABI 20 (the mask row of ggp<4> and the sub-pixel row of ggp<2,32> that came with
+csrc/conv_epilogue.hpp) have no side query to record: their entries hold the plan the library of the commit BEFORE the row
+answered (nparts, tile_m = bm, ws_bytes, family = timing_family from that plan; tile_m_stats = bm of the want_stats plan).
+add_rows() below writes them, with the library of that commit selected and nothing else touched:
+
+    VG_LIB_PATH=<libvaegan_hip.so built from the commit before the rows> python tools/gen_golden_gg_plan.py --add-rows
+
 Geometries: every row of tests/_gg_ref.ALL_CASES under its own switches, and under the default switches every launch of
 the three networks at the benchmarked shapes (tests/_gg_ref.network_launches).  "can_group" holds, per shape, the tile
 rows of every BatchNorm stage of the Discriminator at 2B and the answer the condition of engine.StackEngine.can_group(B, 2)
@@ -121,5 +128,35 @@ def main() -> None:
           sum(len(v) for v in out["networks"].values()), "network launches,", len(out["bn_fused"]), "BatchNorm shapes")
 
 
+def add_rows() -> None:
+    """Entries for the rows of ALL_CASES the fixture does not hold yet, from the plan query of the loaded library (see the
+    module docstring); every recorded entry stays as it is."""
+    sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+    from importlib import import_module
+    import _gg_ref as R
+    ops = import_module(PKG + ".ops")
+    with open(OUT) as f:
+        out = json.load(f)
+    keys = list(next(iter(out["cases"].values()))["plan"])
+    switch_names = sorted({n for c in R.ALL_CASES for n in c.switches})
+    for c in R.ALL_CASES:
+        if c.id in out["cases"]:
+            continue
+        for n in switch_names:
+            os.environ.pop(n, None)
+        os.environ.update(c.switches)
+        ops.reload_switches()
+        g = c.specs()[0]
+        plan = ops.gather_gemm_plan(g, c.dtype, bias=c.has("b"), want_stats=c.has("s"), act=c.act, mask=c.mask)
+        assert R.label(plan) == c.label, (c.id, R.label(plan))
+        out["cases"][c.id] = dict(nparts=plan["nparts"], tile_m=plan["bm"], ws_bytes=plan["ws_bytes"], family=plan["timing_family"],
+                                  tile_m_stats=ops.gather_gemm_plan(g, c.dtype, want_stats=True)["bm"],
+                                  plan={k: list(plan[k]) if k == "detail" else plan[k] for k in keys})
+        print("added", c.id, R.label(plan))
+    with open(OUT, "w") as f:
+        json.dump(out, f, separators=(",", ":"), sort_keys=True)
+        f.write("\n")
+
+
 if __name__ == "__main__":
-    main()
+    add_rows() if "--add-rows" in sys.argv[1:] else main()

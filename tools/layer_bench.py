@@ -3,7 +3,7 @@ host launch overhead): fprop / dgrad / wgrad TFLOP/s for every stage of E, G, D.
 
     python tools/layer_bench.py [S=64] [B=128] [dtype=bf16] [reps=20] [filter-regex]
 
-VG_LIB_PATH selects an alternative build of libvaegan_hip.so (ablation builds)."""
+VG_LIB_PATH selects an alternative build of libvaegan_hip.so."""
 import os
 import re
 import sys

@@ -16,34 +16,16 @@
 //     -> conflict-free ds_read_b128 fragment reads and conflict-free ds_write_b128 staging;
 //   * loads for chunk k+1 are issued before the MFMAs of chunk k and written to the other LDS
 //     buffer after them (T14 issue-early / write-late), one barrier per chunk;
-//   * epilogue: + bias, scatter to the NHWC output (phase/sub-pixel offsets), and optional
-//     per-channel (sum, sum of squares) partials for train-mode BatchNorm, reduced
-//     wave -> LDS -> one slab row per workgroup (deterministic, no atomics).
+//   * epilogue (conv_epilogue.hpp: gg_epilogue, shared with the patch kernel of conv_patch.hpp): + bias, scatter to the
+//     NHWC output (phase/sub-pixel offsets), and optional per-channel (sum, sum of squares) partials for train-mode
+//     BatchNorm, reduced wave -> LDS -> one slab row per workgroup (deterministic, no atomics).
 #include "common.hpp"
 #include <type_traits>
 #include <cstdlib>
 
 namespace {
 
-// activation backward fused into a data-gradient epilogue (vg_gg_desc::mask_x): v = dL/d(activated output) segment
-// (16 bytes, storage dtype), x = the layer's activated output at the same place; returns v * act'(x), rounded again
-template <int DT>
-__device__ __forceinline__ u32x4 mask_segment(u32x4 v, const u32x4& x, int act, float slope) {
-    if constexpr (DT == VG_BF16) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const float xl = __uint_as_float(x[k] << 16), xh = __uint_as_float(x[k] & 0xffff0000u);
-            const float gl = __uint_as_float(v[k] << 16), gh = __uint_as_float(v[k] & 0xffff0000u);
-            const uint32_t lo = ElemT<VG_BF16>::from_f32(act_bwd(xl, gl, act, slope));
-            const uint32_t hi = ElemT<VG_BF16>::from_f32(act_bwd(xh, gh, act, slope));
-            v[k] = lo | (hi << 16);
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) v[k] = __float_as_uint(act_bwd(__uint_as_float(x[k]), __uint_as_float(v[k]), act, slope));
-    }
-    return v;
-}
+#include "conv_epilogue.hpp"
 
 #define VG_WAITCNT_VM(N) asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory")
 
@@ -71,24 +53,10 @@ __device__ __forceinline__ void wait_vmcnt_le(int n) {
 // still 2-3 workgroups per CU: G1 fprop 589 -> 661, G2 703 -> 761 / 595 -> 672, G4 fprop 380 -> 454 TFLOP/s.
 // The 64x64 tile (4 MFMAs per chunk and wave) wants FOUR chunks per stage in two slots (64 KB): D3 fprop 283 -> 318,
 // D3 dgrad 427 -> 475, G1 dgrad 500 -> 583 (2 chunks x 3 slots: 282; 2 x 2: 239; 4 x 3: one workgroup per CU, slower).
-// VG_DMA_KCH / VG_DMA_NBUF override both for sweeps.
 template <int BM, int BN>
 struct DmaRing {
-#if defined(VG_DMA_KCH) && defined(VG_DMA_NBUF)
-    static constexpr int KCH = VG_DMA_KCH, NBUF = VG_DMA_NBUF;
-#else
-#ifndef VG_RING64_KCH
-#define VG_RING64_KCH 4
-#endif
-#ifndef VG_RING64_NBUF
-#define VG_RING64_NBUF 2
-#endif
-#ifndef VG_RING128x64_KCH
-#define VG_RING128x64_KCH 2
-#endif
-    static constexpr int KCH = (BM * BN >= 128 * 128) ? 2 : (BM * BN >= 128 * 64) ? VG_RING128x64_KCH : VG_RING64_KCH;
-    static constexpr int NBUF = (BM * BN >= 128 * 64) ? 2 : VG_RING64_NBUF;
-#endif
+    static constexpr int KCH = (BM * BN >= 128 * 64) ? 2 : 4;    // 64-byte chunks per stage
+    static constexpr int NBUF = 2;                               // ring slots
 };
 
 constexpr int GG_N_MAJOR = 1 << 16;     // ksplit_arg flag of a non-split launch: XCD-major over n tiles
@@ -127,26 +95,8 @@ __global__ __launch_bounds__(256) void gg_kernel(const vg_gg_desc d, const int k
     // split-K launches: z = phase * ksplit + K slice (round 4: the sub-pixel phases of the transposed forms split too)
     const int phase = ksplit > 1 ? (int)blockIdx.z / ksplit : (int)blockIdx.z;
     const int kz = ksplit > 1 ? (int)blockIdx.z - phase * ksplit : 0;
-    // XCD-aware tile order (cdna_hip_programming.md T1): workgroups are dealt round-robin over the 8 XCDs, each
-    // with a private L2.  The launch is 1-D in (m tile, n tile); id -> (xcd = id % 8, slot = id / 8) and the slots
-    // of one XCD walk ALL n tiles of an m tile before moving on, so the gathered A rows of an m tile are fetched
-    // into one XCD's L2 once and re-used by its other n tiles (speed only; any placement is correct).
-    int bx, by;
-    {
-        const int n_tiles = (d.N + BN - 1) / BN;
-        const int id = blockIdx.x;
-        const int xcd = id & 7, slot = id >> 3;
-        if (!SPLITK && (ksplit_arg & GG_N_MAJOR)) {
-            // weights larger than the input (n_major() below): an XCD owns n tiles (n % 8 == xcd) and walks all m
-            // tiles of one before the next, so it streams 1/8 of the WEIGHTS and all of the (smaller) input
-            const int mt = (int)gridDim.x / n_tiles;
-            bx = slot % mt;
-            by = (slot / mt) * 8 + xcd;
-        } else {
-            by = slot % n_tiles;
-            bx = (slot / n_tiles) * 8 + xcd;
-        }
-    }
+    const GgTile tile = gg_tile_of_block<BN>(d.N, SPLITK ? 0 : ksplit_arg, GG_N_MAJOR);
+    const int bx = tile.bx, by = tile.by;
     const int m_tiles_ = (d.B * d.GH * d.GW + BM - 1) / BM;
     if (bx >= m_tiles_) return;                             // padding blocks of the last group of 8 m tiles
     const int m0 = bx * BM;
@@ -270,9 +220,6 @@ __global__ __launch_bounds__(256) void gg_kernel(const vg_gg_desc d, const int k
     // (an explicit ds_read / MFMA scheduling pipeline -- __builtin_amdgcn_sched_group_barrier, next chunk's reads
     // between this chunk's MFMAs -- was measured here and changes nothing: the loop waits on DMA arrival, not on LDS)
     auto compute = [&](int buf) {
-#ifdef VG_ABLATE_COMPUTE
-        return;
-#endif
         if constexpr (DT == VG_FP8) {
             // v_mfma_scale_f32_16x16x128_f8f6f4: lane (row|col = lane & 15, k group = lane >> 4) holds 32 e4m3 values.
             // Any assignment of the 128 k indices to (lane group, byte) is valid as long as A and B use the same one
@@ -329,13 +276,6 @@ __global__ __launch_bounds__(256) void gg_kernel(const vg_gg_desc d, const int k
                 const int r = wn * (BN / WN) + j * 16 + fr;
                 fb[j] = *reinterpret_cast<const u32x4*>(sb + r * 64 + ((fg ^ ((-(r >> 2)) & 3)) << 4));
             }
-#ifdef VG_ABLATE_MFMA
-#pragma unroll
-            for (int i = 0; i < TM; ++i) asm volatile("" ::"v"(fa[i]));
-#pragma unroll
-            for (int j = 0; j < TN; ++j) asm volatile("" ::"v"(fb[j]));
-            continue;
-#endif
             if constexpr (DT == VG_F32) {
 #pragma unroll
                 for (int kk = 0; kk < 4; ++kk)
@@ -477,9 +417,7 @@ __global__ __launch_bounds__(256) void gg_kernel(const vg_gg_desc d, const int k
             const int ahead = min(NBUF - 2, nstages - 1 - ks);
             wait_vmcnt_le(ahead * LDMA);
             __builtin_amdgcn_s_barrier();
-#ifndef VG_ABLATE_LOAD
             if (ks + NBUF - 1 < nstages) issue(wb);
-#endif
             compute(rb);
             rb = rb == NBUF - 1 ? 0 : rb + 1;
             wb = wb == NBUF - 1 ? 0 : wb + 1;
@@ -523,127 +461,13 @@ __global__ __launch_bounds__(256) void gg_kernel(const vg_gg_desc d, const int k
                 }
         return;
     }
-    // (1) BatchNorm partial statistics straight from the accumulators (valid rows / real channels only);
-    // (2) the C tile goes through LDS so that every lane writes one 16-byte run of channels of one output pixel
-    //     (NHWC) instead of 2/4-byte scatters; output pixel offsets come from an LDS table filled once per
-    //     workgroup (no per-element integer division for the sub-pixel scatter).
-    const bool flat = (d.nphase == 1 && d.OSY == 1 && d.OSX == 1 && d.GH == d.OH && d.GW == d.OW);
-    for (int r = tid; r < BM; r += 256) {
-        const int m = m0 + r;
-        int op = -1;
-        if (m < M) {
-            if (flat) {
-                op = m;
-            } else {
-                const int b = m / GHW;
-                const int rem = m - b * GHW;
-                const int gy = rem / d.GW;
-                const int gx = rem - gy * d.GW;
-                const int oy = gy * d.OSY + d.ooy[phase];
-                const int ox = gx * d.OSX + d.oox[phase];
-                if (oy < d.OH && ox < d.OW) op = (b * d.OH + oy) * d.OW + ox;
-            }
-        }
-        opix_tab[r] = op;
-    }
-    float biasv[TN];
-    int ncol[TN];
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-        ncol[j] = n0 + wn * (BN / WN) + j * 16 + fr;
-        biasv[j] = (d.bias != nullptr && ncol[j] < d.N) ? d.bias[ncol[j]] : 0.f;
-    }
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc[i][j][r] += biasv[j];
-    if (d.act != VG_ACT_NONE) {                        // activation of a layer without BatchNorm, fused
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) acc[i][j][r] = act_fwd(acc[i][j][r], d.act, d.act_slope);
-    }
-    __syncthreads();                                   // opix_tab visible; main-loop LDS reads are done
-
-    if (d.stats != nullptr) {
-        float* red = reinterpret_cast<float*>(smem);   // [WM][BN][2]
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            float a = 0.f, b = 0.f;
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int row = wm * (BM / WM) + i * 16 + fg * 4 + r;
-                    if (opix_tab[row] >= 0) {
-                        const float v = acc[i][j][r];
-                        a += v;
-                        b += v * v;
-                    }
-                }
-            a += __shfl_xor(a, 16); a += __shfl_xor(a, 32);
-            b += __shfl_xor(b, 16); b += __shfl_xor(b, 32);
-            if (fg == 0) {
-                const int c = wn * (BN / WN) + j * 16 + fr;
-                red[(wm * BN + c) * 2 + 0] = a;
-                red[(wm * BN + c) * 2 + 1] = b;
-            }
-        }
-        __syncthreads();
-        if (tid < BN && n0 + tid < d.N) {
-            float a = 0.f, b = 0.f;
-#pragma unroll
-            for (int w = 0; w < WM; ++w) { a += red[(w * BN + tid) * 2]; b += red[(w * BN + tid) * 2 + 1]; }
-            const int64_t part = (int64_t)phase * m_tiles_ + bx;
-            d.stats[(part * 2 + 0) * d.N + n0 + tid] = a;
-            d.stats[(part * 2 + 1) * d.N + n0 + tid] = b;
-        }
-        __syncthreads();
-    }
-
     // C tile staging: pitch padded by 16 B; the tile is written in NPASS row blocks when it exceeds the LDS buffers
     constexpr int NPASS = (BM * (BN * ESZO + 16) <= NBUF * STAGE) ? 1 : WM;
     constexpr int PROWS = BM / NPASS;
     constexpr int CPITCH = BN * ESZO + ((PROWS * (BN * ESZO + 16) <= NBUF * STAGE) ? 16 : 0);
     static_assert(PROWS * CPITCH <= NBUF * STAGE, "C tile pass does not fit in LDS");
-    constexpr int SEGS = BN * ESZO / 16;                // 16-byte segments per tile row
-    unsigned char* Yb = reinterpret_cast<unsigned char*>(d.Y);
-    const int oc_bytes = d.OC * ESZO;
-#pragma unroll
-    for (int pass = 0; pass < NPASS; ++pass) {
-        const bool mine = (NPASS == 1) || (wm == pass);
-        if (mine) {
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const int row = wm * (BM / WM) + i * 16 + fg * 4 + r - pass * PROWS;
-                        const int col = wn * (BN / WN) + j * 16 + fr;
-                        typename EO::type* dst = reinterpret_cast<typename EO::type*>(smem + row * CPITCH) + col;
-                        *dst = EO::from_f32(acc[i][j][r]);
-                    }
-        }
-        __syncthreads();
-        for (int u = tid; u < PROWS * SEGS; u += 256) {
-            const int row = u / SEGS, seg = u - row * SEGS;
-            const int op = opix_tab[pass * PROWS + row];
-            const int cb = n0 * ESZO + seg * 16;        // byte offset of this segment inside the output pixel
-            if (op >= 0 && cb < oc_bytes) {
-                u32x4 v = *reinterpret_cast<const u32x4*>(smem + row * CPITCH + seg * 16);
-                if (d.mask_x != nullptr)
-                    v = mask_segment<DTO>(v, *reinterpret_cast<const u32x4*>(reinterpret_cast<const unsigned char*>(d.mask_x) +
-                                                                           (int64_t)op * oc_bytes + cb), d.mask_act, d.mask_slope);
-                *reinterpret_cast<u32x4*>(Yb + (int64_t)op * oc_bytes + cb) = v;
-            }
-        }
-        if (pass + 1 < NPASS) __syncthreads();
-    }
+    static_assert(WM * BN * 8 <= NBUF * STAGE, "statistics scratch does not fit in LDS");
+    gg_epilogue<DTO, BM, BN, WM, WN, 256, NPASS, CPITCH, false>(d, acc, smem, opix_tab, GgWhere{tid, wm, wn, fr, fg, phase, bx, m_tiles_, M, GHW, m0, n0});
 }
 
 template <int DT>
@@ -690,7 +514,7 @@ __global__ __launch_bounds__(256) void splitk_reduce2_kernel(const vg_gg_desc d,
     const int m0 = blockIdx.x * bm, n0 = blockIdx.y * 64;
     const int M = d.B * d.GH * d.GW, GHW = d.GH * d.GW;
     const int rl = tid / LPR, cv = (tid % LPR) * VE;
-    const bool flat = (d.nphase == 1 && d.OSY == 1 && d.OSX == 1 && d.GH == d.OH && d.GW == d.OW);
+    const bool flat = gg_flat(d);
     const int64_t kstride = (int64_t)Mpad * Npad;
     const float* base = d.ws + (int64_t)phase * ksplit * kstride;
     float s1[VE], s2[VE], bv[VE];
@@ -702,20 +526,7 @@ __global__ __launch_bounds__(256) void splitk_reduce2_kernel(const vg_gg_desc d,
     }
     for (int r = rl; r < bm; r += RPP) {
         const int m = m0 + r;
-        int op = -1;
-        if (m < M) {
-            if (flat) {
-                op = m;
-            } else {
-                const int b = m / GHW;
-                const int rem = m - b * GHW;
-                const int gy = rem / d.GW;
-                const int gx = rem - gy * d.GW;
-                const int oy = gy * d.OSY + d.ooy[phase];
-                const int ox = gx * d.OSX + d.oox[phase];
-                if (oy < d.OH && ox < d.OW) op = (b * d.OH + oy) * d.OW + ox;
-            }
-        }
+        const int op = gg_out_pixel(d, flat, phase, m, M, GHW);
         if (op < 0 || n0 + cv >= d.OC) continue;
         float v[VE];
 #pragma unroll
@@ -793,7 +604,7 @@ inline int patch256x64_min() { return vg_sw().patch256x64_min; }
 inline bool bigk_split_ok(const vg_gg_desc* d, bool bf16) {
     if (!bf16 || vg_sw().splitk_bigk == 0 || !use_dma() || d->zeros == nullptr) return false;
     const int M = d->B * d->GH * d->GW;
-    const bool flat = d->nphase == 1 && d->OSY == 1 && d->OSX == 1 && d->GH == d->OH && d->GW == d->OW;
+    const bool flat = gg_flat(*d);
     if (!flat || d->stats != nullptr || d->act != VG_ACT_NONE || d->mask_x != nullptr) return false;
     const int t128 = tiles_of(M, d->N, 128, 128);
     const int nstages = (d->Kp * 2) / 128;                        // 2 chunks of 64 bytes per stage
@@ -857,6 +668,14 @@ inline int validate(const vg_gg_desc* d, int dtype) {
     return 0;
 }
 
+// 64-byte K chunks per main-loop stage of gg_kernel<DT, bm, bn, .., DMA>
+inline int stage_chunks(int dtype, int bm, int bn, bool dma) {
+    if (!dma) return dtype == VG_F32 ? 1 : 2;
+    if (bm == 128 && bn == 128) return DmaRing<128, 128>::KCH;
+    if (bm == 128 && bn == 64) return DmaRing<128, 64>::KCH;
+    return DmaRing<64, 64>::KCH;
+}
+
 // Split K for skinny problems -- few output tiles, long K.  Round 4: also with sub-pixel phases and with BatchNorm statistics
 // (formed by the slab reduce, splitk_reduce2_kernel), on the LDS-DMA ring; never with a fused activation or mask (their
 // epilogues need final values).  `dma`: the split launch will run on the DMA kernel (stage = DmaRing<bm, bn>::KCH chunks).
@@ -866,15 +685,14 @@ inline bool split_dma_ok(const vg_gg_desc* d, int dtype, TileCfg t) {
 inline SplitK plan_splitk(const vg_gg_desc* d, int dtype, TileCfg t) {
     SplitK r{1, 0, 0};
     const int M = d->B * d->GH * d->GW;
-    const bool flat = d->nphase == 1 && d->OSY == 1 && d->OSX == 1 && d->GH == d->OH && d->GW == d->OW;
+    const bool flat = gg_flat(*d);
     const bool general = vg_sw().splitk_general != 0 && dtype == VG_BF16;     // phases / statistics allowed
     if (d->act != VG_ACT_NONE || d->mask_x != nullptr || dtype == VG_FP8) return r;
     if ((!flat || d->stats != nullptr) && !general) return r;
     if (t.bm == 256 || t.bn < 64) return r;                     // 256-row / narrow tiles: patch, 4-phase and edge kernels only
     const int esz = dtype == VG_F32 ? 4 : 2;
     const bool dma = split_dma_ok(d, dtype, t);
-    int kch = dtype == VG_BF16 ? 2 : 1;
-    if (dma) kch = t.bm == 128 ? (t.bn == 128 ? 2 : VG_RING128x64_KCH) : VG_RING64_KCH;
+    const int kch = stage_chunks(dtype, t.bm, t.bn, dma);
     const int nstages = ((d->Kp * esz) / 64 + kch - 1) / kch;
     const int gx = (M + t.bm - 1) / t.bm, gy = (d->N + t.bn - 1) / t.bn;
     const int tiles = gx * gy * d->nphase;
@@ -921,14 +739,6 @@ struct GGPlan {
     Q4Geo qg;                       // family VG_GG_PHASE4
 };
 
-// 64-byte K chunks per main-loop stage of gg_kernel<DT, bm, bn, .., DMA>
-inline int stage_chunks(int dtype, int bm, int bn, bool dma) {
-    if (!dma) return dtype == VG_F32 ? 1 : 2;
-    if (bm == 128 && bn == 128) return DmaRing<128, 128>::KCH;
-    if (bm == 128 && bn == 64) return DmaRing<128, 64>::KCH;
-    return DmaRing<64, 64>::KCH;
-}
-
 inline void plan_generic(const vg_gg_desc* d, int dtype, GGPlan* P) {
     vg_gg_plan& p = P->p;
     const TileCfg t{p.bm, p.bn};
@@ -943,7 +753,7 @@ inline void plan_generic(const vg_gg_desc* d, int dtype, GGPlan* P) {
     const int kch = stage_chunks(dtype, t.bm, t.bn, dma);
     p.nstages = ((d->Kp * esz) / 64 + kch - 1) / kch;
     if (split) {
-        const bool flat = d->nphase == 1 && d->OSY == 1 && d->OSX == 1 && d->GH == d->OH && d->GW == d->OW;
+        const bool flat = gg_flat(*d);
         p.ksplit = P->sk.ksplit;
         p.stages_per_split = P->sk.sps;
         // the round-1 reduce is elementwise over the flat output; phases and statistics need the tile form
@@ -993,7 +803,7 @@ inline int make_plan(const vg_gg_desc* d, int dtype, GGPlan* P) {
         // patch DMA rounds = the NR of ggp_kernel: 3 for the 8-wave tiles and for the 128 x 64 tile whose patch has <= 192 pixels
         const bool nr3 = t.bm == 128 && t.bn == 64 && P->pg.NPP <= 192 && patch_nr3();
         p.detail[1] = nr3 ? 3 : 0;                             // the NR_ template argument (0: by tile shape)
-        p.detail[0] = (t.bm == 256 || nr3 || GP_TPS != 2) ? 3 : 4;
+        p.detail[0] = (t.bm == 256 || nr3) ? 3 : 4;
         return 0;
     }
     if (t.bm == 256 && t.bn >= 64) return VG_EINVAL;           // (env flipped between planning and launch)
@@ -1079,12 +889,6 @@ inline int launch_patch(const vg_gg_desc* d, hipStream_t s, const GGPlan& P) {
 }
 
 }  // namespace
-
-#ifdef VG_DBG_STAMPS
-extern "C" int vg_debug_stamps(unsigned long long* host_out, int n) {
-    return (int)hipMemcpyFromSymbol(host_out, HIP_SYMBOL(vg_dbg_stamps), (size_t)n * 8);
-}
-#endif
 
 extern "C" int vg_gather_gemm_plan(const vg_gg_desc* d, int dtype, vg_gg_plan* out) {
     int rc = validate(d, dtype);

@@ -15,10 +15,7 @@
 //   * bias, (Leaky)ReLU of a BatchNorm-less layer and the per-channel BatchNorm partial sums ride in the epilogue,
 //     one slab row per workgroup exactly as gg_kernel emits them (bn_act.hip reads either).
 
-#ifndef VG_NK_GP
-#define VG_NK_GP 4
-#endif
-constexpr int NK_GP = VG_NK_GP;        // 16-pixel MFMA row groups per wave, worked as two halves
+constexpr int NK_GP = 4;               // 16-pixel MFMA row groups per wave, worked as two halves
 constexpr int NK_BM = 64 * NK_GP;
 
 inline bool narrowk_enabled() { return vg_sw().edge != 0; }      // VG_EDGE (common.hpp: switches are read once at load)
@@ -31,7 +28,7 @@ inline bool narrowk_ok(const vg_gg_desc* d, int dtype) {
     if (d->Kp % 32 != 0 || d->Kp > 128 || d->Kp < d->TH * d->TW * 8 || d->TW > 4) return false;
     if ((int64_t)d->B * d->GH * d->GW >= (1 << 24)) return false;                             // float-reciprocal divisions
     if ((int64_t)d->B * d->IH * d->IW >= (1 << 28)) return false;                             // 32-bit byte offsets into the input
-    if (!(d->OSY == 1 && d->OSX == 1 && d->GH == d->OH && d->GW == d->OW)) return false;     // flat output
+    if (!gg_flat(*d)) return false;
     return true;
 }
 
@@ -140,8 +137,8 @@ __global__ __launch_bounds__(256) void ggn_kernel(const vg_gg_desc d) {
                         s1 += v;
                         s2 += v * v;
                     }
-            s1 += __shfl_xor(s1, 16); s1 += __shfl_xor(s1, 32);
-            s2 += __shfl_xor(s2, 16); s2 += __shfl_xor(s2, 32);
+            gg_quad_sum(s1);
+            gg_quad_sum(s2);
             if (fg == 0) {
                 red[(wave * N + nt * 16 + fr) * 2 + 0] = s1;
                 red[(wave * N + nt * 16 + fr) * 2 + 1] = s2;
@@ -361,8 +358,8 @@ __global__ __launch_bounds__(256, 2) void ggn_stream_kernel(const vg_gg_desc d, 
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) {
                 float t1 = s1[nt], t2 = s2[nt];
-                t1 += __shfl_xor(t1, 16); t1 += __shfl_xor(t1, 32);
-                t2 += __shfl_xor(t2, 16); t2 += __shfl_xor(t2, 32);
+                gg_quad_sum(t1);
+                gg_quad_sum(t2);
                 if (fg == 0) {
                     red[(wave * N + nt * 16 + fr) * 2 + 0] = t1;
                     red[(wave * N + nt * 16 + fr) * 2 + 1] = t2;

@@ -214,8 +214,8 @@ __global__ __launch_bounds__(256, BN == 16 ? 3 : 2) void ggq_kernel(const vg_gg_
                         a += v;
                         b += v * v;
                     }
-                a += __shfl_xor(a, 16); a += __shfl_xor(a, 32);
-                b += __shfl_xor(b, 16); b += __shfl_xor(b, 32);
+                gg_quad_sum(a);
+                gg_quad_sum(b);
                 if (fg == 0) {
                     const int c = j * 16 + fr;
                     red[((wave * 4 + p) * BN + c) * 2 + 0] = a;

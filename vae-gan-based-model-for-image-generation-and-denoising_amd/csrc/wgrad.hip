@@ -333,13 +333,7 @@ __global__ __launch_bounds__(256) void wgrad_bf16_kernel(const vg_wg_desc d, int
 // Ring shape (measured, S=64 B=128 layer sweep, TFLOP/s incl. the slab reduce; register-staged kernel: G1 365,
 // G2 438, G3 487): 32 rows x 3 slots 350 / 430 / 448, 32 x 4 355 / 410 / 451, 32 x 2 357 / 422 / 451,
 // 64 rows x 2 slots 391 / 480 / 512 -- the barrier count per FLOP is what matters, not the depth of the ring.
-#ifndef VG_WD_SM
-#define VG_WD_SM 64
-#endif
-#ifndef VG_WD_NBUF
-#define VG_WD_NBUF 2
-#endif
-constexpr int WD_SM = VG_WD_SM, WD_NBUF = VG_WD_NBUF, WD_STAGE = 2 * WD_SM * WB_PITCH;     // 16 KB per 32-row stage (P | Q)
+constexpr int WD_SM = 64, WD_NBUF = 2, WD_STAGE = 2 * WD_SM * WB_PITCH;     // 16 KB per 32-row stage (P | Q)
 
 #define WG_WAITCNT_VM(N) asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory")
 
@@ -393,9 +387,6 @@ __global__ __launch_bounds__(256) void wgrad_bf16_dma_kernel(const vg_wg_desc d,
         }
     };
     auto issue_stage = [&](int buf, int slot, int ms) {
-#ifdef VG_ABL_NO_LOAD
-        return;
-#endif
         unsigned char* sp = smem + buf * WD_STAGE;
         unsigned char* sq = sp + WD_SM * WB_PITCH;
         // all row-table entries of this lane's rows FIRST (one LDS round trip; read next to their use they were two
@@ -454,7 +445,6 @@ __global__ __launch_bounds__(256) void wgrad_bf16_dma_kernel(const vg_wg_desc d,
         if (s + WD_NBUF < nstage) fill_table((s + WD_NBUF) & 3, m_begin + (s + WD_NBUF) * WD_SM);
         const unsigned char* sp = smem + rb * WD_STAGE;
         const unsigned char* sq = sp + WD_SM * WB_PITCH;
-#ifndef VG_ABLATE_COMPUTE
 #pragma unroll
         for (int ks = 0; ks < WD_SM / 32; ++ks) {
             bf16x8 a[4], b[4];
@@ -468,7 +458,6 @@ __global__ __launch_bounds__(256) void wgrad_bf16_dma_kernel(const vg_wg_desc d,
                 for (int j = 0; j < 4; ++j)
                     acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i], b[j], acc[i][j], 0, 0, 0);
         }
-#endif
         rb = rb == WD_NBUF - 1 ? 0 : rb + 1;
         wb = wb == WD_NBUF - 1 ? 0 : wb + 1;
     }
@@ -486,11 +475,7 @@ __global__ __launch_bounds__(256) void wgrad_bf16_dma_kernel(const vg_wg_desc d,
                 const int kq = kq0 + wkq * 64 + j * 16 + fi;
                 // the reduce kernel never reads the padding of a partly used tile (narrow layers: 3-channel
                 // image operands, 32/64-channel outputs): do not spend slab bandwidth on it
-#ifdef VG_ABL_NO_EPI
-                if (np < d.NP && kq < KQ && acc[i][j][r] == 123.456f) slab[(int64_t)np * ldk + kq] = acc[i][j][r];
-#else
                 if (np < d.NP && kq < KQ) slab[(int64_t)np * ldk + kq] = acc[i][j][r];
-#endif
             }
 }
 
