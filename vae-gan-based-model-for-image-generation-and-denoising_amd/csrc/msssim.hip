@@ -20,12 +20,12 @@
 //                         the clamp (coefficient 0) writes zeros and computes nothing
 //   5. collapse  (d)      one thread per element of d: the sum over the levels and the one read-modify-write (skipped
 //                         where the sum is zero: d of a clamped image comes back bit for bit)
-// Every element has one owner in every launch: no atomics, the same bits run to run and eager vs. replayed.  The tile pass is
-// that of ssimloss.hip (which is left as it is): 52 x 52 staged inputs, ONE constant per tile and input subtracted before
-// the moments (the per-tile shift: a flat tile has exactly zero variance), the pointwise step without fma contraction with
-// the ratios formed first, so that identical images give cs = S = 1 exactly at every level.  For the cs levels
-// Du = -cs / B2, Dc = 2 / B2, Dm = -(2 (mu_u - cu) Du + (mu_v - cv) Dc): the terms through the means' own ratio are absent.
-// LDS of the tile kernel: 2 x 52 x 53 + 5 x 52 x 43 floats = 66.8 KB -> two workgroups per CU.  No host synchronisation.
+// Every element has one owner in every launch: no atomics, the same bits run to run and eager vs. replayed.  The tile pass --
+// staging with the per-tile shift, the four separable passes, the pointwise step without fma contraction in its S and cs
+// forms, the window -- is csrc/ssim_tile.hpp, shared with ssimloss.hip; the reasoning about cancellation and contraction
+// (why identical images give cs = S = 1 exactly at every level) is there.  What is here: the level lookup, the clamp
+// early-out, the forward launch's skip of the items outside the tile, the stores, and launches 1, 3 and 5.
+// No host synchronisation.
 #include "common.hpp"
 
 #include <climits>
@@ -33,18 +33,10 @@
 
 namespace {
 
-constexpr int NT = 256;                 // threads per workgroup
-constexpr int TS = 32;                  // tile of a level's pixels (TS x TS); also the pyramid's base block
-constexpr int KW = 11, HW5 = 5;         // window, half window
-constexpr int RI = TS + 4 * HW5;        // 52: staged inputs (tile + 10 each side)
-constexpr int RS = TS + 2 * HW5;        // 42: maps (tile + 5 each side)
-constexpr int RIP = RI + 1, RSP = RS + 1, TSP = TS + 1;      // padded LDS rows
+#include "ssim_tile.hpp"                // NT, TS (also the pyramid's base block), KW, HW5, Gauss11 and the tile pass
+
 constexpr int MAXM = 5;
 constexpr int TIMING_FAMILY = 5;
-static_assert(RS % 3 == 0 && TS % 4 == 0 && (TS / 4) * TS == NT, "thread maps below");
-static_assert(3 * RS * RSP <= 2 * RI * RIP && 3 * RS * TSP <= 5 * RI * RSP, "aliased LDS regions");
-
-struct Gauss11 { float g[KW]; };
 
 struct Level {
     int H, W, tiles_x, tiles_per_plane;
@@ -146,12 +138,13 @@ __global__ __launch_bounds__(NT) void msssim_pyramid_kernel(const float* __restr
 template <bool BWD>
 __global__ __launch_bounds__(NT) void msssim_tile_kernel(const float* __restrict__ a, const float* __restrict__ b,
                                                          float* __restrict__ ws, Plan pl, Gauss11 gw) {
-    __shared__ float sin_[2 * RI * RIP];        // u - cu, v - cv; later the three derivative maps [3][RS][RSP]
-    __shared__ float tmp[5 * RI * RSP];         // row-pass results [5][RI][RSP]; later the backward's [3][RS][TSP]
+    __shared__ float sin_[SSIM_LDS_IN];
+    __shared__ float tmp[SSIM_LDS_TMP];
     __shared__ float redf[4][2];
     __shared__ double redd[4];
     float* su = sin_;
     float* sv = sin_ + RI * RIP;
+    float* sD = sin_;                                   // the derivative maps take the staged inputs' place
     const int tid = threadIdx.x;
     int lev = 0;
     for (int j = 1; j < pl.M; ++j)
@@ -179,190 +172,32 @@ __global__ __launch_bounds__(NT) void msssim_tile_kernel(const float* __restrict
         }
     }
 
-    // ---- stage the tile and its halo; pixels outside the plane read 0 and are never used by an interior window
-    float tu = 0.f, tv = 0.f;
-    for (int e = tid; e < RI * RI; e += NT) {
-        const int i = e / RI, j = e % RI;
-        const int y = ty0 - 2 * HW5 + i, x = tx0 - 2 * HW5 + j;
-        float u = 0.f, v = 0.f;
-        if (y >= 0 && y < H && x >= 0 && x < W) {
-            u = (pa[(int64_t)y * W + x] + 1.f) * 0.5f;
-            v = (pb[(int64_t)y * W + x] + 1.f) * 0.5f;
-            tu += u;
-            tv += v;
-        }
-        su[i * RIP + j] = u;
-        sv[i * RIP + j] = v;
-    }
-    tu = wave_sum(tu);
-    tv = wave_sum(tv);
-    if ((tid & 63) == 0) { redf[tid >> 6][0] = tu; redf[tid >> 6][1] = tv; }
-    __syncthreads();
-    const int ny = min(ty0 + TS + 2 * HW5, H) - max(ty0 - 2 * HW5, 0), nx = min(tx0 + TS + 2 * HW5, W) - max(tx0 - 2 * HW5, 0);
-    const float inv_cnt = 1.f / (float)(ny * nx);
-    const float cu = (redf[0][0] + redf[1][0] + redf[2][0] + redf[3][0]) * inv_cnt;
-    const float cv = (redf[0][1] + redf[1][1] + redf[2][1] + redf[3][1]) * inv_cnt;
-    for (int e = tid; e < RI * RI; e += NT) {          // the elements this thread wrote itself
-        const int i = e / RI, j = e % RI;
-        su[i * RIP + j] -= cu;
-        sv[i * RIP + j] -= cv;
-    }
-    __syncthreads();
-
-    // the thread's own four pixels (column qc, rows qr0 .. qr0 + 3 of the tile): u - cu, v - cv, kept for the last step
-    const int qc = tid % TS, qr0 = (tid / TS) * 4;
+    const SsimShift sh = ssim_stage_shift(pa, pb, H, W, ty0, tx0, su, sv, redf);
+    const int qc = tid % TS, qr0 = (tid / TS) * 4;      // the thread's own four pixels of the level's gradient plane
     float uq[4], vq[4];
-    if (BWD) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            uq[j] = su[(qr0 + j + 2 * HW5) * RIP + qc + 2 * HW5];
-            vq[j] = sv[(qr0 + j + 2 * HW5) * RIP + qc + 2 * HW5];
-        }
-    }
-
-    // ---- forward row pass: [RI rows][RS columns], three adjacent columns per thread
-    for (int it = tid; it < RI * (RS / 3); it += NT) {
-        const int r = it / (RS / 3), c0 = (it % (RS / 3)) * 3;
-        // the forward launch sums the tile's own pixels only: rows [5, 47) and columns [5, 37) of the row pass feed them
-        if (!BWD && (r < HW5 || r >= RI - HW5 || c0 + 2 < HW5 || c0 >= HW5 + TS)) continue;
-        float xu[KW + 2], xv[KW + 2];
-#pragma unroll
-        for (int k = 0; k < KW + 2; ++k) {
-            xu[k] = su[r * RIP + c0 + k];
-            xv[k] = sv[r * RIP + c0 + k];
-        }
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            float m0 = 0.f, m1 = 0.f, m2 = 0.f, m3 = 0.f, m4 = 0.f;
-#pragma unroll
-            for (int k = 0; k < KW; ++k) {
-                const float wu = gw.g[k] * xu[j + k], wv = gw.g[k] * xv[j + k];
-                m0 += wu;
-                m1 += wv;
-                m2 += wu * xu[j + k];
-                m3 += wv * xv[j + k];
-                m4 += wu * xv[j + k];
-            }
-            const int o = r * RSP + c0 + j;
-            tmp[o] = m0;
-            tmp[RI * RSP + o] = m1;
-            tmp[2 * RI * RSP + o] = m2;
-            tmp[3 * RI * RSP + o] = m3;
-            tmp[4 * RI * RSP + o] = m4;
-        }
-    }
-    __syncthreads();                                   // sin_ is dead from here on: the derivative maps take its place
-
-    // ---- forward column pass, the map and its derivative maps: [RS][RS], three adjacent rows per thread
-    const float c1 = 0.01f * 0.01f, c2 = 0.03f * 0.03f;
-    float* sD = sin_;
-    double acc = 0.0;
-    for (int it = tid; it < (RS / 3) * RS; it += NT) {
-        const int c = it % RS, r0 = (it / RS) * 3;
-        if (!BWD && (c < HW5 || c >= HW5 + TS || r0 + 2 < HW5 || r0 >= HW5 + TS)) continue;
-        float m[5][3];
-#pragma unroll
-        for (int q = 0; q < 5; ++q) {
-            float x[KW + 2];
-#pragma unroll
-            for (int k = 0; k < KW + 2; ++k) x[k] = tmp[(q * RI + r0 + k) * RSP + c];
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                float s = 0.f;
-#pragma unroll
-                for (int k = 0; k < KW; ++k) s += gw.g[k] * x[j + k];
-                m[q][j] = s;
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            const int i = r0 + j;
-            const int y = ty0 - HW5 + i, x = tx0 - HW5 + c;
-            float dm = 0.f, du = 0.f, dc = 0.f;
-            if (y >= HW5 && y < H - HW5 && x >= HW5 && x < W - HW5) {
-                // Contraction OFF and the ratios A1 / B1, A2 / B2 formed first (see ssimloss.hip): for a == b they are exactly
-                // 1, dc = -2 du and dm = 0 at every level, in the cs form as in the full one.
-#pragma clang fp contract(off)
-                const float mus = m[0][j], mvs = m[1][j];              // shifted means
-                const float suu = m[2][j] - mus * mus, svv = m[3][j] - mvs * mvs, suv = m[4][j] - mus * mvs;
-                const float A2 = 2.f * suv + c2, B2 = (suu + svv) + c2;
-                const float r2 = A2 / B2;
-                float val;
-                if (cs_only) {
-                    val = r2;
-                    du = -r2 / B2;
-                    dc = 2.f / B2;
-                    dm = -(2.f * mus * du + mvs * dc);
-                } else {
-                    const float mu = mus + cu, mv = mvs + cv;
-                    const float A1 = 2.f * (mu * mv) + c1, B1 = (mu * mu + mv * mv) + c1;
-                    const float r1 = A1 / B1;
-                    val = r1 * r2;
-                    du = -val / B2;
-                    dc = 2.f * r1 / B2;
-                    dm = (2.f * mv * r2 - 2.f * mu * val) / B1 - (2.f * mus * du + mvs * dc);
-                }
-                if (i >= HW5 && i < HW5 + TS && c >= HW5 && c < HW5 + TS) acc += (double)val;    // the tile's own pixel
-            }
-            if (BWD) {
-                sD[i * RSP + c] = dm;
-                sD[RS * RSP + i * RSP + c] = du;
-                sD[2 * RS * RSP + i * RSP + c] = dc;
-            }
-        }
-    }
+    if (BWD) ssim_own_pixels(su, sv, qc, qr0, uq, vq);
+    // the forward launch sums the tile's own pixels only: it skips the row- and column-pass items that feed no such pixel
+    // and never writes the derivative maps
+    ssim_fwd_rows(su, sv, tmp, gw, !BWD);
+    __syncthreads();                                    // su, sv are dead from here on
+    const double acc = ssim_fwd_cols(tmp, sD, gw, H, W, ty0, tx0, sh, cs_only, BWD, !BWD);
     if (!BWD) {
-        acc = wave_sum_d(acc);
-        if ((tid & 63) == 0) redd[tid >> 6] = acc;
-        __syncthreads();
-        if (tid == 0) ws[pl.o_partial + blockIdx.x] = (float)(redd[0] + redd[1] + redd[2] + redd[3]);
+        const float sum = ssim_tile_sum(acc, redd);
+        if (tid == 0) ws[pl.o_partial + blockIdx.x] = sum;
         return;
     }
     __syncthreads();
 
-    // ---- backward row pass: [RS rows][TS tile columns] of the three maps, four adjacent columns per thread
-    for (int it = tid; it < RS * (TS / 4); it += NT) {
-        const int r = it / (TS / 4), c0 = (it % (TS / 4)) * 4;
-#pragma unroll
-        for (int q = 0; q < 3; ++q) {
-            float x[KW + 3];
-#pragma unroll
-            for (int k = 0; k < KW + 3; ++k) x[k] = sD[q * RS * RSP + r * RSP + c0 + k];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                float s = 0.f;
-#pragma unroll
-                for (int k = 0; k < KW; ++k) s += gw.g[k] * x[j + k];
-                tmp[(q * RS + r) * TSP + c0 + j] = s;
-            }
-        }
-    }
+    ssim_bwd_rows(sD, tmp, gw);
     __syncthreads();
-
-    // ---- backward column pass; the thread's own four pixels of the level's gradient plane are WRITTEN
     float wsum[3][4];
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-        float x[KW + 3];
-#pragma unroll
-        for (int k = 0; k < KW + 3; ++k) x[k] = tmp[(q * RS + qr0 + k) * TSP + qc];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            float s = 0.f;
-#pragma unroll
-            for (int k = 0; k < KW; ++k) s += gw.g[k] * x[j + k];
-            wsum[q][j] = s;
-        }
-    }
+    ssim_bwd_cols(tmp, gw, qc, qr0, wsum);
     float* pg = ws + pl.o_gpyr + l.g_off + plane * H * W;
     const int x = tx0 + qc;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int y = ty0 + qr0 + j;
-        if (y < H && x < W) {
-#pragma clang fp contract(off)
-            pg[(int64_t)y * W + x] = coef * (wsum[0][j] + (2.f * uq[j] * wsum[1][j] + vq[j] * wsum[2][j]));
-        }
+        if (y < H && x < W) pg[(int64_t)y * W + x] = ssim_grad_pixel(coef, wsum, uq, vq, j);      // WRITTEN, not added
     }
 }
 
@@ -457,10 +292,7 @@ extern "C" int vg_msssim_loss_forward_backward(const float* a, const float* b, f
     }
     VG_CHECK_ARG(ws && ws_bytes >= p.total_floats * 4, VG_EINVAL);
     VG_CHECK_ARG((reinterpret_cast<uintptr_t>(ws) & 7u) == 0, VG_EALIGN);
-    Gauss11 gw;
-    double g[KW], gs = 0.0;
-    for (int k = 0; k < KW; ++k) gs += (g[k] = std::exp(-((k - HW5) * (k - HW5)) / (2.0 * 1.5 * 1.5)));
-    for (int k = 0; k < KW; ++k) gw.g[k] = (float)(g[k] / gs);
+    const Gauss11 gw = ssim_window();
     float* wsf = static_cast<float*>(ws);
     hipStream_t s = vg_stream(stream);
     int rc;

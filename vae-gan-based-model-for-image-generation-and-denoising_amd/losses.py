@@ -61,6 +61,32 @@ class MSELoss(nn.Module):
         return _MSEFn.apply(input, target)
 
 
+msssim_weights = ops.msssim_weights
+
+
+def _check_images(who, input, target, multi_scale=False, scales=None):
+    """The argument checks of ``SSIMLoss`` and ``MSSSIMLoss`` (``who``), in the order they report: device, dtype, one
+    [B,C,H,W] shape, the size (single scale: the 11 x 11 window; multi_scale: ``msssim_weights``, whose weights are
+    returned), a constant target."""
+    for name, t in (("input", input), ("target", target)):
+        if not t.is_cuda:
+            raise RuntimeError(f"vaegan_amd.{who} needs {name} on the MI355X ('cuda'); there is no CPU path")
+        if t.dtype != torch.float32:
+            raise TypeError(f"vaegan_amd.{who} supports float32 images only, got {name} of {t.dtype}")
+    if input.dim() != 4 or input.shape != target.shape:
+        raise ValueError(f"vaegan_amd.{who} needs input and target of one [B,C,H,W] shape, got {tuple(input.shape)} "
+                         f"and {tuple(target.shape)}")
+    weights = None
+    if multi_scale:
+        weights = msssim_weights(input.shape[2], input.shape[3], scales)      # ValueError: too small for the scales
+    elif input.shape[2] < 11 or input.shape[3] < 11:
+        raise ValueError(f"vaegan_amd.{who} needs images of at least 11 x 11 pixels (the 11 x 11 window), got "
+                         f"{input.shape[2]} x {input.shape[3]}")
+    if target.requires_grad:
+        raise NotImplementedError(f"vaegan_amd.{who} treats the target as a constant; detach it")
+    return weights
+
+
 class _SSIMFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a, b):
@@ -82,23 +108,8 @@ class SSIMLoss(nn.Module):
     loss.  One HIP launch computes the value and the gradient w.r.t. ``input``; ``target`` is a constant (no gradient)."""
 
     def forward(self, input, target):
-        for name, t in (("input", input), ("target", target)):
-            if not t.is_cuda:
-                raise RuntimeError(f"vaegan_amd.SSIMLoss needs {name} on the MI355X ('cuda'); there is no CPU path")
-            if t.dtype != torch.float32:
-                raise TypeError(f"vaegan_amd.SSIMLoss supports float32 images only, got {name} of {t.dtype}")
-        if input.dim() != 4 or input.shape != target.shape:
-            raise ValueError(f"vaegan_amd.SSIMLoss needs input and target of one [B,C,H,W] shape, got {tuple(input.shape)} "
-                             f"and {tuple(target.shape)}")
-        if input.shape[2] < 11 or input.shape[3] < 11:
-            raise ValueError(f"vaegan_amd.SSIMLoss needs images of at least 11 x 11 pixels (the 11 x 11 window), got "
-                             f"{input.shape[2]} x {input.shape[3]}")
-        if target.requires_grad:
-            raise NotImplementedError("vaegan_amd.SSIMLoss treats the target as a constant; detach it")
+        _check_images("SSIMLoss", input, target)
         return _SSIMFn.apply(input, target)
-
-
-msssim_weights = ops.msssim_weights
 
 
 def trainer_scales(ssim_scales, H, W):
@@ -143,15 +154,5 @@ class MSSSIMLoss(nn.Module):
         self.scales = scales
 
     def forward(self, input, target):
-        for name, t in (("input", input), ("target", target)):
-            if not t.is_cuda:
-                raise RuntimeError(f"vaegan_amd.MSSSIMLoss needs {name} on the MI355X ('cuda'); there is no CPU path")
-            if t.dtype != torch.float32:
-                raise TypeError(f"vaegan_amd.MSSSIMLoss supports float32 images only, got {name} of {t.dtype}")
-        if input.dim() != 4 or input.shape != target.shape:
-            raise ValueError(f"vaegan_amd.MSSSIMLoss needs input and target of one [B,C,H,W] shape, got {tuple(input.shape)} "
-                             f"and {tuple(target.shape)}")
-        weights = msssim_weights(input.shape[2], input.shape[3], self.scales)      # ValueError: too small for the scales
-        if target.requires_grad:
-            raise NotImplementedError("vaegan_amd.MSSSIMLoss treats the target as a constant; detach it")
+        weights = _check_images("MSSSIMLoss", input, target, multi_scale=True, scales=self.scales)
         return _MSSSIMFn.apply(input, target, weights)
