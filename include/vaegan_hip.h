@@ -719,6 +719,18 @@ int vg_ssim(const float* a, const float* b, int B, int C, int H, int W, float* o
  * rng: device memory, two 64-bit words {seed, iteration counter}.  Counter-based Philox4x32-10 keyed by the seed;
  * counter = (element index >> 2 in the reference's NCHW / [B][L] order, draw id 0..255, iteration counter); one block
  * gives four normals (two Box-Muller pairs, cosine and sine of each): element i is component i & 3 of block i >> 2.
+ * Word layout (Philox4x32-10 of Salmon et al., SC'11, as Random123 publishes it: multipliers 0xD2511F53 / 0xCD9E8D57, key
+ * increments 0x9E3779B9 / 0xBB67AE85, ten rounds), with blk = i >> 2, step = the iteration counter (the epoch position in
+ * "Degraded pairs" below), draw in [0, 256) and step < 2^56:
+ *   counter c0 = blk & 0xFFFFFFFF             key k0 = seed & 0xFFFFFFFF
+ *           c1 = blk >> 32                        k1 = seed >> 32
+ *           c2 = step & 0xFFFFFFFF
+ *           c3 = ((step >> 32) << 8 | draw) & 0xFFFFFFFF
+ * so the draw ids are 256 disjoint streams of every (seed, step).  Output words (w0, w1, w2, w3); a uniform is
+ * u01(w) = (w >> 8) * 2^-24.  Normals, in f32: u(w) = ((float)w + 0.5f) * 2^-32 in (0, 1], r = sqrt(-2 ln max(u(wa), 1e-30f)),
+ * t = 6.283185307179586f * u(wb); components 0, 1 = r cos t, r sin t of (wa, wb) = (w0, w1), components 2, 3 those of
+ * (w2, w3); logarithm, sine and cosine are the fast device intrinsics, so |n| <= sqrt(-2 ln 2^-33) = 6.77.
+ * tests/_philox_ref.py restates exactly this on the host (tests/test_philox_cpu.py, tests/test_gpu_philox.py).
  * The `_rng` forms of the consuming kernels are identical to their eps-pointer forms with
  * eps[i] = N(seed, iteration, draw, i); vg_randn materialises exactly that tensor (tests, and callers that want
  * the draw itself).  vg_rng_advance (one thread) bumps the iteration counter: launch it once at the top of every
@@ -770,7 +782,8 @@ int vg_reparam_kl_backward_rng(const void* mulv, const float* lv_clamped, const 
  *
  * Random draws.  Philox4x32-10 exactly as for the in-kernel N(0,1) noise below: key = seed, and the counter word that
  * carries the iteration there carries pos = pos0 + b here, the sample's POSITION IN THE EPOCH'S ORDER (not its batch slot):
- * a sample's degradation does not depend on batch size, rank or world size.  seed and pos0 (< 2^56) travel by value.
+ * a sample's degradation does not depend on batch size, rank or world size.  seed and pos0 travel by value; every position
+ * pos0 .. pos0 + B - 1 is below 2^56 (VG_EINVAL otherwise: position 2^56 would wrap onto position 0).
  * With e = c*H*W + h*W + w, the element's index within its image, and word(draw, i) = output word i & 3 of Philox block
  * i >> 2 of that draw at (seed, pos):
  *   draw VG_DRAW_DEGRADE_NORMAL: n = element e of what vg_randn(out, C*H*W, {seed, pos}, draw) materialises;

@@ -193,6 +193,10 @@ bool geom_ok(const DegradeGeom& g, int H, int W) {
            g.y1 - g.max_size > g.y0 && g.x1 - 1 <= W && g.y1 - 1 <= H;
 }
 
+// every position pos0 .. pos0 + B - 1 (B > 0) below 2^56: the counter word that carries pos >> 32 keeps its low byte for the
+// draw id, and a position of 2^56 would wrap onto position 0
+bool positions_ok(uint64_t pos0, int B) { return (pos0 >> 56) == 0 && ((pos0 + (uint64_t)(B - 1)) >> 56) == 0; }
+
 }  // namespace
 
 extern "C" int vg_rand_u01(float* out, int64_t n, const uint64_t* rng, int draw, void* stream) {
@@ -207,7 +211,7 @@ extern "C" int vg_rand_u01(float* out, int64_t n, const uint64_t* rng, int draw,
 extern "C" int vg_degrade_params(uint64_t seed, uint64_t pos0, int B, float noise_max_std, int rect, int H, int W,
                                  int min_size, int max_size, int x0, int x1, int y0, int y1, float* out, void* stream) {
     const DegradeGeom g{rect ? 1 : 0, min_size, max_size, x0, x1, y0, y1};
-    VG_CHECK_ARG(out && B > 0 && H > 0 && W > 0 && (pos0 >> 56) == 0 && geom_ok(g, H, W), VG_EINVAL);
+    VG_CHECK_ARG(out && B > 0 && H > 0 && W > 0 && positions_ok(pos0, B) && geom_ok(g, H, W), VG_EINVAL);
     hipLaunchKernelGGL(degrade_params_kernel, dim3((B + 255) / 256), dim3(256), 0, vg_stream(stream),
                        (unsigned long long)seed, (unsigned long long)pos0, B, noise_max_std, g, out);
     return VG_LAUNCH_RC();
@@ -218,7 +222,7 @@ extern "C" int vg_gather_degrade_u8(const uint8_t* images, int64_t N, const int6
                                     int min_size, int max_size, int x0, int x1, int y0, int y1, float* clean,
                                     float* noisy, void* nhwc, int CP, int dtype, void* stream) {
     const DegradeGeom g{rect ? 1 : 0, min_size, max_size, x0, x1, y0, y1};
-    VG_CHECK_ARG(images && idx && clean && noisy && N > 0 && B > 0 && C > 0 && H > 0 && W > 0 && (pos0 >> 56) == 0 &&
+    VG_CHECK_ARG(images && idx && clean && noisy && N > 0 && B > 0 && C > 0 && H > 0 && W > 0 && positions_ok(pos0, B) &&
                  (int64_t)H * W < (1ll << 30) && geom_ok(g, H, W), VG_EINVAL);
     if (nhwc) {
         VG_CHECK_ARG(dtype == VG_F32 || dtype == VG_BF16, VG_ENOSUP);
