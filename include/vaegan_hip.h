@@ -83,7 +83,9 @@ extern "C" {
                                  (added within 31, nothing changed) multi-scale SSIM loss: vg_msssim_loss_forward_backward
                                  (+ _ws_bytes); timing family 5;
                                  (added within 31, nothing changed) test-time latent refinement: vg_bn_act_backward_eval,
-                                 vg_masked_mse_rows (+ _ws_doubles), vg_latent_adam / VG_LATENT_* */
+                                 vg_masked_mse_rows (+ _ws_doubles), vg_latent_adam / VG_LATENT_*;
+                                 (added within 31, no version move, nothing changed) classical-denoiser baseline:
+                                 vg_nlm_denoise, vg_noise_sigma */
 int vg_abi_version(void);
 /* The library reads its optional kernel-selection switches (VG_* environment variables, DESIGN.md "Runtime switches")
  * ONCE, when it is loaded; nothing on a launch path calls getenv.  A process that changes one of them afterwards
@@ -1440,6 +1442,47 @@ int vg_tile_gather(const uint8_t* src_u8, const float* src_f32, int N, int C, in
 int vg_tile_blend(const float* tiles, float* out, int N, int C, int H, int W, int S, int ny, int nx,
                   const int32_t* oy, const int32_t* ox, const int32_t* first_y, const int32_t* count_y, const float* coef_y,
                   int wy, const int32_t* first_x, const int32_t* count_x, const float* coef_x, int wx, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Non-local means baseline and blind noise estimate (not in the reference; added within ABI 31; csrc/nlm.hip): the classical,
+ * parameter-free denoiser the evaluation passes report between the noisy input and the model (denoise.py, baselines.py).
+ *
+ * vg_nlm_denoise: non-local means (Buades, Coll & Morel 2005), pixelwise, uniform patch kernel.  x f32 NCHW [B][C][H][W],
+ * contiguous; y of the same shape, y != x (no overlap).  Patch radius P in 0..3, search radius R in 1..10.
+ *   Padding.   x~ is x extended by P + R on every side by reflection without repeating the edge (numpy mode="reflect");
+ *              min(H, W) >= P + R + 1 is required, so one reflection suffices.
+ *   Distance.  For pixel p and each of the K = (2R+1)^2 offsets t (candidates outside the image are the reflected pixels):
+ *              d2(p,t) = (1 / (C (2P+1)^2)) * sum_c sum_{|delta|_inf <= P} (x~_c(p+delta) - x~_c(p+t+delta))^2
+ *   Weight.    a = max(d2 - 2 sigma_b^2, 0) / h_b^2,  w = exp(-a).  The centre offset has d2 = 0 and w = 1.
+ *   Output.    y_c(p) = (sum_t w x~_c(p+t)) / (sum_t w); the final quotient is ONE correctly rounded f32 division, not a
+ *              reciprocal multiply.
+ *   Per image. sigma_b = sigma[b * sigma_stride] (a device pointer with an element stride, so the call reads column 1 of the
+ *              degraded loader's [B][8] rectangle records in place); sigma == NULL means 0.  h_b = h_factor * sigma_b + h_const.
+ *              If h_b is not finite or <= 0, or sigma_b is not finite, image b is copied through bit for bit.
+ *   Guarantees. Images are independent of each other.  No atomics: two runs are bit-identical.  Nothing is allocated and
+ *              there is no host synchronisation: the launch can be captured into a graph.  One launch.
+ *   Non-finite pixels may spread within their own image; every access stays in bounds.
+ *   Arithmetic. f32 throughout: squared differences by fma over the channels, the patch sum as a separable box sum (rows,
+ *              then columns), d2 = S * fl(1 / (C (2P+1)^2)), the weight as ONE hardware base-2 exponential of
+ *              max(d2 - 2 sigma^2, 0) * fl(-log2(e) / h^2) (1 ulp; results below 2^-126 are 0), sums over t in row-major
+ *              offset order by fma.  tests/_nlm_ref.py counts the first-order error bound of this sequence.
+ * VG_EINVAL, checked on the host before the launch: x or y NULL, or the two buffers overlapping; B, C, H or W < 1; C > 4;
+ * P outside 0..3 or R outside 1..10; min(H, W) < P + R + 1; sigma != NULL with sigma_stride < 1; h_factor or h_const not finite
+ * or negative, or both zero; B C H W > 2^31 - 1 elements, B > 65535 or ceil(H / 16) > 65535 (the launch grid: 16 x 16 output
+ * tiles in x / y, images in z), (B - 1) sigma_stride > 2^31 - 1.  VG_EALIGN: a pointer that is not 4-byte aligned (x may sit
+ * anywhere on the 4-byte grid: 16-byte loads are used only where an address allows them).
+ *
+ * vg_noise_sigma: Immerkaer's (1996) fast noise-variance estimate, per image.  With N = [[1,-2,1],[-2,4,-2],[1,-2,1]]:
+ *     S_b     = sum_c sum_{1 <= i <= H-2, 1 <= j <= W-2} |(x_c * N)(i,j)|           (interior only, no padding)
+ *     sigma_b = (float)((double)S_b * k),   k = sqrt(pi / 2) / (6 C (H-2) (W-2))   computed in double on the host
+ * written to sigma[b * sigma_stride].  The mask response is evaluated and summed in f64 in a fixed order (one workgroup per
+ * image: rows to waves, columns to lanes, xor butterfly, waves in order): repeatable bit for bit, no atomics, no workspace, no
+ * host synchronisation, one launch.  VG_EINVAL: x or sigma NULL; B or C < 1; H or W < 3; sigma_stride < 1; C (H - 2) or
+ * (B - 1) sigma_stride > 2^31 - 1 (B itself is the grid's x dimension).  VG_EALIGN: a pointer not 4-byte aligned.
+ * ---------------------------------------------------------------------------------------- */
+int vg_nlm_denoise(const float* x, float* y, int B, int C, int H, int W, int patch_radius, int search_radius,
+                   const float* sigma, int sigma_stride, float h_factor, float h_const, void* stream);
+int vg_noise_sigma(const float* x, int B, int C, int H, int W, float* sigma, int sigma_stride, void* stream);
 
 #ifdef __cplusplus
 }

@@ -27,8 +27,12 @@ CenterCrop on the device), ``resample_coeffs``, ``resize_geometry``.  Tiled deno
 (not in the reference): ``denoise_tiled``, ``tiled_denoise_eval``, ``tiled_test_epoch`` and ``tiling`` -- ``tile_plan`` /
 ``TilePlan``: overlapping S x S tiles cut and blended back on the device with a separable window.  Test-time latent
 refinement (not in the reference; GAN-inversion denoising / inpainting): ``LatentRefiner`` -- Adam on the latent of the frozen
-networks against the input outside its occlusion rectangle, and ``paired_test_epoch(..., refine=)``.
+networks against the input outside its occlusion rectangle, and ``paired_test_epoch(..., refine=)``.  Classical-denoiser
+baseline (not in the reference): ``NLMeans`` (``baselines``) -- non-local means on the device with the loader's own or a
+blindly estimated noise level (``ops.nlm_denoise``, ``ops.noise_sigma``), and ``baseline=`` on ``paired_test_epoch`` /
+``tiled_test_epoch``.
 """
+from . import baselines  # noqa: F401
 from . import cluster  # noqa: F401
 from . import data  # noqa: F401
 from . import geometry  # noqa: F401
@@ -36,6 +40,7 @@ from . import latent  # noqa: F401
 from . import metrics  # noqa: F401
 from .data import ResidentImages, resample_coeffs, resize_geometry
 from .augment import DiffAugment
+from .baselines import NLMeans
 from .ddp import GradReducer
 from .ema import EMA
 from . import tiling  # noqa: F401
@@ -61,4 +66,5 @@ __all__ = ["ConvBlock", "Encoder", "Generator", "Discriminator", "weights_init",
            "EMA", "clip_grad_norm_", "DiffAugment", "AdamW", "LRSchedule",
            "tiling", "TilePlan", "tile_plan", "denoise_tiled", "tiled_denoise_eval", "tiled_test_epoch",
            "metrics", "FeatureStats", "frechet_distance", "precision_recall", "encoder_features", "kernel_distance",
-           "cluster", "KMeans", "ndb", "evaluate_generation_ndb", "MSSSIMLoss", "msssim_weights", "LatentRefiner"]
+           "cluster", "KMeans", "ndb", "evaluate_generation_ndb", "MSSSIMLoss", "msssim_weights", "LatentRefiner",
+           "baselines", "NLMeans"]

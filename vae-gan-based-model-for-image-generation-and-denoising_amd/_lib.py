@@ -265,6 +265,8 @@ SIGNATURES = {
     "vg_tnconv_supported": (c_int, [POINTER(TNDesc)]),
     "vg_tnconv": (c_int, [POINTER(TNDesc), _P]),
     "vg_tnconv_plan": (c_int, [POINTER(TNDesc), POINTER(TNPlan)]),
+    "vg_nlm_denoise": (c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _F, _F, _P]),
+    "vg_noise_sigma": (c_int, [_P, _I, _I, _I, _I, _P, _I, _P]),
 }
 
 LIB_PATH = os.environ.get("VG_LIB_PATH") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libvaegan_hip.so")

@@ -13,6 +13,7 @@ import torch
 from . import geometry as G
 from . import ops
 from . import tiling
+from .baselines import NLMeans, make_baseline
 from .capture import HostMirrors, capture, replay
 from .engine import GradSink
 from .metrics import FeaturePass
@@ -163,7 +164,7 @@ def validation_epoch(encoder, decoder, loader: Iterable[torch.Tensor], n_samples
 
 @torch.no_grad()
 def paired_test_epoch(encoder, decoder, loader: Iterable, n_samples: Optional[int] = None, noise_fn=None,
-                      regions: bool = False, ms_ssim: bool = False, refine=None) -> Dict[str, float]:
+                      regions: bool = False, ms_ssim: bool = False, refine=None, baseline=None) -> Dict[str, float]:
     """The reference's test pass over (noisy, clean) pairs, main_vae.py:251-266:
 
         encoder.eval(); decoder.eval()                                                 (:251-252)
@@ -196,7 +197,15 @@ def paired_test_epoch(encoder, decoder, loader: Iterable, n_samples: Optional[in
     ``refine.refine(noisy, rects=loader.last_rects)`` from the Encoder's mean, the occlusion rectangle left out of its loss
     -- and the result gains ``recon_loss_refined``, ``ssim_refined`` and ``psnr_refined`` of the refined reconstruction vs
     ``clean`` (with regions=True also the five region keys suffixed ``_refined``), accumulated on the device and read in the
-    same host sync.  The loader must offer ``want_rects``, which the pass turns on and restores as regions=True does."""
+    same host sync.  The loader must offer ``want_rects``, which the pass turns on and restores as regions=True does.
+    baseline (default None: exactly the keys and the launches above): a ``baselines.NLMeans``, the string "nlm" (its
+    defaults) or a dict of its keywords.  Every noisy batch ALSO goes through non-local means -- the classical, parameter-free
+    denoiser between the input and the model -- and the result gains ``recon_loss_nlm``, ``ssim_nlm`` and ``psnr_nlm`` of its
+    output vs ``clean`` (with ms_ssim=True also ``ms_ssim_nlm``, with regions=True also the five region keys suffixed
+    ``_nlm``), accumulated on the device and read in the same host sync.  ``sigma="oracle"`` (NLMeans' default) reads the
+    noise level the loader drew per image, ``loader.last_rects[:, 1]``, in place: it needs a degraded loader, whose
+    ``want_rects`` the pass turns on and restores; ``"estimate"`` (blind, ops.noise_sigma) and a number need no rectangles."""
+    nlm = make_baseline("paired_test_epoch", baseline)
     refiner = None
     if refine is not None:
         if isinstance(refine, LatentRefiner):
@@ -207,9 +216,10 @@ def paired_test_epoch(encoder, decoder, loader: Iterable, n_samples: Optional[in
             raise ValueError("paired_test_epoch: refine must be a LatentRefiner or a dict of its keywords")
         if refiner.E is not encoder or refiner.G is not decoder:
             raise ValueError("paired_test_epoch: the LatentRefiner was built on other networks")
-    need_rects = regions or refiner is not None
+    need_rects = regions or refiner is not None or (nlm is not None and nlm.needs_rects)
     if need_rects and not (hasattr(loader, "want_rects") and getattr(loader, "degrade", None) is not None and loader.degrade.pairs):
-        raise RuntimeError(f"paired_test_epoch: {'regions=True' if regions else 'refine'} needs a degraded data.DeviceLoader "
+        why = "regions=True" if regions else ("refine" if refiner is not None else "baseline with sigma='oracle'")
+        raise RuntimeError(f"paired_test_epoch: {why} needs a degraded data.DeviceLoader "
                            f"(want_rects)")
     encoder.eval(), decoder.eval()                                                   # :251-252
     dev = next(encoder.parameters()).device
@@ -230,6 +240,9 @@ def paired_test_epoch(encoder, decoder, loader: Iterable, n_samples: Optional[in
     if refiner is not None:
         acc_ref = ops.zeros_f32(2, dev)                                              # [sum(b * ssim(refined)), sum(b * mse_mean(refined))]
         stats_ref = torch.zeros(4, dtype=torch.float64, device=dev) if regions else None
+    if nlm is not None:
+        acc_nlm = ops.zeros_f32(3 if ms_ssim else 2, dev)                            # [sum(b * ssim(nlm)), sum(b * mse_mean(nlm))(, sum(b * ms_ssim(nlm)))]
+        stats_nlm = torch.zeros(4, dtype=torch.float64, device=dev) if regions else None
     try:
         for i, (noisy, clean) in enumerate(loader):
             if not (noisy.is_cuda and clean.is_cuda):
@@ -273,6 +286,16 @@ def paired_test_epoch(encoder, decoder, loader: Iterable, n_samples: Optional[in
                 ops.axpy(acc_ref[1:2], mse_ref, float(b), out=acc_ref[1:2])
                 if regions:
                     ops.region_mse_forward_backward(refined, clean, loader.last_rects, 1.0, 1.0, stats=stats_ref)
+            if nlm is not None:
+                filtered = nlm(noisy, rects=loader.last_rects if nlm.needs_rects else None)
+                mse_nlm = torch.empty(1, dtype=torch.float32, device=dev)
+                ops.mse_forward_backward(filtered, clean, 1.0, mse_nlm, False)
+                ops.axpy(acc_nlm[0:1], ops.ssim(filtered, clean), float(b), out=acc_nlm[0:1])
+                ops.axpy(acc_nlm[1:2], mse_nlm, float(b), out=acc_nlm[1:2])
+                if ms_ssim:
+                    ops.axpy(acc_nlm[2:3], ops.ms_ssim(filtered, clean), float(b), out=acc_nlm[2:3])
+                if regions:
+                    ops.region_mse_forward_backward(filtered, clean, loader.last_rects, 1.0, 1.0, stats=stats_nlm)
             seen += b
             batches += 1
     finally:
@@ -287,7 +310,12 @@ def paired_test_epoch(encoder, decoder, loader: Iterable, n_samples: Optional[in
         parts = [p.double() for p in parts] + [acc_ms.double()]                      # (f32 -> f64 is exact)
     if refiner is not None:
         parts = [p.double() for p in parts] + [acc_ref.double()] + ([stats_ref] if regions else [])
+    if nlm is not None:
+        parts = [p.double() for p in parts] + [acc_nlm.double()] + ([stats_nlm] if regions else [])
     host = (torch.cat(parts) if len(parts) > 1 else acc).tolist()                    # the one host sync
+    if nlm is not None:                                                              # the baseline's tail comes off first
+        nnlm = (3 if ms_ssim else 2) + (4 if regions else 0)
+        host, host_nlm = host[:-nnlm], host[-nnlm:]
     if refiner is not None:                                                          # the refined tail, then today's layout
         nref = 6 if regions else 2
         host, host_ref = host[:-nref], host[-nref:]
@@ -318,6 +346,16 @@ def paired_test_epoch(encoder, decoder, loader: Iterable, n_samples: Optional[in
             m_valid = s_valid / n_valid if n_valid > 0 else 0.0
             out.update({"mse_hole_refined": m_hole, "mse_valid_refined": m_valid, "psnr_hole_refined": psnr(m_hole),
                         "psnr_valid_refined": psnr(m_valid), "hole_fraction_refined": n_hole / (n_hole + n_valid)})
+    if nlm is not None:
+        out.update({"recon_loss_nlm": host_nlm[1] / seen, "ssim_nlm": host_nlm[0] / seen, "psnr_nlm": psnr(host_nlm[1] / seen)})
+        if ms_ssim:
+            out["ms_ssim_nlm"] = host_nlm[2] / seen
+        if regions:
+            s_hole, s_valid, n_hole, n_valid = host_nlm[-4:]
+            m_hole = s_hole / n_hole if n_hole > 0 else 0.0
+            m_valid = s_valid / n_valid if n_valid > 0 else 0.0
+            out.update({"mse_hole_nlm": m_hole, "mse_valid_nlm": m_valid, "psnr_hole_nlm": psnr(m_hole),
+                        "psnr_valid_nlm": psnr(m_valid), "hole_fraction_nlm": n_hole / (n_hole + n_valid)})
     return out
 
 
@@ -666,13 +704,19 @@ def tiled_denoise_eval(encoder, decoder, img: torch.Tensor, sigma: float = 0.05,
 
 
 @torch.no_grad()
-def tiled_test_epoch(encoder, decoder, pairs: Iterable, ms_ssim: bool = False, **tiling_kw) -> Dict[str, float]:
+def tiled_test_epoch(encoder, decoder, pairs: Iterable, ms_ssim: bool = False, baseline=None, **tiling_kw) -> Dict[str, float]:
     """paired_test_epoch at full resolution: ``pairs`` yields (noisy, clean) device batches f32 [b,C,H,W] in [-1,1], each
     denoised with ``denoise_tiled(encoder, decoder, noisy, **tiling_kw)``.  Accumulation stays on the device (per batch the
     mean squared error and the mean SSIM, weighed by the batch's image count); ONE host sync at the end.  Returns python
     floats: psnr, ssim, recon_loss (mean squared error per element) of recon vs clean, psnr_noisy, ssim_noisy of the input,
     samples, tiles.  ms_ssim=True (default False: nothing changes) adds ``ms_ssim`` and ``ms_ssim_noisy`` (ops.ms_ssim, the
-    default scales of the image size), accumulated like ssim and read in the same sync."""
+    default scales of the image size), accumulated like ssim and read in the same sync.
+    baseline (default None: nothing changes): as in paired_test_epoch, a ``baselines.NLMeans``, "nlm" or a dict of its keywords;
+    here there are whole large images and no loader, so the noise level is ``sigma="estimate"`` (what "nlm" means here) or a
+    number -- "oracle" is refused.  The filter runs on the full H x W image, no tiling, and the result gains ``recon_loss_nlm``,
+    ``ssim_nlm``, ``psnr_nlm`` (and ``ms_ssim_nlm`` with ms_ssim=True), read in the same sync."""
+    nlm = make_baseline("tiled_test_epoch", baseline, allow_oracle=False)
+    acc_nlm = None
     acc = None                                           # sum over batches of b * [mse(recon), ssim(recon), mse(noisy), ssim(noisy)]
     seen = tiles = 0
     for noisy, clean in pairs:
@@ -695,13 +739,29 @@ def tiled_test_epoch(encoder, decoder, pairs: Iterable, ms_ssim: bool = False, *
         if ms_ssim:
             ops.axpy(acc[4:5], ops.ms_ssim(recon, clean), float(b), out=acc[4:5])
             ops.axpy(acc[5:6], ops.ms_ssim(noisy, clean), float(b), out=acc[5:6])
+        if nlm is not None:
+            acc_nlm = ops.zeros_f32(3 if ms_ssim else 2, dev) if acc_nlm is None else acc_nlm   # b * [mse, ssim(, ms_ssim)] of the baseline
+            filtered = nlm(noisy)
+            mse_nlm = torch.empty(1, dtype=torch.float32, device=dev)
+            ops.mse_forward_backward(filtered, clean, 1.0, mse_nlm, False)
+            ops.axpy(acc_nlm[0:1], mse_nlm, float(b), out=acc_nlm[0:1])
+            ops.axpy(acc_nlm[1:2], ops.ssim(filtered, clean), float(b), out=acc_nlm[1:2])
+            if ms_ssim:
+                ops.axpy(acc_nlm[2:3], ops.ms_ssim(filtered, clean), float(b), out=acc_nlm[2:3])
         seen += b
         tiles += _tile_count(encoder, clean, tiling_kw)
     if seen == 0:
         raise RuntimeError("tiled_test_epoch: pairs yielded no batch")
-    mse_r, ssim_r, mse_n, ssim_n, *ms = (float(v) / seen for v in acc.tolist())  # the one host sync
+    host = (acc if nlm is None else torch.cat([acc, acc_nlm])).tolist()            # the one host sync
+    if nlm is not None:
+        host, host_nlm = host[:acc.numel()], [float(v) / seen for v in host[acc.numel():]]
+    mse_r, ssim_r, mse_n, ssim_n, *ms = (float(v) / seen for v in host)
     out = {"psnr": _psnr(mse_r), "ssim": ssim_r, "recon_loss": mse_r, "psnr_noisy": _psnr(mse_n), "ssim_noisy": ssim_n,
            "samples": seen, "tiles": tiles}
     if ms_ssim:
         out["ms_ssim"], out["ms_ssim_noisy"] = ms
+    if nlm is not None:
+        out.update({"recon_loss_nlm": host_nlm[0], "ssim_nlm": host_nlm[1], "psnr_nlm": _psnr(host_nlm[0])})
+        if ms_ssim:
+            out["ms_ssim_nlm"] = host_nlm[2]
     return out

@@ -1840,6 +1840,63 @@ def masked_mse_rows(a, b, rects, gscale=1.0, loss_rows=None, want_grad=False, ou
     return da
 
 
+# ---- classical-denoiser baseline (csrc/nlm.hip; baselines.NLMeans) ---------------------------------------------------------
+def _sigma_column(what, sigma, B, device):
+    """-> (tensor kept alive, element stride) of a per-image f32 noise level: None, a number, [B] or a strided 1-D view."""
+    if sigma is None:
+        return None, 1
+    if isinstance(sigma, (int, float)) and not isinstance(sigma, bool):
+        return torch.full((B,), float(sigma), dtype=torch.float32, device=device), 1
+    if not isinstance(sigma, torch.Tensor) or not sigma.is_cuda or sigma.dtype != torch.float32 or sigma.dim() != 1 or \
+            sigma.shape[0] != B or (B > 1 and sigma.stride(0) < 1):
+        raise RuntimeError(f"{what}: sigma must be None, a number, or a device f32 tensor [B] (a strided 1-D view such as "
+                           f"rects[:, 1] is read in place)")
+    if sigma.device != device:
+        raise RuntimeError(f"{what}: sigma is on {sigma.device}, x on {device}")
+    return sigma, (sigma.stride(0) if B > 1 else 1)
+
+
+def nlm_denoise(x, sigma=None, *, patch_radius=2, search_radius=7, h_factor=0.8, h_const=0.0, out=None):
+    """Non-local means of an f32 [B,C,H,W] batch (vg_nlm_denoise; C <= 4): pixelwise, uniform (2P+1)^2 patch, (2R+1)^2 search
+    window, reflect padding, weight exp(-max(d2 - 2 sigma_b^2, 0) / h_b^2) with h_b = h_factor * sigma_b + h_const.  sigma: None
+    (0), a number (materialised once as a [B] tensor) or a device f32 tensor -- [B], or a strided 1-D view such as
+    ``loader.last_rects[:, 1]``, read in place.  An image whose h_b is not a finite positive number is copied through.  One
+    launch, no host synchronisation, no atomics.  -> out (f32 of x's shape, not x) or a new tensor."""
+    what = "nlm_denoise"
+    _need_cuda(x, out)
+    if x.dtype != torch.float32 or x.dim() != 4:
+        raise RuntimeError(f"{what}: x must be an f32 [B,C,H,W] tensor")
+    B, C, H, W = x.shape
+    if out is not None and (out.dtype != torch.float32 or out.shape != x.shape or out.device != x.device):
+        raise RuntimeError(f"{what}: out must be f32 of x's shape on x's device")
+    for name, v in (("patch_radius", patch_radius), ("search_radius", search_radius)):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise RuntimeError(f"{what}: {name} must be an integer")
+    sig, stride = _sigma_column(what, sigma, B, x.device)
+    y = out if out is not None else torch.empty_like(x)
+    L.check(L.load().vg_nlm_denoise(x.data_ptr(), y.data_ptr(), B, C, H, W, patch_radius, search_radius, L.ptr(sig), stride,
+                                    float(h_factor), float(h_const), L.stream_ptr()), "vg_nlm_denoise")
+    return y
+
+
+def noise_sigma(x, out=None):
+    """Blind per-image noise level of an f32 [B,C,H,W] batch, H, W >= 3 (vg_noise_sigma; Immerkaer 1996): the mean absolute
+    response of the 3 x 3 mask [[1,-2,1],[-2,4,-2],[1,-2,1]] over the interior, times sqrt(pi/2) / 6.  -> f32 [B] (``out``: a
+    1-D f32 tensor or strided view of B elements, written in place).  One launch, fixed summation order, no host sync."""
+    what = "noise_sigma"
+    _need_cuda(x)
+    if x.dtype != torch.float32 or x.dim() != 4:
+        raise RuntimeError(f"{what}: x must be an f32 [B,C,H,W] tensor")
+    B, C, H, W = x.shape
+    if out is not None and (not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != torch.float32 or
+                            out.dim() != 1 or out.shape[0] != B or (B > 1 and out.stride(0) < 1) or out.device != x.device):
+        raise RuntimeError(f"{what}: out must be an f32 tensor [B] on x's device (a strided 1-D view is written in place)")
+    s = out if out is not None else torch.empty(B, dtype=torch.float32, device=x.device)
+    L.check(L.load().vg_noise_sigma(x.data_ptr(), B, C, H, W, s.data_ptr(), s.stride(0) if B > 1 else 1, L.stream_ptr()),
+            "vg_noise_sigma")
+    return s
+
+
 LATENT_MODE = {"init": L.VG_LATENT_INIT, "update": L.VG_LATENT_UPDATE, "track": L.VG_LATENT_TRACK}
 
 
