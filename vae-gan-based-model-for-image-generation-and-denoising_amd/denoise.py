@@ -19,6 +19,120 @@ from .engine import GradSink
 from .metrics import FeaturePass
 
 
+def _default_draws(dev, eps_shape, z_shape):
+    """The default draws of one batch: ONE advance() of the device noise stream (HIP Philox, keyed by torch's device seed),
+    then draw 0 = the image noise and draw 1 = the latent noise.  A shape of None: that draw is not generated.
+    -> (eps or None, eps_z or None)"""
+    ns = ops.default_noise(dev)
+    ns.advance()
+    return (None if eps_shape is None else ns.randn(tuple(eps_shape), 0),
+            None if z_shape is None else ns.randn(tuple(z_shape), 1))
+
+
+def _reconstruct(encoder, decoder, noisy_h, b: int, eps_z, train_e: bool = False, train_g: bool = False, out=None):
+    """The reconstruction step of every pass (vaegan_code.py:158-163, main_vae.py:258-260): Encoder on the NHWC input ->
+    reparameterise with eps_z -> Generator -> Tanh into an NCHW f32 image (``out``: written there).
+    -> (recon, mulv [b, MP], the clamped logvar)"""
+    dt = encoder._dt
+    mulv, _ = encoder._engine.forward(noisy_h, b, train_e, keep=False)
+    mulv = mulv.view(b, -1)
+    z, lvc = ops.reparam_forward(mulv, eps_z, encoder.latent_dim, G.padc(decoder.nz, dt), dt)
+    pre, _ = decoder._engine.forward(z, b, train_g, keep=False)
+    return ops.nhwc_to_nchw(pre, decoder.nc, dt, apply_tanh=True, out=out), mulv, lvc
+
+
+def _psnr(mse: float) -> float:
+    mse01 = mse / 4.0                                                      # ((a+1)/2 - (b+1)/2)^2 = (a-b)^2 / 4
+    return float("inf") if mse01 == 0 else 10.0 * math.log10(1.0 / mse01)
+
+
+def _region_keys(suffix: str, sums) -> Dict[str, float]:
+    """{S_hole, S_valid, n_hole, n_valid} of a pass -> the five region keys; an empty region reports mse 0.0 and psnr inf."""
+    s_hole, s_valid, n_hole, n_valid = sums
+    m_hole = s_hole / n_hole if n_hole > 0 else 0.0
+    m_valid = s_valid / n_valid if n_valid > 0 else 0.0
+    return {"mse_hole" + suffix: m_hole, "mse_valid" + suffix: m_valid, "psnr_hole" + suffix: _psnr(m_hole),
+            "psnr_valid" + suffix: _psnr(m_valid), "hole_fraction" + suffix: n_hole / (n_hole + n_valid)}
+
+
+class _Quality:
+    """What every pass measures of ONE candidate image (the reconstruction, the noisy input, the refined reconstruction, the
+    filtered image) against the clean one: per batch the MSE and the mean SSIM, with ms_ssim the MS-SSIM, each added times the
+    batch's image count into its own f32 slot on the device, and with regions the f64 {S_hole, S_valid, n_hole, n_valid} that
+    ops.region_mse_forward_backward accumulates.  ``_allocate`` gives the candidates of a pass their slots, ``_read`` is the
+    pass's one host read, and ``result`` names this candidate's part of it with its suffix.  A further candidate is one more
+    instance."""
+
+    def __init__(self, suffix: str, ms_ssim: bool = False, regions: bool = False):
+        self.suffix, self.ms_ssim, self.regions = suffix, ms_ssim, regions
+        self.slots = 3 if ms_ssim else 2                # f32: [sum(b * mse), sum(b * ssim)(, sum(b * ms_ssim))]
+        self.acc = self.stats = None                    # _allocate: one view per slot, the f64 [4] region statistics
+
+    def update(self, x, clean, b: int, rects=None, mse=None, store: bool = False) -> None:
+        """mse: the f32 slot holding mse_mean(x, clean) when the pass has computed it already.  store=True (a pass of one
+        batch, weight 1): the MSE kernel writes its slot itself, no add."""
+        if store:
+            ops.mse_forward_backward(x, clean, 1.0, self.acc[0], False)
+        else:
+            if mse is None:
+                mse = torch.empty(1, dtype=torch.float32, device=clean.device)
+                ops.mse_forward_backward(x, clean, 1.0, mse, False)
+            ops.axpy(self.acc[0], mse, float(b), out=self.acc[0])
+        ops.axpy(self.acc[1], ops.ssim(x, clean), float(b), out=self.acc[1])
+        if self.ms_ssim:
+            ops.axpy(self.acc[2], ops.ms_ssim(x, clean), float(b), out=self.acc[2])
+        if self.regions:
+            ops.region_mse_forward_backward(x, clean, rects, 1.0, 1.0, stats=self.stats)   # w_hole = 1, no gradient
+
+    def result(self, sums, stats, seen: int):
+        """Host only.  sums: this candidate's f32 slots as read, stats: its four region sums (None without regions)
+        -> (its recon_loss / ssim / psnr keys, its ms_ssim key or {}, its five region keys or {}), all carrying the suffix."""
+        s = self.suffix
+        mse_sum, ssim_sum, *ms_sum = sums
+        main = {"recon_loss" + s: mse_sum / seen, "ssim" + s: ssim_sum / seen, "psnr" + s: _psnr(mse_sum / seen)}
+        ms = {"ms_ssim" + s: ms_sum[0] / seen} if self.ms_ssim else {}
+        return main, ms, _region_keys(s, stats) if self.regions else {}
+
+
+def _allocate(dev, own: int, qs) -> torch.Tensor:
+    """The device sums of a pass in ONE zeroed f32 buffer: ``own`` slots of the pass itself, then the slots of every candidate
+    in qs, front to back; a candidate with regions gets its f64 statistics beside it.  -> the buffer"""
+    buf = ops.zeros_f32(own + sum(q.slots for q in qs), dev)
+    at = own
+    for q in qs:
+        q.acc, at = [buf[i:i + 1] for i in range(at, at + q.slots)], at + q.slots
+        q.stats = torch.zeros(4, dtype=torch.float64, device=dev) if q.regions else None
+    return buf
+
+
+def _read(buf, qs) -> list:
+    """The ONE host sync of a pass -> _allocate's buffer, then the region statistics of every candidate that has them (the
+    f32 slots are widened to sit next to them, which is exact)."""
+    stats = [q.stats for q in qs if q.regions]
+    return (torch.cat([buf.double()] + stats) if stats else buf).tolist()
+
+
+def _results(qs, host, own: int, seen: int) -> list:
+    """Cut _read's list as _allocate laid it out, front to back -> the ``result`` of every candidate."""
+    out, at, st = [], own, own + sum(q.slots for q in qs)
+    for q in qs:
+        out.append(q.result(host[at:at + q.slots], host[st:st + 4] if q.regions else None, seen))
+        at, st = at + q.slots, st + (4 if q.regions else 0)
+    return out
+
+
+def _add_optional(out: dict, base, further=()) -> dict:
+    """The keys behind the flags, in the passes' order: the ms_ssim key of every ``base`` candidate (the reconstruction, the
+    noisy input), then their region keys; a ``further`` candidate (refined, nlm) reports all it has, together."""
+    for kind in (1, 2):
+        for r in base:
+            out.update(r[kind])
+    for cand in further:
+        for part in cand:
+            out.update(part)
+    return out
+
+
 @torch.no_grad()
 def denoise_eval(encoder, decoder, img: torch.Tensor, sigma: float = 0.05, eps: Optional[torch.Tensor] = None,
                  eps_z: Optional[torch.Tensor] = None, alpha_kl: float = 0.1,
@@ -35,13 +149,11 @@ def denoise_eval(encoder, decoder, img: torch.Tensor, sigma: float = 0.05, eps: 
         raise RuntimeError("denoise_eval needs the batch on the MI355X ('cuda'); there is no CPU path")
     dt = encoder._dt
     B, C = img.shape[0], img.shape[1]
-    L = encoder.latent_dim
     img = img.contiguous()
-    if (eps is None and noisy is None) or eps_z is None:
-        ns = ops.default_noise(img.device)                   # HIP Philox draws keyed by torch's device seed
-        ns.advance()
-        eps = ns.randn(tuple(img.shape), 0) if eps is None and noisy is None else eps
-        eps_z = ns.randn((B, L), 1) if eps_z is None else eps_z
+    draw_eps = eps is None and noisy is None
+    if draw_eps or eps_z is None:
+        drawn = _default_draws(img.device, img.shape if draw_eps else None, (B, encoder.latent_dim) if eps_z is None else None)
+        eps, eps_z = drawn[0] if draw_eps else eps, drawn[1] if eps_z is None else eps_z
     if noisy is not None:
         if not noisy.is_cuda or noisy.shape != img.shape:
             raise RuntimeError("denoise_eval: noisy must be a device batch of img's shape")
@@ -49,20 +161,14 @@ def denoise_eval(encoder, decoder, img: torch.Tensor, sigma: float = 0.05, eps: 
         noisy_h = ops.nchw_to_nhwc(noisy, G.padc(C, dt), dt)
     else:
         noisy_h, noisy = ops.noisy_clamp_to_nhwc(img, eps, sigma, G.padc(C, dt), dt)
-    mulv, _ = encoder._engine.forward(noisy_h, B, encoder.training, keep=False)
-    mulv = mulv.view(B, -1)
-    z, lvc = ops.reparam_forward(mulv, eps_z, L, G.padc(decoder.nz, dt), dt)
-    pre, _ = decoder._engine.forward(z, B, decoder.training, keep=False)
-    recon = ops.nhwc_to_nchw(pre, decoder.nc, dt, apply_tanh=True)
+    recon, mulv, lvc = _reconstruct(encoder, decoder, noisy_h, B, eps_z, encoder.training, decoder.training)
     scal = ops.zeros_f32(4, img.device)
     ops.mse_forward_backward(recon, img, 1.0, scal[0:1], False)            # recon_loss (:165)
-    ops.kl_forward(mulv, lvc, L, 1.0, dt, out=scal[1:2])                   # KL sum, no /B (:166)
+    ops.kl_forward(mulv, lvc, encoder.latent_dim, 1.0, dt, out=scal[1:2])  # KL sum, no /B (:166)
     ssim_t = ops.ssim(recon, img)
     recon_loss, kl = (float(v) for v in scal[:2].tolist())
-    mse01 = recon_loss / 4.0                                                # ((a+1)/2 - (b+1)/2)^2 = (a-b)^2 / 4
-    psnr = float("inf") if mse01 == 0 else 10.0 * math.log10(1.0 / mse01)
     out = {"noisy": noisy, "recon": recon, "recon_loss": recon_loss, "kl_loss": kl,
-           "val_loss": recon_loss + alpha_kl * kl, "psnr": psnr}
+           "val_loss": recon_loss + alpha_kl * kl, "psnr": _psnr(recon_loss)}
     if ms_ssim:
         out["ssim"], out["ms_ssim"] = torch.cat([ssim_t, ops.ms_ssim(recon, img)]).tolist()
     else:
@@ -108,7 +214,8 @@ def validation_epoch(encoder, decoder, loader: Iterable[torch.Tensor], n_samples
         raise RuntimeError("validation_epoch: kid_subsets needs a feature_fn (KID is a feature-space metric)")
     encoder.eval(), decoder.eval()                                                   # :147-148
     dev = next(encoder.parameters()).device
-    acc = ops.zeros_f32(5 if ms_ssim else 4, dev)  # [sum(recon + a*kl), sum(b * ssim_b), sum(b * mse_b), sum(kl)(, sum(b * ms_ssim_b))]
+    qs = [_Quality("", ms_ssim)]                                                     # :170-174 (ssim.update), MSE for the PSNR
+    sums = _allocate(dev, 2, qs)                                                     # [sum(recon + a*kl), sum(kl)], the candidate's
     seen = batches = 0
     dt, L = encoder._dt, encoder.latent_dim
     feats = FeaturePass(feature_fn, kid_subsets is not None) if feature_fn is not None else None
@@ -117,29 +224,16 @@ def validation_epoch(encoder, decoder, loader: Iterable[torch.Tensor], n_samples
             raise RuntimeError("validation_epoch needs device batches (data.DeviceLoader); there is no CPU path")
         img = img.contiguous()
         b, C = img.shape[0], img.shape[1]
-        if noise_fn is not None:
-            eps, eps_z = noise_fn(i, img)
-        else:
-            ns = ops.default_noise(dev)
-            ns.advance()
-            eps, eps_z = ns.randn(tuple(img.shape), 0), ns.randn((b, L), 1)
+        eps, eps_z = noise_fn(i, img) if noise_fn is not None else _default_draws(dev, img.shape, (b, L))
         noisy_h, _ = ops.noisy_clamp_to_nhwc(img, eps, sigma, G.padc(C, dt), dt)     # :153-154
-        mulv, _ = encoder._engine.forward(noisy_h, b, False, keep=False)
-        mulv = mulv.view(b, -1)
-        z, lvc = ops.reparam_forward(mulv, eps_z, L, G.padc(decoder.nz, dt), dt)     # :160-162
-        pre, _ = decoder._engine.forward(z, b, False, keep=False)
-        recon = ops.nhwc_to_nchw(pre, decoder.nc, dt, apply_tanh=True)               # :163
+        recon, mulv, lvc = _reconstruct(encoder, decoder, noisy_h, b, eps_z)         # :160-163
         scal = torch.empty(2, dtype=torch.float32, device=dev)
         ops.mse_forward_backward(recon, img, 1.0, scal[0:1], False)                  # :165
         ops.kl_forward(mulv, lvc, L, 1.0, dt, out=scal[1:2])                         # :166 (sum, not / B)
-        ssim_b = ops.ssim(recon, img)                                                # :170-174 (mean over the batch)
-        ops.axpy(acc[0:1], scal[0:1], 1.0, out=acc[0:1])
-        ops.axpy(acc[0:1], scal[1:2], alpha_kl, out=acc[0:1])                        # :167
-        ops.axpy(acc[1:2], ssim_b, float(b), out=acc[1:2])
-        ops.axpy(acc[2:3], scal[0:1], float(b), out=acc[2:3])
-        ops.axpy(acc[3:4], scal[1:2], 1.0, out=acc[3:4])
-        if ms_ssim:
-            ops.axpy(acc[4:5], ops.ms_ssim(recon, img), float(b), out=acc[4:5])
+        ops.axpy(sums[0:1], scal[0:1], 1.0, out=sums[0:1])
+        ops.axpy(sums[0:1], scal[1:2], alpha_kl, out=sums[0:1])                      # :167
+        ops.axpy(sums[1:2], scal[1:2], 1.0, out=sums[1:2])
+        qs[0].update(recon, img, b, mse=scal[0:1])
         if feats is not None:
             feats.update(img, recon)
         seen += b
@@ -147,14 +241,7 @@ def validation_epoch(encoder, decoder, loader: Iterable[torch.Tensor], n_samples
     if batches == 0:
         raise RuntimeError("validation_epoch: the loader yielded no batch")
     kid = feats.kid(int(kid_subsets), int(kid_subset_size), int(kid_seed)) if kid_subsets is not None else None
-    val_sum, ssim_sum, mse_sum, kl_sum, *ms_sum = (float(v) for v in acc.tolist())  # the one host sync
-    n = seen if n_samples is None else int(n_samples)
-    mse01 = mse_sum / seen / 4.0
-    out = {"val_loss": val_sum / n, "ssim": ssim_sum / seen,
-           "psnr": float("inf") if mse01 == 0 else 10.0 * math.log10(1.0 / mse01),
-           "recon_loss": mse_sum / seen, "kl_loss": kl_sum / batches, "samples": seen, "batches": batches}
-    if ms_ssim:
-        out["ms_ssim"] = ms_sum[0] / seen
+    out = _validation_result(qs, _read(sums, qs), seen, batches, seen if n_samples is None else int(n_samples))
     if feats is not None:
         out["fid"] = feats.fid()
     if kid is not None:
@@ -224,25 +311,18 @@ def paired_test_epoch(encoder, decoder, loader: Iterable, n_samples: Optional[in
     encoder.eval(), decoder.eval()                                                   # :251-252
     dev = next(encoder.parameters()).device
     dt, L = encoder._dt, encoder.latent_dim
-    # [sum(mse_sum + kl), sum(b * ssim(recon)), sum(b * mse_mean(recon)), sum(kl), sum(b * ssim(noisy)), sum(b * mse_mean(noisy))]
-    acc = ops.zeros_f32(6, dev)
-    acc_ms = ops.zeros_f32(2, dev) if ms_ssim else None                              # [sum(b * ms_ssim(recon)), sum(b * ms_ssim(noisy))]
-    seen = batches = numel = 0
+    recon_q, noisy_q = _Quality("", ms_ssim, regions), _Quality("_noisy", ms_ssim, regions)
+    refined_q = _Quality("_refined", False, regions) if refiner is not None else None
+    nlm_q = _Quality("_nlm", ms_ssim, regions) if nlm is not None else None
+    qs = [q for q in (recon_q, noisy_q, refined_q, nlm_q) if q is not None]
+    sums = _allocate(dev, 2, qs)                                                     # [sum(mse_sum + kl), sum(kl)], the candidates'
+    seen = batches = 0
     offers = hasattr(loader, "want_nhwc") and getattr(loader, "degrade", None) is not None and loader.degrade.pairs
     if offers:
         loader.want_nhwc(G.padc(loader.dataset.image_shape[0], dt), dt)
-    stats = None
     if need_rects:
         rects_were_on = bool(getattr(loader, "_rects", False))
         loader.want_rects(True)
-    if regions:
-        stats = torch.zeros(2, 4, dtype=torch.float64, device=dev)                   # {S_hole, S_valid, n_hole, n_valid} of recon, noisy
-    if refiner is not None:
-        acc_ref = ops.zeros_f32(2, dev)                                              # [sum(b * ssim(refined)), sum(b * mse_mean(refined))]
-        stats_ref = torch.zeros(4, dtype=torch.float64, device=dev) if regions else None
-    if nlm is not None:
-        acc_nlm = ops.zeros_f32(3 if ms_ssim else 2, dev)                            # [sum(b * ssim(nlm)), sum(b * mse_mean(nlm))(, sum(b * ms_ssim(nlm)))]
-        stats_nlm = torch.zeros(4, dtype=torch.float64, device=dev) if regions else None
     try:
         for i, (noisy, clean) in enumerate(loader):
             if not (noisy.is_cuda and clean.is_cuda):
@@ -250,52 +330,23 @@ def paired_test_epoch(encoder, decoder, loader: Iterable, n_samples: Optional[in
             noisy, clean = noisy.contiguous(), clean.contiguous()
             b, C = clean.shape[0], clean.shape[1]
             noisy_h = loader.last_nhwc if offers else ops.nchw_to_nhwc(noisy, G.padc(C, dt), dt)
+            rects = loader.last_rects if need_rects else None
             eps_z = noise_fn(i, noisy) if noise_fn is not None else None
             if eps_z is None:
-                ns = ops.default_noise(dev)
-                ns.advance()
-                eps_z = ns.randn((b, L), 1)
-            mulv, _ = encoder._engine.forward(noisy_h, b, False, keep=False)         # :258
-            mulv = mulv.view(b, -1)
-            z, lvc = ops.reparam_forward(mulv, eps_z, L, G.padc(decoder.nz, dt), dt)  # :259
-            pre, _ = decoder._engine.forward(z, b, False, keep=False)
-            recon = ops.nhwc_to_nchw(pre, decoder.nc, dt, apply_tanh=True)           # :260
-            scal = torch.empty(3, dtype=torch.float32, device=dev)
+                eps_z = _default_draws(dev, None, (b, L))[1]
+            recon, mulv, lvc = _reconstruct(encoder, decoder, noisy_h, b, eps_z)     # :258-260
+            scal = torch.empty(2, dtype=torch.float32, device=dev)
             ops.mse_forward_backward(recon, clean, 1.0, scal[0:1], False)            # mean; * numel = :262's sum
             ops.kl_forward(mulv, lvc, L, 1.0, dt, out=scal[1:2])                     # :263
-            ops.mse_forward_backward(noisy, clean, 1.0, scal[2:3], False)
-            ssim_r, ssim_n = ops.ssim(recon, clean), ops.ssim(noisy, clean)
-            if regions:
-                ops.region_mse_forward_backward(recon, clean, loader.last_rects, 1.0, 1.0, stats=stats[0])
-                ops.region_mse_forward_backward(noisy, clean, loader.last_rects, 1.0, 1.0, stats=stats[1])
-            ops.axpy(acc[0:1], scal[0:1], float(clean.numel()), out=acc[0:1])
-            ops.axpy(acc[0:1], scal[1:2], 1.0, out=acc[0:1])                         # :264
-            ops.axpy(acc[1:2], ssim_r, float(b), out=acc[1:2])
-            ops.axpy(acc[2:3], scal[0:1], float(b), out=acc[2:3])
-            ops.axpy(acc[3:4], scal[1:2], 1.0, out=acc[3:4])
-            ops.axpy(acc[4:5], ssim_n, float(b), out=acc[4:5])
-            ops.axpy(acc[5:6], scal[2:3], float(b), out=acc[5:6])
-            if ms_ssim:
-                ops.axpy(acc_ms[0:1], ops.ms_ssim(recon, clean), float(b), out=acc_ms[0:1])
-                ops.axpy(acc_ms[1:2], ops.ms_ssim(noisy, clean), float(b), out=acc_ms[1:2])
+            ops.axpy(sums[0:1], scal[0:1], float(clean.numel()), out=sums[0:1])
+            ops.axpy(sums[0:1], scal[1:2], 1.0, out=sums[0:1])                       # :264
+            ops.axpy(sums[1:2], scal[1:2], 1.0, out=sums[1:2])
+            recon_q.update(recon, clean, b, rects, mse=scal[0:1])
+            noisy_q.update(noisy, clean, b, rects)
             if refiner is not None:
-                refined = refiner.refine(noisy, rects=loader.last_rects)["recon"]
-                mse_ref = torch.empty(1, dtype=torch.float32, device=dev)
-                ops.mse_forward_backward(refined, clean, 1.0, mse_ref, False)
-                ops.axpy(acc_ref[0:1], ops.ssim(refined, clean), float(b), out=acc_ref[0:1])
-                ops.axpy(acc_ref[1:2], mse_ref, float(b), out=acc_ref[1:2])
-                if regions:
-                    ops.region_mse_forward_backward(refined, clean, loader.last_rects, 1.0, 1.0, stats=stats_ref)
+                refined_q.update(refiner.refine(noisy, rects=rects)["recon"], clean, b, rects)
             if nlm is not None:
-                filtered = nlm(noisy, rects=loader.last_rects if nlm.needs_rects else None)
-                mse_nlm = torch.empty(1, dtype=torch.float32, device=dev)
-                ops.mse_forward_backward(filtered, clean, 1.0, mse_nlm, False)
-                ops.axpy(acc_nlm[0:1], ops.ssim(filtered, clean), float(b), out=acc_nlm[0:1])
-                ops.axpy(acc_nlm[1:2], mse_nlm, float(b), out=acc_nlm[1:2])
-                if ms_ssim:
-                    ops.axpy(acc_nlm[2:3], ops.ms_ssim(filtered, clean), float(b), out=acc_nlm[2:3])
-                if regions:
-                    ops.region_mse_forward_backward(filtered, clean, loader.last_rects, 1.0, 1.0, stats=stats_nlm)
+                nlm_q.update(nlm(noisy, rects=rects if nlm.needs_rects else None), clean, b, rects)
             seen += b
             batches += 1
     finally:
@@ -305,63 +356,25 @@ def paired_test_epoch(encoder, decoder, loader: Iterable, n_samples: Optional[in
             loader.want_rects(rects_were_on)
     if batches == 0:
         raise RuntimeError("paired_test_epoch: the loader yielded no batch")
-    parts = [acc.double(), stats.flatten()] if regions else [acc]
-    if ms_ssim:
-        parts = [p.double() for p in parts] + [acc_ms.double()]                      # (f32 -> f64 is exact)
-    if refiner is not None:
-        parts = [p.double() for p in parts] + [acc_ref.double()] + ([stats_ref] if regions else [])
-    if nlm is not None:
-        parts = [p.double() for p in parts] + [acc_nlm.double()] + ([stats_nlm] if regions else [])
-    host = (torch.cat(parts) if len(parts) > 1 else acc).tolist()                    # the one host sync
-    if nlm is not None:                                                              # the baseline's tail comes off first
-        nnlm = (3 if ms_ssim else 2) + (4 if regions else 0)
-        host, host_nlm = host[:-nnlm], host[-nnlm:]
-    if refiner is not None:                                                          # the refined tail, then today's layout
-        nref = 6 if regions else 2
-        host, host_ref = host[:-nref], host[-nref:]
-    tot, ssim_sum, mse_sum, kl_sum, ssim_n_sum, mse_n_sum = (float(v) for v in host[:6])
-    n = seen if n_samples is None else int(n_samples)
+    return _paired_result(qs, _read(sums, qs), seen, batches, seen if n_samples is None else int(n_samples))
 
-    def psnr(mse):
-        mse01 = mse / 4.0                                                  # ((a+1)/2 - (b+1)/2)^2 = (a-b)^2 / 4
-        return float("inf") if mse01 == 0 else 10.0 * math.log10(1.0 / mse01)
-    out = {"test_loss": tot / n, "recon_loss": mse_sum / seen, "kl_loss": kl_sum / seen, "ssim": ssim_sum / seen,
-           "psnr": psnr(mse_sum / seen), "ssim_noisy": ssim_n_sum / seen, "psnr_noisy": psnr(mse_n_sum / seen),
+
+def _validation_result(qs, host, seen: int, batches: int, n: int) -> Dict[str, float]:
+    """Host only.  host: validation_epoch's read, [sum(recon + a*kl), sum(kl)] then the reconstruction's slots."""
+    (r,) = _results(qs, host, 2, seen)
+    out = {"val_loss": host[0] / n, "ssim": r[0]["ssim"], "psnr": r[0]["psnr"], "recon_loss": r[0]["recon_loss"],
+           "kl_loss": host[1] / batches, "samples": seen, "batches": batches}
+    return _add_optional(out, (r,))
+
+
+def _paired_result(qs, host, seen: int, batches: int, n: int) -> Dict[str, float]:
+    """Host only.  host: paired_test_epoch's read, [sum(mse_sum + kl), sum(kl)] then the sums of every candidate in qs: the
+    reconstruction, the noisy input and whichever further candidates (refined, nlm) the pass had."""
+    r, noisy, *further = _results(qs, host, 2, seen)
+    out = {"test_loss": host[0] / n, "recon_loss": r[0]["recon_loss"], "kl_loss": host[1] / seen, "ssim": r[0]["ssim"],
+           "psnr": r[0]["psnr"], "ssim_noisy": noisy[0]["ssim_noisy"], "psnr_noisy": noisy[0]["psnr_noisy"],
            "samples": seen, "batches": batches}
-    if ms_ssim:
-        out["ms_ssim"], out["ms_ssim_noisy"] = host[-2] / seen, host[-1] / seen
-    if regions:
-        for suffix, (s_hole, s_valid, n_hole, n_valid) in (("", host[6:10]), ("_noisy", host[10:14])):
-            m_hole = s_hole / n_hole if n_hole > 0 else 0.0
-            m_valid = s_valid / n_valid if n_valid > 0 else 0.0
-            out.update({"mse_hole" + suffix: m_hole, "mse_valid" + suffix: m_valid,
-                        "psnr_hole" + suffix: psnr(m_hole), "psnr_valid" + suffix: psnr(m_valid),
-                        "hole_fraction" + suffix: n_hole / (n_hole + n_valid)})
-    if refiner is not None:
-        out.update({"recon_loss_refined": host_ref[1] / seen, "ssim_refined": host_ref[0] / seen,
-                    "psnr_refined": psnr(host_ref[1] / seen)})
-        if regions:
-            s_hole, s_valid, n_hole, n_valid = host_ref[2:6]
-            m_hole = s_hole / n_hole if n_hole > 0 else 0.0
-            m_valid = s_valid / n_valid if n_valid > 0 else 0.0
-            out.update({"mse_hole_refined": m_hole, "mse_valid_refined": m_valid, "psnr_hole_refined": psnr(m_hole),
-                        "psnr_valid_refined": psnr(m_valid), "hole_fraction_refined": n_hole / (n_hole + n_valid)})
-    if nlm is not None:
-        out.update({"recon_loss_nlm": host_nlm[1] / seen, "ssim_nlm": host_nlm[0] / seen, "psnr_nlm": psnr(host_nlm[1] / seen)})
-        if ms_ssim:
-            out["ms_ssim_nlm"] = host_nlm[2] / seen
-        if regions:
-            s_hole, s_valid, n_hole, n_valid = host_nlm[-4:]
-            m_hole = s_hole / n_hole if n_hole > 0 else 0.0
-            m_valid = s_valid / n_valid if n_valid > 0 else 0.0
-            out.update({"mse_hole_nlm": m_hole, "mse_valid_nlm": m_valid, "psnr_hole_nlm": psnr(m_hole),
-                        "psnr_valid_nlm": psnr(m_valid), "hole_fraction_nlm": n_hole / (n_hole + n_valid)})
-    return out
-
-
-def _psnr(mse: float) -> float:
-    mse01 = mse / 4.0                                                      # ((a+1)/2 - (b+1)/2)^2 = (a-b)^2 / 4
-    return float("inf") if mse01 == 0 else 10.0 * math.log10(1.0 / mse01)
+    return _add_optional(out, (r, noisy), further)
 
 
 def _finite_nonneg(name: str, v) -> float:
@@ -490,13 +503,6 @@ class LatentRefiner:
                         z_out=buf["z_eng"], objective=buf["objective"], lr=self.lr, betas=self.betas, eps=self.eps,
                         alpha_adv=self.alpha_adv, prior_weight=self.prior_weight)
 
-    def _decode(self, z_eng, B: int) -> torch.Tensor:
-        Gn, dt = self.G, self.dt
-        if Gn.fused_tail(B):
-            return Gn._engine.forward(z_eng, B, False, keep=False, tail={})[0]
-        pre, _ = Gn._engine.forward(z_eng, B, False, keep=False)
-        return ops.nhwc_to_nchw(pre, Gn.nc, dt, apply_tanh=True)
-
     def _engines(self):
         return [n._engine for n in (self.G, self.D) if n is not None]
 
@@ -553,9 +559,7 @@ class LatentRefiner:
             if init == "mu":
                 eps_z = ops.zeros_f32(B * L, dev).view(B, L)
             elif eps_z is None:
-                ns = ops.default_noise(dev)             # HIP Philox draws keyed by torch's device seed
-                ns.advance()
-                eps_z = ns.randn((B, L), 1)
+                eps_z = _default_draws(dev, None, (B, L))[1]
             z0_eng, _ = ops.reparam_forward(mulv.view(B, -1), eps_z.contiguous(), L, ZP, dt)
         else:
             z0_eng = ops.prior_forward(init.contiguous(), B, L, ZP, dt)
@@ -575,7 +579,7 @@ class LatentRefiner:
                 self.captures += 1
         start()
         z0 = st["z"].clone()
-        recon0 = self._decode(buf["z_eng"], B)
+        recon0 = Gn.decode_eval(buf["z_eng"], B)
         for k in range(self.steps):                     # no host value inside: `steps` launches sequences / replays in a row
             if cap is not None:
                 replay(cap)
@@ -591,7 +595,7 @@ class LatentRefiner:
             buf["objective0"].copy_(buf["objective"])
         z = (st["best_z"] if self.keep_best else st["z"]).clone()
         objective = (st["best_loss"] if self.keep_best else buf["objective"]).clone()
-        recon = self._decode(ops.prior_forward(z, B, L, ZP, dt), B)
+        recon = Gn.decode_eval(ops.prior_forward(z, B, L, ZP, dt), B)
         return {"recon": recon, "z": z, "z0": z0, "recon0": recon0, "objective0": buf["objective0"].clone(),
                 "objective": objective, "steps": self.steps}
 
@@ -636,21 +640,15 @@ def denoise_tiled(encoder, decoder, images, *, stride: Optional[int] = None, win
             raise RuntimeError(f"denoise_tiled: eps_z must be a device f32 [{T}, {L}] tensor (one row per tile)")
         eps_z = eps_z.contiguous()
     elif sample:
-        ns = ops.default_noise(dev)                      # HIP Philox draws keyed by torch's device seed
-        ns.advance()
-        eps_z = ns.randn((T, L), 1)
+        eps_z = _default_draws(dev, None, (T, L))[1]
     else:
         eps_z = ops.zeros_f32(T * L, dev).view(T, L)     # z = mu
     encoder.eval(), decoder.eval()
-    CP, ZP = G.padc(C, dt), G.padc(decoder.nz, dt)
     tiles = torch.empty(T, C, S, S, dtype=torch.float32, device=dev)
     for t0 in range(0, T, int(batch)):
         b = min(int(batch), T - t0)
-        x = ops.tile_gather(src, plan, t0, b, CP, dt)
-        mulv, _ = encoder._engine.forward(x, b, False, keep=False)
-        z, _ = ops.reparam_forward(mulv.view(b, -1), eps_z[t0:t0 + b], L, ZP, dt)
-        pre, _ = decoder._engine.forward(z, b, False, keep=False)
-        ops.nhwc_to_nchw(pre, C, dt, apply_tanh=True, out=tiles[t0:t0 + b])
+        x = ops.tile_gather(src, plan, t0, b, G.padc(C, dt), dt)
+        _reconstruct(encoder, decoder, x, b, eps_z[t0:t0 + b], out=tiles[t0:t0 + b])
     return ops.tile_blend(tiles, plan)
 
 
@@ -682,25 +680,22 @@ def tiled_denoise_eval(encoder, decoder, img: torch.Tensor, sigma: float = 0.05,
         noisy = noisy.contiguous()
     else:
         if eps is None:
-            ns = ops.default_noise(img.device)
-            ns.advance()
-            eps = ns.randn(tuple(img.shape), 0)
+            eps = _default_draws(img.device, img.shape, None)[0]
         _, noisy = ops.noisy_clamp_to_nhwc(img, eps, sigma, G.padc(img.shape[1], dt), dt)
     recon = denoise_tiled(encoder, decoder, noisy, **tiling_kw)
-    scal = ops.zeros_f32(6 if ms_ssim else 4, img.device)    # [mse(recon), mse(noisy), ssim(recon), ssim(noisy)(, ms_ssim(recon), ms_ssim(noisy))]
-    ops.mse_forward_backward(recon, img, 1.0, scal[0:1], False)
-    ops.mse_forward_backward(noisy, img, 1.0, scal[1:2], False)
-    ops.axpy(scal[2:3], ops.ssim(recon, img), 1.0, out=scal[2:3])
-    ops.axpy(scal[3:4], ops.ssim(noisy, img), 1.0, out=scal[3:4])
-    if ms_ssim:
-        ops.axpy(scal[4:5], ops.ms_ssim(recon, img), 1.0, out=scal[4:5])
-        ops.axpy(scal[5:6], ops.ms_ssim(noisy, img), 1.0, out=scal[5:6])
-    mse_r, mse_n, ssim_r, ssim_n, *ms = (float(v) for v in scal.tolist())  # the one host sync
-    out = {"noisy": noisy, "recon": recon, "recon_loss": mse_r, "psnr": _psnr(mse_r), "ssim": ssim_r,
-           "noisy_loss": mse_n, "psnr_noisy": _psnr(mse_n), "ssim_noisy": ssim_n, "tiles": _tile_count(encoder, img, tiling_kw)}
-    if ms_ssim:
-        out["ms_ssim"], out["ms_ssim_noisy"] = ms
-    return out
+    qs = [_Quality("", ms_ssim), _Quality("_noisy", ms_ssim)]
+    sums = _allocate(img.device, 0, qs)
+    for q, x in zip(qs, (recon, noisy)):
+        q.update(x, img, 1, store=True)                  # the one batch of this pass, weight 1
+    return {"noisy": noisy, "recon": recon, **_tiled_eval_result(qs, _read(sums, qs), _tile_count(encoder, img, tiling_kw))}
+
+
+def _tiled_eval_result(qs, host, tiles: int) -> Dict[str, float]:
+    """Host only.  host: tiled_denoise_eval's read, the slots of the reconstruction and of the noisy input (one batch: seen = 1)."""
+    r, noisy = _results(qs, host, 0, 1)
+    out = {"recon_loss": r[0]["recon_loss"], "psnr": r[0]["psnr"], "ssim": r[0]["ssim"], "noisy_loss": noisy[0]["recon_loss_noisy"],
+           "psnr_noisy": noisy[0]["psnr_noisy"], "ssim_noisy": noisy[0]["ssim_noisy"], "tiles": tiles}
+    return _add_optional(out, (r, noisy))
 
 
 @torch.no_grad()
@@ -716,52 +711,30 @@ def tiled_test_epoch(encoder, decoder, pairs: Iterable, ms_ssim: bool = False, b
     number -- "oracle" is refused.  The filter runs on the full H x W image, no tiling, and the result gains ``recon_loss_nlm``,
     ``ssim_nlm``, ``psnr_nlm`` (and ``ms_ssim_nlm`` with ms_ssim=True), read in the same sync."""
     nlm = make_baseline("tiled_test_epoch", baseline, allow_oracle=False)
-    acc_nlm = None
-    acc = None                                           # sum over batches of b * [mse(recon), ssim(recon), mse(noisy), ssim(noisy)]
-    seen = tiles = 0
+    qs = [_Quality("", ms_ssim), _Quality("_noisy", ms_ssim)] + ([_Quality("_nlm", ms_ssim)] if nlm is not None else [])
+    sums, seen, tiles = None, 0, 0
     for noisy, clean in pairs:
         if not (noisy.is_cuda and clean.is_cuda):
             raise RuntimeError("tiled_test_epoch needs device pairs; there is no CPU path")
-        dev = clean.device
-        acc = ops.zeros_f32(6 if ms_ssim else 4, dev) if acc is None else acc
+        sums = _allocate(clean.device, 0, qs) if sums is None else sums
         if noisy.shape != clean.shape or clean.dim() != 4:
             raise RuntimeError("tiled_test_epoch: noisy and clean must be [b,C,H,W] batches of one shape")
         noisy, clean = noisy.contiguous(), clean.contiguous()
         b = clean.shape[0]
-        recon = denoise_tiled(encoder, decoder, noisy, **tiling_kw)
-        scal = torch.empty(2, dtype=torch.float32, device=dev)
-        ops.mse_forward_backward(recon, clean, 1.0, scal[0:1], False)
-        ops.mse_forward_backward(noisy, clean, 1.0, scal[1:2], False)
-        ops.axpy(acc[0:1], scal[0:1], float(b), out=acc[0:1])
-        ops.axpy(acc[1:2], ops.ssim(recon, clean), float(b), out=acc[1:2])
-        ops.axpy(acc[2:3], scal[1:2], float(b), out=acc[2:3])
-        ops.axpy(acc[3:4], ops.ssim(noisy, clean), float(b), out=acc[3:4])
-        if ms_ssim:
-            ops.axpy(acc[4:5], ops.ms_ssim(recon, clean), float(b), out=acc[4:5])
-            ops.axpy(acc[5:6], ops.ms_ssim(noisy, clean), float(b), out=acc[5:6])
-        if nlm is not None:
-            acc_nlm = ops.zeros_f32(3 if ms_ssim else 2, dev) if acc_nlm is None else acc_nlm   # b * [mse, ssim(, ms_ssim)] of the baseline
-            filtered = nlm(noisy)
-            mse_nlm = torch.empty(1, dtype=torch.float32, device=dev)
-            ops.mse_forward_backward(filtered, clean, 1.0, mse_nlm, False)
-            ops.axpy(acc_nlm[0:1], mse_nlm, float(b), out=acc_nlm[0:1])
-            ops.axpy(acc_nlm[1:2], ops.ssim(filtered, clean), float(b), out=acc_nlm[1:2])
-            if ms_ssim:
-                ops.axpy(acc_nlm[2:3], ops.ms_ssim(filtered, clean), float(b), out=acc_nlm[2:3])
+        candidates = [denoise_tiled(encoder, decoder, noisy, **tiling_kw), noisy] + ([nlm(noisy)] if nlm is not None else [])
+        for q, x in zip(qs, candidates):
+            q.update(x, clean, b)
         seen += b
         tiles += _tile_count(encoder, clean, tiling_kw)
     if seen == 0:
         raise RuntimeError("tiled_test_epoch: pairs yielded no batch")
-    host = (acc if nlm is None else torch.cat([acc, acc_nlm])).tolist()            # the one host sync
-    if nlm is not None:
-        host, host_nlm = host[:acc.numel()], [float(v) / seen for v in host[acc.numel():]]
-    mse_r, ssim_r, mse_n, ssim_n, *ms = (float(v) / seen for v in host)
-    out = {"psnr": _psnr(mse_r), "ssim": ssim_r, "recon_loss": mse_r, "psnr_noisy": _psnr(mse_n), "ssim_noisy": ssim_n,
-           "samples": seen, "tiles": tiles}
-    if ms_ssim:
-        out["ms_ssim"], out["ms_ssim_noisy"] = ms
-    if nlm is not None:
-        out.update({"recon_loss_nlm": host_nlm[0], "ssim_nlm": host_nlm[1], "psnr_nlm": _psnr(host_nlm[0])})
-        if ms_ssim:
-            out["ms_ssim_nlm"] = host_nlm[2]
-    return out
+    return _tiled_test_result(qs, _read(sums, qs), seen, tiles)
+
+
+def _tiled_test_result(qs, host, seen: int, tiles: int) -> Dict[str, float]:
+    """Host only.  host: tiled_test_epoch's read, the slots of the reconstruction, the noisy input and, if the pass had one,
+    the baseline."""
+    r, noisy, *further = _results(qs, host, 0, seen)
+    out = {"psnr": r[0]["psnr"], "ssim": r[0]["ssim"], "recon_loss": r[0]["recon_loss"], "psnr_noisy": noisy[0]["psnr_noisy"],
+           "ssim_noisy": noisy[0]["ssim_noisy"], "samples": seen, "tiles": tiles}
+    return _add_optional(out, (r, noisy), further)

@@ -420,15 +420,6 @@ def _device_of(decoder, what: str):
     return dev
 
 
-def _decode(decoder, z_nhwc: torch.Tensor, b: int) -> torch.Tensor:
-    """Generator forward from its engine input -> tanh image NCHW f32; the launches of Generator.forward."""
-    if decoder.fused_tail(b):
-        img, _ = decoder.engine_forward(z_nhwc, b, keep=False, tail={})
-        return img
-    pre, _ = decoder.engine_forward(z_nhwc, b, keep=False)
-    return ops.nhwc_to_nchw(pre, decoder.nc, decoder._dt, apply_tanh=True)
-
-
 def _normal_z(decoder, b: int, eps: Optional[torch.Tensor]) -> torch.Tensor:
     """z ~ N(0, I) [b, nz] (main_vae.py:552-553, :364-365) in the decoder's input layout."""
     dt = decoder._dt
@@ -532,7 +523,7 @@ def _evaluate_generation(decoder, val_loader, prior, noise_fn, feature_fn, k, re
             z = prior.sample_z(b, decoder, u, v, eps)
         else:
             z = _normal_z(decoder, b, inj)
-        fake = _decode(decoder, z, b)
+        fake = decoder.decode_eval(z, b)
         ops.axpy(acc, ops.ssim(fake, real), float(b), out=acc)
         if feats is not None:
             feats.update(real, fake)
@@ -588,4 +579,4 @@ def sample_images(decoder, z: Optional[torch.Tensor] = None, n: int = 64,
         zh = prior.sample_z(n, decoder)
     else:
         zh = _normal_z(decoder, n, None)
-    return ops.to_u8(_decode(decoder, zh, n), grid_cols)
+    return ops.to_u8(decoder.decode_eval(zh, n), grid_cols)

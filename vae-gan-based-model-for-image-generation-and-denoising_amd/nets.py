@@ -343,6 +343,15 @@ class Generator(_EngineNet):
         image (+ the noisy NHWC copy for the Discriminator) itself."""
         return self._engine.tn(len(self._engine.stages) - 1, B, "fprop") is not None
 
+    def decode_eval(self, z_nhwc, B):
+        """z_nhwc: [B,1,1,ZP] engine dtype -> tanh image NCHW f32 in EVAL mode (BatchNorm on the running statistics, whatever
+        self.training says), nothing kept for a backward; the launches of forward.  What the generation passes (latent.py)
+        and the latent refiner (denoise.py) decode with."""
+        if self.fused_tail(B):
+            return self._engine.forward(z_nhwc, B, False, keep=False, tail={})[0]
+        pre, _ = self._engine.forward(z_nhwc, B, False, keep=False)
+        return ops.nhwc_to_nchw(pre, self.nc, self._dt, apply_tanh=True)
+
     def _forward_impl(self, z, keep):
         if z.dim() != 4 or z.shape[1] != self.nz or z.shape[2] != 1 or z.shape[3] != 1:
             raise RuntimeError(f"Generator expects z of shape [B,{self.nz},1,1], got {tuple(z.shape)}")
