@@ -85,7 +85,10 @@ extern "C" {
                                  (added within 31, nothing changed) test-time latent refinement: vg_bn_act_backward_eval,
                                  vg_masked_mse_rows (+ _ws_doubles), vg_latent_adam / VG_LATENT_*;
                                  (added within 31, no version move, nothing changed) classical-denoiser baseline:
-                                 vg_nlm_denoise, vg_noise_sigma */
+                                 vg_nlm_denoise, vg_noise_sigma;
+                                 (added within 31, no version move, nothing changed) noise models of the degraded pairs and
+                                 the median baseline: vg_gather_degrade_u8_ex, vg_degrade_params_ex / VG_NOISE_*,
+                                 VG_DRAW_DEGRADE_IMPULSE / _SALT, vg_median_filter */
 int vg_abi_version(void);
 /* The library reads its optional kernel-selection switches (VG_* environment variables, DESIGN.md "Runtime switches")
  * ONCE, when it is loaded; nothing on a launch path calls getenv.  A process that changes one of them afterwards
@@ -800,10 +803,46 @@ int vg_reparam_kl_backward_rng(const void* mulv, const float* lv_clamped, const 
  * vg_degrade_params: out f32 [B][8] = {s, sigma = s * noise_max_std, rect_h, rect_w, x, y, 0, 0} of positions
  * pos0 .. pos0 + B - 1 (rect == 0: the four geometry entries are 0); for inspection, plots and tests.
  * idx outside [0, N) is clamped to 0 (the host validates).  VG_EINVAL for empty ranges or a rectangle outside the image.
+ *
+ * Noise models (not in the reference; added within ABI 31).  vg_gather_degrade_u8_ex and vg_degrade_params_ex take the same
+ * arguments plus `int kind, float impulse_max_p, float salt_ratio`; the two entry points above are the model
+ * (VG_NOISE_GAUSSIAN, impulse_max_p = 0) and the _ex entries called with it write the same bits.  Per element, all f32, every
+ * product, sum, quotient and root rounded on its own (no fused multiply-add):
+ *   base = the clean value, or the rectangle fill 2*f - 1                                                  (as above)
+ *   lo   = normalize ? -1 : 0,   span = normalize ? 2 : 1                      (black and the width of the value mapping)
+ *   g    = max((base - lo) / span, 0)          (the intensity in [0, 1]; the max matters: with normalize == 0 a rectangle
+ *                                               fill can be negative)
+ *   f    = 1        VG_NOISE_GAUSSIAN (0)  additive noise, the reference's model
+ *        = g        VG_NOISE_SPECKLE  (1)  multiplicative speckle: standard deviation proportional to the intensity
+ *        = sqrt(g)  VG_NOISE_SHOT     (2)  signal-dependent shot noise: variance proportional to the intensity (the normal
+ *                                          approximation of Poisson counts; the root is the correctly rounded one)
+ *   t    = min(max(base + ((n * s) * noise_max_std) * f, -1), 1)
+ * with the same n, s and noise_max_std as above: s * noise_max_std is the standard deviation AT WHITE (g = 1) for all three
+ * kinds, and f = 1 is the expression above bit for bit.
+ * Impulses (salt and pepper) on top, only when impulse_max_p > 0: p_b = s * impulse_max_p is the image's hit probability;
+ *   element e is hit when u01(word(VG_DRAW_DEGRADE_IMPULSE, e)) < p_b, and a hit element becomes
+ *   1 (salt) when u01(word(VG_DRAW_DEGRADE_SALT, e)) < salt_ratio, else lo (pepper), whatever t was.
+ * The salt word is evaluated only where an element is hit (as the fill word only where the rectangle is touched); both are
+ * materialised by vg_rand_u01(out, C*H*W, {seed, pos}, draw).  clean is never touched; the NHWC copy carries the impulses.
+ * vg_degrade_params_ex: out f32 [B][8] = {s, s * noise_max_std, rect_h, rect_w, x, y, p_b = s * impulse_max_p, (float)kind}.
+ * VG_EINVAL: kind outside 0..2; impulse_max_p or salt_ratio outside [0, 1] or not finite; everything the two entry points
+ * above refuse.
  * ---------------------------------------------------------------------------------------- */
 #define VG_DRAW_DEGRADE_NORMAL 16
 #define VG_DRAW_DEGRADE_FILL   17
 #define VG_DRAW_DEGRADE_PARAMS 18
+#define VG_DRAW_DEGRADE_IMPULSE 19
+#define VG_DRAW_DEGRADE_SALT 20
+#define VG_NOISE_GAUSSIAN 0
+#define VG_NOISE_SPECKLE  1
+#define VG_NOISE_SHOT     2
+int vg_gather_degrade_u8_ex(const uint8_t* images, int64_t N, const int64_t* idx, int B, int C, int H, int W, uint64_t seed,
+                            uint64_t pos0, float noise_max_std, int rect, int normalize, int min_size, int max_size, int x0,
+                            int x1, int y0, int y1, float* clean, float* noisy, void* nhwc, int CP, int dtype, int kind,
+                            float impulse_max_p, float salt_ratio, void* stream);
+int vg_degrade_params_ex(uint64_t seed, uint64_t pos0, int B, float noise_max_std, int rect, int H, int W, int min_size,
+                         int max_size, int x0, int x1, int y0, int y1, float* out, int kind, float impulse_max_p,
+                         float salt_ratio, void* stream);
 int vg_gather_degrade_u8(const uint8_t* images, int64_t N, const int64_t* idx, int B, int C, int H, int W, uint64_t seed,
                          uint64_t pos0, float noise_max_std, int rect, int normalize, int min_size, int max_size, int x0,
                          int x1, int y0, int y1, float* clean, float* noisy, void* nhwc, int CP, int dtype, void* stream);
@@ -1483,6 +1522,21 @@ int vg_tile_blend(const float* tiles, float* out, int N, int C, int H, int W, in
 int vg_nlm_denoise(const float* x, float* y, int B, int C, int H, int W, int patch_radius, int search_radius,
                    const float* sigma, int sigma_stride, float h_factor, float h_const, void* stream);
 int vg_noise_sigma(const float* x, int B, int C, int H, int W, float* sigma, int sigma_stride, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Median baseline (not in the reference; added within ABI 31; csrc/median.hip): the textbook filter against impulse noise,
+ * where non-local means with a Gaussian sigma has nothing to hold on to.
+ * vg_median_filter: y_c(p) = the median of the (2r+1)^2 values of channel c around p, r = radius in {1, 2}; x f32 NCHW
+ * [B][C][H][W] contiguous, y of the same shape, no overlap with x.  Border: x extended by r on every side by reflection
+ * without repeating the edge (numpy mode="reflect"); min(H, W) >= r + 1, so one reflection suffices.  The output is one of
+ * the window's values, selected by a branch-free min / max network: exact for finite inputs (a NaN in a window gives an
+ * unspecified value of that window; +0 and -0 compare equal, either may come out).  Channels and images are independent;
+ * one launch, no atomics, no workspace, no host synchronisation.
+ * VG_EINVAL: x or y NULL or overlapping; B, C, H or W < 1; radius outside 1..2; min(H, W) < radius + 1; B C H W or B C
+ * > 2^31 - 1, ceil(H / 16) or ceil(W / 64) > 65535 (the grid: planes in x, 64 x 16 output tiles in z / y).  VG_EALIGN: a
+ * pointer not 4-byte aligned (16-byte stores are used where W % 4 == 0 and y is 16-byte aligned).
+ * ---------------------------------------------------------------------------------------- */
+int vg_median_filter(const float* x, float* y, int B, int C, int H, int W, int radius, void* stream);
 
 #ifdef __cplusplus
 }

@@ -29,8 +29,9 @@ CenterCrop on the device), ``resample_coeffs``, ``resize_geometry``.  Tiled deno
 refinement (not in the reference; GAN-inversion denoising / inpainting): ``LatentRefiner`` -- Adam on the latent of the frozen
 networks against the input outside its occlusion rectangle, and ``paired_test_epoch(..., refine=)``.  Classical-denoiser
 baseline (not in the reference): ``NLMeans`` (``baselines``) -- non-local means on the device with the loader's own or a
-blindly estimated noise level (``ops.nlm_denoise``, ``ops.noise_sigma``), and ``baseline=`` on ``paired_test_epoch`` /
-``tiled_test_epoch``.
+blindly estimated noise level (``ops.nlm_denoise``, ``ops.noise_sigma``), ``Median`` -- the (2r+1)^2 median filter
+(``ops.median_filter``), and ``baseline=`` on ``paired_test_epoch`` / ``tiled_test_epoch``.  Noise models of the degraded
+pairs (not in the reference): ``data.Degrade(noise_model="gaussian" | "speckle" | "shot", impulse_max_p=, salt_ratio=)``.
 """
 from . import baselines  # noqa: F401
 from . import cluster  # noqa: F401
@@ -40,7 +41,7 @@ from . import latent  # noqa: F401
 from . import metrics  # noqa: F401
 from .data import ResidentImages, resample_coeffs, resize_geometry
 from .augment import DiffAugment
-from .baselines import NLMeans
+from .baselines import Median, NLMeans
 from .ddp import GradReducer
 from .ema import EMA
 from . import tiling  # noqa: F401
@@ -67,4 +68,4 @@ __all__ = ["ConvBlock", "Encoder", "Generator", "Discriminator", "weights_init",
            "tiling", "TilePlan", "tile_plan", "denoise_tiled", "tiled_denoise_eval", "tiled_test_epoch",
            "metrics", "FeatureStats", "frechet_distance", "precision_recall", "encoder_features", "kernel_distance",
            "cluster", "KMeans", "ndb", "evaluate_generation_ndb", "MSSSIMLoss", "msssim_weights", "LatentRefiner",
-           "baselines", "NLMeans"]
+           "baselines", "NLMeans", "Median"]

@@ -23,6 +23,7 @@ VG_PROLOGUE_MAX = 4
 VG_TILE_MAX_COVER = 8
 VG_LATENT_INIT, VG_LATENT_UPDATE, VG_LATENT_TRACK = 0, 1, 2
 VG_LRS_CONST, VG_LRS_LINEAR, VG_LRS_COSINE, VG_LRS_EXP, VG_LRS_STEP = 0, 1, 2, 3, 4
+VG_NOISE_GAUSSIAN, VG_NOISE_SPECKLE, VG_NOISE_SHOT = 0, 1, 2
 ABI_VERSION = 31
 
 VG_ENOSUP = -3
@@ -267,6 +268,10 @@ SIGNATURES = {
     "vg_tnconv_plan": (c_int, [POINTER(TNDesc), POINTER(TNPlan)]),
     "vg_nlm_denoise": (c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _F, _F, _P]),
     "vg_noise_sigma": (c_int, [_P, _I, _I, _I, _I, _P, _I, _P]),
+    "vg_gather_degrade_u8_ex": (c_int, [_P, _L, _P, _I, _I, _I, _I, _U, _U, _F, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I,
+                                        _I, _I, _F, _F, _P]),
+    "vg_degrade_params_ex": (c_int, [_U, _U, _I, _F, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _F, _F, _P]),
+    "vg_median_filter": (c_int, [_P, _P, _I, _I, _I, _I, _I, _P]),
 }
 
 LIB_PATH = os.environ.get("VG_LIB_PATH") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libvaegan_hip.so")

@@ -24,6 +24,8 @@ class NLMeans:
     ``__call__(noisy, rects=None)`` -> f32 [B,C,H,W]; noisy: f32 [B,C,H,W] on the MI355X, C <= 4, min(H, W) >= P + R + 1.
     Two launches at most, no host synchronisation.  An image whose level is 0 (or not finite) comes back unchanged."""
 
+    name = "nlm"
+
     def __init__(self, patch_radius: int = 2, search_radius: int = 7, h_factor: float = DEFAULT_H_FACTOR, sigma="oracle"):
         for name, v, lo, hi in (("patch_radius", patch_radius, 0, 3), ("search_radius", search_radius, 1, 10)):
             if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
@@ -64,24 +66,67 @@ class NLMeans:
                                h_factor=self.h_factor)
 
 
-def make_baseline(what: str, baseline, allow_oracle: bool = True) -> Optional[NLMeans]:
-    """``baseline=`` of the evaluation passes: None, an NLMeans, the string "nlm" or a dict of NLMeans' keywords."""
+class Median:
+    """Median filter (``ops.median_filter``): the per-channel (2r+1)^2 median, r = radius in {1, 2}, reflect padding -- the
+    textbook baseline under impulse noise (salt and pepper), where a Gaussian sigma tells non-local means nothing.  It has no
+    noise-level parameter and reads no rectangles.
+
+    ``__call__(noisy, rects=None)`` -> f32 [B,C,H,W]; noisy: f32 [B,C,H,W] on the MI355X, min(H, W) >= radius + 1.  One launch,
+    no host synchronisation."""
+
+    name = "median"
+    needs_rects = False
+
+    def __init__(self, radius: int = 1):
+        if isinstance(radius, bool) or not isinstance(radius, int) or not 1 <= radius <= 2:
+            raise ValueError(f"radius must be an integer in 1..2, got {radius!r}")
+        self.radius = radius
+
+    @torch.no_grad()
+    def __call__(self, noisy: torch.Tensor, rects: Optional[torch.Tensor] = None) -> torch.Tensor:
+        what = "Median"
+        if not isinstance(noisy, torch.Tensor) or not noisy.is_cuda:
+            raise RuntimeError(f"{what} needs the batch on the MI355X ('cuda'); there is no CPU path")
+        if noisy.dim() != 4 or noisy.dtype != torch.float32:
+            raise RuntimeError(f"{what}: noisy must be float32 [B,C,H,W]")
+        return ops.median_filter(noisy.contiguous(), self.radius)
+
+
+_ACCEPTS = "None, an NLMeans, a Median, 'nlm', 'median' or a dict of NLMeans' keywords or with the key 'radius'"
+
+
+def make_baseline(what: str, baseline, allow_oracle: bool = True):
+    """``baseline=`` of the evaluation passes: None, an NLMeans or a Median, the string "nlm" or "median", or a dict -- of
+    NLMeans' keywords, or ``{"radius": r}`` for a Median.  The result's ``name`` suffixes the result keys."""
     if baseline is None:
         return None
-    if isinstance(baseline, NLMeans):
-        nlm = baseline
+    if isinstance(baseline, (NLMeans, Median)):
+        made = baseline
     elif isinstance(baseline, str):
-        if baseline != "nlm":
-            raise ValueError(f"{what}: baseline must be None, an NLMeans, 'nlm' or a dict of its keywords, got {baseline!r}")
-        nlm = NLMeans() if allow_oracle else NLMeans(sigma="estimate")
+        if baseline == "median":
+            made = Median()
+        elif baseline == "nlm":
+            made = NLMeans() if allow_oracle else NLMeans(sigma="estimate")
+        else:
+            raise ValueError(f"{what}: baseline must be {_ACCEPTS}, got {baseline!r}")
     elif isinstance(baseline, dict):
         try:
-            nlm = NLMeans(**baseline)
+            made = Median(**baseline) if "radius" in baseline else NLMeans(**baseline)
         except TypeError as e:
             raise ValueError(f"{what}: baseline: {e}") from None
     else:
-        raise ValueError(f"{what}: baseline must be None, an NLMeans, 'nlm' or a dict of its keywords")
-    if nlm.needs_rects and not allow_oracle:
+        raise ValueError(f"{what}: baseline must be {_ACCEPTS}")
+    if made.needs_rects and not allow_oracle:
         raise ValueError(f"{what}: there is no loader whose noise levels could be read: the baseline needs sigma='estimate' "
                          f"or a number")
-    return nlm
+    return made
+
+
+def check_oracle_sigma(what: str, baseline, loader) -> None:
+    """sigma="oracle" reads column 1 of the loader's rectangle records as the standard deviation of additive Gaussian noise.
+    Under any other noise model of the loader's ``Degrade`` that column is not one: refuse instead of filtering with it."""
+    degrade = getattr(loader, "degrade", None)
+    if isinstance(baseline, NLMeans) and baseline.sigma == "oracle" and degrade is not None and not degrade.pure_gaussian:
+        raise ValueError(f"{what}: the loader degrades with {degrade!r}; column 1 of its rectangle records (s * noise_max_std) "
+                         f"is then not a Gaussian sigma, which NLMeans(sigma='oracle') takes it for: use sigma='estimate' or "
+                         f"a number")

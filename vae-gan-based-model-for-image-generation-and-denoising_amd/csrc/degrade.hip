@@ -3,6 +3,9 @@
 // with a per-image standard deviation, clamp to [-1, 1]) and, optionally, the degraded batch in the engine's NHWC layout.
 // Streaming kernel: at S = 64, C = 3 an image is 12 KB read and 96 KB (+ 64 KB NHWC bf16) written.  The draw contract
 // (which Philox word feeds which number) is stated in include/vaegan_hip.h, "Degraded pairs".
+// Noise models (vg_gather_degrade_u8_ex): both gather kernels are templated on <KIND, IMP> -- the factor the normal is
+// scaled by (1, g, sqrt(g)) and whether impulses are laid on top.  <VG_NOISE_GAUSSIAN, false> is the reference's model and
+// the only instantiation vg_gather_degrade_u8 launches; every line the other models add sits behind `if constexpr`.
 #include "common.hpp"
 #include "noise.hpp"
 
@@ -52,17 +55,46 @@ __device__ __forceinline__ float degrade_value(float clean, bool in_rect, uint32
     const float t = base + (n * s) * nms;
     return fminf(fmaxf(t, -1.0f), 1.0f);
 }
+// The signal-dependent models: the same sum with the noise term scaled by f = g (speckle) or sqrt(g) (shot), g the base
+// value mapped to [0, 1] -- (n * s) * nms stays the standard deviation at white.  max(., 0): with normalize == 0 a
+// rectangle fill 2u - 1 can be negative.  The quotient divides by 2 or 1 and is exact.  The root is the correctly rounded one:
+// sqrtf, which hipcc expands to v_sqrt_f32 plus the fma correction steps (-fhip-fp32-correctly-rounded-divide-sqrt, its
+// default).  NOT __fsqrt_rn: in this toolchain's headers that name is the native root, 1 ulp, unless the rounded OCML
+// operations are compiled in -- the bitwise test of the shot model caught the difference.
+template <int KIND>
+__device__ __forceinline__ float degrade_value_scaled(float clean, bool in_rect, uint32_t fill_word, float n, float s, float nms,
+                                                      int normalize) {
+#pragma clang fp contract(off)
+    const float base = in_rect ? u01_from_word(fill_word) * 2.0f - 1.0f : clean;
+    const float lo = normalize ? -1.0f : 0.0f, span = normalize ? 2.0f : 1.0f;
+    const float g = fmaxf((base - lo) / span, 0.0f);
+    const float f = KIND == VG_NOISE_SPECKLE ? g : sqrtf(g);
+    const float t = base + ((n * s) * nms) * f;
+    return fminf(fmaxf(t, -1.0f), 1.0f);
+}
+template <int KIND>
+__device__ __forceinline__ float degrade_model_value(float clean, bool in_rect, uint32_t fill_word, float n, float s, float nms,
+                                                     int normalize) {
+    if constexpr (KIND == VG_NOISE_GAUSSIAN) return degrade_value(clean, in_rect, fill_word, n, s, nms);
+    else return degrade_value_scaled<KIND>(clean, in_rect, fill_word, n, s, nms, normalize);
+}
+// Impulses (salt and pepper) of one image: element e is hit when u01(word(VG_DRAW_DEGRADE_IMPULSE, e)) < p_b, p_b = s * impulse_max_p,
+// and becomes 1 when u01(word(VG_DRAW_DEGRADE_SALT, e)) < salt_ratio, else the value mapping's black.
+struct DegradeImpulse { float max_p, salt_ratio; };
+__device__ __forceinline__ uint32_t word_of(const uint32_t (&w)[4], uint32_t sel) {
+    return sel == 0 ? w[0] : sel == 1 ? w[1] : sel == 2 ? w[2] : w[3];
+}
 
 // Four consecutive pixels of a row per thread (W % 4 == 0, C <= 4): C dword loads of the 4 * C source bytes, one Philox
 // block per channel for the four normals (and one more for the fill uniforms where the quad touches the rectangle),
 // float4 stores to every plane of clean / noisy, one pixel store per NHWC pixel.  bpi: workgroups per image.
-template <int C, int DT>
+template <int C, int DT, int KIND, bool IMP>
 __global__ __launch_bounds__(256) void gather_degrade_x4_kernel(const uint8_t* __restrict__ images,
                                                                 const int64_t* __restrict__ idx, int64_t N, int W, int HW,
                                                                 int bpi, unsigned long long seed, unsigned long long pos0,
                                                                 float nms, int normalize, DegradeGeom g,
                                                                 float* __restrict__ clean, float* __restrict__ noisy,
-                                                                void* __restrict__ nhwc, int CP) {
+                                                                void* __restrict__ nhwc, int CP, DegradeImpulse imp) {
     const int b = blockIdx.x / bpi;
     const int q = (blockIdx.x - b * bpi) * 256 + threadIdx.x;
     const int Q = HW >> 2;
@@ -93,7 +125,22 @@ __global__ __launch_bounds__(256) void gather_degrade_x4_kernel(const uint8_t* _
                 const int k = px * C + c;              // byte k of the 4 * C loaded
                 cl[px] = byte_to_float((raw[k >> 2] >> (8 * (k & 3))) & 0xffu, normalize);
                 const bool in_rect = touches && w0 + px >= im.x && w0 + px < im.x + im.rw;
-                v[px][c] = degrade_value(cl[px], in_rect, fw[px], nz.v[px], im.s, nms);
+                v[px][c] = degrade_model_value<KIND>(cl[px], in_rect, fw[px], nz.v[px], im.s, nms, normalize);
+            }
+            if constexpr (IMP) {                       // the impulse words of the quad: one block, as the fill's
+                const float p_b = __fmul_rn(im.s, imp.max_p);
+                uint32_t iw[4];
+                philox4x32_10(seed, pos, VG_DRAW_DEGRADE_IMPULSE, blk, iw);
+                bool hit[4], any = false;
+#pragma unroll
+                for (int px = 0; px < 4; ++px) { hit[px] = u01_from_word(iw[px]) < p_b; any = any || hit[px]; }
+                if (any) {
+                    uint32_t sw[4];
+                    philox4x32_10(seed, pos, VG_DRAW_DEGRADE_SALT, blk, sw);
+#pragma unroll
+                    for (int px = 0; px < 4; ++px)
+                        if (hit[px]) v[px][c] = u01_from_word(sw[px]) < imp.salt_ratio ? 1.0f : (normalize ? -1.0f : 0.0f);
+                }
             }
             const int64_t dst = ((int64_t)b * C + c) * HW + p;
             *reinterpret_cast<float4*>(clean + dst) = float4{cl[0], cl[1], cl[2], cl[3]};
@@ -122,13 +169,13 @@ __global__ __launch_bounds__(256) void gather_degrade_x4_kernel(const uint8_t* _
 
 // One pixel per thread, any W and C: the same expressions element by element (philox_randn is the one-element form of
 // philox_randn4; a fill uniform is word e & 3 of block e >> 2), so both kernels write the same bits.
-template <int DT>
+template <int DT, int KIND, bool IMP>
 __global__ __launch_bounds__(256) void gather_degrade_kernel(const uint8_t* __restrict__ images,
                                                              const int64_t* __restrict__ idx, int64_t N, int C, int W, int HW,
                                                              int bpi, unsigned long long seed, unsigned long long pos0,
                                                              float nms, int normalize, DegradeGeom g,
                                                              float* __restrict__ clean, float* __restrict__ noisy,
-                                                             void* __restrict__ nhwc, int CP) {
+                                                             void* __restrict__ nhwc, int CP, DegradeImpulse imp) {
     const int b = blockIdx.x / bpi;
     const int p = (blockIdx.x - b * bpi) * 256 + threadIdx.x;
     if (p >= HW) return;
@@ -154,7 +201,17 @@ __global__ __launch_bounds__(256) void gather_degrade_kernel(const uint8_t* __re
                 if (in_rect) philox4x32_10(seed, pos, VG_DRAW_DEGRADE_FILL, e >> 2, fw);
                 const uint32_t sel = (uint32_t)(e & 3ull);
                 const uint32_t fword = sel == 0 ? fw[0] : sel == 1 ? fw[1] : sel == 2 ? fw[2] : fw[3];
-                v[k] = degrade_value(cl, in_rect, fword, philox_randn(seed, pos, VG_DRAW_DEGRADE_NORMAL, e), im.s, nms);
+                v[k] = degrade_model_value<KIND>(cl, in_rect, fword, philox_randn(seed, pos, VG_DRAW_DEGRADE_NORMAL, e), im.s, nms,
+                                                 normalize);
+                if constexpr (IMP) {
+                    uint32_t iw[4];
+                    philox4x32_10(seed, pos, VG_DRAW_DEGRADE_IMPULSE, e >> 2, iw);
+                    if (u01_from_word(word_of(iw, sel)) < __fmul_rn(im.s, imp.max_p)) {
+                        uint32_t sw[4];
+                        philox4x32_10(seed, pos, VG_DRAW_DEGRADE_SALT, e >> 2, sw);
+                        v[k] = u01_from_word(word_of(sw, sel)) < imp.salt_ratio ? 1.0f : (normalize ? -1.0f : 0.0f);
+                    }
+                }
                 const int64_t dst = ((int64_t)b * C + c) * HW + p;
                 clean[dst] = cl;
                 noisy[dst] = v[k];
@@ -165,14 +222,15 @@ __global__ __launch_bounds__(256) void gather_degrade_kernel(const uint8_t* __re
 }
 
 __global__ __launch_bounds__(256) void degrade_params_kernel(unsigned long long seed, unsigned long long pos0, int B, float nms,
-                                                             DegradeGeom g, float* __restrict__ out) {
+                                                             DegradeGeom g, float* __restrict__ out, float impulse_max_p,
+                                                             int kind) {
     const int b = blockIdx.x * 256 + threadIdx.x;
     if (b >= B) return;
     const DegradeImage im = degrade_image(seed, pos0 + (unsigned long long)b, g);
     float* o = out + (int64_t)b * 8;
     o[0] = im.s; o[1] = __fmul_rn(im.s, nms);
     o[2] = (float)im.rh; o[3] = (float)im.rw; o[4] = (float)im.x; o[5] = (float)im.y;
-    o[6] = 0.f; o[7] = 0.f;
+    o[6] = __fmul_rn(im.s, impulse_max_p); o[7] = (float)kind;      // the reference's model: s * 0 = +0 and 0, as ever
 }
 
 __global__ __launch_bounds__(256) void rand_u01_fill_kernel(float* __restrict__ out, int64_t n,
@@ -208,21 +266,26 @@ extern "C" int vg_rand_u01(float* out, int64_t n, const uint64_t* rng, int draw,
     return VG_LAUNCH_RC();
 }
 
-extern "C" int vg_degrade_params(uint64_t seed, uint64_t pos0, int B, float noise_max_std, int rect, int H, int W,
-                                 int min_size, int max_size, int x0, int x1, int y0, int y1, float* out, void* stream) {
-    const DegradeGeom g{rect ? 1 : 0, min_size, max_size, x0, x1, y0, y1};
-    VG_CHECK_ARG(out && B > 0 && H > 0 && W > 0 && positions_ok(pos0, B) && geom_ok(g, H, W), VG_EINVAL);
-    hipLaunchKernelGGL(degrade_params_kernel, dim3((B + 255) / 256), dim3(256), 0, vg_stream(stream),
-                       (unsigned long long)seed, (unsigned long long)pos0, B, noise_max_std, g, out);
-    return VG_LAUNCH_RC();
-}
+namespace {
 
-extern "C" int vg_gather_degrade_u8(const uint8_t* images, int64_t N, const int64_t* idx, int B, int C, int H, int W,
-                                    uint64_t seed, uint64_t pos0, float noise_max_std, int rect, int normalize,
-                                    int min_size, int max_size, int x0, int x1, int y0, int y1, float* clean,
-                                    float* noisy, void* nhwc, int CP, int dtype, void* stream) {
-    const DegradeGeom g{rect ? 1 : 0, min_size, max_size, x0, x1, y0, y1};
-    VG_CHECK_ARG(images && idx && clean && noisy && N > 0 && B > 0 && C > 0 && H > 0 && W > 0 && positions_ok(pos0, B) &&
+struct GatherArgs {
+    const uint8_t* images; int64_t N; const int64_t* idx; int B, C, H, W; uint64_t seed, pos0; float noise_max_std;
+    int normalize; DegradeGeom g; float* clean; float* noisy; void* nhwc; int CP, dtype; void* stream;
+};
+
+// the launch of one model: the argument checks of both entry points, then the quad or the scalar kernel of <KIND, IMP>
+template <int KIND, bool IMP>
+int gather_degrade_launch(const GatherArgs& a, DegradeImpulse imp) {
+    const uint8_t* images = a.images;
+    const int64_t* idx = a.idx;
+    const int64_t N = a.N;
+    const int B = a.B, C = a.C, H = a.H, W = a.W, normalize = a.normalize, CP = a.CP;
+    int dtype = a.dtype;
+    const DegradeGeom g = a.g;
+    float *clean = a.clean, *noisy = a.noisy;
+    void* nhwc = a.nhwc;
+    const float noise_max_std = a.noise_max_std;
+    VG_CHECK_ARG(images && idx && clean && noisy && N > 0 && B > 0 && C > 0 && H > 0 && W > 0 && positions_ok(a.pos0, B) &&
                  (int64_t)H * W < (1ll << 30) && geom_ok(g, H, W), VG_EINVAL);
     if (nhwc) {
         VG_CHECK_ARG(dtype == VG_F32 || dtype == VG_BF16, VG_ENOSUP);
@@ -232,22 +295,22 @@ extern "C" int vg_gather_degrade_u8(const uint8_t* images, int64_t N, const int6
         dtype = VG_F32;
     }
     const int HW = H * W;
-    const unsigned long long s = seed, p0 = pos0;
+    const unsigned long long s = a.seed, p0 = a.pos0;
     const bool quad = W % 4 == 0 && C <= 4 && vg_aligned16(clean) && vg_aligned16(noisy) &&
                       (reinterpret_cast<uintptr_t>(images) & 3u) == 0;
     const int units = quad ? HW / 4 : HW;
     const int bpi = (units + 255) / 256;
     VG_CHECK_ARG((int64_t)B * bpi < (1ll << 31), VG_EINVAL);
     const dim3 grid((unsigned)((int64_t)B * bpi)), block(256);
-    hipStream_t st = vg_stream(stream);
+    hipStream_t st = vg_stream(a.stream);
 #define DEGRADE_X4(CC)                                                                                                     \
     do {                                                                                                                   \
         if (dtype == VG_F32)                                                                                               \
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(gather_degrade_x4_kernel<CC, VG_F32>), grid, block, 0, st, images, idx, N, W, HW, bpi, s,  \
-                               p0, noise_max_std, normalize, g, clean, noisy, nhwc, CP);                                   \
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(gather_degrade_x4_kernel<CC, VG_F32, KIND, IMP>), grid, block, 0, st, images, idx, N, W,  \
+                               HW, bpi, s, p0, noise_max_std, normalize, g, clean, noisy, nhwc, CP, imp);                  \
         else                                                                                                               \
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(gather_degrade_x4_kernel<CC, VG_BF16>), grid, block, 0, st, images, idx, N, W, HW, bpi, s, \
-                               p0, noise_max_std, normalize, g, clean, noisy, nhwc, CP);                                   \
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(gather_degrade_x4_kernel<CC, VG_BF16, KIND, IMP>), grid, block, 0, st, images, idx, N, W, \
+                               HW, bpi, s, p0, noise_max_std, normalize, g, clean, noisy, nhwc, CP, imp);                  \
     } while (0)
     if (quad) {
         switch (C) {
@@ -257,12 +320,70 @@ extern "C" int vg_gather_degrade_u8(const uint8_t* images, int64_t N, const int6
             default: DEGRADE_X4(4); break;
         }
     } else if (dtype == VG_F32) {
-        hipLaunchKernelGGL(gather_degrade_kernel<VG_F32>, grid, block, 0, st, images, idx, N, C, W, HW, bpi, s, p0,
-                           noise_max_std, normalize, g, clean, noisy, nhwc, CP);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(gather_degrade_kernel<VG_F32, KIND, IMP>), grid, block, 0, st, images, idx, N, C, W, HW,
+                           bpi, s, p0, noise_max_std, normalize, g, clean, noisy, nhwc, CP, imp);
     } else {
-        hipLaunchKernelGGL(gather_degrade_kernel<VG_BF16>, grid, block, 0, st, images, idx, N, C, W, HW, bpi, s, p0,
-                           noise_max_std, normalize, g, clean, noisy, nhwc, CP);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(gather_degrade_kernel<VG_BF16, KIND, IMP>), grid, block, 0, st, images, idx, N, C, W, HW,
+                           bpi, s, p0, noise_max_std, normalize, g, clean, noisy, nhwc, CP, imp);
     }
 #undef DEGRADE_X4
     return VG_LAUNCH_RC();
 }
+
+// kind in 0..2, both probabilities finite and in [0, 1] (a NaN fails every comparison)
+bool model_ok(int kind, float impulse_max_p, float salt_ratio) {
+    return kind >= VG_NOISE_GAUSSIAN && kind <= VG_NOISE_SHOT && impulse_max_p >= 0.f && impulse_max_p <= 1.f &&
+           salt_ratio >= 0.f && salt_ratio <= 1.f;
+}
+
+}  // namespace
+
+extern "C" int vg_degrade_params(uint64_t seed, uint64_t pos0, int B, float noise_max_std, int rect, int H, int W,
+                                 int min_size, int max_size, int x0, int x1, int y0, int y1, float* out, void* stream) {
+    return vg_degrade_params_ex(seed, pos0, B, noise_max_std, rect, H, W, min_size, max_size, x0, x1, y0, y1, out,
+                                VG_NOISE_GAUSSIAN, 0.f, 0.5f, stream);
+}
+
+extern "C" int vg_degrade_params_ex(uint64_t seed, uint64_t pos0, int B, float noise_max_std, int rect, int H, int W,
+                                    int min_size, int max_size, int x0, int x1, int y0, int y1, float* out, int kind,
+                                    float impulse_max_p, float salt_ratio, void* stream) {
+    const DegradeGeom g{rect ? 1 : 0, min_size, max_size, x0, x1, y0, y1};
+    VG_CHECK_ARG(out && B > 0 && H > 0 && W > 0 && positions_ok(pos0, B) && geom_ok(g, H, W), VG_EINVAL);
+    VG_CHECK_ARG(model_ok(kind, impulse_max_p, salt_ratio), VG_EINVAL);
+    hipLaunchKernelGGL(degrade_params_kernel, dim3((B + 255) / 256), dim3(256), 0, vg_stream(stream),
+                       (unsigned long long)seed, (unsigned long long)pos0, B, noise_max_std, g, out, impulse_max_p, kind);
+    return VG_LAUNCH_RC();
+}
+
+extern "C" int vg_gather_degrade_u8(const uint8_t* images, int64_t N, const int64_t* idx, int B, int C, int H, int W,
+                                    uint64_t seed, uint64_t pos0, float noise_max_std, int rect, int normalize,
+                                    int min_size, int max_size, int x0, int x1, int y0, int y1, float* clean,
+                                    float* noisy, void* nhwc, int CP, int dtype, void* stream) {
+    const GatherArgs a{images, N, idx, B, C, H, W, seed, pos0, noise_max_std, normalize,
+                       DegradeGeom{rect ? 1 : 0, min_size, max_size, x0, x1, y0, y1}, clean, noisy, nhwc, CP, dtype, stream};
+    return gather_degrade_launch<VG_NOISE_GAUSSIAN, false>(a, DegradeImpulse{0.f, 0.f});
+}
+
+extern "C" int vg_gather_degrade_u8_ex(const uint8_t* images, int64_t N, const int64_t* idx, int B, int C, int H, int W,
+                                       uint64_t seed, uint64_t pos0, float noise_max_std, int rect, int normalize,
+                                       int min_size, int max_size, int x0, int x1, int y0, int y1, float* clean,
+                                       float* noisy, void* nhwc, int CP, int dtype, int kind, float impulse_max_p,
+                                       float salt_ratio, void* stream) {
+    VG_CHECK_ARG(model_ok(kind, impulse_max_p, salt_ratio), VG_EINVAL);
+    const GatherArgs a{images, N, idx, B, C, H, W, seed, pos0, noise_max_std, normalize,
+                       DegradeGeom{rect ? 1 : 0, min_size, max_size, x0, x1, y0, y1}, clean, noisy, nhwc, CP, dtype, stream};
+    const DegradeImpulse imp{impulse_max_p, salt_ratio};
+    if (impulse_max_p > 0.f) {
+        switch (kind) {
+            case VG_NOISE_GAUSSIAN: return gather_degrade_launch<VG_NOISE_GAUSSIAN, true>(a, imp);
+            case VG_NOISE_SPECKLE: return gather_degrade_launch<VG_NOISE_SPECKLE, true>(a, imp);
+            default: return gather_degrade_launch<VG_NOISE_SHOT, true>(a, imp);
+        }
+    }
+    switch (kind) {
+        case VG_NOISE_GAUSSIAN: return gather_degrade_launch<VG_NOISE_GAUSSIAN, false>(a, imp);   // the old entry's kernels
+        case VG_NOISE_SPECKLE: return gather_degrade_launch<VG_NOISE_SPECKLE, false>(a, imp);
+        default: return gather_degrade_launch<VG_NOISE_SHOT, false>(a, imp);
+    }
+}
+

@@ -28,6 +28,9 @@ size.  They cannot equal torch's CPU generator; the distribution and the arithme
 (tests/test_gpu_degrade.py).  The epoch seed is the int64 base seed that ``iter(DataLoader)`` draws from the default
 generator -- the number a real DataLoader hands its workers as their RNG seed -- so ``utils.configure_seed`` governs
 the noise, every epoch differs, and no default-RNG state is consumed beyond what the plain loader consumes.
+Noise models (not in the reference): ``Degrade(noise_model="speckle" | "shot", impulse_max_p=, salt_ratio=)`` scales the same
+normal by the intensity or its root and lays salt-and-pepper impulses on top, in the same kernel pass from the same keyed
+draws (include/vaegan_hip.h "Degraded pairs", noise models; tests/test_gpu_noise_models.py); the defaults are the model above.
 ``image_size`` (``decode_folder`` / ``from_folder`` / 'LQ'): V0's ``Resize`` + ``CenterCrop`` (:26-30).  ``resize_on="host"``
 (the default): at decode time with PIL, so the resident set is frozen at the size asked for.  ``resize_on="device"``: the
 files are decoded ONCE at their own size and uploaded; ``ResidentImages.resized(image_size)`` then makes any member of
@@ -175,19 +178,51 @@ class Degrade:
     """Settings of the degraded-pair path (CelebADatasetV0's noise_max_std / rect, dataset_code.py:14) plus the value
     mapping: normalize=True maps bytes like the 'HQ' dataset, (u/255 - 0.5)/0.5 -- the range the clamp to [-1, 1] and the
     Tanh decoder assume; normalize=False is V0's literal u/255.  noise_max_std=None: clean batches only (no pairs), in
-    that value mapping."""
+    that value mapping.
+    noise_model (not in the reference; include/vaegan_hip.h "Degraded pairs", noise models): what the per-image level
+    s * noise_max_std scales -- "gaussian" additive noise (the reference's), "speckle" noise proportional to the intensity
+    (sonar), "shot" noise whose variance is proportional to the intensity (low light, ranging); the level is the standard
+    deviation at white for all three.  impulse_max_p > 0 lays salt-and-pepper impulses on top (drop-outs and spurious
+    returns): image b has hit probability s_b * impulse_max_p, a hit is white with probability salt_ratio, else black.
+    The defaults are the reference's model, bit for bit what the loader made before it had these."""
 
-    def __init__(self, noise_max_std: Optional[float], rect: bool = True, normalize: bool = True):
+    NOISE_MODELS = ("gaussian", "speckle", "shot")
+
+    def __init__(self, noise_max_std: Optional[float], rect: bool = True, normalize: bool = True,
+                 noise_model: str = "gaussian", impulse_max_p: float = 0.0, salt_ratio: float = 0.5):
         if noise_max_std is not None and not noise_max_std >= 0:
             raise ValueError("noise_max_std must be >= 0 or None")
+        if noise_model not in self.NOISE_MODELS:
+            raise ValueError(f"noise_model must be 'gaussian', 'speckle' or 'shot', got {noise_model!r}")
+        for name, v in (("impulse_max_p", impulse_max_p), ("salt_ratio", salt_ratio)):
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0.0 <= v <= 1.0:
+                raise ValueError(f"{name} must be a number in [0, 1], got {v!r}")
         self.noise_max_std, self.rect, self.normalize = noise_max_std, bool(rect), bool(normalize)
+        self.noise_model, self.impulse_max_p, self.salt_ratio = noise_model, float(impulse_max_p), float(salt_ratio)
 
     @property
     def pairs(self) -> bool:
         return self.noise_max_std is not None
 
+    @property
+    def pure_gaussian(self) -> bool:
+        """Column 1 of the rectangle records (s * noise_max_std) is the standard deviation of additive Gaussian noise."""
+        return self.noise_model == "gaussian" and self.impulse_max_p == 0.0
+
+    @property
+    def model_kw(self) -> dict:
+        """The noise-model keywords of ops.gather_degrade_u8 / ops.degrade_params."""
+        return dict(kind=self.noise_model, impulse_max_p=self.impulse_max_p, salt_ratio=self.salt_ratio)
+
     def __repr__(self):
-        return f"Degrade(noise_max_std={self.noise_max_std}, rect={self.rect}, normalize={self.normalize})"
+        extra = ""
+        if self.noise_model != "gaussian":
+            extra += f", noise_model={self.noise_model!r}"
+        if self.impulse_max_p != 0.0:
+            extra += f", impulse_max_p={self.impulse_max_p}"
+        if self.salt_ratio != 0.5:
+            extra += f", salt_ratio={self.salt_ratio}"
+        return f"Degrade(noise_max_std={self.noise_max_std}, rect={self.rect}, normalize={self.normalize}{extra})"
 
 
 RESIZE_CHUNK = 8192          # images per resize launch / per upload of a raw set (218 x 178 x 3: 0.95 GB)
@@ -271,7 +306,7 @@ class ResidentImages:
         rect = degrade.rect and degrade.pairs
         noisy, clean, _ = ops.gather_degrade_u8(self.images, idx, seed, pos0, degrade.noise_max_std or 0.0, rect,
                                                 degrade.normalize, degrade_bounds(H, W) if rect else None,
-                                                out_clean=out, out_noisy=out_noisy, nhwc=nhwc)
+                                                out_clean=out, out_noisy=out_noisy, nhwc=nhwc, **degrade.model_kw)
         return noisy, clean
 
     def __getitem__(self, i: int) -> torch.Tensor:
@@ -406,13 +441,14 @@ class DeviceLoader:
                 H, W = self.dataset.images.shape[1:3]
                 rect = self.degrade.rect and self.degrade.pairs
                 self.last_rects = ops.degrade_params(self.last_base_seed, lo, idx.numel(), self.degrade.noise_max_std or 0.0,
-                                                     rect, H, W, degrade_bounds(H, W) if rect else None, idx.device)
+                                                     rect, H, W, degrade_bounds(H, W) if rect else None, idx.device,
+                                                     **self.degrade.model_kw)
             yield (noisy, clean) if self.degrade.pairs else clean
 
 
 def get_dataset_loaders(path, batch_size=64, train_p=0.9, dataset_size=None, device="cuda", rank=0, world=1,
                         workers=None, dataset_type="HQ", image_size=(64, 64), noise_max_std=None, rect=True,
-                        normalize=None, resize_on="host"):
+                        normalize=None, resize_on="host", noise_model="gaussian", impulse_max_p=0.0, salt_ratio=0.5):
     """dataset_code.py:167-178 -> (train_loader, test_loader, image_shape).
     dataset_type 'HQ' (:168-169): the files as they are, values (u/255 - 0.5)/0.5.  'LQ' (:170-171, CelebADatasetV0):
     Resize + CenterCrop to image_size, values u/255; resize_on="host": at decode time with PIL, "device": the files are
@@ -420,10 +456,12 @@ def get_dataset_loaders(path, batch_size=64, train_p=0.9, dataset_size=None, dev
     unless dataset_type is 'LQ' and resize_on="device": then it is taken as a raw set and ``path.resized(image_size)`` is
     what the loaders serve -- one raw resident set feeds every member of the size family.
     normalize overrides the value mapping (default: True for 'HQ', False for 'LQ').  noise_max_std set: both loaders
-    yield (noisy, clean) pairs with `rect` (the call the reference's own test script asks for, main_vae.py:240).
+    yield (noisy, clean) pairs with `rect` (the call the reference's own test script asks for, main_vae.py:240);
+    noise_model / impulse_max_p / salt_ratio are ``Degrade``'s (not in the reference; the defaults are its model).
     The defaults are the 'HQ' clean-batch loaders."""
     if dataset_type not in ("HQ", "LQ"):
         raise ValueError("dataset_type must be 'HQ' or 'LQ'")
+    model = Degrade(noise_max_std, rect, True, noise_model, impulse_max_p, salt_ratio)      # validates before any decoding
     lq = dataset_type == "LQ"
     on_device = _check_resize_on(resize_on)
     if isinstance(path, ResidentImages):
@@ -431,7 +469,8 @@ def get_dataset_loaders(path, batch_size=64, train_p=0.9, dataset_size=None, dev
     else:
         ds = ResidentImages.from_folder(path, dataset_size, device, workers, image_size if lq else None, resize_on)
     normalize = (not lq) if normalize is None else bool(normalize)
-    degrade = None if (noise_max_std is None and normalize) else Degrade(noise_max_std, rect, normalize)
+    degrade = None if (noise_max_std is None and normalize) else Degrade(noise_max_std, rect, normalize, model.noise_model,
+                                                                         model.impulse_max_p, model.salt_ratio)
     train_idx, test_idx = random_split_indices(len(ds), train_p)
     train = DeviceLoader(ds, train_idx, batch_size, shuffle=True, rank=rank, world=world, degrade=degrade)
     test = DeviceLoader(ds, test_idx, batch_size, shuffle=False, rank=rank, world=world, degrade=degrade)

@@ -13,7 +13,7 @@ import torch
 from . import geometry as G
 from . import ops
 from . import tiling
-from .baselines import NLMeans, make_baseline
+from .baselines import NLMeans, check_oracle_sigma, make_baseline
 from .capture import HostMirrors, capture, replay
 from .engine import GradSink
 from .metrics import FeaturePass
@@ -291,8 +291,12 @@ def paired_test_epoch(encoder, decoder, loader: Iterable, n_samples: Optional[in
     output vs ``clean`` (with ms_ssim=True also ``ms_ssim_nlm``, with regions=True also the five region keys suffixed
     ``_nlm``), accumulated on the device and read in the same host sync.  ``sigma="oracle"`` (NLMeans' default) reads the
     noise level the loader drew per image, ``loader.last_rects[:, 1]``, in place: it needs a degraded loader, whose
-    ``want_rects`` the pass turns on and restores; ``"estimate"`` (blind, ops.noise_sigma) and a number need no rectangles."""
+    ``want_rects`` the pass turns on and restores; ``"estimate"`` (blind, ops.noise_sigma) and a number need no rectangles.
+    That level is a Gaussian sigma only under the default ``Degrade``: with another noise_model or with impulses "oracle" raises
+    ValueError.  A ``baselines.Median``, "median" or ``{"radius": r}`` runs the median filter instead -- the baseline that means
+    something under impulse noise -- and the same keys come suffixed ``_median``."""
     nlm = make_baseline("paired_test_epoch", baseline)
+    check_oracle_sigma("paired_test_epoch", nlm, loader)
     refiner = None
     if refine is not None:
         if isinstance(refine, LatentRefiner):
@@ -313,7 +317,7 @@ def paired_test_epoch(encoder, decoder, loader: Iterable, n_samples: Optional[in
     dt, L = encoder._dt, encoder.latent_dim
     recon_q, noisy_q = _Quality("", ms_ssim, regions), _Quality("_noisy", ms_ssim, regions)
     refined_q = _Quality("_refined", False, regions) if refiner is not None else None
-    nlm_q = _Quality("_nlm", ms_ssim, regions) if nlm is not None else None
+    nlm_q = _Quality("_" + nlm.name, ms_ssim, regions) if nlm is not None else None
     qs = [q for q in (recon_q, noisy_q, refined_q, nlm_q) if q is not None]
     sums = _allocate(dev, 2, qs)                                                     # [sum(mse_sum + kl), sum(kl)], the candidates'
     seen = batches = 0
@@ -709,9 +713,10 @@ def tiled_test_epoch(encoder, decoder, pairs: Iterable, ms_ssim: bool = False, b
     baseline (default None: nothing changes): as in paired_test_epoch, a ``baselines.NLMeans``, "nlm" or a dict of its keywords;
     here there are whole large images and no loader, so the noise level is ``sigma="estimate"`` (what "nlm" means here) or a
     number -- "oracle" is refused.  The filter runs on the full H x W image, no tiling, and the result gains ``recon_loss_nlm``,
-    ``ssim_nlm``, ``psnr_nlm`` (and ``ms_ssim_nlm`` with ms_ssim=True), read in the same sync."""
+    ``ssim_nlm``, ``psnr_nlm`` (and ``ms_ssim_nlm`` with ms_ssim=True), read in the same sync.  A ``baselines.Median``, "median" or
+    ``{"radius": r}``: the median filter, keys suffixed ``_median``."""
     nlm = make_baseline("tiled_test_epoch", baseline, allow_oracle=False)
-    qs = [_Quality("", ms_ssim), _Quality("_noisy", ms_ssim)] + ([_Quality("_nlm", ms_ssim)] if nlm is not None else [])
+    qs = [_Quality("", ms_ssim), _Quality("_noisy", ms_ssim)] + ([_Quality("_" + nlm.name, ms_ssim)] if nlm is not None else [])
     sums, seen, tiles = None, 0, 0
     for noisy, clean in pairs:
         if not (noisy.is_cuda and clean.is_cuda):

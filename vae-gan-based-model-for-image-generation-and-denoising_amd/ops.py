@@ -846,7 +846,9 @@ def resize_u8(images_u8, geometry, idx=None, out=None, band=0):
 
 # draw ids of the degraded-pair data path (include/vaegan_hip.h "Degraded pairs"; 0..2 belong to the training iteration)
 DRAW_DEGRADE_NORMAL, DRAW_DEGRADE_FILL, DRAW_DEGRADE_PARAMS = 16, 17, 18
+DRAW_DEGRADE_IMPULSE, DRAW_DEGRADE_SALT = 19, 20
 _NO_BOUNDS = (0, 0, 0, 0, 0, 0)
+NOISE_KIND = {"gaussian": L.VG_NOISE_GAUSSIAN, "speckle": L.VG_NOISE_SPECKLE, "shot": L.VG_NOISE_SHOT}
 
 
 def rand_u01(n: int, state: torch.Tensor, draw: int, out=None) -> torch.Tensor:
@@ -872,12 +874,28 @@ def _degrade_bounds(rect, bounds):
     return tuple(int(v) for v in bounds)
 
 
+def _noise_model(what, kind, impulse_max_p, salt_ratio):
+    """-> None for the reference's model (the old entry points serve it), else (kind id, impulse_max_p, salt_ratio)."""
+    if kind not in NOISE_KIND:
+        raise ValueError(f"{what}: kind must be 'gaussian', 'speckle' or 'shot', got {kind!r}")
+    for name, v in (("impulse_max_p", impulse_max_p), ("salt_ratio", salt_ratio)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0.0 <= v <= 1.0:
+            raise ValueError(f"{what}: {name} must be a number in [0, 1], got {v!r}")
+    if kind == "gaussian" and impulse_max_p == 0:
+        return None
+    return NOISE_KIND[kind], float(impulse_max_p), float(salt_ratio)
+
+
 def gather_degrade_u8(images_u8, idx, seed, pos0, noise_max_std, rect, normalize, bounds=None, out_clean=None,
-                      out_noisy=None, nhwc=None):
+                      out_noisy=None, nhwc=None, kind="gaussian", impulse_max_p=0.0, salt_ratio=0.5):
     """(noisy, clean) pair batch in one pass over the resident u8 set (vg_gather_degrade_u8; dataset_code.py:35-65).
     images_u8 [N,H,W,C] uint8, idx [B] int64, both on the device; seed / pos0: python ints, pos0 = position of idx[0]
     in the epoch's order.  nhwc: None, or (CP, dtype) / a preallocated [B,H,W,CP] engine tensor that also receives
-    `noisy` in the Encoder's input layout.  -> (noisy NCHW f32, clean NCHW f32, nhwc tensor or None)."""
+    `noisy` in the Encoder's input layout.  kind / impulse_max_p / salt_ratio: the noise model (include/vaegan_hip.h "Degraded
+    pairs", noise models) -- "gaussian" | "speckle" | "shot", plus salt-and-pepper impulses with per-image probability
+    s * impulse_max_p; the defaults are the reference's model and call the entry point they always called, anything else
+    goes to vg_gather_degrade_u8_ex.  -> (noisy NCHW f32, clean NCHW f32, nhwc tensor or None)."""
+    model = _noise_model("gather_degrade_u8", kind, impulse_max_p, salt_ratio)
     _need_cuda(images_u8, idx, out_clean, out_noisy, nhwc if isinstance(nhwc, torch.Tensor) else None)
     if images_u8.dtype != torch.uint8 or idx.dtype != torch.int64 or images_u8.dim() != 4:
         raise RuntimeError("gather_degrade_u8: images must be uint8 [N,H,W,C], idx int64 [B]")
@@ -900,21 +918,29 @@ def gather_degrade_u8(images_u8, idx, seed, pos0, noise_max_std, rect, normalize
     for t in (clean, noisy):
         if tuple(t.shape) != (B, C, H, W) or t.dtype != torch.float32:
             raise RuntimeError("gather_degrade_u8: outputs must be f32 [B,C,H,W]")
-    L.check(L.load().vg_gather_degrade_u8(images_u8.data_ptr(), N, idx.data_ptr(), B, C, H, W, int(seed), int(pos0),
-                                          float(noise_max_std), 1 if rect else 0, 1 if normalize else 0,
-                                          *_degrade_bounds(rect, bounds), clean.data_ptr(), noisy.data_ptr(), L.ptr(y), CP,
-                                          dtype, L.stream_ptr()), "vg_gather_degrade_u8")
+    args = (images_u8.data_ptr(), N, idx.data_ptr(), B, C, H, W, int(seed), int(pos0), float(noise_max_std), 1 if rect else 0,
+            1 if normalize else 0, *_degrade_bounds(rect, bounds), clean.data_ptr(), noisy.data_ptr(), L.ptr(y), CP, dtype)
+    if model is None:
+        L.check(L.load().vg_gather_degrade_u8(*args, L.stream_ptr()), "vg_gather_degrade_u8")
+    else:
+        L.check(L.load().vg_gather_degrade_u8_ex(*args, *model, L.stream_ptr()), "vg_gather_degrade_u8_ex")
     return noisy, clean, y
 
 
-def degrade_params(seed, pos0, B, noise_max_std, rect, H, W, bounds=None, device="cuda") -> torch.Tensor:
-    """-> f32 [B,8] on the device: s, sigma = s*noise_max_std, rect_h, rect_w, x, y, 0, 0 of epoch positions
-    pos0 .. pos0+B-1 (vg_degrade_params): what gather_degrade_u8 uses for the same seed and positions."""
+def degrade_params(seed, pos0, B, noise_max_std, rect, H, W, bounds=None, device="cuda", kind="gaussian", impulse_max_p=0.0,
+                   salt_ratio=0.5) -> torch.Tensor:
+    """-> f32 [B,8] on the device: s, sigma = s*noise_max_std, rect_h, rect_w, x, y, p = s*impulse_max_p, kind id of epoch
+    positions pos0 .. pos0+B-1 (vg_degrade_params; vg_degrade_params_ex for another noise model than the default, whose last
+    two columns are 0, 0): what gather_degrade_u8 uses for the same seed and positions."""
+    model = _noise_model("degrade_params", kind, impulse_max_p, salt_ratio)
     out = torch.empty(B, 8, dtype=torch.float32, device=device)
     _need_cuda(out)
     _degrade_key(seed, pos0)
-    L.check(L.load().vg_degrade_params(int(seed), int(pos0), B, float(noise_max_std), 1 if rect else 0, H, W,
-                                       *_degrade_bounds(rect, bounds), out.data_ptr(), L.stream_ptr()), "vg_degrade_params")
+    args = (int(seed), int(pos0), B, float(noise_max_std), 1 if rect else 0, H, W, *_degrade_bounds(rect, bounds), out.data_ptr())
+    if model is None:
+        L.check(L.load().vg_degrade_params(*args, L.stream_ptr()), "vg_degrade_params")
+    else:
+        L.check(L.load().vg_degrade_params_ex(*args, *model, L.stream_ptr()), "vg_degrade_params_ex")
     return out
 
 
@@ -1895,6 +1921,26 @@ def noise_sigma(x, out=None):
     L.check(L.load().vg_noise_sigma(x.data_ptr(), B, C, H, W, s.data_ptr(), s.stride(0) if B > 1 else 1, L.stream_ptr()),
             "vg_noise_sigma")
     return s
+
+
+def median_filter(x, radius=1, out=None):
+    """Per-channel (2r+1)^2 median of an f32 [B,C,H,W] batch, r = radius in {1, 2} (vg_median_filter): reflect padding as
+    nlm_denoise, min(H, W) >= r + 1; the output is one of the window's values, exact for finite inputs.  One launch, no host
+    synchronisation, no atomics.  -> out (f32 of x's shape, contiguous, not x) or a new tensor."""
+    what = "median_filter"
+    _need_cuda(x, out)
+    if x.dtype != torch.float32 or x.dim() != 4:
+        raise RuntimeError(f"{what}: x must be an f32 [B,C,H,W] tensor")
+    if isinstance(radius, bool) or not isinstance(radius, int):
+        raise RuntimeError(f"{what}: radius must be an integer")
+    x = x.contiguous()
+    B, C, H, W = x.shape
+    if out is not None and (out.dtype != torch.float32 or out.shape != x.shape or out.device != x.device or
+                            not out.is_contiguous()):
+        raise RuntimeError(f"{what}: out must be contiguous f32 of x's shape on x's device")
+    y = out if out is not None else torch.empty_like(x)
+    L.check(L.load().vg_median_filter(x.data_ptr(), y.data_ptr(), B, C, H, W, radius, L.stream_ptr()), "vg_median_filter")
+    return y
 
 
 LATENT_MODE = {"init": L.VG_LATENT_INIT, "update": L.VG_LATENT_UPDATE, "track": L.VG_LATENT_TRACK}
