@@ -3,7 +3,12 @@ against the numpy restatement tests/_tiling_ref.py.  The gather and the exact-in
 that every product and partial sum of theirs is an f32 number) are compared bit for bit; random inputs within the bound
 counted from the roundings (_tiling_ref.blend_bound).  No expectation is taken from the kernel under test.  Every kernel
 output is a NaN-filled slice of a larger NaN-filled buffer: a stale right answer in recycled memory cannot pass, and a store
-before or past the output shows in the guard rows."""
+before or past the output shows in the guard rows.
+Beyond the small shapes: the blend past one workgroup along x and y and over every table width (the cases of
+_tiling_ref.BLEND_CASES, whose reasons tests/test_tiling_cpu.py asserts), the gather at the engines' tile sizes 64, 128, 256
+and with pixels of two 16-byte units, the header's "Table safety" promise entry by entry, a graph replay, and S = 128 end to
+end.  Not covered: S = 256 end to end, table entries of large magnitude, and tensors of more than 2^31 elements (the 64-bit
+offsets of the blend): the first two for the reasons given at their tests, the last because it needs gigabytes per case."""
 import numpy as np
 import pytest
 import torch
@@ -172,14 +177,243 @@ def test_round_trip_gather_then_blend_returns_the_image():
     assert err <= R.blend_bound(p, float(np.abs(img).max()))
 
 
+# ---- blend past one workgroup and over the whole table width ---------------------------------------------------------
+def case_id(c):
+    return "x".join(map(str, c))
+
+
+WIDE_CASES = [(c, 0) for c in R.BLEND_CASES] + [(c, 1) for c, q in R.BLEND_CASES.items() if q["vector_store"]]
+
+
+@pytest.mark.parametrize("case,shift", WIDE_CASES, ids=[case_id(c) + ("_shifted" if s else "") for c, s in WIDE_CASES])
+def test_blend_past_one_workgroup_and_over_the_whole_table_width(case, shift):
+    """Every case of _tiling_ref.BLEND_CASES (tests/test_tiling_cpu.py asserts what each reaches: a second and third workgroup
+    along x, a second to ninth along y, x tables of 2 to 8 slots, whole and straddling groups in one launch at S = 64, 128,
+    256), hann, N = 2 (1 at S = 256), C = 3, tiles uniform in [-1, 1]: bit for bit against the f32 restatement, within the
+    counted bound of the f64 one, guards intact, a second launch the same bits.  The W % 4 == 0 cases run again with the
+    output off 16-byte alignment: the scalar stores on the data of the vector stores.
+    Bound (cover_y + cover_x + 3) 2^-24 max|r| (_tiling_ref.blend_bound).  Measured on the MI355X, error / bound in the
+    table's order: 0.30, 0.23, 0.30, 0.21, 0.21, 0.14, 0.097, 0.10, 0.26, 0.27, 0.29 (errors 1.1e-7 to 1.4e-7; the shifted
+    runs give the figures of the unshifted ones, being the same bits)."""
+    H, W, S, stride = case
+    p = R.plan(H, W, S, stride)
+    N, C = (1 if S == 256 else 2), 3
+    tiles = R.uniform_tiles(p, N, C, seed=H + W)
+    got = blend(p, tiles, N, C, shift)
+    err = np.abs(got.astype(np.float64) - R.blend_f64(p, tiles)).max()
+    bound = R.blend_bound(p, float(np.abs(tiles).max()))
+    print("blend vs f64:", case, "shift", shift, "max error", err, "bound", bound, "ratio", err / bound)
+    assert np.array_equal(bits(got), bits(R.blend_f32_fast(p, tiles)))
+    assert err <= bound
+    assert np.array_equal(bits(blend(p, tiles, N, C, shift)), bits(got))
+
+
+# ---- gather at every engine's tile size ------------------------------------------------------------------------------
+def gather_source(src, N, C, H, W, seed):
+    rng = np.random.default_rng(seed)
+    if src == "u8":
+        host = rng.integers(0, 256, size=(N, H, W, C), dtype=np.uint8)
+        host[0, 0, 0, :], host[-1, -1, -1, :] = 0, 255
+        return host, dict(images_u8=host)
+    host = rng.uniform(-1, 1, size=(N, C, H, W)).astype(np.float32)
+    return host, dict(images_f32=host)
+
+
+@pytest.mark.parametrize("dt", [G.F32, G.BF16], ids=["f32", "bf16"])
+@pytest.mark.parametrize("src", ["u8", "f32"])
+@pytest.mark.parametrize("case", list(R.GATHER_CASES), ids=case_id)
+def test_gather_at_the_engines_tile_sizes(case, src, dt):
+    """S = 64, 128, 256 (grid.z 1, 2, 4), two images a few pixels larger than S with odd flush origins on both axes; the chunk
+    is the last two tiles of image 0 and the first of image 1: it straddles the images and ends short of the list."""
+    H, W, S = case
+    p, plan = R.plan(H, W, S), T.tile_plan(H, W, S)
+    per, C = p.ny * p.nx, 3
+    t0, B, CP = per - 2, 3, G.padc(C, dt)
+    host, kw = gather_source(src, 2, C, H, W, seed=S)
+    want = R.gather(p, t0, B, CP, **kw)
+    images = torch.from_numpy(host).to(DEV)
+    n = B * S * S * CP
+    buf, out = guarded(n, ops.TORCH_DT[dt])
+    got = ops.tile_gather(images, plan, t0, B, CP, dt, out=out.view(B, S, S, CP))
+    assert guards_intact(buf, n)
+    gb = act_bits(got, dt)
+    assert np.array_equal(gb, want_bits(want, dt))
+    assert not np.any(gb[..., C:])                                        # pad channels are zero bits
+    for b in (0, 1, 2):                                                    # first, last of image 0, first of image 1 (= last)
+        n_img, k = divmod(t0 + b, per)
+        assert n_img == (b == 2)
+        ky, kx = divmod(k, p.nx)
+        y0, x0 = int(p.oy[ky]), int(p.ox[kx])
+        if src == "u8":
+            crop = images[n_img, y0:y0 + S, x0:x0 + S, :].contiguous()[None]
+            x = ops.gather_normalize_u8(crop, torch.zeros(1, dtype=torch.int64, device=DEV))
+        else:
+            x = images[n_img:n_img + 1, :, y0:y0 + S, x0:x0 + S].contiguous()
+        assert np.array_equal(act_bits(ops.nchw_to_nhwc(x, CP, dt), dt)[0], gb[b]), b
+
+
+@pytest.mark.parametrize("src", ["u8", "f32"])
+@pytest.mark.parametrize("dt,C,CP", [(G.F32, 5, 8), (G.BF16, 9, 16)], ids=["f32_C5_CP8", "bf16_C9_CP16"])
+def test_gather_of_pixels_wider_than_one_16_byte_unit(dt, C, CP, src):
+    """Two trips of the channel loop; the pad channels are in the last unit only, next to a real channel."""
+    p, plan = R.plan(GH, GW, GS, GSTRIDE), T.tile_plan(GH, GW, GS, GSTRIDE)
+    assert G.per16(dt) < C < CP == 2 * G.per16(dt)
+    t0, B = 4, 5
+    host, kw = gather_source(src, 2, C, GH, GW, seed=C)
+    want = R.gather(p, t0, B, CP, **kw)
+    n = B * GS * GS * CP
+    buf, out = guarded(n, ops.TORCH_DT[dt])
+    got = ops.tile_gather(torch.from_numpy(host).to(DEV), plan, t0, B, CP, dt, out=out.view(B, GS, GS, CP))
+    assert guards_intact(buf, n)
+    gb = act_bits(got, dt)
+    assert np.array_equal(gb[..., :C], want_bits(want, dt)[..., :C]) and np.any(gb[..., C - 1])
+    assert not np.any(gb[..., C:])                                        # every pad channel is zero bits
+
+
+# ---- table safety ---------------------------------------------------------------------------------------------------
+L = ops.L                                                # the ctypes face of the library: the C entry points themselves
+TABLE_PAD = 16                                           # guard elements around every table (the furthest table access is 1 out)
+
+
+def guarded_table(a, before, after):
+    """A host table inside a sentinel-filled device allocation -> (allocation, its host image, the table's slice)."""
+    a = np.ascontiguousarray(a)
+    host = np.concatenate([np.full(TABLE_PAD, before, a.dtype), a.ravel(), np.full(TABLE_PAD, after, a.dtype)])
+    buf = torch.from_numpy(host).to(DEV)
+    return buf, host, buf[TABLE_PAD:TABLE_PAD + a.size]
+
+
+def guarded_tables(q):
+    """The eight tables of q in guarded device memory.  Sentinels: an origin read one before its table is 0 and one behind it
+    is the flush origin L - S, so that the local coordinate formed from it is a valid one and cannot hide a missing tile-index
+    check behind the local-coordinate check; coefficients NaN; first / count (indexed by the coordinate only) 0."""
+    nan = float("nan")
+    spec = dict(oy=(0, q.H - q.S), ox=(0, q.W - q.S), first_y=(0, 0), count_y=(0, 0), first_x=(0, 0), count_x=(0, 0),
+                coef_y=(nan, nan), coef_x=(nan, nan))
+    return {k: guarded_table(getattr(q, k), *spec[k]) for k in spec}
+
+
+def tables_untouched(tabs):
+    return all(np.array_equal(bits(buf.cpu().numpy()), bits(host)) for buf, host, _ in tabs.values())
+
+
+@pytest.mark.parametrize("edit", R.BLEND_EDIT_NAMES)
+@pytest.mark.parametrize("path", ["reg", "wide"])
+def test_blend_gives_the_promised_result_for_bad_table_entries(path, edit):
+    """include/vaegan_hip.h, "Table safety": count clamped to [0, width]; a tile index outside [0, ny) / [0, nx) or a local
+    coordinate outside [0, S) drops the term.  One kind of bad entry per case (_tiling_ref.blend_table_edits), over the x
+    tables held in registers ("reg": every group whole, so the check of the whole-group path has to refuse and the scalar
+    path has to drop) and the wide ones read one float at a time.  Expected: the restatement applying those words.
+    Every bad entry is off by one, and the tile buffer, the output and the tables are slices of larger allocations whose
+    guards reach at least as far as the furthest address a kernel without that check could form from the entry (reach, worked
+    out per entry in blend_table_edits, computed by an unchecked host emulation in tests/test_tiling_cpu.py, and held against
+    the guard below).  Such a kernel reads a NaN guard or a neighbouring tile and fails the comparison; it does not leave its
+    allocations.  Left out: entries whose unchecked address has no such bound -- large magnitudes like INT_MAX, where
+    first + j or the offset arithmetic itself may wrap."""
+    p = R.safety_plan(path)
+    N, C, S = 2, 2, p.S
+    q, reach = R.blend_table_edits(p, C)[edit]
+    tiles = R.uniform_tiles(p, N, C, seed=41)
+    want = R.blend_f32_table_safe(q, tiles)
+    guard = (p.nx + 1) * C * S * S                                         # floats on either side of the tile buffer
+    assert reach <= guard
+    tbuf = torch.full((tiles.size + 2 * guard,), float("nan"), dtype=torch.float32, device=DEV)
+    tdev = tbuf[guard:guard + tiles.size]
+    tdev.copy_(torch.from_numpy(tiles).reshape(-1))
+    tabs = guarded_tables(q)
+    ptr = {k: v[2].data_ptr() for k, v in tabs.items()}
+    n = N * C * p.H * p.W
+    obuf, out = guarded(n)
+    L.check(L.load().vg_tile_blend(tdev.data_ptr(), out.data_ptr(), N, C, p.H, p.W, S, p.ny, p.nx, ptr["oy"], ptr["ox"],
+                                   ptr["first_y"], ptr["count_y"], ptr["coef_y"], q.coef_y.shape[1], ptr["first_x"],
+                                   ptr["count_x"], ptr["coef_x"], q.coef_x.shape[1], L.stream_ptr()), "vg_tile_blend")
+    got = out.cpu().numpy().reshape(N, C, p.H, p.W)
+    assert guards_intact(obuf, n) and tables_untouched(tabs)
+    assert bool(torch.isnan(tbuf[:guard]).all() and torch.isnan(tbuf[guard + tiles.size:]).all())
+    assert np.isfinite(got).all(), np.argwhere(~np.isfinite(got))[:4]
+    assert np.array_equal(bits(got), bits(want)), np.argwhere(bits(got) != bits(want))[:4]
+
+
+@pytest.mark.parametrize("edit", R.GATHER_EDIT_NAMES)
+@pytest.mark.parametrize("src", ["u8", "f32"])
+def test_gather_writes_a_zero_tile_for_an_origin_off_the_image(src, edit):
+    """"An origin outside the image writes a zero tile": one origin at -1 or L - S + 1 per case (both axes), all 12 tiles of two
+    images gathered; the tiles of that origin are zero bits, the others what they were.  The image set is a slice of a larger
+    allocation (NaN for f32, 255 for u8) with 2 W C elements on either side: a kernel without the check reads at most one row
+    (W pixels; C bytes each in the u8 set) before image 0 or behind the last image, and writes a non-zero tile."""
+    p = R.plan(GH, GW, GS, GSTRIDE)
+    q, reach = R.gather_origin_edits(p)[edit]
+    N, C, CP, B = 2, 3, 4, 12
+    host, kw = gather_source(src, N, C, GH, GW, seed=5)
+    want = R.gather_table_safe(q, 0, B, CP, **kw)
+    guard = 2 * GW * C
+    assert reach * (C if src == "u8" else 1) <= guard
+    sbuf = torch.full((host.size + 2 * guard,), 255 if src == "u8" else float("nan"),
+                      dtype=torch.uint8 if src == "u8" else torch.float32, device=DEV)
+    sdev = sbuf[guard:guard + host.size]
+    sdev.copy_(torch.from_numpy(host).reshape(-1))
+    oy, ox = guarded_table(q.oy, 0, GH - GS), guarded_table(q.ox, 0, GW - GS)
+    n = B * GS * GS * CP
+    obuf, out = guarded(n)
+    L.check(L.load().vg_tile_gather(sdev.data_ptr() if src == "u8" else None, None if src == "u8" else sdev.data_ptr(), N, C, GH, GW,
+                                    GS, p.ny, p.nx, oy[2].data_ptr(), ox[2].data_ptr(), 0, B, out.data_ptr(), CP, G.F32,
+                                    L.stream_ptr()), "vg_tile_gather")
+    got = out.cpu().numpy().reshape(B, GS, GS, CP)
+    assert guards_intact(obuf, n) and tables_untouched(dict(oy=oy, ox=ox))
+    assert np.array_equal(bits(got), bits(want))
+    zero = [b for b in range(B) if not bits(got[b]).any()]
+    assert len(zero) == {"oy": 2 * p.nx, "ox": 2 * p.ny}[edit[:2]]
+
+
+# ---- graph replay ---------------------------------------------------------------------------------------------------
+def test_gather_and_blend_replay_from_a_graph():
+    """(101, 83), S = 64, stride 32, N = 2: vg_tile_gather -> vg_nhwc_to_nchw -> vg_tile_blend captured on one side stream into
+    NaN-filled buffers (the tables uploaded by the eager run before).  One replay gives the eager bits, which are those of the
+    restatement: the gather copies, the blend of the copied tiles in f32."""
+    H, W, S, stride = 101, 83, 64, 32
+    p, plan = R.plan(H, W, S, stride), T.tile_plan(H, W, S, stride)
+    N, C, CP = 2, 3, 4
+    Tn = N * p.ny * p.nx
+    img = np.random.default_rng(9).uniform(-1, 1, size=(N, C, H, W)).astype(np.float32)
+    x = torch.from_numpy(img).to(DEV)
+    nan = float("nan")
+
+    def run(nhwc, tiles, out):
+        ops.tile_gather(x, plan, 0, Tn, CP, G.F32, out=nhwc)
+        ops.nhwc_to_nchw(nhwc, C, G.F32, out=tiles)
+        return ops.tile_blend(tiles, plan, out=out)
+
+    def buffers():
+        return (torch.full((Tn, S, S, CP), nan, device=DEV), torch.full((Tn, C, S, S), nan, device=DEV), guarded(img.size))
+    nhwc, tiles, (buf, out) = buffers()
+    eager = run(nhwc, tiles, out.view(N, C, H, W)).cpu().numpy()
+    assert guards_intact(buf, img.size)
+    want_tiles = np.ascontiguousarray(np.transpose(R.gather(p, 0, Tn, CP, images_f32=img)[..., :C], (0, 3, 1, 2)))
+    assert np.array_equal(bits(tiles.cpu().numpy()), bits(want_tiles))
+    assert np.array_equal(bits(eager), bits(R.blend_f32_fast(p, want_tiles)))
+    nhwc_g, tiles_g, (buf_g, out_g) = buffers()
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.stream(s):
+        with torch.cuda.graph(g, stream=s):                                       # one stream, no parallel branches
+            run(nhwc_g, tiles_g, out_g.view(N, C, H, W))
+    torch.cuda.current_stream().wait_stream(s)
+    g.replay()
+    torch.cuda.synchronize()
+    assert guards_intact(buf_g, img.size)
+    assert np.array_equal(bits(tiles_g.cpu().numpy()), bits(want_tiles))
+    assert np.array_equal(bits(out_g.cpu().numpy().reshape(N, C, H, W)), bits(eager))
+
+
 # ---- end to end ---------------------------------------------------------------------------------------------------
 S64 = 64
 
 
-def make_nets(dtype="fp32"):
+def make_nets(dtype="fp32", S=S64):
     V.configure_seed(42)
-    e = V.Encoder([3, S64, S64], 100, dtype=dtype)
-    g = V.Generator(nz=100, img_size=S64, dtype=dtype)
+    e = V.Encoder([3, S, S], 100, dtype=dtype)
+    g = V.Generator(nz=100, img_size=S, dtype=dtype)
     g.apply(V.weights_init)
     e.to(DEV), g.to(DEV)
     return e, g
@@ -311,6 +545,37 @@ def test_bf16_engines_run_and_stay_in_range():
     u8 = torch.randint(0, 256, (1, 70, 90, 3), dtype=torch.uint8, generator=torch.Generator().manual_seed(31)).to(DEV)
     out = V.denoise_tiled(e, g, u8, window="tri", sample=False)
     assert out.shape == (1, 3, 70, 90) and bool(torch.isfinite(out).all()) and float(out.abs().max()) <= 1.0
+
+
+def test_denoise_tiled_at_s128_equals_the_loop_from_public_pieces():
+    """The twin of the S = 64 test with the S = 128 engines (gather grid.z 2): 3 x 150 x 203, default stride 64: 2 x 3 tiles,
+    x origins 0, 64, 75 (the flush one odd), batch=4 -> chunks of 4 + 2.  Bit for bit against the f32 restatement of the loop's
+    tiles; against the f64 one within the counted bound (covers 2 + 3, k = 3: 8 * 2^-24 = 4.77e-7 with |r| <= 1).
+    Measured on the MI355X: 3.8e-10, error / bound 7.9e-4 (the tiles of the untrained networks are below 4e-3).  S = 256 end to end is left out (two more engines to build for a blend and a gather
+    whose grids the kernel-level cases above already reach)."""
+    S, H, W = 128, 150, 203
+    e, g = make_nets(S=S)
+    p = R.plan(H, W, S)
+    assert (p.ny, p.nx) == (2, 3) and p.oy.tolist() == [0, 22] and p.ox.tolist() == [0, 64, 75] and p.stride == 64
+    img = image(1, H, W, 40)
+    eps_z = normal((6, 100), 41)
+    got = V.denoise_tiled(e, g, img, batch=4, eps_z=eps_z)
+    assert not e.training and not g.training
+    crops = torch.stack([img[0, :, y0:y0 + S, x0:x0 + S] for y0 in p.oy for x0 in p.ox]).contiguous()
+    recon = torch.cat([V.denoise_eval(e, g, crops[a:b], noisy=crops[a:b], eps_z=eps_z[a:b])["recon"] for a, b in ((0, 4), (4, 6))])
+    tiles = recon.cpu().numpy()
+    assert got.shape == (1, 3, H, W) and got.dtype == torch.float32
+    err = np.abs(got.cpu().numpy().astype(np.float64) - R.blend_f64(p, tiles)).max()
+    print("S = 128 end to end vs the f64 blend of the loop's tiles: max error", err, "bound", R.blend_bound(p, 1.0),
+          "ratio", err / R.blend_bound(p, 1.0), "max|tile|", float(np.abs(tiles).max()))
+    assert float(np.abs(tiles).max()) <= 1.0 and err <= R.blend_bound(p, 1.0)
+    assert np.array_equal(bits(got.cpu().numpy()), bits(R.blend_f32_fast(p, tiles)))
+
+
+def test_bf16_engines_at_s128_run_and_stay_in_range():
+    e, g = make_nets("bf16", S=128)
+    out = V.denoise_tiled(e, g, image(1, 150, 203, 42), batch=4)
+    assert out.shape == (1, 3, 150, 203) and bool(torch.isfinite(out).all()) and float(out.abs().max()) <= 1.0
 
 
 def test_refused_inputs_raise(nets):

@@ -1,7 +1,9 @@
 """CPU: tiled denoising before any kernel runs.  (1) tiling.tile_plan against the restatement tests/_tiling_ref.py: origins,
 cover ranges, coefficient rows, refused plans; (2) the f64 blend against torch's F.fold on uniform-stride geometries; (3) the
 exact-input cases of the GPU tests really are exact (every product and partial sum representable, held against Fraction
-arithmetic), so a bitwise comparison there has no blind spot; (4) the C ABI declarations, the ctypes table, host-side argument
+arithmetic), so a bitwise comparison there has no blind spot; (3b) the slot-vectorised restatement equals the pixel loop bit
+for bit, the large cases reach the launch geometry they are there for, and the bad-table cases stay inside their guards even
+for a blend without checks; (4) the C ABI declarations, the ctypes table, host-side argument
 validation of the two entry points, the package exports and the "no CPU path" errors."""
 import ctypes
 import math
@@ -188,6 +190,193 @@ def test_normalisation_restated_as_torch_does_it():
     assert np.array_equal(R.normalize_u8(u), want)
     x = np.array([1.0, -1.0, 0.1, 1.00390625, 1.01171875, 3.0e-40], dtype=np.float32)
     assert np.array_equal(R.bf16_round(x), torch.from_numpy(x).bfloat16().view(torch.int16).numpy().view(np.uint16))
+
+
+# ---- 3b. the restatement that scales, the case table, the bad tables ----------------------------------------------------
+def _loop_table_safe(p, tiles):
+    """blend_f32's pixel loop with the header's "Table safety" words written out: the form the slot-vectorised one is held to."""
+    S, per = p.S, p.ny * p.nx
+    N, C = tiles.shape[0] // per, tiles.shape[1]
+    wy, wx = p.coef_y.shape[1], p.coef_x.shape[1]
+    r = tiles.reshape(N, p.ny, p.nx, C, S, S)
+    out = np.zeros((N, C, p.H, p.W), dtype=np.float32)
+    for y in range(p.H):
+        for x in range(p.W):
+            acc = np.zeros((N, C), dtype=np.float32)
+            for jy in range(min(max(int(p.count_y[y]), 0), wy)):              # count clamped to [0, width]
+                ky = int(p.first_y[y]) + jy
+                if not 0 <= ky < p.ny or not 0 <= y - int(p.oy[ky]) < S:        # tile index / local coordinate: term dropped
+                    continue
+                inner = np.zeros((N, C), dtype=np.float32)
+                for jx in range(min(max(int(p.count_x[x]), 0), wx)):
+                    kx = int(p.first_x[x]) + jx
+                    if not 0 <= kx < p.nx or not 0 <= x - int(p.ox[kx]) < S:
+                        continue
+                    inner = inner + p.coef_x[x, jx] * r[:, ky, kx, :, y - p.oy[ky], x - p.ox[kx]]
+                acc = acc + p.coef_y[y, jy] * inner
+            out[:, :, y, x] = acc
+    return out
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+@pytest.mark.parametrize("H,W,S,stride,window", EXACT_CASES + [
+    (13, 37, 8, 3, "hann"), (37, 13, 8, 3, "hann"), (12, 24, 8, 3, "hann"),   # the cover count differs from coordinate to coordinate
+    (16, 15, 8, 1, "hann"), (37, 29, 8, 3, "tri")])
+def test_slot_vectorised_blend_equals_the_pixel_loop_bit_for_bit(H, W, S, stride, window):
+    p = R.plan(H, W, S, stride, window)
+    if (H, W) == (13, 37):
+        assert sorted(set(p.count_x.tolist())) == [1, 2, 3] and sorted(set(p.count_y.tolist())) == [1, 2, 3]
+    tiles = R.uniform_tiles(p, 2, 3, seed=H * W)
+    want = R.blend_f32(p, tiles)
+    assert np.array_equal(_bits(R.blend_f32_fast(p, tiles)), _bits(want))
+    assert np.array_equal(_bits(R.blend_f32_table_safe(p, tiles)), _bits(want))   # a sound table needs none of the clauses
+    assert np.array_equal(_bits(_loop_table_safe(p, tiles)), _bits(want))
+
+
+def test_slot_vectorised_blend_with_hand_made_tables_wider_than_the_cover():
+    p = R.dyadic_tables(R.plan(23, 9, 8, 2, "tri"), 5)
+    assert int(p.count_x.max()) == 2 and int(p.count_y.max()) == 5 and p.coef_x.shape[1] == 5
+    tiles = R.uniform_tiles(p, 2, 1, seed=3)
+    assert np.array_equal(_bits(R.blend_f32_fast(p, tiles)), _bits(R.blend_f32(p, tiles)))
+
+
+@pytest.mark.parametrize("case", list(R.BLEND_CASES), ids=lambda c: "x".join(map(str, c)))
+def test_blend_cases_reach_the_paths_they_are_there_for(case):
+    H, W, S, stride = case
+    p = R.plan(H, W, S, stride)
+    assert R.same_plan(p, T.tile_plan(H, W, S, stride))
+    got, want = R.case_properties(p), R.BLEND_CASES[case]
+    assert got == want, (got, want)
+    assert got["blend_grid"] == (math.ceil(H / 32), math.ceil(math.ceil(W / 4) / 64)) and got["gather_grid"][1] == math.ceil(S / 64)
+    if got["groups"] is not None:
+        assert sum(got["groups"]) == math.ceil(W / 4) and got["cover"][1] <= 4
+
+
+def test_the_case_table_as_a_whole_reaches_every_row_of_the_gap_list():
+    props = list(R.BLEND_CASES.values())
+    assert max(q["blend_grid"][1] for q in props) == 3 and max(q["blend_grid"][0] for q in props) == 9
+    assert {q["cover"][1] for q in props} >= {2, 3, 4, 8}
+    assert any(q["cover"] == (R.MAX_COVER, R.MAX_COVER) and not q["vector_store"] for q in props)
+    assert any(q["groups"] is None and q["vector_store"] for q in props)            # wide x table with the 16-byte store
+    for zgrid in (1, 2, 4):                                                          # S = 64, 128, 256
+        assert any(q["gather_grid"][1] == zgrid and q["groups"] and min(q["groups"]) > 0 for q in props)
+    # a second workgroup along x in each store form and in each read path
+    assert any(q["blend_grid"][1] > 1 and q["vector_store"] and q["groups"][1] == 0 for q in props)
+    assert any(q["blend_grid"][1] > 1 and not q["vector_store"] and q["groups"][0] == 0 for q in props)
+    assert any(q["blend_grid"][1] > 1 and q["cover"][1] == 4 for q in props)
+    assert R.case_properties(R.plan(12, 24, 8, 1))["cover"] == (5, 8)              # a real plan with 5 to 8 covering tiles
+
+
+@pytest.mark.parametrize("case", list(R.GATHER_CASES), ids=lambda c: "x".join(map(str, c)))
+def test_gather_cases_have_odd_flush_origins_and_the_engines_grid(case):
+    H, W, S = case
+    p, want = R.plan(H, W, S), R.GATHER_CASES[case]
+    assert p.oy.tolist() == want["oy"] and p.ox.tolist() == want["ox"] and p.oy[-1] % 2 == 1 and p.ox[-1] % 2 == 1
+    assert R.case_properties(p)["gather_grid"] == want["gather_grid"] == (math.ceil(S / 4), math.ceil(S / 64))
+    assert 2 * p.ny * p.nx <= 12 and (S < 256 or 2 * p.ny * p.nx <= 8)
+
+
+@pytest.mark.parametrize("path", ["reg", "wide"])
+def test_bad_table_entries_and_their_restatement(path):
+    """Every edit really holds the bad entry it is named for, is off by one only, changes the result where it should, and the
+    slot-vectorised table-safe restatement equals the pixel loop that spells the header's words out."""
+    p = R.safety_plan(path)
+    assert (p.coef_x.shape[1] <= 4) == (path == "reg")
+    if path == "reg":
+        assert R.group_kinds(p) == (p.W // 4, 0)
+    C = 2
+    tiles = R.uniform_tiles(p, 2, C, seed=17)
+    sound = R.blend_f32(p, tiles)
+    edits = R.blend_table_edits(p, C)
+    assert tuple(edits) == R.BLEND_EDIT_NAMES
+    for name, (q, reach) in edits.items():
+        want = _loop_table_safe(q, tiles)
+        assert np.array_equal(_bits(R.blend_f32_table_safe(q, tiles)), _bits(want)), name
+        assert np.isfinite(want).all() and not np.array_equal(_bits(want), _bits(sound)), name
+        assert 0 <= reach <= p.nx * C * p.S * p.S
+        for k in ("oy", "ox", "first_y", "first_x"):                        # off by one: no entry further than 1 from a sound one
+            assert np.abs(getattr(q, k).astype(np.int64) - getattr(p, k)).max() <= 1, (name, k)
+        assert (q.first_y + q.count_y).max() <= p.ny + 1 and (q.first_x + q.count_x).max() <= p.nx + 1
+        assert q.count_y.max() <= q.coef_y.shape[1] + 1 and q.count_x.max() <= q.coef_x.shape[1] + 1 and min(q.count_y.min(), q.count_x.min()) >= -1
+    q = edits["count=-1"][0]
+    want = R.blend_f32_table_safe(q, tiles)
+    assert not want[:, :, 2, :].any() and not want[:, :, :, 4:8].any()      # clamped to 0 terms: the element is 0
+    q = edits["first_x=-1"][0]
+    assert np.all(q.first_x[:4] == -1) and np.all(q.coef_x[:4] > 0)
+
+
+def _blend_without_any_check(q, tiles, guard):
+    """What a blend that formed its addresses WITHOUT the promised checks would do with q's tables, on the host: the tile
+    buffer between `guard` NaN floats, an origin read one outside its table giving the sentinel the GPU test puts there (0
+    before, L - S behind), a coefficient read behind its table NaN.  -> (result, furthest offset before the buffer, behind it)."""
+    S, SS, per = q.S, q.S * q.S, q.ny * q.nx
+    N, C = tiles.shape[0] // per, tiles.shape[1]
+    wy, wx = q.coef_y.shape[1], q.coef_x.shape[1]
+    flat = np.concatenate([np.full(guard, np.nan, np.float32), tiles.ravel(), np.full(guard, np.nan, np.float32)])
+    ky_flat, kx_flat = (np.concatenate([k.ravel(), np.full(16, np.nan, np.float32)]) for k in (q.coef_y, q.coef_x))
+    plane = (np.arange(N)[:, None] * per * C + np.arange(C)[None, :]) * SS                # [N, C]: tile 0 of image n, channel c
+
+    def origin(o, k, L):
+        return 0 if k < 0 else L - S if k >= o.size else int(o[k])
+    out = np.zeros((N, C, q.H, q.W), dtype=np.float32)
+    before = behind = 0
+    with np.errstate(invalid="ignore"):
+        for y in range(q.H):
+            for x in range(q.W):
+                acc = np.zeros((N, C), dtype=np.float32)
+                for jy in range(max(int(q.count_y[y]), 0)):
+                    ky = int(q.first_y[y]) + jy
+                    assert -1 <= ky <= q.ny and jy <= wy
+                    inner = np.zeros((N, C), dtype=np.float32)
+                    for jx in range(max(int(q.count_x[x]), 0)):
+                        kx = int(q.first_x[x]) + jx
+                        assert -1 <= kx <= q.nx and jx <= wx
+                        addr = plane + (ky * q.nx + kx) * C * SS + (y - origin(q.oy, ky, q.H)) * S + (x - origin(q.ox, kx, q.W))
+                        before, behind = max(before, -int(addr.min())), max(behind, int(addr.max()) - (tiles.size - 1))
+                        assert before <= guard and behind <= guard, "the guards of the GPU test would not hold this entry"
+                        inner = inner + kx_flat[x * wx + jx] * flat[guard + addr]
+                    acc = acc + ky_flat[y * wy + jy] * inner
+                out[:, :, y, x] = acc
+    return out, before, behind
+
+
+@pytest.mark.parametrize("path", ["reg", "wide"])
+def test_a_blend_without_the_checks_stays_inside_the_guards_and_fails_the_comparison(path):
+    """The design of the GPU table-safety test, computed instead of argued: for every edit, the addresses an unchecked blend
+    forms leave the tile buffer by exactly the edit's stated reach, which the guards cover, and its result differs from the
+    promised one (it read a NaN guard, a neighbouring tile or a coefficient of another slot), so the GPU comparison would fail
+    without an out-of-range access.  count = -1 needs no check to be safe: the loop simply does not run."""
+    p = R.safety_plan(path)
+    N, C = 2, 2
+    guard = (p.nx + 1) * C * p.S * p.S                                       # as tests/test_gpu_tiling.py
+    tiles = R.uniform_tiles(p, N, C, seed=41)
+    sound, before, behind = _blend_without_any_check(p, tiles, guard)
+    assert (before, behind) == (0, 0) and np.array_equal(_bits(sound), _bits(R.blend_f32(p, tiles)))
+    for name, (q, reach) in R.blend_table_edits(p, C).items():
+        got, before, behind = _blend_without_any_check(q, tiles, guard)
+        assert max(before, behind) == reach <= guard, (name, before, behind, reach)
+        assert min(before, behind) == 0, name
+        same = np.array_equal(_bits(got), _bits(R.blend_f32_table_safe(q, tiles)))
+        assert same == (name == "count=-1"), name
+
+
+def test_gather_origin_edits_and_their_restatement():
+    p = R.plan(13, 11, 8, 3)
+    img = np.random.default_rng(2).uniform(-1, 1, size=(2, 3, 13, 11)).astype(np.float32)
+    sound = R.gather(p, 0, 12, 4, images_f32=img)
+    assert np.array_equal(R.gather_table_safe(p, 0, 12, 4, images_f32=img), sound)
+    edits = R.gather_origin_edits(p)
+    assert tuple(edits) == R.GATHER_EDIT_NAMES
+    for name, (q, reach) in edits.items():
+        got = R.gather_table_safe(q, 0, 12, 4, images_f32=img)
+        zero = np.array([not got[b].any() for b in range(12)])
+        ky, kx = np.divmod(np.arange(12) % 6, p.nx)
+        bad = {"oy=-1": ky == 0, "oy=H-S+1": ky == p.ny - 1, "ox=-1": kx == 0, "ox=W-S+1": kx == p.nx - 1}[name]
+        assert np.array_equal(zero, bad), name
+        assert np.array_equal(got[~bad], sound[~bad]) and reach in (1, p.W)
 
 
 # ---- 4. the library, host side --------------------------------------------------------------------------------------
