@@ -88,7 +88,9 @@ extern "C" {
                                  vg_nlm_denoise, vg_noise_sigma;
                                  (added within 31, no version move, nothing changed) noise models of the degraded pairs and
                                  the median baseline: vg_gather_degrade_u8_ex, vg_degrade_params_ex / VG_NOISE_*,
-                                 VG_DRAW_DEGRADE_IMPULSE / _SALT, vg_median_filter */
+                                 VG_DRAW_DEGRADE_IMPULSE / _SALT, vg_median_filter;
+                                 (added within 31, no version move, nothing changed) spectral generation metric:
+                                 vg_spectrum_profiles (+ _ws_bytes), vg_spectrum_accum */
 int vg_abi_version(void);
 /* The library reads its optional kernel-selection switches (VG_* environment variables, DESIGN.md "Runtime switches")
  * ONCE, when it is loaded; nothing on a launch path calls getenv.  A process that changes one of them afterwards
@@ -1537,6 +1539,50 @@ int vg_noise_sigma(const float* x, int B, int C, int H, int W, float* sigma, int
  * pointer not 4-byte aligned (16-byte stores are used where W % 4 == 0 and y is 16-byte aligned).
  * ---------------------------------------------------------------------------------------- */
 int vg_median_filter(const float* x, float* y, int B, int C, int H, int W, int radius, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Spectral generation metric (not in the reference for images -- it compares the Welch PSD of real and generated EEG,
+ * test_eegglow.py:25-46, :79-95; added within ABI 31; csrc/spectrum.hip): per-image binned power spectra of an f32 NCHW
+ * batch, the quantity in which stacks of up-convolutions fail (Durall et al. 2020).  The transform is GENERIC: a separable
+ * complex transform whose two matrices, the weight map and the bins are the caller's tables (spectrum.py builds windowed
+ * DFT tables, the Hermitian-half weight and radial bins), so integer tables with integer images give integer results
+ * bit for bit.  With Wh = W / 2 + 1, per image b and channel c, every input converted to f64 exactly:
+ *     m       = center ? (sum of the plane) / (H W) : 0        the sum in f64 in this order: partial[t] = sum of plane[i]
+ *               over i = t, t + 256, ... ascending (t = 0 .. 255), then partial[t] += partial[t + s] for s = 128, 64, .., 1;
+ *               one division
+ *     Y[y][v] = sum_x (x[y][x] - m) tw[x][v]                   tw_re, tw_im f64 [W][Wh]
+ *     Z[u][v] = sum_y th[u][y] Y[y][v]   (complex)             th_re, th_im f64 [H][H]
+ *     P[u][v] = sum_c (Z_re^2 + Z_im^2), c ascending
+ *     prof[b][k] = sum over j in [bin_start[k], bin_start[k+1]) of weight[order[j]] P[order[j]], added in ascending j
+ * weight f64 [H][Wh]; order int32 [bin_start[n_bins]] (flat indices u Wh + v), bin_start int32 [n_bins + 1]: CSR.  The
+ * matrix products run on v_mfma_f64_16x16x4_f64 (the order of additions inside a product is the hardware's); rows and
+ * columns past H, W, Wh are staged as zeros and never multiplied in; the negation of the complex product is applied to an
+ * operand.  The bin sum's order is part of the contract: no atomics anywhere, a call is repeatable bit for bit, images are
+ * independent of each other.  Three launches (mean -- skipped without center --, transform, bins), nothing allocated, no
+ * host synchronisation.
+ *   Table safety. An `order` entry outside [0, H Wh) contributes nothing and is never dereferenced.  With nnz =
+ *   bin_start[n_bins] clamped into [0, H Wh], a bin whose bounds are not 0 <= bin_start[k] <= bin_start[k+1] <= nnz
+ *   contributes nothing (prof = 0): whatever the device tables hold, nothing outside the buffers is read (order must hold
+ *   nnz entries) and nothing outside prof / power / ws is written.
+ *   power f64 [B][H][Wh] or NULL: the channel-summed map P; with NULL it lives in ws.  prof f64 [B][n_bins].
+ *   ws: vg_spectrum_ws_bytes = 8 (B C + B H Wh) bytes (the plane means, then the map), a host-only query.
+ * VG_EINVAL, checked on the host before any launch: a NULL pointer (power excepted; `bytes` of the query); an output
+ * (prof, power, ws) overlapping an input or another output; B < 1, C outside 1..4, H or W outside 2..256, B C H W or
+ * B n_bins > 2^31 - 1; n_bins outside 1..H Wh; center outside {0, 1}; ws_bytes below the query's answer.  VG_EALIGN: x, order
+ * or bin_start not 4-byte aligned (x may sit anywhere on the 4-byte grid), an f64 buffer or ws not 8-byte aligned.
+ *
+ * vg_spectrum_accum: sum[k] += prof[b][k] and sumsq[k] += prof[b][k]^2 for b = 0 .. B - 1 ascending, each bin by one thread
+ * (s = sum[k]; s += p_0; s += p_1; ...; the squares enter by a fused multiply-add, q = fma(p_b, p_b, q): one rounding a
+ * step): prof f64 [B][n_bins], sum and sumsq f64 [n_bins].  One launch, repeatable.
+ * VG_EINVAL: a NULL pointer, overlapping buffers, B < 1, n_bins outside 1..256 * 129, B n_bins > 2^31 - 1.  VG_EALIGN: a
+ * pointer not 8-byte aligned.
+ * ---------------------------------------------------------------------------------------- */
+int vg_spectrum_ws_bytes(int B, int C, int H, int W, int64_t* bytes);
+int vg_spectrum_profiles(const float* x, int B, int C, int H, int W, int center, const double* tw_re, const double* tw_im,
+                         const double* th_re, const double* th_im, const double* weight, const int32_t* order,
+                         const int32_t* bin_start, int n_bins, double* power, double* prof, void* ws, int64_t ws_bytes,
+                         void* stream);
+int vg_spectrum_accum(const double* prof, int B, int n_bins, double* sum, double* sumsq, void* stream);
 
 #ifdef __cplusplus
 }

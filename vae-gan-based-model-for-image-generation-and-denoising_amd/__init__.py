@@ -32,6 +32,10 @@ baseline (not in the reference): ``NLMeans`` (``baselines``) -- non-local means 
 blindly estimated noise level (``ops.nlm_denoise``, ``ops.noise_sigma``), ``Median`` -- the (2r+1)^2 median filter
 (``ops.median_filter``), and ``baseline=`` on ``paired_test_epoch`` / ``tiled_test_epoch``.  Noise models of the degraded
 pairs (not in the reference): ``data.Degrade(noise_model="gaussian" | "speckle" | "shot", impulse_max_p=, salt_ratio=)``.
+Spectral generation metric (not in the reference for images): ``spectrum`` -- ``spectrum_plan`` / ``SpectrumPlan``, the
+windowed DFT tables and radial bins of an image size; ``SpectrumStats`` and ``spectral_distance`` (``metrics``): running
+radially binned power spectra on the device (``ops.spectrum_profiles``, ``ops.spectrum_accum``, f64 MFMA) and the log-spectral
+distance / high-frequency share of two image sets; ``evaluate_generation_spectrum`` adds them to a generation pass.
 """
 from . import baselines  # noqa: F401
 from . import cluster  # noqa: F401
@@ -49,10 +53,12 @@ from .denoise import (LatentRefiner, denoise_eval, denoise_tiled, paired_test_ep
                       validation_epoch)
 from .tiling import TilePlan, tile_plan
 from .graphed import graphed
+from . import spectrum  # noqa: F401
 from .latent import (GaussianMixturePrior, LatentPrior, encode_dataset, evaluate_generation, evaluate_generation_ndb,
-                     sample_images)
+                     evaluate_generation_spectrum, sample_images)
 from .cluster import KMeans
-from .metrics import FeatureStats, encoder_features, frechet_distance, kernel_distance, ndb, precision_recall
+from .metrics import (FeatureStats, SpectrumStats, encoder_features, frechet_distance, kernel_distance, ndb,
+                      precision_recall, spectral_distance)
 from .losses import BCELoss, MSELoss, MSSSIMLoss, SSIMLoss, msssim_weights
 from .nets import ConvBlock, Discriminator, Encoder, Generator, weights_init
 from .optim import Adam, AdamW, LRSchedule, clip_grad_norm_
@@ -68,4 +74,5 @@ __all__ = ["ConvBlock", "Encoder", "Generator", "Discriminator", "weights_init",
            "tiling", "TilePlan", "tile_plan", "denoise_tiled", "tiled_denoise_eval", "tiled_test_epoch",
            "metrics", "FeatureStats", "frechet_distance", "precision_recall", "encoder_features", "kernel_distance",
            "cluster", "KMeans", "ndb", "evaluate_generation_ndb", "MSSSIMLoss", "msssim_weights", "LatentRefiner",
-           "baselines", "NLMeans", "Median"]
+           "baselines", "NLMeans", "Median",
+           "spectrum", "SpectrumStats", "spectral_distance", "evaluate_generation_spectrum"]

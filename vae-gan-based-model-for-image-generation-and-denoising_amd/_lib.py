@@ -272,6 +272,9 @@ SIGNATURES = {
                                         _I, _I, _F, _F, _P]),
     "vg_degrade_params_ex": (c_int, [_U, _U, _I, _F, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _F, _F, _P]),
     "vg_median_filter": (c_int, [_P, _P, _I, _I, _I, _I, _I, _P]),
+    "vg_spectrum_ws_bytes": (c_int, [_I, _I, _I, _I, POINTER(c_int64)]),
+    "vg_spectrum_profiles": (c_int, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _L, _P]),
+    "vg_spectrum_accum": (c_int, [_P, _I, _I, _P, _P, _P]),
 }
 
 LIB_PATH = os.environ.get("VG_LIB_PATH") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libvaegan_hip.so")

@@ -25,7 +25,8 @@ import torch
 from . import geometry as G
 from . import ops
 from .cluster import KMeans
-from .metrics import FeaturePass, _pr_result, ndb_statistics
+from . import spectrum as _spectrum
+from .metrics import FeaturePass, SpectrumStats, _pr_result, _spectral_distance, ndb_statistics
 
 
 def _loader_samples(loader) -> int:
@@ -473,7 +474,8 @@ def evaluate_generation(decoder, val_loader: Iterable[torch.Tensor],
     with ``kid_seed``, degree 3, gamma 1 / D, coef 1); the result gains ``kid_mean`` and ``kid_std`` (population standard
     deviation), read in the same host sync.  Not in the reference; single process, like precision / recall.
 
-    NDB of the pass's features: ``evaluate_generation_ndb`` (this function's keyword list is pinned)."""
+    NDB of the pass's features: ``evaluate_generation_ndb`` (this function's keyword list is pinned); the radial power
+    spectra of the pass's images: ``evaluate_generation_spectrum``."""
     return _evaluate_generation(decoder, val_loader, prior, noise_fn, feature_fn, k, real_stats, kid_subsets,
                                 kid_subset_size, kid_seed, None)
 
@@ -499,9 +501,34 @@ def evaluate_generation_ndb(decoder, val_loader: Iterable[torch.Tensor], ndb_bin
                                 (int(ndb_bins), float(ndb_alpha), int(ndb_seed)))
 
 
+@torch.no_grad()
+def evaluate_generation_spectrum(decoder, val_loader: Iterable[torch.Tensor], spectrum_bins: Optional[int] = None,
+                                 window: str = "hann", **kwargs) -> Dict[str, float]:
+    """``evaluate_generation(decoder, val_loader, **kwargs)`` whose result also holds ``lsd_db``, ``hf_excess_db``,
+    ``hf_share_real`` and ``hf_share_fake`` (``metrics.spectral_distance`` with its defaults): the ``real`` and ``fake``
+    images of every batch also go to two ``metrics.SpectrumStats`` over ``spectrum.spectrum_plan(H, W, spectrum_bins,
+    window)`` -- radially binned power spectra on the device, no network and no feature_fn needed.  It is the one metric of
+    the pass that sees the top octave, where stacks of ConvTranspose2d fail (Durall et al. 2020).  The 2 x 2 n_bins sums
+    are read in the pass's final host sync; every other key is what ``evaluate_generation`` returns.  Not in the reference
+    for images (it compares mean PSDs of EEG, test_eegglow.py:25-46)."""
+    names = ("prior", "noise_fn", "feature_fn", "k", "real_stats", "kid_subsets", "kid_subset_size", "kid_seed")
+    unknown = sorted(set(kwargs) - set(names))
+    if unknown:
+        raise TypeError(f"evaluate_generation_spectrum: unknown keyword(s) {unknown}")
+    if window not in _spectrum.WINDOWS:
+        raise RuntimeError(f"evaluate_generation_spectrum: window must be one of {_spectrum.WINDOWS}, got {window!r}")
+    if spectrum_bins is not None and (isinstance(spectrum_bins, bool) or not isinstance(spectrum_bins, int) or spectrum_bins < 1):
+        raise RuntimeError(f"evaluate_generation_spectrum: spectrum_bins must be a positive integer or None, got {spectrum_bins!r}")
+    defaults = dict(prior=None, noise_fn=None, feature_fn=None, k=3, real_stats=None, kid_subsets=None, kid_subset_size=1000,
+                    kid_seed=0)
+    defaults.update(kwargs)
+    return _evaluate_generation(decoder, val_loader, *(defaults[n] for n in names), None, (spectrum_bins, window))
+
+
 def _evaluate_generation(decoder, val_loader, prior, noise_fn, feature_fn, k, real_stats, kid_subsets, kid_subset_size,
-                         kid_seed, ndb):
-    """The pass behind ``evaluate_generation`` (ndb None) and ``evaluate_generation_ndb`` (ndb = (bins, alpha, seed))."""
+                         kid_seed, ndb, spectrum=None):
+    """The pass behind ``evaluate_generation`` (ndb None), ``evaluate_generation_ndb`` (ndb = (bins, alpha, seed)) and
+    ``evaluate_generation_spectrum`` (spectrum = (n_bins or None, window); default None: off)."""
     if kid_subsets is not None and feature_fn is None:
         raise RuntimeError("evaluate_generation: kid_subsets needs a feature_fn (KID is a feature-space metric)")
     decoder.eval()
@@ -509,6 +536,7 @@ def _evaluate_generation(decoder, val_loader, prior, noise_fn, feature_fn, k, re
     acc = ops.zeros_f32(1, dev)
     seen = batches = 0
     feats = FeaturePass(feature_fn, True, real_stats) if feature_fn is not None else None
+    spec = None
     for i, real in enumerate(val_loader):
         if not real.is_cuda:
             raise RuntimeError("evaluate_generation needs device batches (data.DeviceLoader); there is no CPU path")
@@ -527,19 +555,35 @@ def _evaluate_generation(decoder, val_loader, prior, noise_fn, feature_fn, k, re
         ops.axpy(acc, ops.ssim(fake, real), float(b), out=acc)
         if feats is not None:
             feats.update(real, fake)
+        if spectrum is not None:
+            if spec is None:
+                plan = _spectrum.spectrum_plan(int(real.shape[2]), int(real.shape[3]), spectrum[0], spectrum[1])
+                spec = (SpectrumStats(plan, dev), SpectrumStats(plan, dev))
+            spec[0].update(real)
+            spec[1].update(fake)
         seen += b
         batches += 1
     if batches == 0:
         raise RuntimeError("evaluate_generation: the loader yielded no batch")
+    spec_parts = [spec[0].sum, spec[1].sum] if spec is not None else []
     if feats is None:
-        return {"ssim": float(acc.item()) / seen, "samples": seen, "batches": batches}   # the one host sync
+        if spec is None:
+            return {"ssim": float(acc.item()) / seen, "samples": seen, "batches": batches}   # the one host sync
+        ssim_sum, *sp = torch.cat([acc.double()] + spec_parts).tolist()                  # the one host sync
+        out = {"ssim": ssim_sum / seen, "samples": seen, "batches": batches}
+        out.update(_spectrum_result(spec, sp))
+        return out
     counts = feats.pr_counts(int(k))
     parts = [acc.double(), counts.double()]
     if kid_subsets is not None:
         parts.append(feats.kid(int(kid_subsets), int(kid_subset_size), int(kid_seed)))
     if ndb is not None:
         parts.append(feats.ndb_counts(ndb[0], ndb[2]).double().reshape(-1))            # exact: counts are below 2^53
+    parts += spec_parts
     ssim_sum, fake_in_real, real_in_fake, *kid = torch.cat(parts).tolist()             # the one host sync
+    if spec is not None:
+        sp = kid[len(kid) - 2 * spec[0].plan.n_bins:]
+        kid = kid[:len(kid) - 2 * spec[0].plan.n_bins]
     if ndb is not None:
         bins = np.asarray(kid[len(kid) - 2 * ndb[0]:]).reshape(2, ndb[0])
         kid = kid[:len(kid) - 2 * ndb[0]]
@@ -551,7 +595,16 @@ def _evaluate_generation(decoder, val_loader, prior, noise_fn, feature_fn, k, re
     if ndb is not None:
         st = ndb_statistics(bins[0], bins[1], ndb[1])
         out.update(ndb=st["ndb"], ndb_over_k=st["ndb_over_k"], js_divergence=st["js_divergence"])
+    if spec is not None:
+        out.update(_spectrum_result(spec, sp))
     return out
+
+
+def _spectrum_result(spec, sums) -> Dict[str, float]:
+    """The four spectral keys from the two running sums read in the pass's host sync (real first, then fake)."""
+    nb = spec[0].plan.n_bins
+    d = _spectral_distance(spec[0].plan, np.asarray(sums[:nb]) / spec[0].n, np.asarray(sums[nb:]) / spec[1].n, 1, 0.5)
+    return {key: d[key] for key in ("lsd_db", "hf_excess_db", "hf_share_real", "hf_share_fake")}
 
 
 @torch.no_grad()

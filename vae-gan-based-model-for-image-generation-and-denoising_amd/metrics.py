@@ -123,6 +123,117 @@ def frechet_distance(real: FeatureStats, fake: FeatureStats) -> float:
     return float(d @ d + np.trace(s1) + np.trace(s2) - 2.0 * c)
 
 
+class SpectrumStats:
+    """Running binned power spectra of an image stream, the twin of ``FeatureStats`` for the spectral metric (not in the
+    reference for images; it compares mean Welch PSDs of real and generated EEG, test_eegglow.py:25-46): ``sum`` and
+    ``sumsq`` f64 [n_bins] of the per-image profiles of ``plan`` (a ``spectrum.SpectrumPlan``) and the image count ``n`` (a
+    python int).  ``update`` runs on the device (vg_spectrum_profiles, vg_spectrum_accum) and is deterministic; an instance
+    on the CPU only HOLDS state.  No network is involved: the metric sees the top octave that every feature space built on
+    strided convolutions throws away."""
+
+    def __init__(self, plan, device="cuda", center: bool = True):
+        from .spectrum import SpectrumPlan
+        if not isinstance(plan, SpectrumPlan):
+            raise RuntimeError("SpectrumStats: plan must be a spectrum.SpectrumPlan (spectrum.spectrum_plan(H, W))")
+        if not isinstance(center, bool):
+            raise RuntimeError("SpectrumStats: center must be a bool")
+        self.plan, self.center, self.n = plan, center, 0
+        self.sum = torch.zeros(plan.n_bins, dtype=torch.float64, device=device)
+        self.sumsq = torch.zeros(plan.n_bins, dtype=torch.float64, device=device)
+
+    def update(self, images: torch.Tensor) -> "SpectrumStats":
+        """images f32 [b, C, H, W] on the device, any b >= 0 (ragged batches).  No host sync."""
+        if not self.sum.is_cuda:
+            raise RuntimeError("SpectrumStats.update needs the statistics on the MI355X ('cuda'); there is no CPU path")
+        if not isinstance(images, torch.Tensor) or not images.is_cuda:
+            raise RuntimeError("SpectrumStats.update needs images on the MI355X ('cuda'); there is no CPU path")
+        if images.dtype != torch.float32 or images.dim() != 4 or tuple(images.shape[2:]) != (self.plan.H, self.plan.W):
+            raise RuntimeError(f"SpectrumStats.update: images must be f32 [b, C, {self.plan.H}, {self.plan.W}], got "
+                               f"{images.dtype} {tuple(images.shape)}")
+        if images.shape[0] == 0:
+            return self
+        ops.spectrum_accum(ops.spectrum_profiles(images.contiguous(), self.plan, self.center), self.sum, self.sumsq)
+        self.n += int(images.shape[0])
+        return self
+
+    def merge(self, other: "SpectrumStats") -> "SpectrumStats":
+        """Add another stream's sums (another rank's, another shard's): the statistics are additive."""
+        if not self.plan.same_bins(other.plan) or self.center != other.center:
+            raise RuntimeError(f"SpectrumStats.merge: the plans differ ({self.plan} vs {other.plan})")
+        self.sum += other.sum.to(self.sum.device)
+        self.sumsq += other.sumsq.to(self.sumsq.device)
+        self.n += other.n
+        return self
+
+    def mean_profile(self) -> np.ndarray:
+        """sum / n as a host f64 array [n_bins] (one copy of n_bins doubles)."""
+        if self.n < 1:
+            raise RuntimeError("SpectrumStats.mean_profile: no image yet")
+        return self.sum.cpu().numpy() / self.n
+
+    def var_profile(self) -> np.ndarray:
+        """(sumsq - n mean^2) / (n - 1): the sample variance of the per-image profiles, a host f64 array [n_bins]."""
+        if self.n < 2:
+            raise RuntimeError("SpectrumStats.var_profile needs at least two images")
+        m = self.sum.cpu().numpy() / self.n
+        return (self.sumsq.cpu().numpy() - self.n * m * m) / (self.n - 1)
+
+    def state_dict(self) -> Dict[str, torch.Tensor]:
+        return {"sum": self.sum, "sumsq": self.sumsq, "n": torch.tensor(self.n, dtype=torch.int64)}
+
+    def load_state_dict(self, sd: Dict[str, torch.Tensor]) -> "SpectrumStats":
+        s, q = sd["sum"], sd["sumsq"]
+        nb = self.plan.n_bins
+        if s.dtype != torch.float64 or q.dtype != torch.float64 or tuple(s.shape) != (nb,) or tuple(q.shape) != (nb,):
+            raise RuntimeError(f"SpectrumStats: sum and sumsq must be f64 [{nb}]")
+        dev = self.sum.device
+        self.sum, self.sumsq, self.n = s.to(dev).contiguous().clone(), q.to(dev).contiguous().clone(), int(sd["n"])
+        return self
+
+
+def _spectral_distance(plan, mean_real: np.ndarray, mean_fake: np.ndarray, skip_bins: int, hf_from: float) -> Dict[str, object]:
+    """``spectral_distance`` on two host mean profiles."""
+    k = np.arange(plan.n_bins)
+    live = (k >= skip_bins) & (plan.counts > 0)
+    both = live & (mean_real > 0) & (mean_fake > 0)
+    d = 10.0 * np.log10(mean_real[both] / mean_fake[both])
+    lsd = float(np.sqrt(np.mean(d * d))) if d.size else float("nan")
+    hf = live & (plan.frac_lo >= hf_from)
+    share = []
+    for m in (mean_real, mean_fake):
+        tot = float(m[live].sum())
+        share.append(float(m[hf].sum()) / tot if tot > 0 else float("nan"))
+    excess = 10.0 * math.log10(share[1] / share[0]) if share[0] > 0 and share[1] > 0 else float("nan")
+    return {"lsd_db": lsd, "hf_share_real": share[0], "hf_share_fake": share[1], "hf_excess_db": excess,
+            "bins_used": int(both.sum()), "bins_skipped": int(live.sum() - both.sum()), "mean_real": mean_real,
+            "mean_fake": mean_fake, "centers": plan.centers.copy()}
+
+
+def spectral_distance(real: SpectrumStats, fake: SpectrumStats, skip_bins: int = 1, hf_from: float = 0.5) -> Dict[str, object]:
+    """Two image sets compared by their mean binned power spectra (host numpy f64 on 2 n_bins doubles):
+
+        lsd_db         the log-spectral distance: the RMS of 10 log10(mean_real[k] / mean_fake[k]) over the bins k >= skip_bins
+                       that hold at least one frequency (skip_bins = 1 leaves the lowest bin, DC and its leakage, out)
+        hf_share_real  the share of the power of the bins k >= skip_bins that lies in bins whose lower edge is at or above
+        hf_share_fake  hf_from of r_max (the Nyquist corner, sqrt(1/2) cycles per pixel)
+        hf_excess_db   10 log10(hf_share_fake / hf_share_real): > 0, the generator puts too much into the top of the band
+
+    plus mean_real, mean_fake, centers (cycles per pixel), bins_used and bins_skipped: a bin where either mean is 0 has no
+    log ratio; it is left out of lsd_db and counted.  lsd_db is symmetric in its arguments, hf_excess_db changes sign."""
+    if not isinstance(real, SpectrumStats) or not isinstance(fake, SpectrumStats):
+        raise RuntimeError("spectral_distance: real and fake must be SpectrumStats")
+    if not real.plan.same_bins(fake.plan) or real.center != fake.center:
+        raise RuntimeError(f"spectral_distance: the plans differ ({real.plan} vs {fake.plan})")
+    if isinstance(skip_bins, bool) or not isinstance(skip_bins, int) or not 0 <= skip_bins < real.plan.n_bins:
+        raise RuntimeError(f"spectral_distance: skip_bins must be an integer in [0, n_bins = {real.plan.n_bins}), got {skip_bins!r}")
+    hf_from = float(hf_from)
+    if not 0.0 <= hf_from <= 1.0:
+        raise RuntimeError(f"spectral_distance: hf_from is a fraction of r_max in [0, 1], got {hf_from}")
+    if real.n < 1 or fake.n < 1:
+        raise RuntimeError("spectral_distance needs at least one image on each side")
+    return _spectral_distance(real.plan, real.mean_profile(), fake.mean_profile(), skip_bins, hf_from)
+
+
 def _pr_counts(real_feats: torch.Tensor, fake_feats: torch.Tensor, k: int) -> torch.Tensor:
     """int64 [2] on the device: (fake rows inside the real manifold, real rows inside the fake manifold)."""
     _check_feats(real_feats, None, "precision_recall")

@@ -1943,6 +1943,57 @@ def median_filter(x, radius=1, out=None):
     return y
 
 
+def spectrum_profiles(x, plan, center=True, want_power=False):
+    """Binned power spectra of an f32 [B,C,H,W] batch, B >= 1, C <= 4 (vg_spectrum_profiles): ``plan`` is a
+    ``spectrum.SpectrumPlan`` of the batch's H x W (its tables are uploaded once per device); ``center`` subtracts every
+    plane's mean first.  -> prof f64 [B, n_bins], or (prof, power f64 [B, H, W // 2 + 1]) with ``want_power``: the
+    channel-summed |Z|^2 map.  f64 MFMA, fixed summation order, no atomics, no host synchronisation."""
+    from .spectrum import SpectrumPlan
+    what = "spectrum_profiles"
+    _need_cuda(x)
+    if not isinstance(plan, SpectrumPlan):
+        raise RuntimeError(f"{what}: plan must be a spectrum.SpectrumPlan (spectrum.spectrum_plan(H, W))")
+    if x.dtype != torch.float32 or x.dim() != 4:
+        raise RuntimeError(f"{what}: x must be an f32 [B,C,H,W] tensor")
+    if not isinstance(center, bool) or not isinstance(want_power, bool):
+        raise RuntimeError(f"{what}: center and want_power must be bools")
+    B, C, H, W = x.shape
+    if (H, W) != (plan.H, plan.W):
+        raise RuntimeError(f"{what}: the plan is for {plan.H} x {plan.W} images, x is {H} x {W}")
+    if B < 1 or not 1 <= C <= 4:
+        raise RuntimeError(f"{what}: need B >= 1 and 1 <= C <= 4, got B={B} C={C}")
+    lib = L.load()
+    need = ctypes.c_int64(0)
+    L.check(lib.vg_spectrum_ws_bytes(B, C, H, W, byref(need)), "vg_spectrum_ws_bytes")
+    ws = WS.get("spectrum", need.value, x.device)
+    t = plan.device_tables(x.device)
+    prof = torch.empty(B, plan.n_bins, dtype=torch.float64, device=x.device)
+    power = torch.empty(B, H, plan.Wh, dtype=torch.float64, device=x.device) if want_power else None
+    L.check(lib.vg_spectrum_profiles(x.data_ptr(), B, C, H, W, int(center), t["tw_re"].data_ptr(), t["tw_im"].data_ptr(),
+                                     t["th_re"].data_ptr(), t["th_im"].data_ptr(), t["weight"].data_ptr(),
+                                     t["order"].data_ptr(), t["bin_start"].data_ptr(), plan.n_bins, L.ptr(power),
+                                     prof.data_ptr(), ws.data_ptr(), ws.numel() * 4, L.stream_ptr()), "vg_spectrum_profiles")
+    return (prof, power) if want_power else prof
+
+
+def spectrum_accum(prof, sum, sumsq):
+    """Running profile statistics (vg_spectrum_accum): sum f64 [n_bins] += prof[b], sumsq += prof[b]^2 over the rows of prof
+    f64 [b, n_bins] in ascending b (b >= 0), one thread per bin.  In place; no host sync.  -> (sum, sumsq)."""
+    what = "spectrum_accum"
+    _need_cuda(prof, sum, sumsq)
+    if prof.dtype != torch.float64 or prof.dim() != 2:
+        raise RuntimeError(f"{what}: prof must be an f64 [b, n_bins] tensor")
+    b, n = prof.shape
+    if (sum.dtype != torch.float64 or sumsq.dtype != torch.float64 or tuple(sum.shape) != (n,) or tuple(sumsq.shape) != (n,)
+            or sum.device != prof.device or sumsq.device != prof.device):
+        raise RuntimeError(f"{what}: sum and sumsq must be f64 [{n}] on prof's device")
+    if b == 0:
+        return sum, sumsq
+    L.check(L.load().vg_spectrum_accum(prof.data_ptr(), b, n, sum.data_ptr(), sumsq.data_ptr(), L.stream_ptr()),
+            "vg_spectrum_accum")
+    return sum, sumsq
+
+
 LATENT_MODE = {"init": L.VG_LATENT_INIT, "update": L.VG_LATENT_UPDATE, "track": L.VG_LATENT_TRACK}
 
 
